@@ -10,7 +10,15 @@ One process per GPU, data parallel over RCCL (weak scaling: per-GPU batch fixed)
 JSON line.  Workload = BASELINE.json configs[1] (downstream mode, 1-channel 96^3, batch 4 per GPU,
 window 7x7x7) unless --workload says otherwise.  Inputs are resident in HBM before the timed region.
 
-Extra objects on the line:
+A plain run sets up, runs the untimed settle and warm-up steps, times --steps steps and prints the line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, `config`).  Model, optimizer and batch
+are seeded and the settle phase is a fixed number of steps, so the same arguments give the same inputs and the same
+training trajectory from run to run.  --dump-outputs DIR then writes what the last timed step returned to its caller --
+the loss, the parameters the optimizer updated with their gradients, the floating-point buffers (BatchNorm running
+statistics; the EMA teacher's parameters in the students/teacher modes) -- as DIR/<name>.npy in float32, so two builds
+can be compared output for output (a fixed, seeded sample of every array when they exceed 64 MB together).
+
+--full adds the figures that need more than the timed steps, as extra objects on the line:
   roofline            the DOMINANT kernel family of the step: the window-attention forward of the stage-0 blocks (the kernel
                       BASELINE.json's north star sets its MFMA target on).  achieved = algorithmic FLOPs 4 Nq Nk hd per
                       (window, head) / mean launch duration, measured with HIP events on the launch stream inside the timed
@@ -51,19 +59,28 @@ def parse():
     ap.add_argument("--window", default="7,7,7")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (0 = the workload's)")
     ap.add_argument("--dropout", type=float, default=0.0, help="attn_drop = proj_drop (the yml default is 0.1)")
-    ap.add_argument("--settle", type=float, default=1.0, help="seconds of untimed steps before the warm-up (>= 10 steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--settle", type=int, default=200,
+                    help="untimed steps before the warm-up (a fixed count: the dumped outputs of two runs must match; "
+                         "N > 1 ranks run 30)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline kernels (HIP events inside the timed region) and the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--graph", action="store_true",
                     help="record the step in HIP graphs and time replays (train.GraphedStep: with --gpus N one flat gradient "
                          "all-reduce runs between the forward+backward graph and the optimizer graph; dropout through the device "
-                         "epoch word); the roofline kernels are then timed in a few eager steps AFTER the timed region")
+                         "epoch word); with --full the roofline kernels are then timed in a few eager steps AFTER the timed region")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for --gpus > 1 (nccl = RCCL; gloo lets several ranks share one GPU in tests)")
     ap.add_argument("--device", type=int, default=-1, help="GPU index (default: LOCAL_RANK)")
     ap.add_argument("--fp8-attn", action="store_true",
                     help="BASELINE.json configs[4]'s named arithmetic: E4M3 MFMA window-attention forward in the head_dim < 16 blocks "
                          "(an experiment that measured slower and less accurate than bf16: off by default, DESIGN.md section 8)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.settle < 0:
+        ap.error("--steps must be >= 1, --warmup and --settle >= 0")
+    return args
 
 
 def conv_flops(desc):
@@ -178,6 +195,43 @@ def attn_issue_bound_seconds(desc, n_cu=256, clock_hz=2.4e9):
     return pairs / 512.0 * (8 * 8.4 + 4 * 4.5 + 3 * 8.0) / (n_cu * 4) / clock_hz
 
 
+DUMP_LIMIT = 64_000_000 - (1 << 20)  # bytes of array data: the .npy headers fit in the rest of the 64 MB
+
+
+def step_outputs(net, opt, loss, ssl):
+    """What one training step hands back to its caller: the loss, the parameters the optimizer updated and their
+    gradients, the floating-point buffers, and in the students/teacher modes the teacher parameters the EMA moved."""
+    mod = getattr(net, "module", net)
+    updated = {id(p) for g in opt.param_groups for p in g["params"]}
+    outs = {"loss": loss}
+    for n, p in mod.named_parameters():
+        if id(p) in updated or (ssl and n.startswith("net_teacher.")):
+            outs["param." + n] = p
+            if p.grad is not None:
+                outs["grad." + n] = p.grad
+    for n, b in mod.named_buffers():
+        if b.is_floating_point():
+            outs["buffer." + n] = b
+    return outs
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """Write each tensor as ``path/<name>.npy`` in float32.  When together they exceed ``limit`` bytes, every array keeps
+    the same share of its flattened elements, chosen by a generator seeded per array: the sample depends on the shapes
+    only, so two runs or two builds write the same positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    share = min(1.0, limit / max(total, 1))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if share < 1.0:
+            a = a.reshape(-1)
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:int(a.numel() * share)]
+            a = a[idx.sort().values]
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+
+
 def main():
     args = parse()
     import mivp_amd
@@ -233,38 +287,40 @@ def main():
 
         one_step = train.graphed_train_step(net, opt, conf, x, y) if args.graph else eager_step
 
-    # the largest MFMA-shaped kernel: the last decoder stage's conv_concat (implicit GEMM, K = 27*144, N = 48)
     hc = conf.hidden_channels
-    dom_cin, dom_cout = hc[0] + hc[1], hc[0]
-    _lib.profile_select(("mivp_conv3d_halo_fwd", "mivp_conv3d_fwd"),
-                        lambda a: a[0]._obj.Cin == dom_cin and a[0]._obj.Cout == dom_cout, key="roofline")
-    # the stage-0 window-attention forward launches (encoder stage 0 and the last decoder stage: C = hidden_channels[0])
-    _lib.profile_select("mivp_win_attn_fwd", lambda a: a[0]._obj.C == hc[0] and a[0]._obj.has_mask == 0, key="attn")
-    _lib.profile_select("mivp_win_attn_fwd", lambda a: a[0]._obj.C == hc[0] and a[0]._obj.has_mask != 0, key="attn_shift")
+    if args.full:
+        # the largest MFMA-shaped kernel: the last decoder stage's conv_concat (implicit GEMM, K = 27*144, N = 48)
+        dom_cin, dom_cout = hc[0] + hc[1], hc[0]
+        _lib.profile_select(("mivp_conv3d_halo_fwd", "mivp_conv3d_fwd"),
+                            lambda a: a[0]._obj.Cin == dom_cin and a[0]._obj.Cout == dom_cout, key="roofline")
+        # the stage-0 window-attention forward launches (encoder stage 0 and the last decoder stage: C = hidden_channels[0])
+        _lib.profile_select("mivp_win_attn_fwd", lambda a: a[0]._obj.C == hc[0] and a[0]._obj.has_mask == 0, key="attn")
+        _lib.profile_select("mivp_win_attn_fwd", lambda a: a[0]._obj.C == hc[0] and a[0]._obj.has_mask != 0, key="attn_shift")
 
     def sync():
         train.barrier_sync(dev)
 
-    # settle phase (untimed, before the W warm-up steps): the first ~20 steps after start-up run 15-25 % slower on
-    # this pool (clock ramp from the low-power state, allocator growth); measured with tools/cpu_bound_check.py
-    t_settle = time.perf_counter()
-    n_settle = 0
-    # under DDP every rank must run the same number of steps (each one is a collective): fixed count there
-    while (n_settle < 30) if world > 1 else (n_settle < 10 or (time.perf_counter() - t_settle < args.settle and n_settle < 200)):
+    # settle phase (untimed, before the W warm-up steps): the first ~20 steps after start-up run 15-25 % slower
+    # (clock ramp from the low-power state, allocator growth); measured with tools/cpu_bound_check.py.
+    # A fixed count, not a time: the state the timed steps start from must not depend on how fast the settle ran, and
+    # under DDP every rank must run the same number of steps (each one is a collective)
+    n_settle = 30 if world > 1 else args.settle
+    for i in range(n_settle):
         one_step()
-        n_settle += 1
-        if n_settle % 10 == 0:
+        if (i + 1) % 10 == 0:
             torch.cuda.synchronize()
     for _ in range(args.warmup):
         one_step()
     sync()
-    _lib.profile_reset(True)
+    _lib.profile_reset(args.full)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = one_step()
     sync()
     dt = time.perf_counter() - t0
-    if args.graph:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(net, opt, loss, ssl))
+    if args.graph and args.full:
         # a replay issues no C-ABI calls from Python, so the per-kernel event pairs have nothing to wrap: the same kernels
         # are timed in eager steps of the same state, outside the timed region
         loss = loss.clone()
@@ -327,10 +383,11 @@ def main():
                        "backend": args.backend if world > 1 else None,
                        "launch": ("hip-graph replay (step recorded once" + ("; flat gradient all-reduce between the two graphs)" if world > 1 else ")"))
                                  if args.graph else "eager (one C-ABI call per kernel)"},
-            "roofline": roof, "roofline_conv": roof_conv,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(conf, size)
+        if args.full:
+            line["roofline"], line["roofline_conv"] = roof, roof_conv
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(conf, size)
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -9,7 +9,8 @@ are imported through a synthetic parent package that skips
     refmodules.swin_transformer.{swin_block,down}
     refmodules.multi_head_attention.{window_attention,relative_positional_encoding}
 
-    refmodules.losses.clustered_prototype_loss, refmodules.momentum_model            (G8: students/teacher step)
+    refmodules.losses.clustered_prototype_loss, refmodules.momentum_model            (G8: students/teacher step;
+                                                                                      G8b: around this package's SwinUnetR)
     refmodules.utils  (G9: MeanIoU, DiceCoefficient, WarmupCosineSchedule, map_label_indices; the file imports cv2 at
                        the top for its PNG viewers only, so an EMPTY placeholder module named cv2 is registered first --
                        no cv2 function is ever called by the four symbols captured here)
@@ -405,6 +406,46 @@ def gen_momentum():
                                      "param_order": [k for k, _ in mm.net_student.named_parameters()]})
 
 
+def seed_momentum_pair(mm, seed=5):
+    """Student then teacher parameters, in named_parameters() order, drawn from one seeded generator (also run by
+    tests/test_host_logic.py, which must draw the same values)."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for net in (mm.net_student, mm.net_teacher):
+            for _, p in net.named_parameters():
+                p.copy_(torch.randn(p.shape, generator=g))
+
+
+def gen_momentum_product():
+    """G8b: the reference's MomentumModel around THIS package's SwinUnetR (``tiny`` workload conf, a backbone-training mode):
+    the parameter pairing it builds through ``architecture(conf=conf)``, one ``update_teacher`` from seeded values (per
+    parameter: float64 sum and the first 16 elements; the model has ~9.5 M parameters) and ``copy_state_dict``."""
+    from refmodules.momentum_model import MomentumModel
+    root = os.path.dirname(os.path.dirname(OUT))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import mivp_amd  # noqa: F401
+    from mivp_amd import train
+    from mivp_amd.swin_unetr import SwinUnetR
+    conf, _, _ = train.make_conf("tiny")
+    conf.training_mode = "self_supervised_learning_all"
+    mm = MomentumModel(conf, SwinUnetR)
+    seed_momentum_pair(mm)
+    mm.update_teacher()
+    arrays = {}
+    for k, v in mm.net_teacher.named_parameters():
+        arrays[f"teacher1_sum/{k}"] = torch.tensor([v.detach().double().sum()])
+        arrays[f"teacher1_head/{k}"] = v.detach().reshape(-1)[:16].clone()
+    mm.copy_state_dict()
+    copied = all(torch.equal(a, b) for a, b in zip(mm.net_student.parameters(), mm.net_teacher.parameters()))
+    frozen = all(not q.requires_grad for q in mm.net_teacher.parameters())
+    _save("momentum_model_product", arrays, {
+        "tau": conf.tau, "seed": 5, "copy_state_dict_copies": copied, "copy_state_dict_freezes_teacher": frozen,
+        "param_order": [k for k, _ in mm.net_student.named_parameters()],
+        "teacher_order": [k for k, _ in mm.net_teacher.named_parameters()],
+        "shapes": [list(p.shape) for p in mm.net_student.parameters()]})
+
+
 def gen_utils():
     """G9: metrics / schedule / label mapping of modules/utils.py:14-89,372-388 (the reference's own code, see the module
     docstring for the empty cv2 placeholder)."""
@@ -453,6 +494,7 @@ if __name__ == "__main__":
     if "--only-g8g9" in sys.argv:
         gen_prototype_loss()
         gen_momentum()
+        gen_momentum_product()
         gen_utils()
         sys.exit(0)
     gen_relpe(rpe)
@@ -464,4 +506,5 @@ if __name__ == "__main__":
     gen_unetr(su)
     gen_prototype_loss()
     gen_momentum()
+    gen_momentum_product()
     gen_utils()

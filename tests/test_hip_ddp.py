@@ -221,7 +221,7 @@ def _bench_rank(rank, world, port, q, extra=()):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--device", "0",
-                        "--workload", "tiny", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *extra],
+                        "--workload", "tiny", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", *extra],
                        env=env, capture_output=True, text=True, timeout=600)
     q.put((rank, r.returncode, r.stdout, r.stderr[-2000:]))
 

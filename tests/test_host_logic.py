@@ -56,34 +56,41 @@ def test_bn_momentum_none_is_cumulative_average():
 
 def test_reference_momentum_model_accepts_the_product_class():
     """Drop-in: the REFERENCE's MomentumModel (momentum_model/momentum_model.py:4-36) builds two product SwinUnetR instances
-    through ``architecture(conf=conf)`` and pairs their parameters by zip order.  Runs where /root/reference is mounted (the
-    build container); construction, the EMA update and copy_state_dict need no GPU."""
-    import os
-    import sys
-    import types
-    import pytest
-    ref = "/root/reference/src/modules"
-    if not os.path.isdir(ref):
-        pytest.skip("reference not mounted")
+    through ``architecture(conf=conf)`` and pairs their parameters by zip order.  What the reference's class did with this
+    package's SwinUnetR is stored in ``momentum_model_product`` (tests/golden/gen_golden.py G8b: the pairing, one EMA step from
+    seeded values, copy_state_dict); the package's MomentumModel, which restates the reference's (pinned by the
+    ``momentum_model`` fixture), repeats it here.  Construction, the EMA update and copy_state_dict need no GPU."""
+    from conftest import load_fixture
     import mivp_amd
     from mivp_amd import train
+    from mivp_amd.students_teacher import MomentumModel
     from mivp_amd.swin_unetr import SwinUnetR
-    if "refmodules" not in sys.modules:
-        parent = types.ModuleType("refmodules")
-        parent.__path__ = [ref]
-        sys.modules["refmodules"] = parent
-    from refmodules.momentum_model import MomentumModel
+    fx = load_fixture("momentum_model_product")
     conf, _, _ = train.make_conf("tiny")
     conf.training_mode = "self_supervised_learning_all"
+    assert conf.tau == fx.meta["tau"]
     mm = MomentumModel(conf, SwinUnetR)
     names_s = [k for k, _ in mm.net_student.named_parameters()]
     assert names_s == [k for k, _ in mm.net_teacher.named_parameters()] and len(names_s) > 200
+    assert names_s == fx.meta["param_order"] == fx.meta["teacher_order"]
+    assert [list(p.shape) for p in mm.net_student.parameters()] == fx.meta["shapes"]
+    g = torch.Generator().manual_seed(fx.meta["seed"])            # gen_golden.seed_momentum_pair: the same draws
+    with torch.no_grad():
+        for net in (mm.net_student, mm.net_teacher):
+            for _, p in net.named_parameters():
+                p.copy_(torch.randn(p.shape, generator=g))
     t0 = [p.detach().clone() for p in mm.net_teacher.parameters()]
     mm.update_teacher()
     for a, t, s in zip(t0, mm.net_teacher.parameters(), mm.net_student.parameters()):
         assert torch.allclose(t, conf.tau * a + (1 - conf.tau) * s.detach())
+    for k, t in mm.net_teacher.named_parameters():
+        assert torch.allclose(t.detach().reshape(-1)[:16], fx["teacher1_head"][k], rtol=1e-6, atol=1e-7), k
+        want = float(fx["teacher1_sum"][k])
+        assert abs(float(t.detach().double().sum()) - want) <= 1e-6 * max(1.0, float(t.detach().double().abs().sum())), k
     mm.copy_state_dict()
+    assert fx.meta["copy_state_dict_copies"] and fx.meta["copy_state_dict_freezes_teacher"]
     assert all(torch.equal(a, b) for a, b in zip(mm.net_student.parameters(), mm.net_teacher.parameters()))
+    assert all(not p.requires_grad for p in mm.net_teacher.parameters())
     # the optimizer recipe of the reference's trainer (students_teacher.py:27-68) resolves against the product's helpers
     n = (sum(p.numel() for _, p in mm.net_student.named_parameters_decoder())
          + sum(p.numel() for _, p in mm.net_student.named_parameters_encoder()))
