@@ -609,6 +609,44 @@ int mivp_convt_fwd(int32_t B, const int32_t* dims, const int32_t* stride, int32_
 int mivp_convt_dgrad(int32_t B, const int32_t* dims, const int32_t* stride, int32_t Cin, int32_t Cout, const void* dy,
                      const void* w2, void* dx, mivp_stream_t stream);
 
+/* Phase-1 multi-view self-supervised step (ABI 13; modules/multi_view.py:115-176, utils.py:267-350,
+ * losses/contrastive_pair_loss.py).  Volumes are fp32 CHANNELS-FIRST [B][C][H][W][D] contiguous (out["reconstruction"] of
+ * the model is channels-last storage: the same bytes at C = 1, a channels-first copy otherwise).  dims = {H, W, D},
+ * mshape = masking patch {mh, mw, md} (host arrays); the patch grid is dims / mshape.
+ *   codes int32 [2B]: rotation counts k_i[0..B) then k_j[0..B) (rot90 in the (H, W) plane, H == W)
+ *   keep  uint32 [2][ceil(n_patches / 32)]: one bit per masking patch and view, patch (ph, pw, pd) -> bit
+ *         (ph*gw + pw)*gd + pd; SET = visible (the reference's ``~mask``), shared by every sample and channel
+ *   perm  int32 [1]: x_k = perm(x_i), 0 H<->W, 1 H<->D, 2 W<->D (cubes only)
+ *   vec   float [5]: reconstruction, rotation, contrastive, mutual, weighted total
+ * All of codes / keep / perm / gscale are DEVICE data: a recorded graph is refreshed by rewriting their content.
+ *
+ * mivp_mv_views: x_i / x_j = mask(rot90(x)), and x_k = perm(x_i) when xk != NULL (a second launch; 64 x 64 LDS tile
+ *   transpose for the swaps that move D).
+ * mivp_mv_rec_loss: value pass of rec = MSE over both views of (rec_v*k_v, x_v*k_v) / (1 - ratio) (when do_rec) and of
+ *   mut = MSE(perm(rec_k)*k_i, rec_i*k_i) / (1 - ratio) (when rk != NULL) -> vec[0], vec[3];
+ *   workspace: mivp_mv_rec_ws() floats.
+ * mivp_mv_rec_grad: d rec_i, d rec_j, d rec_k of w_rec*rec + mut, times gscale[0] (device, NULL = 1).
+ * mivp_mv_heads: one workgroup; rotation CE over cat(rot_i, rot_j) [2B][4] with targets codes, and NT-Xent
+ *   (ContrastivePairLoss, temperature temp) of z_i, z_j [B][dim]; 2B <= 64, dim <= 1024; roti / zi may be NULL (term off).
+ *   Value mode (dzi == droti == NULL): vec[1], vec[2] and vec[4] = w_rec*vec[0] + w_rot*vec[1] + w_con*vec[2] + vec[3]
+ *   (vec[0] / vec[3] read when has_recmut, else written 0).  Gradient mode: dzi / dzj scaled by gscale[0]*w_con and
+ *   droti / drotj by gscale[0]*w_rot; vec untouched.  workspace: mivp_mv_heads_ws(B, dim) floats.                       */
+int mivp_mv_views(const float* x, int32_t B, int32_t C, const int32_t* dims, const int32_t* mshape, const int32_t* codes,
+                  const void* keep, const int32_t* perm, float* xi, float* xj, float* xk, mivp_stream_t stream);
+size_t mivp_mv_rec_ws(void);
+int mivp_mv_rec_loss(const float* ri, const float* rj, const float* xi, const float* xj, const float* rk, int32_t B,
+                     int32_t C, const int32_t* dims, const int32_t* mshape, const void* keep, const int32_t* perm,
+                     int32_t do_rec, float ratio, float* workspace, float* vec, mivp_stream_t stream);
+int mivp_mv_rec_grad(const float* ri, const float* rj, const float* xi, const float* xj, const float* rk, int32_t B,
+                     int32_t C, const int32_t* dims, const int32_t* mshape, const void* keep, const int32_t* perm,
+                     int32_t do_rec, float ratio, float w_rec, const float* gscale, float* dri, float* drj, float* drk,
+                     mivp_stream_t stream);
+size_t mivp_mv_heads_ws(int32_t B, int32_t dim);
+int mivp_mv_heads(const float* zi, const float* zj, int32_t B, int32_t dim, float temp, const float* roti, const float* rotj,
+                  const int32_t* codes, float w_rec, float w_rot, float w_con, int32_t has_recmut, float* workspace,
+                  const float* gscale, float* dzi, float* dzj, float* droti, float* drotj, float* vec,
+                  mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ __all__ = ["_lib", "geometry"]
 
 def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
-    if name in ("swin_ops", "ops", "swin_unetr", "train"):
+    if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":

@@ -36,6 +36,11 @@ WORKLOADS = {
     # every parameter trains on the segmentation objective (students_teacher.py:25-68,190-197), 96^3
     "sup_all": dict(training_mode="supervised_learning_all", use_encoder_prompting=False, use_decoder_prompting=False,
                     input_channels=1, size=96, batch=4),
+    # phase 1 (multi_view.py, example_scripts/phase1_example.sh): encoder + proxy heads, reconstruction + rotation +
+    # contrastive on, mutual off (example_configs.yml:71-86), encoder prompting as the phase-1 script passes it, 96^3
+    "ssl_enc": dict(training_mode="self_supervised_learning_encoder", use_encoder_prompting=True,
+                    use_decoder_prompting=False, input_channels=1, size=96, batch=4, use_reconstruction=True,
+                    use_rotation_prediction=True, use_contrastive_learning=True, use_mutual_learning=False),
     # smoke-sized
     "tiny": dict(training_mode="downstream", use_encoder_prompting=True, use_decoder_prompting=True,
                  input_channels=1, size=32, batch=2),
@@ -61,7 +66,13 @@ def make_conf(workload: str, window=(7, 7, 7), dropout: float = 0.0) -> Tuple[Na
         weight_decay_prompt_tokens=0.1,
         # students-teacher trainer (example_configs.yml:84-99)
         tau=0.99, reduction_factor=4, fwhm=128, k_means_iterations=3, use_prototype_assignment=True, use_real_label=True,
-        warmup_steps_students_teacher=100, t_total_students_teacher=2400, **w)
+        warmup_steps_students_teacher=100, t_total_students_teacher=2400,
+        # multi-view trainer (example_configs.yml:71-86); roi_size is the volume the views are cut from
+        masking_shape=[2, 2, 2], masking_ratio=0.2, weight_rec=0.2, weight_rot=0.5, weight_con=0.3,
+        max_epochs_multi_view=400, lr_multi_view=5e-4, weight_decay_multi_view=0.1, num_samples_multi_view=7,
+        batch_size_multi_view=2, warmup_steps_multi_view=100, t_total_multi_view=4000, roi_size=[size, size, size])
+    for k, v in w.items():
+        setattr(conf, k, v)
     return conf, size, batch
 
 
@@ -142,6 +153,15 @@ def build_optimizer(model, conf: Namespace, capturable: bool = False):
     core = model.module if hasattr(model, "module") else model
     core = core.net_student if hasattr(core, "net_student") else core      # MomentumModel: the student trains
     mode = conf.training_mode
+    if mode == "self_supervised_learning_encoder":
+        # MultiViewTrainer.configure_optimizers (multi_view.py:57-85): the encoder partition (proxy heads included in this
+        # mode), then the encoder prompt tokens with their own lr / weight decay
+        lr, wd = float(conf.lr_multi_view), float(conf.weight_decay_multi_view)
+        groups = [{"params": [p for _, p in core.named_parameters_encoder()], "lr": lr, "weight_decay": wd}]
+        if conf.use_encoder_prompting:
+            groups.append({"params": [p for _, p in core.named_parameters_prompt_tokens_encoder()],
+                           "lr": float(conf.lr_prompt_tokens), "weight_decay": float(conf.weight_decay_prompt_tokens)})
+        return FusedAdamW(groups, lr=lr, weight_decay=wd, capturable=capturable)
     if mode == "downstream":
         params = [p for _, p in core.named_parameters_downstream()]
         return FusedAdamW(params, lr=float(conf.lr_downstream), weight_decay=float(conf.weight_decay_downstream), capturable=capturable)
@@ -169,6 +189,8 @@ def build_scheduler(opt, conf: Namespace):
     from .optim import WarmupCosineSchedule
     if conf.training_mode == "downstream":
         return None
+    if conf.training_mode == "self_supervised_learning_encoder":          # multi_view.py:76-85
+        return WarmupCosineSchedule(opt, warmup_steps=int(conf.warmup_steps_multi_view), t_total=int(conf.t_total_multi_view))
     return WarmupCosineSchedule(opt, warmup_steps=int(conf.warmup_steps_students_teacher), t_total=int(conf.t_total_students_teacher))
 
 
@@ -184,6 +206,9 @@ def step_loss(out: dict, conf: Namespace, y) -> torch.Tensor:
     if mode in ("supervised_learning_all", "supervised_learning_decoder"):
         from .losses import dice_loss
         return dice_loss(out["seg_pred"], y, conf.include_background)
+    if mode == "self_supervised_learning_encoder":
+        raise ValueError(f"{mode}: the phase-1 step has several forwards per step, use mivp_amd.multiview.multiview_step "
+                         "(multi_view.py:115-176)")
     raise ValueError(f"{mode}: use mivp_amd.students_teacher.students_teacher_step (students_teacher.py:150-207)")
 
 
