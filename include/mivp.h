@@ -647,6 +647,32 @@ int mivp_mv_heads(const float* zi, const float* zj, int32_t B, int32_t dim, floa
                   const float* gscale, float* dzi, float* dzj, float* droti, float* drotj, float* vec,
                   mivp_stream_t stream);
 
+/* Whole-volume sliding-window prediction (ABI 14, csrc/stitch.hip; mivp_amd/inference.py SlidingWindowPredictor).
+ * dims = image {H, W, D}, pad = zeros in front per axis, pdims = padded size max(dims, roi), roi = window size (host arrays).
+ * table int32 [n_entries][4] = (o0, o1, o2, valid), origins in padded coordinates, n_entries a multiple of B; entry w is slot
+ * w % B of sub-batch w / B.  sub_idx: DEVICE int32 [1], the current sub-batch, read by gather and blend and bumped by
+ * mivp_window_advance (a recorded graph of gather -> model -> blend -> advance replays the next sub-batch each time).
+ *   mivp_window_gather: vol f32 [1][Cin][H][W][D] (Cin <= 4) -> out f32 [B][Cin][roi] contiguous; zero outside the image and
+ *     for invalid entries; 16-byte row accesses where aligned.
+ *   mivp_window_blend: acc f32 [pdims][C] += w * logits, wsum f32 [pdims] += w, w(i, j, k) = max(w0[i] * w1[j] * w2[k],
+ *     w_floor) (device tables), for every valid window of the sub-batch; logits f32 [B][roi][C] (channels_last) or [B][C][roi].
+ *     No float atomics: each voxel adds its covering windows in increasing window index (bitwise independent of B).
+ *     ubox = host {U0, U1, U2}: the largest union box of a sub-batch's windows (sizes the grid).  C <= 16.
+ *   mivp_stitch_finalize: per image voxel acc / wsum -> labels uint8 [H][W][D] (first arg-max), logits f32 [C][H][W][D] when
+ *     non-NULL, and when target f32 [H][W][D] is non-NULL counts int64 [C][3] += as mivp_seg_counts.
+ *   mivp_window_advance: sub_idx[0] += 1 (one thread). */
+int mivp_window_gather(const float* vol, int32_t Cin, const int32_t* dims, const int32_t* pad, const int32_t* pdims,
+                       const int32_t* roi, const int32_t* table, int32_t n_entries, const int32_t* sub_idx, int32_t B,
+                       float* out, mivp_stream_t stream);
+int mivp_window_blend(const float* logits, int32_t channels_last, int32_t C, const int32_t* pdims, const int32_t* roi,
+                      const int32_t* table, int32_t n_entries, const int32_t* sub_idx, int32_t B, const int32_t* ubox,
+                      const float* w0, const float* w1, const float* w2, float w_floor, float* acc, float* wsum,
+                      mivp_stream_t stream);
+int mivp_stitch_finalize(const float* acc, const float* wsum, int32_t C, const int32_t* dims, const int32_t* pad,
+                         const int32_t* pdims, uint8_t* labels, float* logits, const float* target, void* counts,
+                         mivp_stream_t stream);
+int mivp_window_advance(int32_t* sub_idx, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

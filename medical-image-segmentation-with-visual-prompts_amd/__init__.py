@@ -14,10 +14,13 @@ __all__ = ["_lib", "geometry"]
 
 def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
-    if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview"):
+    if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
         from .swin_unetr import SwinUnetR
         return SwinUnetR
+    if name in ("SlidingWindowPredictor", "predict_volume", "evaluate_volume"):
+        from . import inference
+        return getattr(inference, name)
     raise AttributeError(name)

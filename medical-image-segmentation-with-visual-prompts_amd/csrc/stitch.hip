@@ -1,0 +1,235 @@
+// Whole-volume sliding-window prediction (ABI 14, mivp_amd/inference.py SlidingWindowPredictor): the windows of one
+// sub-batch are cut out of the resident volume straight into the model's input tensor, the model's logits are blended
+// into a whole-volume accumulator with a separable importance map, and one pass turns the accumulator into a label map
+// (plus, on request, the blended logits and the whole-volume Dice / IoU counts).
+//
+// Every kernel reads the sub-batch index from a device word (`sub_idx`) that mivp_window_advance bumps at the end of a
+// sub-batch, so gather -> model -> blend -> advance records once as a graph and replays without host work.
+//
+// Window table: int32 [n_entries][4] = (o0, o1, o2, valid), origins in PADDED-volume coordinates (a volume axis shorter
+// than the roi is zero-padded to the roi; `pad` voxels in front).  Entry w belongs to sub-batch w / B, slot w % B.
+//
+// The blend is a gather over voxels, with no float atomics: one thread per voxel of the union box of the sub-batch's
+// windows loads its accumulator, adds the weighted logits of the covering windows in increasing window index, and
+// stores it.  Sub-batches run in stream order, so every voxel sums its contributions in global window order whatever the
+// sub-batch size.
+#include "common.hpp"
+#include <limits.h>
+
+namespace {
+constexpr int MAXC = 16;
+constexpr int TPB = 256;
+
+struct Geo {
+    int n[3];      // image size
+    int pad[3];    // zeros in front of the image (padded volume coordinates = image coordinates + pad)
+    int p[3];      // padded size, max(n, roi)
+    int r[3];      // roi
+};
+
+// one thread = four consecutive D outputs of one (window, channel, i, j) row
+__global__ __launch_bounds__(TPB) void k_window_gather(const float* __restrict__ vol, int Cin, Geo g,
+                                                       const int* __restrict__ table, int n_entries,
+                                                       const int* __restrict__ sub_idx, int B, int vec_ok,
+                                                       float* __restrict__ out) {
+    const int r2q = (g.r[2] + 3) >> 2;
+    const long total = (long)B * Cin * g.r[0] * g.r[1] * r2q;
+    const long t = (long)blockIdx.x * TPB + threadIdx.x;
+    if (t >= total) return;
+    const int q = (int)(t % r2q);
+    const long row = t / r2q;                                  // ((b * Cin + c) * r0 + i) * r1 + j
+    const int j = (int)(row % g.r[1]);
+    long rest = row / g.r[1];
+    const int i = (int)(rest % g.r[0]);
+    rest /= g.r[0];
+    const int c = (int)(rest % Cin);
+    const int b = (int)(rest / Cin);
+    const long w = (long)sub_idx[0] * B + b;
+    bool ok = w >= 0 && w < n_entries && table[w * 4 + 3] != 0;
+    int h = 0, x1 = 0, d0 = 0;
+    if (ok) {
+        h = table[w * 4 + 0] + i - g.pad[0];
+        x1 = table[w * 4 + 1] + j - g.pad[1];
+        d0 = table[w * 4 + 2] + 4 * q - g.pad[2];
+    }
+    ok = ok && h >= 0 && h < g.n[0] && x1 >= 0 && x1 < g.n[1];
+    const float* src = vol + (((long)c * g.n[0] + (ok ? h : 0)) * g.n[1] + (ok ? x1 : 0)) * g.n[2];
+    float* dst = out + row * g.r[2] + 4 * q;
+    if (vec_ok) {                                              // D % 4 == 0, r2 % 4 == 0, 16-byte aligned bases
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok && d0 >= 0 && d0 + 4 <= g.n[2] && (d0 & 3) == 0) {
+            v = *reinterpret_cast<const float4*>(src + d0);
+        } else if (ok) {
+            v.x = (d0 >= 0 && d0 < g.n[2]) ? src[d0] : 0.f;
+            v.y = (d0 + 1 >= 0 && d0 + 1 < g.n[2]) ? src[d0 + 1] : 0.f;
+            v.z = (d0 + 2 >= 0 && d0 + 2 < g.n[2]) ? src[d0 + 2] : 0.f;
+            v.w = (d0 + 3 >= 0 && d0 + 3 < g.n[2]) ? src[d0 + 3] : 0.f;
+        }
+        *reinterpret_cast<float4*>(dst) = v;
+    } else {
+        const int kn = min(4, g.r[2] - 4 * q);
+        for (int e = 0; e < kn; ++e) {
+            const int d = d0 + e;
+            dst[e] = (ok && d >= 0 && d < g.n[2]) ? src[d] : 0.f;
+        }
+    }
+}
+
+// one thread = one voxel of the current sub-batch's union box; the grid covers the largest union box (ubox)
+__global__ __launch_bounds__(TPB) void k_window_blend(const float* __restrict__ logits, int channels_last, int C, Geo g,
+                                                      const int* __restrict__ table, int n_entries,
+                                                      const int* __restrict__ sub_idx, int B, int U0, int U1, int U2,
+                                                      const float* __restrict__ w0, const float* __restrict__ w1,
+                                                      const float* __restrict__ w2, float w_floor,
+                                                      float* __restrict__ acc, float* __restrict__ wsum) {
+    const long t = (long)blockIdx.x * TPB + threadIdx.x;
+    if (t >= (long)U0 * U1 * U2) return;
+    const int u2 = (int)(t % U2);
+    const long tr = t / U2;
+    const int u1 = (int)(tr % U1);
+    const int u0 = (int)(tr / U1);
+    const long wbase = (long)sub_idx[0] * B;
+    if (wbase < 0 || wbase >= n_entries) return;
+    const int nb = (int)min((long)B, n_entries - wbase);
+    int lo0 = INT_MAX, lo1 = INT_MAX, lo2 = INT_MAX, hi0 = 0, hi1 = 0, hi2 = 0;
+    for (int b = 0; b < nb; ++b) {
+        const int* e = table + (wbase + b) * 4;
+        if (!e[3]) continue;
+        lo0 = min(lo0, e[0]); lo1 = min(lo1, e[1]); lo2 = min(lo2, e[2]);
+        hi0 = max(hi0, e[0] + g.r[0]); hi1 = max(hi1, e[1] + g.r[1]); hi2 = max(hi2, e[2] + g.r[2]);
+    }
+    if (lo0 >= hi0) return;                                    // no valid window in this sub-batch
+    const int p0 = lo0 + u0, p1 = lo1 + u1, p2 = lo2 + u2;
+    if (p0 >= hi0 || p1 >= hi1 || p2 >= hi2) return;
+    const long v = ((long)p0 * g.p[1] + p1) * g.p[2] + p2;
+    const long rvol = (long)g.r[0] * g.r[1] * g.r[2];
+    float a[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) a[c] = c < C ? acc[v * C + c] : 0.f;
+    float s = wsum[v];
+    bool any = false;
+    for (int b = 0; b < nb; ++b) {                             // increasing window index
+        const int* e = table + (wbase + b) * 4;
+        if (!e[3]) continue;
+        const int i = p0 - e[0], j = p1 - e[1], k = p2 - e[2];
+        if (i < 0 || i >= g.r[0] || j < 0 || j >= g.r[1] || k < 0 || k >= g.r[2]) continue;
+        const float wt = fmaxf(w0[i] * w1[j] * w2[k], w_floor);
+        const long lv = ((long)i * g.r[1] + j) * g.r[2] + k;
+        const float* src = channels_last ? logits + ((long)b * rvol + lv) * C : logits + (long)b * C * rvol + lv;
+        const long cs = channels_last ? 1 : rvol;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) a[c] += wt * src[c * cs];
+        s += wt;
+        any = true;
+    }
+    if (!any) return;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C) acc[v * C + c] = a[c];
+    wsum[v] = s;
+}
+
+// acc / wsum over the image (cropped out of the padded volume), first arg-max, optional logits and counts
+__global__ __launch_bounds__(TPB) void k_stitch_finalize(const float* __restrict__ acc, const float* __restrict__ wsum, int C,
+                                                         Geo g, uint8_t* __restrict__ labels, float* __restrict__ out,
+                                                         const float* __restrict__ target,
+                                                         unsigned long long* __restrict__ counts) {
+    __shared__ unsigned int sm[MAXC * 3];
+    for (int i = threadIdx.x; i < MAXC * 3; i += TPB) sm[i] = 0u;
+    __syncthreads();
+    const long nvox = (long)g.n[0] * g.n[1] * g.n[2];
+    for (long v = (long)blockIdx.x * TPB + threadIdx.x; v < nvox; v += (long)gridDim.x * TPB) {
+        const int d = (int)(v % g.n[2]);
+        const long r = v / g.n[2];
+        const int x1 = (int)(r % g.n[1]);
+        const int h = (int)(r / g.n[1]);
+        const long pv = ((long)(h + g.pad[0]) * g.p[1] + (x1 + g.pad[1])) * g.p[2] + (d + g.pad[2]);
+        const float s = wsum[pv];
+        int best = 0;
+        float bv = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            if (c >= C) break;
+            const float x = acc[pv * C + c] / s;
+            if (out) out[(long)c * nvox + v] = x;
+            if (c == 0 || x > bv) { bv = x; best = c; }       // first maximum, like torch.argmax
+        }
+        labels[v] = (uint8_t)best;
+        if (target) {
+            const float tv = target[v];
+            atomicAdd(&sm[best * 3 + 1], 1u);
+            for (int c = 0; c < C; ++c)
+                if (tv == (float)c) { atomicAdd(&sm[c * 3 + 2], 1u); if (best == c) atomicAdd(&sm[c * 3 + 0], 1u); }
+        }
+    }
+    if (!target) return;                                       // (uniform: the whole grid returns together)
+    __syncthreads();
+    for (int i = threadIdx.x; i < C * 3; i += TPB)
+        if (sm[i]) atomicAdd(&counts[i], (unsigned long long)sm[i]);
+}
+
+// a separate one-thread launch: the blend's workgroups all read the word, so none of them may bump it
+__global__ void k_window_advance(int* __restrict__ sub_idx) { sub_idx[0] = sub_idx[0] + 1; }
+
+bool fill_geo(Geo& g, const int32_t* dims, const int32_t* pad, const int32_t* pdims, const int32_t* roi) {
+    for (int a = 0; a < 3; ++a) {
+        g.n[a] = dims[a]; g.pad[a] = pad[a]; g.p[a] = pdims[a]; g.r[a] = roi[a];
+        if (g.n[a] < 1 || g.r[a] < 1 || g.pad[a] < 0 || g.pad[a] + g.n[a] > g.p[a] || g.r[a] > g.p[a]) return false;
+    }
+    return (long)g.p[0] * g.p[1] * g.p[2] < (1L << 31) / MAXC;
+}
+}  // namespace
+
+extern "C" int mivp_window_gather(const float* vol, int32_t Cin, const int32_t* dims, const int32_t* pad, const int32_t* pdims,
+                                  const int32_t* roi, const int32_t* table, int32_t n_entries, const int32_t* sub_idx,
+                                  int32_t B, float* out, mivp_stream_t stream) {
+    MIVP_REQUIRE(vol && out && table && sub_idx && dims && pad && pdims && roi);
+    MIVP_REQUIRE(Cin >= 1 && Cin <= 4 && B >= 1 && n_entries >= B && n_entries % B == 0);
+    Geo g;
+    MIVP_REQUIRE(fill_geo(g, dims, pad, pdims, roi));
+    const int vec_ok = (reinterpret_cast<uintptr_t>(vol) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) &&
+                       g.n[2] % 4 == 0 && g.r[2] % 4 == 0;
+    const long total = (long)B * Cin * g.r[0] * g.r[1] * ((g.r[2] + 3) / 4);
+    hipLaunchKernelGGL(k_window_gather, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, vol,
+                       (int)Cin, g, table, (int)n_entries, sub_idx, (int)B, vec_ok, out);
+    return mivp_check_launch("window_gather");
+}
+
+extern "C" int mivp_window_blend(const float* logits, int32_t channels_last, int32_t C, const int32_t* pdims,
+                                 const int32_t* roi, const int32_t* table, int32_t n_entries, const int32_t* sub_idx,
+                                 int32_t B, const int32_t* ubox, const float* w0, const float* w1, const float* w2,
+                                 float w_floor, float* acc, float* wsum, mivp_stream_t stream) {
+    MIVP_REQUIRE(logits && table && sub_idx && pdims && roi && ubox && w0 && w1 && w2 && acc && wsum);
+    MIVP_REQUIRE(C >= 1 && C <= MAXC && B >= 1 && n_entries >= B && n_entries % B == 0);
+    const int32_t zero[3] = {0, 0, 0};
+    Geo g;
+    MIVP_REQUIRE(fill_geo(g, pdims, zero, pdims, roi));
+    for (int a = 0; a < 3; ++a) MIVP_REQUIRE(ubox[a] >= g.r[a] && ubox[a] <= g.p[a]);
+    const long total = (long)ubox[0] * ubox[1] * ubox[2];
+    hipLaunchKernelGGL(k_window_blend, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, logits,
+                       (int)(channels_last != 0), (int)C, g, table, (int)n_entries, sub_idx, (int)B, (int)ubox[0],
+                       (int)ubox[1], (int)ubox[2], w0, w1, w2, w_floor, acc, wsum);
+    return mivp_check_launch("window_blend");
+}
+
+extern "C" int mivp_stitch_finalize(const float* acc, const float* wsum, int32_t C, const int32_t* dims, const int32_t* pad,
+                                    const int32_t* pdims, uint8_t* labels, float* logits, const float* target, void* counts,
+                                    mivp_stream_t stream) {
+    MIVP_REQUIRE(acc && wsum && labels && dims && pad && pdims && C >= 1 && C <= MAXC);
+    MIVP_REQUIRE((target == nullptr) == (counts == nullptr));
+    Geo g;
+    const int32_t one[3] = {1, 1, 1};
+    MIVP_REQUIRE(fill_geo(g, dims, pad, pdims, one));
+    const long nvox = (long)g.n[0] * g.n[1] * g.n[2];
+    const unsigned grid = (unsigned)((nvox + TPB - 1) / TPB > 2048 ? 2048 : (nvox + TPB - 1) / TPB);
+    hipLaunchKernelGGL(k_stitch_finalize, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, acc, wsum, (int)C, g, labels, logits,
+                       target, (unsigned long long*)counts);
+    return mivp_check_launch("stitch_finalize");
+}
+
+extern "C" int mivp_window_advance(int32_t* sub_idx, mivp_stream_t stream) {
+    MIVP_REQUIRE(sub_idx);
+    hipLaunchKernelGGL(k_window_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)sub_idx);
+    return mivp_check_launch("window_advance");
+}

@@ -5,8 +5,10 @@ and the metric counts accumulated by one kernel per sub-batch (no ``.item()`` in
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Sequence, Tuple
+import math
+from typing import Dict, List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -113,3 +115,292 @@ def summarize(values: List[float]) -> Tuple[float, float]:
     """mean and (population) standard deviation over the volumes, as logged by segmentation.py:297-300."""
     mean = sum(values) / len(values)
     return mean, (sum((v - mean) ** 2 for v in values) / len(values)) ** 0.5
+
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Whole-volume prediction: every voxel predicted, overlapping windows blended on the device (csrc/stitch.hip, DESIGN 4.15)
+# ---------------------------------------------------------------------------------------------------------------------
+def _check_overlap(overlap: float):
+    if not (0.0 <= float(overlap) < 1.0):
+        raise ValueError(f"overlap must be in [0, 1), got {overlap}")
+
+
+def _check_shape3(name: str, v: Sequence[int]) -> Tuple[int, int, int]:
+    t = tuple(int(a) for a in v)
+    if len(t) != 3 or min(t) < 1:
+        raise ValueError(f"{name} must be three positive sizes, got {tuple(v)}")
+    return t
+
+
+def window_padding(image_size: Sequence[int], roi: Sequence[int]) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
+    """(zeros in front per axis, padded size per axis): an axis shorter than the roi is padded to the roi, (r - n) // 2
+    in front and the rest behind; other axes are not padded."""
+    n, r = _check_shape3("image_size", image_size), _check_shape3("roi", roi)
+    pad = tuple((ri - ni) // 2 if ni < ri else 0 for ni, ri in zip(n, r))
+    return pad, tuple(max(ni, ri) for ni, ri in zip(n, r))
+
+
+def window_origins(image_size: Sequence[int], roi: Sequence[int], overlap: float) -> np.ndarray:
+    """Window origins int32 [N, 3] in padded-volume coordinates (``window_padding``), row-major over the per-axis counts.
+
+    The placement follows MONAI ``sliding_window_inference``'s conventions, written out here (MONAI is not a dependency,
+    so parity with it is not pinned by a test): per axis, on the padded size n and roi r,
+    ``interval = max(int(r * (1 - overlap)), 1)``, ``count = ceil((n - r) / interval) + 1`` and window i starts at
+    ``min(i * interval, n - r)``, so the last window is flush with the end."""
+    _check_overlap(overlap)
+    _, p = window_padding(image_size, roi)
+    axes = []
+    for n, r in zip(p, roi):
+        interval = max(int(r * (1.0 - float(overlap))), 1)
+        count = int(math.ceil((n - r) / interval)) + 1
+        axes.append([min(i * interval, n - r) for i in range(count)])
+    g = np.stack(np.meshgrid(*[np.asarray(a, dtype=np.int32) for a in axes], indexing="ij"), axis=-1)
+    return g.reshape(-1, 3).astype(np.int32)
+
+
+def window_table(origins: np.ndarray, sub_batch: int) -> np.ndarray:
+    """The device table: int32 [ceil(N / sub_batch) * sub_batch, 4] = (o0, o1, o2, valid); padding entries are invalid."""
+    if int(sub_batch) < 1:
+        raise ValueError("sub_batch must be >= 1")
+    n = origins.shape[0]
+    total = -(-n // int(sub_batch)) * int(sub_batch)
+    t = np.zeros((total, 4), dtype=np.int32)
+    t[:n, :3] = origins
+    t[:n, 3] = 1
+    return t
+
+
+def importance_tables(roi: Sequence[int], mode: str = "gaussian", sigma_scale: float = 0.125):
+    """The separable importance map as three 1-D float64 tables and the floor it is clamped at from below:
+    w(i, j, k) = max(t0[i] * t1[j] * t2[k], floor).  ``"constant"``: all ones.  ``"gaussian"``:
+    t_d(i) = exp(-(i - r_d // 2)^2 / (2 sigma_d^2)), sigma_d = sigma_scale * r_d, floor = max(min(map), 1e-3)."""
+    r = _check_shape3("roi", roi)
+    if mode == "constant":
+        return [np.ones(n, dtype=np.float64) for n in r], 1.0
+    if mode != "gaussian":
+        raise ValueError(f"mode must be 'gaussian' or 'constant', got {mode!r}")
+    if not float(sigma_scale) > 0:
+        raise ValueError("sigma_scale must be > 0")
+    tabs = []
+    for n in r:
+        sigma = float(sigma_scale) * n
+        i = np.arange(n, dtype=np.float64)
+        tabs.append(np.exp(-((i - n // 2) ** 2) / (2.0 * sigma * sigma)))
+    floor = max(float(np.prod([t.min() for t in tabs])), 1e-3)
+    return tabs, floor
+
+
+def _i3(v):
+    return (C.c_int32 * 3)(*[int(a) for a in v])
+
+
+def _model_factor(conf) -> Tuple[int, int, int]:
+    """Per-axis size multiple the SwinUnetR accepts: the patch embedding times the encoder's patch mergings (every stage
+    halves H and W, only the first one D: swin_unetr.py merge_last_dim)."""
+    depth = int(conf.depth_unet)
+    ps = [int(a) for a in conf.input_patch_size]
+    return ps[0] * 2 ** depth, ps[1] * 2 ** depth, ps[2] * 2 ** min(depth, 1)
+
+
+class SlidingWindowPredictor:
+    """Whole-volume sliding-window prediction of a ``downstream`` model on the GPU.
+
+    For one image size it owns the window table, the device sub-batch index, the model's input batch, the blend
+    accumulators and the Dice / IoU count table; ``predict`` / ``evaluate`` can be called for any number of volumes of
+    that size.  Per sub-batch: one gather launch cuts the windows out of the volume into the input batch, the model runs,
+    one blend launch adds ``w * logits`` and ``w`` into the accumulators (gather form, no float atomics: bitwise
+    independent of ``sub_batch``), one launch advances the index.  One finalize launch writes the labels.
+
+    ``graph=True`` records gather -> model -> blend -> advance once (after two eager sub-batches that pack the weight
+    caches) and replays it ``ceil(N / sub_batch)`` times with no host work in between: bitwise equal to eager.  The graph
+    holds the model's weights as they were when it was recorded; build a new predictor after changing them."""
+
+    def __init__(self, model, image_size: Sequence[int], in_channels: int, num_classes: int, roi: Sequence[int],
+                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                 graph: bool = False):
+        self.image_size = _check_shape3("image_size", image_size)
+        self.roi = _check_shape3("roi", roi)
+        _check_overlap(overlap)
+        if int(sub_batch) < 1:
+            raise ValueError("sub_batch must be >= 1")
+        if not 1 <= int(in_channels) <= 4:
+            raise ValueError("in_channels must be in 1..4")
+        if not 1 <= int(num_classes) <= 16:
+            raise ValueError("num_classes must be in 1..16")
+        conf = getattr(model, "conf", None)
+        if conf is not None:
+            if getattr(conf, "training_mode", "downstream") != "downstream":
+                raise ValueError("SlidingWindowPredictor needs a 'downstream' model (its output is out['downstream'])")
+            if int(conf.input_channels) != int(in_channels):
+                raise ValueError(f"in_channels {in_channels} does not match the model's input_channels {conf.input_channels}")
+            if int(conf.output_channels_downstream) != int(num_classes):
+                raise ValueError(f"num_classes {num_classes} does not match the model's output_channels_downstream "
+                                 f"{conf.output_channels_downstream}")
+            f = _model_factor(conf)
+            if any(r % m for r, m in zip(self.roi, f)):
+                raise ValueError(f"roi {self.roi} is not a multiple of {f}, the input size multiple of this model")
+        dev = next(iter(model.parameters()), None)
+        dev = dev.device if dev is not None else torch.device("cuda", torch.cuda.current_device())
+        if dev.type != "cuda":
+            raise RuntimeError("SlidingWindowPredictor runs on the GPU: move the model to the device (no CPU fallback)")
+        self.model, self.dev = model, dev
+        self.cin, self.ncls = int(in_channels), int(num_classes)
+        self.sub_batch, self.graph_mode = int(sub_batch), bool(graph)
+        self.overlap, self.mode = float(overlap), mode
+        self.pad, self.pdims = window_padding(self.image_size, self.roi)
+        self.origins = window_origins(self.image_size, self.roi, overlap)
+        self.n_windows = int(self.origins.shape[0])
+        table = window_table(self.origins, self.sub_batch)
+        self.n_sub = table.shape[0] // self.sub_batch
+        # grid of the blend: the largest union box of one sub-batch's windows
+        ubox = [0, 0, 0]
+        for s in range(self.n_sub):
+            o = self.origins[s * self.sub_batch:(s + 1) * self.sub_batch]
+            for a in range(3):
+                ubox[a] = max(ubox[a], int(o[:, a].max() - o[:, a].min()) + self.roi[a])
+        self.ubox = tuple(ubox)
+        tabs, self.w_floor = importance_tables(self.roi, mode, sigma_scale)
+        self.w = [torch.tensor(t, dtype=torch.float32, device=dev) for t in tabs]
+        self.table = torch.from_numpy(table).to(dev)
+        self.sub_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.xb = torch.zeros((self.sub_batch, self.cin) + self.roi, dtype=torch.float32, device=dev)
+        self.acc = torch.zeros(self.pdims + (self.ncls,), dtype=torch.float32, device=dev)
+        self.wsum = torch.zeros(self.pdims, dtype=torch.float32, device=dev)
+        self.counts = torch.zeros((self.ncls, 3), dtype=torch.int64, device=dev)
+        self._a = dict(dims=_i3(self.image_size), pad=_i3(self.pad), pdims=_i3(self.pdims), roi=_i3(self.roi),
+                       ubox=_i3(self.ubox))
+        self.vol = None          # graph mode: the resident volume the recorded gather reads
+        self.graph = None
+
+    # ------------------------------------------------------------------ per sub-batch launches
+    def _gather(self, vol):
+        a = self._a
+        L.call("mivp_window_gather", L.ptr(vol), C.c_int32(self.cin), a["dims"], a["pad"], a["pdims"], a["roi"],
+               L.ptr(self.table), C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch),
+               L.ptr(self.xb), L.stream())
+
+    def _blend(self, out):
+        if tuple(out.shape) != (self.sub_batch, self.ncls) + self.roi:
+            raise ValueError(f"the model returned {tuple(out.shape)}, expected {(self.sub_batch, self.ncls) + self.roi}")
+        base = out.permute(0, 2, 3, 4, 1)
+        if base.is_contiguous() and out.dtype == torch.float32:
+            src, clast = base, 1
+        else:
+            src, clast = out.float().contiguous(), 0
+        a = self._a
+        L.call("mivp_window_blend", L.ptr(src), C.c_int32(clast), C.c_int32(self.ncls), a["pdims"], a["roi"],
+               L.ptr(self.table), C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch),
+               a["ubox"], L.ptr(self.w[0]), L.ptr(self.w[1]), L.ptr(self.w[2]), C.c_float(self.w_floor),
+               L.ptr(self.acc), L.ptr(self.wsum), L.stream())
+
+    def _step(self, vol):
+        self._gather(vol)
+        out = self.model(self.xb)["downstream"]
+        self._blend(out)
+        L.call("mivp_window_advance", L.ptr(self.sub_idx), L.stream())
+        return out
+
+    def _reset(self):
+        self.acc.zero_()
+        self.wsum.zero_()
+        self.sub_idx.zero_()
+
+    def _record(self):
+        """Warm up two sub-batches eagerly on a side stream, then record one sub-batch step."""
+        side = torch.cuda.Stream(device=self.dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._reset()
+            for _ in range(min(2, self.n_sub)):
+                self._step(self.vol)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._out = self._step(self.vol)
+
+    # ------------------------------------------------------------------ whole volume
+    def _check_input(self, x, name="x", channels=None):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError(f"{name} must be a GPU tensor (no CPU fallback)")
+        if x.dim() != 5 or x.shape[0] != 1:
+            raise ValueError(f"{name} must be [1, C, H, W, D] (one volume at a time), got {tuple(x.shape)}")
+        ch = self.cin if channels is None else channels
+        if tuple(x.shape[1:]) != (ch,) + self.image_size:
+            raise ValueError(f"{name} has shape {tuple(x.shape)}, the predictor was built for {(1, ch) + self.image_size}")
+        if x.device != self.dev:
+            raise ValueError(f"{name} is on {x.device}, the model on {self.dev}")
+
+    @torch.no_grad()
+    def _run(self, x, want_logits, seg):
+        self._check_input(x)
+        if self.graph_mode and self.model.training:
+            raise RuntimeError("graph=True needs the model in eval() mode")
+        vol = x.float().contiguous()
+        if self.graph_mode:
+            if self.vol is None:
+                self.vol = torch.empty_like(vol)
+            self.vol.copy_(vol)
+            if self.graph is None:
+                self._record()
+            self._reset()
+            for _ in range(self.n_sub):
+                self.graph.replay()
+        else:
+            self._reset()
+            for _ in range(self.n_sub):
+                self._step(vol)
+        labels = torch.empty((1, 1) + self.image_size, dtype=torch.uint8, device=self.dev)
+        logits = torch.empty((1, self.ncls) + self.image_size, dtype=torch.float32, device=self.dev) if want_logits else None
+        tgt = None
+        if seg is not None:
+            tgt = seg.float().contiguous()
+            self.counts.zero_()
+        a = self._a
+        L.call("mivp_stitch_finalize", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"], a["pad"],
+               a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(tgt), L.ptr(self.counts if seg is not None else None),
+               L.stream())
+        return labels, logits
+
+    def predict(self, x: torch.Tensor, return_logits: bool = False) -> Dict[str, torch.Tensor]:
+        """``x [1, Cin, H, W, D]`` -> ``{"labels": uint8 [1, 1, H, W, D]}`` (+ ``"logits"``: the blended fp32 logits
+        ``[1, C, H, W, D]``)."""
+        labels, logits = self._run(x, return_logits, None)
+        out = {"labels": labels}
+        if return_logits:
+            out["logits"] = logits
+        return out
+
+    def evaluate(self, x: torch.Tensor, seg: torch.Tensor) -> Tuple[float, float]:
+        """(mean IoU, mean Dice) of the whole-volume prediction against ``seg [1, 1, H, W, D]`` (class indices), with the
+        formulas of ``SegMetrics.compute``; the per-class counts stay in ``self.counts``.  One host read."""
+        self._check_input(seg, "seg", channels=1)
+        self._run(x, False, seg)
+        c = self.counts.to(torch.float64).cpu()
+        inter, psum, tsum = c[:, 0], c[:, 1], c[:, 2]
+        iou = (inter / (psum + tsum - inter + 1e-6)).mean()
+        dice = (2 * inter / (psum + tsum + 1e-6)).mean()
+        return float(iou), float(dice)
+
+
+def predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
+                   mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10, graph: bool = False,
+                   return_logits: bool = False) -> Dict[str, torch.Tensor]:
+    """One-shot ``SlidingWindowPredictor(...).predict(x)`` for ``x [1, Cin, H, W, D]``."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        raise ValueError("x must be a [1, C, H, W, D] tensor")
+    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
+                               graph)
+    return p.predict(x, return_logits)
+
+
+def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
+                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                    graph: bool = False) -> Tuple[float, float]:
+    """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg)``: whole-volume (mean IoU, mean Dice)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        raise ValueError("x must be a [1, C, H, W, D] tensor")
+    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
+                               graph)
+    return p.evaluate(x, seg)

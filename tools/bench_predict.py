@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""Whole-volume sliding-window prediction throughput (mivp_amd.inference.SlidingWindowPredictor), eager against one
+recorded graph per sub-batch, timed on device events after a warm-up volume.  Two shapes:
+  cfg1_96  : the cfg1 model (window 7^3), roi 96^3, a 1x1x256x256x160 volume, overlap 0.5, sub-batch 4
+  yml_128x8: window (8, 8, 4), roi 128x128x8, a 1x1x512x512x96 volume, overlap 0.5, sub-batch 10
+One JSON line per (shape, mode): windows/s, volumes/s, ms per volume, and the algorithmic bytes of gather + blend +
+finalize per volume (from the shapes, below).
+
+Kernel shares come from a run under the kernel tracer:
+    rocprofv3 --kernel-trace --stats -d OUT -o pred -- python tools/bench_predict.py --volumes 2
+then ``python tools/bench_predict.py --stats OUT/.../pred_kernel_stats.csv --volumes 2`` prints the stitching kernels'
+share of kernel time and their bytes / time against 6.3 TB/s (bytes of that run, from the traffic model below)."""
+import argparse
+import csv
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM = 6.3e12
+SHAPES = {
+    "cfg1_96": dict(window=(7, 7, 7), roi=(96, 96, 96), image=(256, 256, 160), sub_batch=4),
+    "yml_128x8": dict(window=(8, 8, 4), roi=(128, 128, 8), image=(512, 512, 96), sub_batch=10),
+}
+NCLS, CIN = 2, 1
+
+
+def traffic(name):
+    """Algorithmic bytes of one predicted volume per kernel family: gather reads and writes every window element of each
+    sub-batch (tail slots included); blend reads the logits of the valid windows and reads + writes the accumulator and
+    weight sum over each sub-batch's union box; finalize reads the accumulator and weight sum of every image voxel and
+    writes one label byte."""
+    import numpy as np
+    from mivp_amd.inference import window_origins
+    s = SHAPES[name]
+    roi, B = s["roi"], s["sub_batch"]
+    rvol = int(np.prod(roi))
+    o = window_origins(s["image"], roi, 0.5)
+    n = o.shape[0]
+    n_sub = -(-n // B)
+    box = 0
+    for k in range(n_sub):
+        w = o[k * B:(k + 1) * B]
+        box += int(np.prod([w[:, a].max() - w[:, a].min() + roi[a] for a in range(3)]))
+    nvox = int(np.prod(s["image"]))
+    return {"windows": n, "sub_batches": n_sub,
+            "gather": 2 * n_sub * B * CIN * rvol * 4,
+            "blend": n * rvol * NCLS * 4 + 2 * box * (NCLS + 1) * 4,
+            "finalize": nvox * ((NCLS + 1) * 4 + 1)}
+
+
+def run(name, volumes, warmup):
+    import torch
+    from mivp_amd import train
+    from mivp_amd.inference import SlidingWindowPredictor
+    from mivp_amd.swin_unetr import SwinUnetR
+    s = SHAPES[name]
+    conf, _, _ = train.make_conf("cfg1", window=s["window"])
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = SwinUnetR(conf).to(dev).eval()
+    x = torch.rand((1, CIN) + s["image"], generator=torch.Generator().manual_seed(1)).to(dev)
+    t = traffic(name)
+    algo = t["gather"] + t["blend"] + t["finalize"]
+    out = []
+    for mode in ("eager", "graph"):
+        p = SlidingWindowPredictor(model, s["image"], CIN, NCLS, s["roi"], overlap=0.5, mode="gaussian",
+                                   sub_batch=s["sub_batch"], graph=(mode == "graph"))
+        for _ in range(warmup):
+            labels = p.predict(x)["labels"]
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(volumes):
+            labels = p.predict(x)["labels"]
+        b.record()
+        torch.cuda.synchronize()
+        ms = a.elapsed_time(b) / volumes
+        out.append({"shape": name, "mode": mode, "image": list(s["image"]), "roi": list(s["roi"]),
+                    "sub_batch": s["sub_batch"], "windows": t["windows"], "ms_per_volume": round(ms, 3),
+                    "volumes_per_s": round(1e3 / ms, 3), "windows_per_s": round(t["windows"] * 1e3 / ms, 1),
+                    "stitch_bytes_per_volume": algo, "label_hist": torch.bincount(labels.reshape(-1).long()).tolist()})
+        del p
+        torch.cuda.empty_cache()
+    return out
+
+
+def stats(path, volumes, warmup):
+    """Share of kernel time and bytes / time of the stitching kernels in a profiled run of both shapes."""
+    fam = {"gather": "k_window_gather", "blend": "k_window_blend", "finalize": "k_stitch_finalize",
+           "advance": "k_window_advance"}
+    total_ns, fam_ns, fam_calls = 0.0, {k: 0.0 for k in fam}, {k: 0 for k in fam}
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            ns = float(row.get("TotalDurationNs", 0) or 0)
+            total_ns += ns
+            for k, kname in fam.items():
+                if kname in row.get("Name", ""):
+                    fam_ns[k] += ns
+                    fam_calls[k] += int(row.get("Calls", 0) or 0)
+    # predicts per shape and mode: warm-up + timed volumes; graph recording adds two eager sub-batches (not counted)
+    nvol = 2 * (volumes + warmup)
+    byts = {k: 0 for k in ("gather", "blend", "finalize")}
+    for name in SHAPES:
+        t = traffic(name)
+        for k in byts:
+            byts[k] += nvol * t[k]
+    for k in fam:
+        line = {"kernel": fam[k], "calls": fam_calls[k], "total_ms": round(fam_ns[k] / 1e6, 3),
+                "share_pct": round(100 * fam_ns[k] / total_ns, 3) if total_ns else None}
+        if k in byts and fam_ns[k] > 0:
+            line["bytes"] = byts[k]
+            line["TB_per_s"] = round(byts[k] / fam_ns[k] / 1e3, 3)
+            line["of_6.3TBps"] = round(byts[k] / fam_ns[k] * 1e9 / HBM, 3)
+        print(json.dumps(line))
+    st = sum(fam_ns.values())
+    print(json.dumps({"stitch_share_of_kernel_time_pct": round(100 * st / total_ns, 3) if total_ns else None,
+                      "stitch_vs_rest_pct": round(100 * st / (total_ns - st), 3) if total_ns > st else None}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--volumes", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--shape", choices=list(SHAPES) + ["all"], default="all")
+    ap.add_argument("--stats", help="kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of this tool (all shapes)")
+    a = ap.parse_args()
+    import mivp_amd  # noqa: F401
+    if a.stats:
+        stats(a.stats, a.volumes, a.warmup)
+        return
+    for name in (SHAPES if a.shape == "all" else [a.shape]):
+        try:
+            lines = run(name, a.volumes, a.warmup)
+        except (RuntimeError, ValueError) as exc:                # a shape the model cannot run: say so, go on
+            lines = [{"shape": name, "error": str(exc)[:300]}]
+        for line in lines:
+            print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
