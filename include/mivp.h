@@ -673,6 +673,29 @@ int mivp_stitch_finalize(const float* acc, const float* wsum, int32_t C, const i
                          mivp_stream_t stream);
 int mivp_window_advance(int32_t* sub_idx, mivp_stream_t stream);
 
+/* Surface-distance metrics (ABI 15, csrc/surface.hip; mivp_amd/surface.py).  dims = {H, W, D} (host), volumes
+ * [H][W][D] row-major, fewer than 2^31 voxels.
+ *   mivp_surface_map: pred / target class maps (dtype 0 uint8, 1 int32, 2 int64, 3 float32; values outside [0, C) and
+ *     non-integer floats belong to no class) -> surf uint8 [H][W][D]: the class on surface voxels (in the class, with a
+ *     6-neighbour outside it or outside the volume), 255 elsewhere.  target / surf_target may both be NULL.  counts int64
+ *     [C][2] (pred, target) += surface voxels per class when non-NULL.  C <= 16.
+ *   mivp_edt_sq: out f32 [H][W][D] = squared Euclidean distance (spacing: host f32 {s0, s1, s2} mm per voxel, > 0) to the
+ *     nearest voxel with seeds == cls, +inf when there is none.  Exact integers when spacing == (1, 1, 1).  H, W <= 65535.
+ *     workspace: mivp_edt_ws(dims) bytes, reused by every call in stream order.
+ *   mivp_surface_stats: statistics of dist_sq sampled at {sampled == cls}, whose size *count (DEVICE int64) is:
+ *     record int64 [8] = n, max key, #{sqrt(d2) <= tau}, bits of the float64 sum of sqrt(d2), key at rank lo, key at
+ *     rank hi, lo, hi; keys are the bits of the float32 d2, lo / hi the ranks numpy.percentile(method="linear") reads
+ *     for the quantile q in [0, 1] (virtual index (n - 1) q).  Fields 4-5 are untouched when n == 0.  No float atomics:
+ *     bitwise reproducible.  workspace: mivp_surface_stats_ws(dims) bytes (zeroed by the call). */
+int mivp_surface_map(const void* pred, const void* target, int32_t dtype, int32_t C, const int32_t* dims, uint8_t* surf_pred,
+                     uint8_t* surf_target, void* counts, mivp_stream_t stream);
+size_t mivp_edt_ws(const int32_t* dims);
+int mivp_edt_sq(const uint8_t* seeds, int32_t cls, const int32_t* dims, const float* spacing, float* out, void* workspace,
+                mivp_stream_t stream);
+size_t mivp_surface_stats_ws(const int32_t* dims);
+int mivp_surface_stats(const uint8_t* sampled, int32_t cls, const float* dist_sq, const int32_t* dims, const int64_t* count,
+                       double q, double tau, void* workspace, int64_t* record, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -383,6 +383,28 @@ class SlidingWindowPredictor:
         dice = (2 * inter / (psum + tsum + 1e-6)).mean()
         return float(iou), float(dice)
 
+    def evaluate_surface(self, x: torch.Tensor, seg: torch.Tensor, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                         percentile: float = 95.0, tolerance: float = 1.0,
+                         include_background: bool = False) -> Dict[str, object]:
+        """Surface-distance metrics of the whole-volume prediction against ``seg [1, 1, H, W, D]``: the dict of
+        ``mivp_amd.surface.surface_metrics(predict(x)["labels"], seg, ...)`` plus ``"iou"`` / ``"dice"``, the values
+        ``evaluate`` returns, from the same finalize launch.  One host read for all of them."""
+        from . import surface as S
+        self._check_input(seg, "seg", channels=1)
+        ncls, sp, pc, tol = S._check_metric_args(self.ncls, spacing, percentile, tolerance)
+        labels, _ = self._run(x, False, seg)
+        scount, recs = S._metrics_launch(labels, seg, ncls, sp, pc, tol, include_background)
+        host = torch.cat([self.counts.reshape(-1), scount.reshape(-1), recs.reshape(-1)]).cpu()
+        c = host[:3 * ncls].reshape(ncls, 3).to(torch.float64)
+        inter, psum, tsum = c[:, 0], c[:, 1], c[:, 2]
+        iou = (inter / (psum + tsum - inter + 1e-6)).mean()
+        dice = (2 * inter / (psum + tsum + 1e-6)).mean()
+        rest = host[3 * ncls:].numpy()
+        out = S._metrics_finish(rest[:2 * ncls].reshape(ncls, 2), rest[2 * ncls:].reshape(ncls, 2, S._REC), ncls, pc,
+                                include_background)
+        out["iou"], out["dice"] = float(iou), float(dice)
+        return out
+
 
 def predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10, graph: bool = False,
@@ -404,3 +426,15 @@ def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
                                graph)
     return p.evaluate(x, seg)
+
+
+def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
+                            overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                            graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0), percentile: float = 95.0,
+                            tolerance: float = 1.0, include_background: bool = False) -> Dict[str, object]:
+    """One-shot ``SlidingWindowPredictor(...).evaluate_surface(x, seg, ...)``: whole-volume surface metrics + IoU / Dice."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        raise ValueError("x must be a [1, C, H, W, D] tensor")
+    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
+                               graph)
+    return p.evaluate_surface(x, seg, spacing, percentile, tolerance, include_background)
