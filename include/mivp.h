@@ -696,6 +696,28 @@ size_t mivp_surface_stats_ws(const int32_t* dims);
 int mivp_surface_stats(const uint8_t* sampled, int32_t cls, const float* dist_sq, const int32_t* dims, const int64_t* count,
                        double q, double tau, void* workspace, int64_t* record, mivp_stream_t stream);
 
+/* Connected components (ABI 16, csrc/components.hip; mivp_amd/components.py).  dims = {H, W, D} (host), volumes
+ * [H][W][D] row-major, fewer than 2^31 voxels; x dtype as mivp_surface_map (0 uint8, 1 int32, 2 int64, 3 float32).
+ * connectivity 6, 18 or 26: scipy.ndimage.generate_binary_structure(3, 1 / 2 / 3).  Adjacent voxels are joined when
+ * both take part and hold the same value.  Exact integer arithmetic, bitwise reproducible, no host synchronisation.
+ *   mivp_label_components: every nonzero voxel takes part.  labels int32 [H][W][D] = 0 on background, else 1 + the rank
+ *     of the component's first voxel (raster order) among all components' first voxels (scipy.ndimage.label's
+ *     numbering); *n_out (DEVICE int32) = the number of components.  workspace: mivp_label_ws(dims) bytes.
+ *   mivp_postprocess_labels: the voxels whose class (value in [0, C), integer for floats) is a set bit of class_mask
+ *     (bits 1..C-1 only, not empty) take part.  A component is kept iff its size >= min_size and, when largest, it is the
+ *     largest of its class (ties: the one whose first voxel comes first in raster order); out (same dtype as x, may be x)
+ *     = x with the voxels of removed components set to 0, every other voxel unchanged.  largest = 0 needs min_size > 0.
+ *     When target f32 [H][W][D] is non-NULL, counts int64 [C][3] += (inter, pred, target) of out against it, as
+ *     mivp_stitch_finalize.  C <= 16.  workspace: mivp_postprocess_ws(dims) bytes (8 per voxel + 256), reused by every
+ *     call in stream order. */
+size_t mivp_label_ws(const int32_t* dims);
+int mivp_label_components(const void* x, int32_t dtype, const int32_t* dims, int32_t connectivity, int32_t* labels,
+                          int32_t* n_out, void* workspace, mivp_stream_t stream);
+size_t mivp_postprocess_ws(const int32_t* dims);
+int mivp_postprocess_labels(const void* x, int32_t dtype, const int32_t* dims, int32_t C, uint32_t class_mask,
+                            int64_t min_size, int32_t largest, int32_t connectivity, void* out, const float* target,
+                            void* counts, void* workspace, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

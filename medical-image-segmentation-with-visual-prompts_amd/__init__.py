@@ -14,7 +14,8 @@ __all__ = ["_lib", "geometry"]
 
 def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
-    if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface"):
+    if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
+                "components"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -26,4 +27,7 @@ def __getattr__(name):
     if name in ("surface_map", "distance_transform_sq", "surface_metrics"):
         from . import surface
         return getattr(surface, name)
+    if name in ("label_components", "postprocess_labels"):
+        from . import components
+        return getattr(components, name)
     raise AttributeError(name)

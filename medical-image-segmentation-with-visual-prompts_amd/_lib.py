@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmivp_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 i32, f32, vp, i64 = C.c_int32, C.c_float, C.c_void_p, C.c_int64
 
@@ -75,6 +75,8 @@ def lib():
         _lib.mivp_uphead_fwd_ws.restype = C.c_size_t
         _lib.mivp_edt_ws.restype = C.c_size_t
         _lib.mivp_surface_stats_ws.restype = C.c_size_t
+        _lib.mivp_label_ws.restype = C.c_size_t
+        _lib.mivp_postprocess_ws.restype = C.c_size_t
         ver = _lib.mivp_abi_version()
         if ver != ABI_VERSION:
             raise RuntimeError(f"mivp_amd: ABI version mismatch: library {ver}, binding {ABI_VERSION}")

@@ -256,6 +256,14 @@ static inline unsigned fixed_group_grid(long items, int G, long cap) {
     return (unsigned)blocks;
 }
 
+// class index of a label-map value (surface.hip, components.hip): -1 for values outside [0, C) (and non-integers / NaN
+// for float maps)
+template <typename T> MIVP_DEV int class_of(T v, int C) { return (v >= 0 && v < (T)C) ? (int)v : -1; }
+template <> MIVP_DEV int class_of<uint8_t>(uint8_t v, int C) { return (int)v < C ? (int)v : -1; }
+template <> MIVP_DEV int class_of<float>(float v, int C) {
+    return (v >= 0.f && v < (float)C && v == floorf(v)) ? (int)v : -1;
+}
+
 // error plumbing shared by the C-ABI translation units
 void mivp_set_error(const char* msg);
 int mivp_check_launch(const char* what);

@@ -32,13 +32,6 @@ constexpr int SAMPLE_VOX = 32768;   // voxels per sampling workgroup: bounds a 1
 constexpr int NO_SEED = 1 << 29;
 constexpr int UNROLL = 8;
 
-// a class index, or -1 for values outside [0, C) (and non-integers / NaN for float maps)
-template <typename T> MIVP_DEV int class_of(T v, int C) { return (v >= 0 && v < (T)C) ? (int)v : -1; }
-template <> MIVP_DEV int class_of<uint8_t>(uint8_t v, int C) { return (int)v < C ? (int)v : -1; }
-template <> MIVP_DEV int class_of<float>(float v, int C) {
-    return (v >= 0.f && v < (float)C && v == floorf(v)) ? (int)v : -1;
-}
-
 // one thread per voxel of both maps: class id on surface voxels (6-neighbourhood, the outside counts as background),
 // 255 elsewhere; per-class counts summed in LDS, one integer atomic per (class, map) and workgroup
 template <typename T>

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -272,6 +272,7 @@ class SlidingWindowPredictor:
                        ubox=_i3(self.ubox))
         self.vol = None          # graph mode: the resident volume the recorded gather reads
         self.graph = None
+        self.cc_ws = None        # post-processing workspace (8 bytes per voxel), allocated on first use
 
     # ------------------------------------------------------------------ per sub-batch launches
     def _gather(self, vol):
@@ -333,7 +334,7 @@ class SlidingWindowPredictor:
             raise ValueError(f"{name} is on {x.device}, the model on {self.dev}")
 
     @torch.no_grad()
-    def _run(self, x, want_logits, seg):
+    def _run(self, x, want_logits, seg, post=None):
         self._check_input(x)
         if self.graph_mode and self.model.training:
             raise RuntimeError("graph=True needs the model in eval() mode")
@@ -358,25 +359,44 @@ class SlidingWindowPredictor:
             tgt = seg.float().contiguous()
             self.counts.zero_()
         a = self._a
-        L.call("mivp_stitch_finalize", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"], a["pad"],
-               a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(tgt), L.ptr(self.counts if seg is not None else None),
-               L.stream())
+        counts = self.counts if seg is not None else None
+        if post is None:
+            L.call("mivp_stitch_finalize", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"], a["pad"],
+                   a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(tgt), L.ptr(counts), L.stream())
+        else:
+            # the post-processing rewrites the labels in place; its filter pass, not the finalize, counts them against seg
+            from . import components
+            L.call("mivp_stitch_finalize", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"], a["pad"],
+                   a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(None), L.ptr(None), L.stream())
+            lab = labels[0, 0]
+            self.cc_ws = components._postprocess_launch(lab, lab, post, self.cc_ws,
+                                                        tgt[0, 0] if tgt is not None else None, counts)
         return labels, logits
 
-    def predict(self, x: torch.Tensor, return_logits: bool = False) -> Dict[str, torch.Tensor]:
+    def _post(self, postprocess):
+        from . import components
+        return components.postprocess_kwargs(postprocess, self.ncls)
+
+    def predict(self, x: torch.Tensor, return_logits: bool = False,
+                postprocess: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
         """``x [1, Cin, H, W, D]`` -> ``{"labels": uint8 [1, 1, H, W, D]}`` (+ ``"logits"``: the blended fp32 logits
-        ``[1, C, H, W, D]``)."""
-        labels, logits = self._run(x, return_logits, None)
+        ``[1, C, H, W, D]``).  ``postprocess``: a dict of ``mivp_amd.components.postprocess_labels`` keyword arguments
+        (``largest``, ``min_size``, ``classes``, ``connectivity``) applied to the labels on the device; ``"logits"``
+        stays the blend before post-processing."""
+        post = self._post(postprocess)
+        labels, logits = self._run(x, return_logits, None, post)
         out = {"labels": labels}
         if return_logits:
             out["logits"] = logits
         return out
 
-    def evaluate(self, x: torch.Tensor, seg: torch.Tensor) -> Tuple[float, float]:
+    def evaluate(self, x: torch.Tensor, seg: torch.Tensor, postprocess: Optional[Dict] = None) -> Tuple[float, float]:
         """(mean IoU, mean Dice) of the whole-volume prediction against ``seg [1, 1, H, W, D]`` (class indices), with the
-        formulas of ``SegMetrics.compute``; the per-class counts stay in ``self.counts``.  One host read."""
+        formulas of ``SegMetrics.compute``; the per-class counts stay in ``self.counts``.  One host read.  With
+        ``postprocess`` (as in ``predict``) the counts are those of the post-processed labels."""
+        post = self._post(postprocess)
         self._check_input(seg, "seg", channels=1)
-        self._run(x, False, seg)
+        self._run(x, False, seg, post)
         c = self.counts.to(torch.float64).cpu()
         inter, psum, tsum = c[:, 0], c[:, 1], c[:, 2]
         iou = (inter / (psum + tsum - inter + 1e-6)).mean()
@@ -384,15 +404,17 @@ class SlidingWindowPredictor:
         return float(iou), float(dice)
 
     def evaluate_surface(self, x: torch.Tensor, seg: torch.Tensor, spacing: Sequence[float] = (1.0, 1.0, 1.0),
-                         percentile: float = 95.0, tolerance: float = 1.0,
-                         include_background: bool = False) -> Dict[str, object]:
+                         percentile: float = 95.0, tolerance: float = 1.0, include_background: bool = False,
+                         postprocess: Optional[Dict] = None) -> Dict[str, object]:
         """Surface-distance metrics of the whole-volume prediction against ``seg [1, 1, H, W, D]``: the dict of
         ``mivp_amd.surface.surface_metrics(predict(x)["labels"], seg, ...)`` plus ``"iou"`` / ``"dice"``, the values
-        ``evaluate`` returns, from the same finalize launch.  One host read for all of them."""
+        ``evaluate`` returns, from the same finalize launch.  One host read for all of them.  With ``postprocess`` (as in
+        ``predict``) every value describes the post-processed labels."""
         from . import surface as S
+        post = self._post(postprocess)
         self._check_input(seg, "seg", channels=1)
         ncls, sp, pc, tol = S._check_metric_args(self.ncls, spacing, percentile, tolerance)
-        labels, _ = self._run(x, False, seg)
+        labels, _ = self._run(x, False, seg, post)
         scount, recs = S._metrics_launch(labels, seg, ncls, sp, pc, tol, include_background)
         host = torch.cat([self.counts.reshape(-1), scount.reshape(-1), recs.reshape(-1)]).cpu()
         c = host[:3 * ncls].reshape(ncls, 3).to(torch.float64)
@@ -408,33 +430,34 @@ class SlidingWindowPredictor:
 
 def predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10, graph: bool = False,
-                   return_logits: bool = False) -> Dict[str, torch.Tensor]:
-    """One-shot ``SlidingWindowPredictor(...).predict(x)`` for ``x [1, Cin, H, W, D]``."""
+                   return_logits: bool = False, postprocess: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
+    """One-shot ``SlidingWindowPredictor(...).predict(x, return_logits, postprocess)`` for ``x [1, Cin, H, W, D]``."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
                                graph)
-    return p.predict(x, return_logits)
+    return p.predict(x, return_logits, postprocess)
 
 
 def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
                     mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                    graph: bool = False) -> Tuple[float, float]:
-    """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg)``: whole-volume (mean IoU, mean Dice)."""
+                    graph: bool = False, postprocess: Optional[Dict] = None) -> Tuple[float, float]:
+    """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg, postprocess)``: whole-volume (mean IoU, mean Dice)."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
                                graph)
-    return p.evaluate(x, seg)
+    return p.evaluate(x, seg, postprocess)
 
 
 def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0), percentile: float = 95.0,
-                            tolerance: float = 1.0, include_background: bool = False) -> Dict[str, object]:
+                            tolerance: float = 1.0, include_background: bool = False,
+                            postprocess: Optional[Dict] = None) -> Dict[str, object]:
     """One-shot ``SlidingWindowPredictor(...).evaluate_surface(x, seg, ...)``: whole-volume surface metrics + IoU / Dice."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
                                graph)
-    return p.evaluate_surface(x, seg, spacing, percentile, tolerance, include_background)
+    return p.evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)
