@@ -718,6 +718,37 @@ int mivp_postprocess_labels(const void* x, int32_t dtype, const int32_t* dims, i
                             int64_t min_size, int32_t largest, int32_t connectivity, void* out, const float* target,
                             void* counts, void* workspace, mivp_stream_t stream);
 
+/* Scan preparation and native-grid restore (ABI 17, csrc/scan.hip; mivp_amd/scan.py).  Every entry is one launch of a
+ * resample-gather from a source grid src_dims = {m0, m1, m2} to an output grid out_dims = {k0, k1, k2} (host arrays, both
+ * row-major, fewer than 2^31 voxels each): output axis a walks source axis axes[a] (host array, a permutation of 0..2).
+ * tables: DEVICE int32 [3][K], K = k0 + k1 + k2, output axis a at offset k0 + .. + k(a-1) of each section; section 0 = the
+ * lower source index per output index, section 1 = the upper one, section 2 = the bits of the fp32 weight of the upper one
+ * (flips and the resize are folded into them; indices are clamped to the source axis).  A pure gather (interp = 0, and the
+ * label entries always) reads section 0 only, and tables may then be int32 [K].  dtype: 0 uint8, 1 int32, 3 float32 (as
+ * mivp_label_components), 4 int16.  When output axis 2 does not walk source axis 2, mivp_scan_prepare stages tiles through
+ * LDS and the other three read directly (what measured faster); flags bit 0 forces direct reads, bit 1 staging (same bits
+ * either way).  No workspace, no host synchronisation.
+ *   mivp_scan_prepare: raw [C][m0][m1][m2] (C <= 4) -> out f32 [C][k0][k1][k2].  Per SOURCE voxel
+ *     v = fma(x, map[0], map[1]), clamped to [map[2], map[3]] when clip (map: host f32 [4]); then with interp the blend
+ *     fma(w, hi - lo, lo) along output axis 2, then 1, then 0 (torch trilinear, align_corners = False, when the tables say
+ *     so); without interp out = v at the section-0 tap, exactly.
+ *   mivp_scan_prepare_labels: seg [m0][m1][m2] -> out uint8 [k0][k1][k2], nearest.  A value outside 0..255 or a
+ *     non-integer float writes 0 and sets bad[0] = 1 (DEVICE int32, zeroed by the caller).
+ *   mivp_scan_restore_labels: the same gather for uint8 labels (no range to check).
+ *   mivp_scan_restore_argmax: logits f32 [C][m0][m1][m2] (C <= 16) -> out uint8 [k0][k1][k2] = the first arg-max over the
+ *     classes of the blended logits (as mivp_stitch_finalize breaks ties); the output-size logits are never stored. */
+int mivp_scan_prepare(const void* raw, int32_t dtype, int32_t C, const int32_t* src_dims, const int32_t* out_dims,
+                      const int32_t* axes, const int32_t* tables, int32_t interp, const float* map, int32_t clip,
+                      int32_t flags, float* out, mivp_stream_t stream);
+int mivp_scan_prepare_labels(const void* seg, int32_t dtype, const int32_t* src_dims, const int32_t* out_dims,
+                             const int32_t* axes, const int32_t* tables, int32_t flags, uint8_t* out, int32_t* bad,
+                             mivp_stream_t stream);
+int mivp_scan_restore_labels(const uint8_t* labels, const int32_t* src_dims, const int32_t* out_dims, const int32_t* axes,
+                             const int32_t* tables, int32_t flags, uint8_t* out, mivp_stream_t stream);
+int mivp_scan_restore_argmax(const float* logits, int32_t C, const int32_t* src_dims, const int32_t* out_dims,
+                             const int32_t* axes, const int32_t* tables, int32_t interp, int32_t flags, uint8_t* out,
+                             mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,13 +15,14 @@ __all__ = ["_lib", "geometry"]
 def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
-                "components"):
+                "components", "scan"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
         from .swin_unetr import SwinUnetR
         return SwinUnetR
-    if name in ("SlidingWindowPredictor", "predict_volume", "evaluate_volume", "evaluate_volume_surface"):
+    if name in ("SlidingWindowPredictor", "predict_volume", "evaluate_volume", "evaluate_volume_surface",
+                "predict_scan_volume"):
         from . import inference
         return getattr(inference, name)
     if name in ("surface_map", "distance_transform_sq", "surface_metrics"):
@@ -30,4 +31,7 @@ def __getattr__(name):
     if name in ("label_components", "postprocess_labels"):
         from . import components
         return getattr(components, name)
+    if name in ("ScanGeometry", "prepare_scan", "prepare_labels", "restore_labels", "restore_labels_from_logits"):
+        from . import scan
+        return getattr(scan, name)
     raise AttributeError(name)

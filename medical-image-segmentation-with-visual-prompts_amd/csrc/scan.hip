@@ -1,0 +1,357 @@
+// Scan preparation and native-grid restore around whole-volume prediction (ABI 17, mivp_amd/scan.py).
+//
+// All four entries are one "resample-gather": out[k0][k1][k2] = F(src at the taps of (k0, k1, k2)).  Output axis a walks
+// ONE source axis, axes[a] (a permutation), through per-axis tables built on the host:
+//     tables int32 [3][K], K = k0 + k1 + k2, axis a at offset k0 + .. + k(a-1) of each section:
+//       section 0: lower source index, section 1: upper source index, section 2: bits of the fp32 weight of the upper one.
+// Flips, the resize and its rounding all live in the tables; a pure gather (interp = 0) reads section 0 only.
+//   image   (prepare):          v = clip(fma(x, scale, shift)) per SOURCE voxel, then the eight-point blend
+//   labels  (prepare / restore): nearest, uint8 out; a value outside 0..255 (or a non-integer float) sets *bad
+//   arg-max (restore):          the blend of every class, first maximum wins; the resized logits are never stored
+// The blend is three levels of fma(w, hi - lo, lo): output axis 2 first, then 1, then 0, in both read paths below, so
+// they give the same bits.
+//
+// Two read paths.  When output axis 2 walks the source's innermost axis, rows are read directly (k_scan_direct: adjacent
+// lanes read adjacent -- or, flipped, reversed -- source elements and write adjacent outputs).  When it walks another
+// axis, direct reads are one element per 2-4 KB stride; k_scan_staged then takes a tile of (output axis b that walks the
+// source's innermost axis) x (output axis 2), loads the tile's source footprint row by row along the source's innermost
+// axis into LDS (the value map applied once per source voxel), and blends out of LDS with lanes along output axis 2: both
+// the global reads and the global writes are contiguous runs.  Every table index is clamped to its axis before use.
+#include "common.hpp"
+#include <limits.h>
+
+namespace {
+constexpr int TPB = 256;
+constexpr int MAXC = 16;
+constexpr int T2 = 64;              // staged tile: outputs along output axis 2 (one per lane)
+constexpr int TBMAX = 64;           // staged tile: outputs along output axis b (TBMAX / 4 per thread)
+constexpr int TBMAX_ARGMAX = 32;    // arg-max keeps a running (value, class) per output: half the tile, half the registers
+constexpr int LDS_CAP = 12288;      // floats of staging (48 KB: three workgroups per CU)
+
+enum { MODE_IMAGE = 0, MODE_LABELS = 1, MODE_ARGMAX = 2 };
+
+struct Plan {
+    int m[3];       // source size
+    int k[3];       // output size
+    int sn[3];      // size of the source axis that output axis a walks
+    long ss[3];     // its stride in elements
+    int off[3];     // offset of output axis a inside a table section
+    int K;          // section length
+    int b, c;       // staged path: the output axis (0 or 1) that walks source axis 2, and the other one
+    long msz;       // source voxels per channel
+    long nvox;      // output voxels per channel
+};
+
+struct Map { float s, t, lo, hi; int clip; };
+
+struct Taps { long ol[3], oh[3]; float w[3]; };
+
+__device__ inline int clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+__device__ inline float lerp(float a, float b, float w) { return fmaf(w, b - a, a); }
+
+template <int MODE, typename T>
+__device__ inline float value(const T* __restrict__ p, long i, const Map& mp, int& bad) {
+    const float f = (float)p[i];
+    if (MODE == MODE_IMAGE) {
+        float y = fmaf(f, mp.s, mp.t);
+        if (mp.clip) y = y < mp.lo ? mp.lo : (y > mp.hi ? mp.hi : y);     // a NaN stays a NaN
+        return y;
+    }
+    if (MODE == MODE_LABELS) {
+        const bool ok = f >= 0.f && f <= 255.f && f == truncf(f);
+        if (!ok) bad = 1;
+        return ok ? f : 0.f;
+    }
+    return f;
+}
+
+template <bool INTERP>
+__device__ inline Taps get_taps(const Plan& P, const int* __restrict__ tab, int k0, int k1, int k2) {
+    const int kk[3] = {k0, k1, k2};
+    Taps t;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int e = P.off[a] + kk[a];
+        t.ol[a] = (long)clampi(tab[e], P.sn[a]) * P.ss[a];
+        t.oh[a] = t.ol[a];
+        t.w[a] = 0.f;
+        if (INTERP) {
+            t.oh[a] = (long)clampi(tab[P.K + e], P.sn[a]) * P.ss[a];
+            t.w[a] = __int_as_float(tab[2 * P.K + e]);
+        }
+    }
+    return t;
+}
+
+template <int MODE, typename T, bool INTERP>
+__device__ inline float sample(const T* __restrict__ src, const Taps& t, const Map& mp, int& bad) {
+    if (!INTERP) return value<MODE>(src, t.ol[0] + t.ol[1] + t.ol[2], mp, bad);
+    float y[2];
+#pragma unroll
+    for (int s0 = 0; s0 < 2; ++s0) {
+        const long o0 = s0 ? t.oh[0] : t.ol[0];
+        float x[2];
+#pragma unroll
+        for (int s1 = 0; s1 < 2; ++s1) {
+            const long o1 = o0 + (s1 ? t.oh[1] : t.ol[1]);
+            x[s1] = lerp(value<MODE>(src, o1 + t.ol[2], mp, bad), value<MODE>(src, o1 + t.oh[2], mp, bad), t.w[2]);
+        }
+        y[s0] = lerp(x[0], x[1], t.w[1]);
+    }
+    return lerp(y[0], y[1], t.w[0]);
+}
+
+// one thread = one output voxel (image: of channel blockIdx.y)
+template <int MODE, typename T, bool INTERP>
+__global__ __launch_bounds__(TPB) void k_scan_direct(const T* __restrict__ src, Plan P, const int* __restrict__ tab, Map mp,
+                                                     int Cn, void* __restrict__ out, int* __restrict__ flag) {
+    const long t = (long)blockIdx.x * TPB + threadIdx.x;
+    if (t >= P.nvox) return;
+    const int k2 = (int)(t % P.k[2]);
+    const long r = t / P.k[2];
+    const int k1 = (int)(r % P.k[1]);
+    const int k0 = (int)(r / P.k[1]);
+    const Taps tp = get_taps<INTERP>(P, tab, k0, k1, k2);
+    int bad = 0;
+    if (MODE == MODE_IMAGE) {
+        const int ch = blockIdx.y;
+        static_cast<float*>(out)[(long)ch * P.nvox + t] = sample<MODE, T, INTERP>(src + (long)ch * P.msz, tp, mp, bad);
+    } else if (MODE == MODE_LABELS) {
+        static_cast<uint8_t*>(out)[t] = (uint8_t)sample<MODE, T, false>(src, tp, mp, bad);
+        if (bad && flag) flag[0] = 1;
+    } else {
+        int best = 0;
+        float bv = 0.f;
+        for (int ch = 0; ch < Cn; ++ch) {
+            const float x = sample<MODE, T, INTERP>(src + (long)ch * P.msz, tp, mp, bad);
+            if (ch == 0 || x > bv) { bv = x; best = ch; }         // first maximum, like mivp_stitch_finalize
+        }
+        static_cast<uint8_t*>(out)[t] = (uint8_t)best;
+    }
+}
+
+// one workgroup = a tile of TB (output axis b) x T2 (output axis 2) outputs at one index of output axis c (blockIdx.y);
+// image: of channel blockIdx.z.  A tile whose footprint does not fit the staging buffer reads directly.
+template <int MODE, typename T, bool INTERP>
+__global__ __launch_bounds__(TPB) void k_scan_staged(const T* __restrict__ src, Plan P, const int* __restrict__ tab, Map mp,
+                                                     int Cn, int TB, void* __restrict__ out, int* __restrict__ flag) {
+    __shared__ float S[LDS_CAP];
+    __shared__ int rng[4];                                        // min / max source index along b, along axis 2
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b = P.b, c = P.c;
+    const int tiles2 = (P.k[2] + T2 - 1) / T2;
+    const int k20 = (int)(blockIdx.x % tiles2) * T2, kb0 = (int)(blockIdx.x / tiles2) * TB;
+    const int kc = blockIdx.y;
+    const int n2 = min(T2, P.k[2] - k20), nb = min(TB, P.k[b] - kb0);
+    if (tid == 0) { rng[0] = INT_MAX; rng[1] = -1; rng[2] = INT_MAX; rng[3] = -1; }
+    __syncthreads();
+    if (wv < 2) {                                                 // wave 0: axis b, wave 1: axis 2
+        const int a = wv ? 2 : b;
+        if (lane < (wv ? n2 : nb)) {
+            const int e = P.off[a] + (wv ? k20 : kb0) + lane;
+            const int l = clampi(tab[e], P.sn[a]);
+            const int h = INTERP ? clampi(tab[P.K + e], P.sn[a]) : l;
+            atomicMin(&rng[2 * wv], min(l, h));
+            atomicMax(&rng[2 * wv + 1], max(l, h));
+        }
+    }
+    __syncthreads();
+    const int lob = rng[0], lenb = rng[1] - lob + 1, lo2 = rng[2], len2 = rng[3] - lo2 + 1;
+    const int np = INTERP ? 2 : 1;
+    const int pitch = lenb | 1;                                   // odd: lanes along axis 2 read distinct banks
+    const bool fits = (long)np * len2 * pitch <= LDS_CAP;
+    int pc[2];
+    pc[0] = clampi(tab[P.off[c] + kc], P.sn[c]);
+    pc[1] = INTERP ? clampi(tab[P.K + P.off[c] + kc], P.sn[c]) : pc[0];
+    const float wc = INTERP ? __int_as_float(tab[2 * P.K + P.off[c] + kc]) : 0.f;
+    // this lane's taps along axis 2 (rows of the staging buffer)
+    int r2[2] = {0, 0};
+    float w2 = 0.f;
+    if (lane < n2) {
+        const int e = P.off[2] + k20 + lane;
+        r2[0] = (clampi(tab[e], P.sn[2]) - lo2) * pitch;
+        r2[1] = INTERP ? (clampi(tab[P.K + e], P.sn[2]) - lo2) * pitch : r2[0];
+        if (INTERP) w2 = __int_as_float(tab[2 * P.K + e]);
+    }
+    constexpr int NI = (MODE == MODE_ARGMAX ? TBMAX_ARGMAX : TBMAX) / 4;
+    float bv[MODE == MODE_ARGMAX ? NI : 1];
+    int bi[MODE == MODE_ARGMAX ? NI : 1];
+    int bad = 0;
+    const int ch0 = MODE == MODE_IMAGE ? (int)blockIdx.z : 0;
+    const int ch1 = MODE == MODE_ARGMAX ? Cn : ch0 + 1;
+    for (int ch = ch0; ch < ch1; ++ch) {
+        const T* __restrict__ srcc = src + (long)ch * P.msz;
+        if (fits) {
+            if (ch != ch0) __syncthreads();                       // the previous class has been read
+            for (int row = wv; row < np * len2; row += TPB / 64) {
+                const int p = row >= len2 ? 1 : 0;
+                const long base = (long)pc[p] * P.ss[c] + (long)(lo2 + row - p * len2) * P.ss[2] + lob;
+                for (int q = lane; q < lenb; q += 64) S[row * pitch + q] = value<MODE>(srcc, base + q, mp, bad);
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int jb = wv + 4 * i;                            // uniform per wave
+            if (jb >= nb || lane >= n2) continue;
+            const int kb = kb0 + jb, k2 = k20 + lane;
+            const int k0 = b == 0 ? kb : kc, k1 = b == 0 ? kc : kb;
+            float v;
+            if (fits) {
+                const int e = P.off[b] + kb;
+                const int qb0 = clampi(tab[e], P.sn[b]) - lob;
+                if (!INTERP) {
+                    v = S[r2[0] + qb0];
+                } else {
+                    const int qb1 = clampi(tab[P.K + e], P.sn[b]) - lob;
+                    const float wb = __int_as_float(tab[2 * P.K + e]);
+                    const int pl = len2 * pitch;
+                    // x[sc][sb] after the axis-2 level; then axis 1 and axis 0 in that order, whichever of them is b
+                    float x[2][2];
+#pragma unroll
+                    for (int sc = 0; sc < 2; ++sc)
+#pragma unroll
+                        for (int sb = 0; sb < 2; ++sb) {
+                            const int o = sc * pl + (sb ? qb1 : qb0);
+                            x[sc][sb] = lerp(S[o + r2[0]], S[o + r2[1]], w2);
+                        }
+                    if (b == 1) v = lerp(lerp(x[0][0], x[0][1], wb), lerp(x[1][0], x[1][1], wb), wc);
+                    else        v = lerp(lerp(x[0][0], x[1][0], wc), lerp(x[0][1], x[1][1], wc), wb);
+                }
+            } else {
+                const Taps tp = get_taps<INTERP>(P, tab, k0, k1, k2);
+                v = sample<MODE, T, INTERP>(srcc, tp, mp, bad);
+            }
+            const long o = ((long)k0 * P.k[1] + k1) * P.k[2] + k2;
+            if (MODE == MODE_IMAGE) static_cast<float*>(out)[(long)ch * P.nvox + o] = v;
+            else if (MODE == MODE_LABELS) static_cast<uint8_t*>(out)[o] = (uint8_t)v;
+            else if (ch == 0 || v > bv[i]) { bv[i] = v; bi[i] = ch; }
+        }
+    }
+    if (MODE == MODE_ARGMAX) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int jb = wv + 4 * i;
+            if (jb >= nb || lane >= n2) continue;
+            const int k0 = b == 0 ? kb0 + jb : kc, k1 = b == 0 ? kc : kb0 + jb;
+            static_cast<uint8_t*>(out)[((long)k0 * P.k[1] + k1) * P.k[2] + k20 + lane] = (uint8_t)bi[i];
+        }
+    }
+    if (MODE == MODE_LABELS && bad && flag) flag[0] = 1;
+}
+
+bool fill_plan(Plan& P, const int32_t* src_dims, const int32_t* out_dims, const int32_t* axes) {
+    int seen = 0;
+    const long st[3] = {(long)src_dims[1] * src_dims[2], (long)src_dims[2], 1};
+    P.K = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (src_dims[a] < 1 || out_dims[a] < 1 || axes[a] < 0 || axes[a] > 2) return false;
+        seen |= 1 << axes[a];
+        P.m[a] = src_dims[a];
+        P.k[a] = out_dims[a];
+        P.sn[a] = src_dims[axes[a]];
+        P.ss[a] = st[axes[a]];
+        P.off[a] = P.K;
+        P.K += out_dims[a];
+    }
+    if (seen != 7) return false;
+    P.b = axes[0] == 2 ? 0 : 1;
+    P.c = 1 - P.b;
+    P.msz = (long)P.m[0] * P.m[1] * P.m[2];
+    P.nvox = (long)P.k[0] * P.k[1] * P.k[2];
+    return P.msz < (1L << 31) && P.nvox < (1L << 31);
+}
+
+// Rows along output axis b per staged tile so that the footprint bound (tile x scale + 2 per axis, two planes when
+// interpolating) fits the staging buffer; 0 = use the direct kernel.
+// Measured (tools/bench_scan.py): staging wins for the fp32 image, direct reads win for the one-byte label
+// launches and the arg-max, so only the image stages by default; flags bit 0 forces direct reads, bit 1 staging.
+int staged_rows(const Plan& P, int32_t axes2, bool interp, int32_t flags, int tbmax, bool by_default) {
+    if (axes2 == 2 || (flags & 1) || P.k[P.c] > 65535 || !(by_default || (flags & 2))) return 0;
+    const double sb = (double)P.sn[P.b] / P.k[P.b], s2 = (double)P.sn[2] / P.k[2];
+    const long len2 = (long)(T2 * s2) + 3;
+    for (int tb = tbmax; tb >= 4; tb >>= 1) {
+        const long lenb = ((long)(tb * sb) + 3) | 1;
+        if ((interp ? 2 : 1) * len2 * lenb <= LDS_CAP) return tb;
+    }
+    return 0;
+}
+
+template <int MODE, typename T, bool INTERP>
+int launch(const void* src, const Plan& P, int32_t axes2, const int32_t* tab, const Map& mp, int Cn, int32_t flags, void* out,
+           int32_t* flag, mivp_stream_t stream, const char* what) {
+    const int tb = staged_rows(P, axes2, INTERP, flags, MODE == MODE_ARGMAX ? TBMAX_ARGMAX : TBMAX, MODE == MODE_IMAGE);
+    if (tb) {
+        const unsigned tiles = (unsigned)(((P.k[2] + T2 - 1) / T2) * ((P.k[P.b] + tb - 1) / tb));
+        hipLaunchKernelGGL((k_scan_staged<MODE, T, INTERP>), dim3(tiles, (unsigned)P.k[P.c], MODE == MODE_IMAGE ? Cn : 1),
+                           dim3(TPB), 0, (hipStream_t)stream, static_cast<const T*>(src), P, (const int*)tab, mp, Cn, tb, out,
+                           (int*)flag);
+    } else {
+        hipLaunchKernelGGL((k_scan_direct<MODE, T, INTERP>),
+                           dim3((unsigned)((P.nvox + TPB - 1) / TPB), MODE == MODE_IMAGE ? Cn : 1), dim3(TPB), 0,
+                           (hipStream_t)stream, static_cast<const T*>(src), P, (const int*)tab, mp, Cn, out, (int*)flag);
+    }
+    return mivp_check_launch(what);
+}
+
+template <int MODE, bool INTERP>
+int launch_dtype(int32_t dtype, const void* src, const Plan& P, int32_t axes2, const int32_t* tab, const Map& mp, int Cn,
+                 int32_t flags, void* out, int32_t* flag, mivp_stream_t stream, const char* what) {
+    switch (dtype) {
+        case 0: return launch<MODE, uint8_t, INTERP>(src, P, axes2, tab, mp, Cn, flags, out, flag, stream, what);
+        case 1: return launch<MODE, int32_t, INTERP>(src, P, axes2, tab, mp, Cn, flags, out, flag, stream, what);
+        case 3: return launch<MODE, float, INTERP>(src, P, axes2, tab, mp, Cn, flags, out, flag, stream, what);
+        case 4: return launch<MODE, int16_t, INTERP>(src, P, axes2, tab, mp, Cn, flags, out, flag, stream, what);
+    }
+    mivp_set_error("scan: dtype must be 0 (uint8), 1 (int32), 3 (float32) or 4 (int16)");
+    return MIVP_EINVAL;
+}
+}  // namespace
+
+extern "C" int mivp_scan_prepare(const void* raw, int32_t dtype, int32_t C, const int32_t* src_dims, const int32_t* out_dims,
+                                 const int32_t* axes, const int32_t* tables, int32_t interp, const float* map, int32_t clip,
+                                 int32_t flags, float* out, mivp_stream_t stream) {
+    MIVP_REQUIRE(raw && out && src_dims && out_dims && axes && tables && map && C >= 1 && C <= 4);
+    Plan P;
+    MIVP_REQUIRE(fill_plan(P, src_dims, out_dims, axes));
+    const Map mp = {map[0], map[1], map[2], map[3], clip != 0};
+    if (interp)
+        return launch_dtype<MODE_IMAGE, true>(dtype, raw, P, axes[2], tables, mp, C, flags, out, nullptr, stream, "scan_prepare");
+    return launch_dtype<MODE_IMAGE, false>(dtype, raw, P, axes[2], tables, mp, C, flags, out, nullptr, stream, "scan_prepare");
+}
+
+extern "C" int mivp_scan_prepare_labels(const void* seg, int32_t dtype, const int32_t* src_dims, const int32_t* out_dims,
+                                        const int32_t* axes, const int32_t* tables, int32_t flags, uint8_t* out, int32_t* bad,
+                                        mivp_stream_t stream) {
+    MIVP_REQUIRE(seg && out && bad && src_dims && out_dims && axes && tables);
+    Plan P;
+    MIVP_REQUIRE(fill_plan(P, src_dims, out_dims, axes));
+    const Map mp = {1.f, 0.f, 0.f, 0.f, 0};
+    return launch_dtype<MODE_LABELS, false>(dtype, seg, P, axes[2], tables, mp, 1, flags, out, bad, stream,
+                                            "scan_prepare_labels");
+}
+
+extern "C" int mivp_scan_restore_labels(const uint8_t* labels, const int32_t* src_dims, const int32_t* out_dims,
+                                        const int32_t* axes, const int32_t* tables, int32_t flags, uint8_t* out,
+                                        mivp_stream_t stream) {
+    MIVP_REQUIRE(labels && out && src_dims && out_dims && axes && tables);
+    Plan P;
+    MIVP_REQUIRE(fill_plan(P, src_dims, out_dims, axes));
+    const Map mp = {1.f, 0.f, 0.f, 0.f, 0};
+    return launch<MODE_LABELS, uint8_t, false>(labels, P, axes[2], tables, mp, 1, flags, out, nullptr, stream,
+                                               "scan_restore_labels");
+}
+
+extern "C" int mivp_scan_restore_argmax(const float* logits, int32_t C, const int32_t* src_dims, const int32_t* out_dims,
+                                        const int32_t* axes, const int32_t* tables, int32_t interp, int32_t flags, uint8_t* out,
+                                        mivp_stream_t stream) {
+    MIVP_REQUIRE(logits && out && src_dims && out_dims && axes && tables && C >= 1 && C <= MAXC);
+    Plan P;
+    MIVP_REQUIRE(fill_plan(P, src_dims, out_dims, axes));
+    const Map mp = {1.f, 0.f, 0.f, 0.f, 0};
+    if (interp)
+        return launch<MODE_ARGMAX, float, true>(logits, P, axes[2], tables, mp, C, flags, out, nullptr, stream,
+                                                "scan_restore_argmax");
+    return launch<MODE_ARGMAX, float, false>(logits, P, axes[2], tables, mp, C, flags, out, nullptr, stream,
+                                             "scan_restore_argmax");
+}

@@ -342,7 +342,8 @@ class SlidingWindowPredictor:
         if self.graph_mode:
             if self.vol is None:
                 self.vol = torch.empty_like(vol)
-            self.vol.copy_(vol)
+            if vol.data_ptr() != self.vol.data_ptr():            # predict_scan prepares straight into the resident volume
+                self.vol.copy_(vol)
             if self.graph is None:
                 self._record()
             self._reset()
@@ -426,6 +427,66 @@ class SlidingWindowPredictor:
                                 include_background)
         out["iou"], out["dice"] = float(iou), float(dice)
         return out
+
+    # ------------------------------------------------------------------ raw scans (mivp_amd.scan)
+    def _prepare_scan(self, raw, geom, restore, postprocess, intensity):
+        """Checked raw scan -> the model's input on the device: the predictor's resident volume in graph mode, so that the
+        recorded gather reads what the prepare launch wrote."""
+        from . import scan
+        unknown = set(intensity) - {"a_min", "a_max", "b_min", "b_max", "clip"}
+        if unknown:
+            raise ValueError(f"unknown intensity arguments {sorted(unknown)}")
+        r = scan.check_predict_args(self.image_size, self.cin, raw, geom, restore, postprocess)
+        out = None
+        if self.graph_mode and isinstance(r, torch.Tensor) and r.is_cuda:
+            if self.vol is None:
+                self.vol = torch.empty((1, self.cin) + self.image_size, dtype=torch.float32, device=self.dev)
+            out = self.vol
+        return scan.prepare_scan(r, geom, out=out, **intensity)
+
+    def predict_scan(self, raw: torch.Tensor, geom, restore: str = "labels", postprocess: Optional[Dict] = None,
+                     **intensity) -> Dict[str, torch.Tensor]:
+        """A raw scan on its native grid (``[C, H, W, D]`` int16 / uint8 / int32 / float32, ``geom`` a
+        ``mivp_amd.scan.ScanGeometry`` whose model grid is this predictor's image size) -> ``{"labels": uint8
+        [H, W, D]`` on the native grid, ``"labels_oriented"``: uint8 ``[1, 1, H', W', D']`` on the model grid``}``:
+        ``prepare_scan`` -> the sliding-window prediction -> optional post-processing on the model grid -> restore, with
+        no host read.  ``restore="labels"`` resizes the label map back (nearest); ``restore="logits"`` interpolates the
+        blended logits on the native grid and takes the arg-max there (``restore_labels_from_logits``).  ``intensity``:
+        ``a_min``, ``a_max``, ``b_min``, ``b_max``, ``clip`` of ``prepare_scan``."""
+        from . import scan
+        post = self._post(postprocess)
+        x = self._prepare_scan(raw, geom, restore, postprocess, intensity)
+        labels, logits = self._run(x, restore == "logits", None, post)
+        native = scan.restore_labels(labels, geom) if restore == "labels" else scan.restore_labels_from_logits(logits, geom)
+        return {"labels": native, "labels_oriented": labels}
+
+    def evaluate_scan(self, raw: torch.Tensor, seg_native: torch.Tensor, geom, postprocess: Optional[Dict] = None,
+                      **intensity) -> Tuple[float, float]:
+        """``evaluate`` for a raw scan and a ground truth stored on the scan's native grid: ``prepare_labels`` takes the
+        ground truth to the model grid and the scoring happens there, on the grid the model saw (as the reference's
+        ``test()`` does).  Returns (mean IoU, mean Dice)."""
+        from . import scan
+        self._post(postprocess)
+        x = self._prepare_scan(raw, geom, "labels", postprocess, intensity)
+        seg = scan.prepare_labels(seg_native, geom)
+        return self.evaluate(x, seg, postprocess)
+
+
+def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], num_classes: int, out_size=None,
+                        axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
+                        sub_batch: int = 10, graph: bool = False, restore: str = "labels",
+                        postprocess: Optional[Dict] = None, **intensity) -> Dict[str, torch.Tensor]:
+    """One-shot ``SlidingWindowPredictor(...).predict_scan(raw, geom, restore, postprocess, **intensity)`` with
+    ``geom = ScanGeometry.from_affine(raw's spatial shape, affine, axcodes, out_size)``; also returns ``"geometry"``."""
+    from . import scan
+    if not isinstance(raw, torch.Tensor) or raw.dim() not in (3, 4, 5):
+        raise ValueError("raw must be a [C, H, W, D] (or [H, W, D] / [1, C, H, W, D]) tensor")
+    geom = scan.ScanGeometry.from_affine(tuple(raw.shape[-3:]), affine, axcodes, out_size)
+    cin = 1 if raw.dim() == 3 else int(raw.shape[-4])
+    p = SlidingWindowPredictor(model, geom.size, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph)
+    out = p.predict_scan(raw, geom, restore, postprocess, **intensity)
+    out["geometry"] = geom
+    return out
 
 
 def predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,

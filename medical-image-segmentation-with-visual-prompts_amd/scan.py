@@ -1,0 +1,377 @@
+"""Scan preparation and native-grid restore around whole-volume prediction on the GPU (csrc/scan.hip).
+
+The reference prepares a scan on CPU workers with MONAI (src/datasets/transforms.py): ``ScaleIntensityRanged(clip=True)``
+-> ``Orientationd('RAS')`` -> optionally ``Resized`` (trilinear for the image, nearest for the mask).  MONAI and nibabel
+are not dependencies here, so the conventions are written out rather than pinned to them:
+
+- **Grids.**  The *native* grid is the scan as stored, ``[H, W, D]`` contiguous with D fastest, with a 4 x 4 affine from
+  voxel indices to world millimetres (RAS+: x to the right, y to anterior, z to superior).  The *oriented* grid is
+  ``flip(transpose(native, perm), flipped axes)``; the *model* grid is the oriented grid resized to ``out_size`` (or the
+  oriented grid itself).
+- **Orientation rule.**  The columns of the affine's 3 x 3 block are normalised by their norms (the voxel spacing).
+  Native axes are assigned to world axes greedily by decreasing absolute entry (always a permutation); an axis is flipped
+  where the chosen entry's sign disagrees with the requested code (``R``, ``A``, ``S`` are the positive directions).
+- **Intensity map.**  ``v = fma(x, s, t)`` in fp32 with ``s = fp32((b_max - b_min) / (a_max - a_min))`` and
+  ``t = fp32(b_min - a_min * (b_max - b_min) / (a_max - a_min))``, then, with ``clip``, clamped to ``[b_min, b_max]``.
+  It is applied to every source voxel *before* the resize, which is the reference's order.
+- **Resize.**  ``torch.nn.functional.interpolate``: ``mode='trilinear', align_corners=False`` without antialiasing for
+  images and logits, ``mode='nearest'`` for label maps, as per-axis tables (``linear_taps``, ``nearest_indices``).
+
+Four launches, all GPU tensors in and out with no CPU fallback: ``prepare_scan``, ``prepare_labels``, ``restore_labels``
+and ``restore_labels_from_logits``.  ``ScanGeometry`` holds what both directions need and is plain numpy.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.float32: 3, torch.int16: 4}
+_CODES = {"L": (0, -1), "R": (0, 1), "P": (1, -1), "A": (1, 1), "I": (2, -1), "S": (2, 1)}
+FLAG_DIRECT = 1          # read the source directly even when the innermost axis moves (tools/bench_scan.py)
+FLAG_STAGED = 2          # stage tiles through LDS where the default reads directly (labels, arg-max)
+
+
+def _i3(v):
+    return (C.c_int32 * 3)(*[int(a) for a in v])
+
+
+def _shape3(name: str, v) -> Tuple[int, int, int]:
+    try:
+        t = tuple(int(a) for a in v)
+    except TypeError:
+        raise ValueError(f"{name} must be three positive sizes, got {v!r}") from None
+    if len(t) != 3 or min(t) < 1 or any(int(a) != a for a in v):
+        raise ValueError(f"{name} must be three positive sizes, got {tuple(v)}")
+    return t
+
+
+def nearest_indices(n_in: int, n_out: int) -> np.ndarray:
+    """The source index ``F.interpolate(mode='nearest')`` reads for each of ``n_out`` outputs over ``n_in`` inputs:
+    ``min(floor(dst * (n_in / n_out)), n_in - 1)`` with the scale and the product in fp32, as torch computes them."""
+    scale = np.float32(n_in) / np.float32(n_out)
+    src = np.floor(np.arange(n_out, dtype=np.float32) * scale).astype(np.int64)
+    return np.minimum(src, n_in - 1).astype(np.int32)
+
+
+def linear_taps(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``F.interpolate(mode='linear', align_corners=False)`` along one axis as (lower index int32, upper index int32,
+    weight of the upper one float64): ``src = max((dst + 0.5) * n_in / n_out - 0.5, 0)``, ``lo = floor(src)``,
+    ``hi = min(lo + 1, n_in - 1)``, ``w = src - lo``.  Equal sizes give ``lo = dst`` and ``w = 0`` exactly."""
+    src = np.maximum((np.arange(n_out, dtype=np.float64) + 0.5) * (float(n_in) / float(n_out)) - 0.5, 0.0)
+    lo = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
+    hi = np.minimum(lo + 1, n_in - 1)
+    return lo.astype(np.int32), hi.astype(np.int32), src - lo
+
+
+def intensity_map(a_min: float = -1000.0, a_max: float = 1000.0, b_min: float = 0.0, b_max: float = 1.0):
+    """(s, t, lo, hi) as fp32 values: ``v = clamp(fma(x, s, t), lo, hi)`` (the module docstring)."""
+    vals = [float(a_min), float(a_max), float(b_min), float(b_max)]
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"a_min, a_max, b_min, b_max must be finite, got {vals}")
+    if not vals[1] > vals[0]:
+        raise ValueError(f"a_max must be greater than a_min, got a_min={a_min}, a_max={a_max}")
+    if vals[3] < vals[2]:
+        raise ValueError(f"b_max must not be below b_min, got b_min={b_min}, b_max={b_max}")
+    s = (vals[3] - vals[2]) / (vals[1] - vals[0])
+    return tuple(float(np.float32(v)) for v in (s, vals[2] - vals[0] * s, vals[2], vals[3]))
+
+
+class ScanGeometry:
+    """How one scan's native grid maps to the grid the model sees, and back.
+
+    ``shape``: native ``(H, W, D)``.  ``perm`` / ``flip``: oriented axis ``a`` is native axis ``perm[a]``, reversed where
+    ``flip[a]``.  ``oriented_shape``, ``spacing`` (mm per voxel along the oriented axes: the ``spacing=`` of
+    ``surface_metrics`` / ``evaluate_surface`` when there is no resize; ``model_spacing`` after one), ``out_size`` (the
+    resize target or None) and ``size`` (the model grid: ``out_size`` or ``oriented_shape``)."""
+
+    def __init__(self, shape, perm, flip, spacing=(1.0, 1.0, 1.0), out_size=None, axcodes: str = "RAS"):
+        self.shape = _shape3("shape", shape)
+        self.perm = tuple(int(p) for p in perm)
+        if sorted(self.perm) != [0, 1, 2]:
+            raise ValueError(f"perm must be a permutation of (0, 1, 2), got {tuple(perm)}")
+        self.flip = tuple(bool(f) for f in flip)
+        if len(self.flip) != 3:
+            raise ValueError(f"flip must have three entries, got {tuple(flip)}")
+        self.spacing = tuple(float(s) for s in spacing)
+        if len(self.spacing) != 3 or not all(math.isfinite(s) and s > 0 for s in self.spacing):
+            raise ValueError(f"spacing must be three positive sizes in mm, got {tuple(spacing)}")
+        self.oriented_shape = tuple(self.shape[p] for p in self.perm)
+        self.out_size = None if out_size is None else _shape3("out_size", out_size)
+        self.size = self.out_size or self.oriented_shape
+        self.resized = self.size != self.oriented_shape
+        self.inverse = tuple(self.perm.index(j) for j in range(3))
+        self.axcodes = axcodes
+        self._np: Dict[str, tuple] = {}
+        self._dev: Dict[tuple, torch.Tensor] = {}
+
+    @property
+    def model_spacing(self) -> Tuple[float, float, float]:
+        """mm per voxel of the model grid (``spacing`` scaled by the resize)."""
+        return tuple(s * n / m for s, n, m in zip(self.spacing, self.oriented_shape, self.size))
+
+    @classmethod
+    def identity(cls, shape, spacing=(1.0, 1.0, 1.0), out_size=None) -> "ScanGeometry":
+        """A tensor that is already oriented."""
+        return cls(shape, (0, 1, 2), (False, False, False), spacing, out_size)
+
+    @classmethod
+    def from_affine(cls, shape, affine, axcodes: str = "RAS", out_size=None) -> "ScanGeometry":
+        """From the native shape and the scan's 4 x 4 (or 3 x 3) voxel-to-world affine (RAS+ world)."""
+        shape = _shape3("shape", shape)
+        if not isinstance(axcodes, str) or len(axcodes) != 3 or any(ch not in _CODES for ch in axcodes.upper()):
+            raise ValueError(f"axcodes must be three letters, one per axis from L/R, P/A, I/S, got {axcodes!r}")
+        want = [_CODES[ch] for ch in axcodes.upper()]
+        if sorted(w[0] for w in want) != [0, 1, 2]:
+            raise ValueError(f"axcodes must name each of L/R, P/A, I/S once, got {axcodes!r}")
+        a = np.asarray(affine, dtype=np.float64)
+        if a.shape not in ((4, 4), (3, 3)) or not np.all(np.isfinite(a)):
+            raise ValueError(f"affine must be a finite 4 x 4 (or 3 x 3) matrix, got shape {a.shape}")
+        m = a[:3, :3]
+        norms = np.sqrt((m * m).sum(axis=0))
+        if not np.all(norms > 0):
+            raise ValueError("affine is singular: a voxel axis has zero length")
+        r = m / norms
+        if abs(np.linalg.det(r)) < 1e-6:
+            raise ValueError("affine is singular: its voxel axes are linearly dependent")
+        # greedy assignment by decreasing |entry|: r[world, native]
+        native_of_world, sign_of_world = [None] * 3, [1.0] * 3
+        free_w, free_n = {0, 1, 2}, {0, 1, 2}
+        for idx in np.argsort(-np.abs(r), axis=None, kind="stable"):
+            w, n = divmod(int(idx), 3)
+            if w in free_w and n in free_n:
+                native_of_world[w], sign_of_world[w] = n, (1.0 if r[w, n] >= 0 else -1.0)
+                free_w.discard(w)
+                free_n.discard(n)
+        perm = tuple(native_of_world[w] for w, _ in want)
+        flip = tuple(sign_of_world[w] != float(s) for w, s in want)
+        return cls(shape, perm, flip, tuple(float(norms[p]) for p in perm), out_size, axcodes.upper())
+
+    # ------------------------------------------------------------------ per-axis tables (host)
+    def _to_native(self, a: int, idx: np.ndarray) -> np.ndarray:
+        return (self.oriented_shape[a] - 1 - idx) if self.flip[a] else idx
+
+    def tables(self, kind: str):
+        """``(src_dims, out_dims, axes, interp, int32 table)`` of one launch (include/mivp.h, ABI 17).  ``kind``:
+        ``"image"`` / ``"labels"`` native -> model grid, ``"restore_labels"`` / ``"restore_logits"`` model -> native."""
+        if kind in self._np:
+            return self._np[kind]
+        if kind not in ("image", "labels", "restore_labels", "restore_logits"):
+            raise ValueError(f"unknown table kind {kind!r}")
+        interp = self.resized and kind in ("image", "restore_logits")
+        lo, hi, w = [], [], []
+        if kind in ("image", "labels"):
+            src_dims, out_dims, axes = self.shape, self.size, self.perm
+            for a in range(3):
+                n_in, n_out = self.oriented_shape[a], self.size[a]
+                if interp:
+                    l, h, wt = linear_taps(n_in, n_out)
+                else:
+                    l = nearest_indices(n_in, n_out) if n_in != n_out else np.arange(n_out, dtype=np.int32)
+                    h, wt = l, np.zeros(n_out)
+                lo.append(self._to_native(a, l))
+                hi.append(self._to_native(a, h))
+                w.append(wt)
+        else:
+            src_dims, out_dims, axes = self.size, self.shape, self.inverse
+            for j in range(3):
+                a = self.inverse[j]
+                n_in, n_out = self.size[a], self.oriented_shape[a]
+                d = self._to_native(a, np.arange(n_out))          # native index -> oriented index (its own inverse)
+                if interp:
+                    l, h, wt = linear_taps(n_in, n_out)
+                else:
+                    l = nearest_indices(n_in, n_out) if n_in != n_out else np.arange(n_out, dtype=np.int32)
+                    h, wt = l, np.zeros(n_out)
+                lo.append(l[d])
+                hi.append(h[d])
+                w.append(wt[d])
+        sections = [np.concatenate(lo).astype(np.int32)]
+        if interp:
+            sections += [np.concatenate(hi).astype(np.int32), np.concatenate(w).astype(np.float32).view(np.int32)]
+        self._np[kind] = (tuple(src_dims), tuple(out_dims), tuple(axes), bool(interp), np.concatenate(sections))
+        return self._np[kind]
+
+    def device_tables(self, kind: str, device) -> torch.Tensor:
+        key = (kind, str(device))
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.tables(kind)[4]).to(device)
+        return self._dev[key]
+
+    def __repr__(self):
+        return (f"ScanGeometry(shape={self.shape}, perm={self.perm}, flip={self.flip}, spacing={self.spacing}, "
+                f"out_size={self.out_size})")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def _check_geom(geom) -> ScanGeometry:
+    if not isinstance(geom, ScanGeometry):
+        raise ValueError(f"geom must be a ScanGeometry, got {type(geom).__name__}")
+    return geom
+
+
+def _check_tensor(name: str, t, dims: Sequence[int], dtypes) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    if t.dim() not in dims:
+        raise ValueError(f"{name} must have {' or '.join(str(d) for d in dims)} dimensions, got shape {tuple(t.shape)}")
+    if dtypes is not None and t.dtype not in dtypes:
+        raise ValueError(f"{name} must be one of {[str(d).replace('torch.', '') for d in dtypes]}, got {t.dtype}")
+
+
+def _check_gpu(name: str, t: torch.Tensor) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a GPU tensor (no CPU fallback)")
+
+
+def _check_out(out, shape, dtype, like: torch.Tensor):
+    if out is None:
+        return None
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype:
+        raise ValueError(f"out must be a {str(dtype).replace('torch.', '')} tensor of shape {tuple(shape)}")
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+    if out.device != like.device:
+        raise ValueError(f"out is on {out.device}, the input on {like.device}")
+    return out
+
+
+def _volume3(name: str, t: torch.Tensor, want: Tuple[int, int, int]) -> torch.Tensor:
+    """``[H, W, D]`` or ``[1, 1, H, W, D]`` -> ``[H, W, D]`` of the expected size."""
+    if t.dim() == 5:
+        if tuple(t.shape[:2]) != (1, 1):
+            raise ValueError(f"{name} must be [1, 1, H, W, D] or [H, W, D], got {tuple(t.shape)}")
+        t = t[0, 0]
+    if tuple(t.shape) != tuple(want):
+        raise ValueError(f"{name} has spatial size {tuple(t.shape)}, the geometry expects {tuple(want)}")
+    return t
+
+
+def _raw_view(raw, geom: ScanGeometry) -> torch.Tensor:
+    """``[H, W, D]``, ``[C, H, W, D]`` or ``[1, C, H, W, D]`` -> ``[C, H, W, D]`` (checked, still on its device)."""
+    _check_tensor("raw", raw, (3, 4, 5), tuple(_DTYPES))
+    if raw.dim() == 5:
+        if raw.shape[0] != 1:
+            raise ValueError(f"raw must hold one scan ([1, C, H, W, D]), got {tuple(raw.shape)}")
+        raw = raw[0]
+    elif raw.dim() == 3:
+        raw = raw[None]
+    if not 1 <= raw.shape[0] <= 4:
+        raise ValueError(f"raw must have 1..4 channels, got {raw.shape[0]}")
+    if tuple(raw.shape[1:]) != geom.shape:
+        raise ValueError(f"raw has spatial size {tuple(raw.shape[1:])}, the geometry's native shape is {geom.shape}")
+    return raw
+
+
+def prepare_scan(raw: torch.Tensor, geom: ScanGeometry, a_min: float = -1000.0, a_max: float = 1000.0, b_min: float = 0.0,
+                 b_max: float = 1.0, clip: bool = True, out: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+    """A raw scan on its native grid -> the model's input, in one launch: intensity map (with clip), orientation and,
+    when ``geom.out_size`` is set, the trilinear resize.  ``raw``: ``[C, H, W, D]`` (or ``[H, W, D]`` /
+    ``[1, C, H, W, D]``), C <= 4, int16, uint8, int32 or float32.  Returns fp32 ``[1, C, H', W', D']`` (``out`` when
+    given).  Without a resize the result is bit-equal to the intensity map of the transposed and flipped scan."""
+    geom = _check_geom(geom)
+    r = _raw_view(raw, geom)
+    mp = intensity_map(a_min, a_max, b_min, b_max)
+    shape = (1, r.shape[0]) + geom.size
+    out = _check_out(out, shape, torch.float32, r)
+    _check_gpu("raw", r)
+    r = r.contiguous()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=r.device)
+    src, dst, axes, interp, _ = geom.tables("image")
+    L.call("mivp_scan_prepare", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(r.shape[0]), _i3(src), _i3(dst), _i3(axes),
+           L.ptr(geom.device_tables("image", r.device)), C.c_int32(int(interp)), (C.c_float * 4)(*mp),
+           C.c_int32(int(bool(clip))), C.c_int32(int(flags)), L.ptr(out), L.stream())
+    return out
+
+
+def prepare_labels(seg: torch.Tensor, geom: ScanGeometry, out: Optional[torch.Tensor] = None, check: bool = True,
+                   flags: int = 0) -> torch.Tensor:
+    """A label map on the native grid (``[H, W, D]`` or ``[1, 1, H, W, D]``; int16, uint8, int32 or float32 class
+    indices) -> uint8 ``[1, 1, H', W', D']`` on the model grid: orientation and nearest resize.  A value outside 0..255
+    (or a non-integer float) raises ``ValueError``: the kernel sets a device flag, read once here (the one host
+    synchronisation; ``check=False`` skips the read and leaves such voxels 0)."""
+    geom = _check_geom(geom)
+    _check_tensor("seg", seg, (3, 5), tuple(_DTYPES))
+    s = _volume3("seg", seg, geom.shape)
+    shape = (1, 1) + geom.size
+    out = _check_out(out, shape, torch.uint8, s)
+    _check_gpu("seg", s)
+    s = s.contiguous()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=s.device)
+    bad = torch.zeros(1, dtype=torch.int32, device=s.device)
+    src, dst, axes, _, _ = geom.tables("labels")
+    L.call("mivp_scan_prepare_labels", L.ptr(s), C.c_int32(_DTYPES[s.dtype]), _i3(src), _i3(dst), _i3(axes),
+           L.ptr(geom.device_tables("labels", s.device)), C.c_int32(int(flags)), L.ptr(out), L.ptr(bad), L.stream())
+    if check and int(bad.item()) != 0:
+        raise ValueError("seg holds values outside 0..255 (or non-integer values): they do not fit a uint8 label map")
+    return out
+
+
+def restore_labels(labels: torch.Tensor, geom: ScanGeometry, out: Optional[torch.Tensor] = None,
+                   flags: int = 0) -> torch.Tensor:
+    """uint8 labels on the model grid (``[1, 1, H', W', D']`` or ``[H', W', D']``, e.g. ``predict(x)["labels"]``) -> uint8
+    ``[H, W, D]`` on the scan's native grid: nearest resize back to the oriented size, inverse flip and permutation.
+    No host synchronisation."""
+    geom = _check_geom(geom)
+    _check_tensor("labels", labels, (3, 5), (torch.uint8,))
+    v = _volume3("labels", labels, geom.size)
+    out = _check_out(out, geom.shape, torch.uint8, v)
+    _check_gpu("labels", v)
+    v = v.contiguous()
+    if out is None:
+        out = torch.empty(geom.shape, dtype=torch.uint8, device=v.device)
+    src, dst, axes, _, _ = geom.tables("restore_labels")
+    L.call("mivp_scan_restore_labels", L.ptr(v), _i3(src), _i3(dst), _i3(axes),
+           L.ptr(geom.device_tables("restore_labels", v.device)), C.c_int32(int(flags)), L.ptr(out), L.stream())
+    return out
+
+
+def restore_labels_from_logits(logits: torch.Tensor, geom: ScanGeometry, out: Optional[torch.Tensor] = None,
+                               flags: int = 0) -> torch.Tensor:
+    """Blended fp32 logits on the model grid (``[1, C, H', W', D']`` or ``[C, H', W', D']``, C <= 16, what
+    ``predict(x, return_logits=True)["logits"]`` holds) -> uint8 labels ``[H, W, D]`` on the native grid: per native voxel
+    the trilinear interpolation of every class and the arg-max (the lowest class wins a tie).  The native-size logits are
+    never stored.  No host synchronisation."""
+    geom = _check_geom(geom)
+    _check_tensor("logits", logits, (4, 5), (torch.float32,))
+    v = logits
+    if v.dim() == 5:
+        if v.shape[0] != 1:
+            raise ValueError(f"logits must hold one volume ([1, C, H, W, D]), got {tuple(v.shape)}")
+        v = v[0]
+    if not 1 <= v.shape[0] <= 16:
+        raise ValueError(f"logits must have 1..16 classes, got {v.shape[0]}")
+    if tuple(v.shape[1:]) != geom.size:
+        raise ValueError(f"logits have spatial size {tuple(v.shape[1:])}, the geometry's model grid is {geom.size}")
+    out = _check_out(out, geom.shape, torch.uint8, v)
+    _check_gpu("logits", v)
+    v = v.contiguous()
+    if out is None:
+        out = torch.empty(geom.shape, dtype=torch.uint8, device=v.device)
+    src, dst, axes, interp, _ = geom.tables("restore_logits")
+    L.call("mivp_scan_restore_argmax", L.ptr(v), C.c_int32(v.shape[0]), _i3(src), _i3(dst), _i3(axes),
+           L.ptr(geom.device_tables("restore_logits", v.device)), C.c_int32(int(interp)), C.c_int32(int(flags)), L.ptr(out),
+           L.stream())
+    return out
+
+
+def check_predict_args(image_size, in_channels: int, raw, geom, restore: str, postprocess=None) -> torch.Tensor:
+    """The argument checks of ``SlidingWindowPredictor.predict_scan`` (no device work): returns raw as ``[C, H, W, D]``."""
+    geom = _check_geom(geom)
+    if restore not in ("labels", "logits"):
+        raise ValueError(f"restore must be 'labels' or 'logits', got {restore!r}")
+    if restore == "logits" and postprocess is not None:
+        raise ValueError("postprocess works on the label map: use restore='labels' with it")
+    r = _raw_view(raw, geom)
+    if geom.size != tuple(image_size):
+        raise ValueError(f"the geometry's model grid is {geom.size}, the predictor was built for {tuple(image_size)}")
+    if r.shape[0] != int(in_channels):
+        raise ValueError(f"raw has {r.shape[0]} channels, the predictor was built for {in_channels}")
+    return r

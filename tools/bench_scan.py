@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""Scan preparation and restore throughput (mivp_amd.scan), timed on device events after a warm-up, on a 512x512x96 int16
+scan built on the device.  Cases:
+
+- ``prepare identity``: intensity map only (the direct read path);
+- ``prepare moved``: a permutation that moves the innermost axis plus two flips (the staged read path), and the same with
+  the naive strided reads forced (``other_path_ms``);
+- ``prepare moved+resize``: the same geometry with a trilinear resize to 384x384x96, both read paths;
+- ``prepare_labels`` / ``restore_labels`` / ``restore_labels_from_logits`` (2 classes) for the moved geometry, with and
+  without the resize; they read directly by default, and ``other_path_ms`` is the staged path.
+
+Next to each launch the same result composed from eager torch ops on the same GPU (``.float()``, arithmetic, ``clamp``,
+``permute``, ``flip``, ``F.interpolate``) is timed.  One JSON line per case: ms per call, the eager ms, their ratio, the
+algorithmic bytes of the launch (source read once + output written once) and that over time as a fraction of the 6.3 TB/s
+HBM rate DESIGN 4.8 uses."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM = 6.3e12
+SHAPE = (512, 512, 96)
+PERM, FLIP = (2, 0, 1), (True, True, False)          # oriented = (D, H, W) of the native grid: the innermost axis moves
+RESIZED = (96, 384, 384)                              # 512 x 512 -> 384 x 384 in the moved geometry
+
+
+def timed(fn, calls, warmup):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    import torch
+    import torch.nn.functional as F
+    import mivp_amd  # noqa: F401
+    from mivp_amd import scan
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(5)
+    raw = torch.randint(-1500, 1500, (1,) + SHAPE, generator=g, device=dev, dtype=torch.int32).to(torch.int16)
+    seg = torch.randint(0, 2, SHAPE, generator=g, device=dev, dtype=torch.int32).to(torch.uint8)
+    ident = scan.ScanGeometry.identity(SHAPE)
+    moved = scan.ScanGeometry(SHAPE, PERM, FLIP)
+    resized = scan.ScanGeometry(SHAPE, PERM, FLIP, out_size=RESIZED)
+    fdims = [a + 1 for a in range(3) if FLIP[a]]
+    nvox = SHAPE[0] * SHAPE[1] * SHAPE[2]
+
+    def eager_prepare(geom):
+        x = ((raw.float() * 0.0005 + 0.5).clamp(0.0, 1.0)).permute(0, *[1 + p for p in geom.perm])
+        if any(geom.flip):
+            x = x.flip(fdims)
+        x = x.contiguous()[None]
+        if geom.resized:
+            x = F.interpolate(x, size=geom.size, mode="trilinear", align_corners=False)
+        return x
+
+    def eager_labels(geom):
+        x = seg.permute(*geom.perm)
+        if any(geom.flip):
+            x = x.flip([d - 1 for d in fdims])
+        x = x.contiguous()[None, None]
+        if geom.resized:
+            x = F.interpolate(x, size=geom.size, mode="nearest")
+        return x
+
+    def eager_restore(lab, geom):
+        x = lab
+        if geom.resized:
+            x = F.interpolate(x, size=geom.oriented_shape, mode="nearest")
+        x = x[0, 0]
+        if any(geom.flip):
+            x = x.flip([d - 1 for d in fdims])
+        return x.permute(*geom.inverse).contiguous()
+
+    def eager_restore_logits(lg, geom):
+        x = lg
+        if geom.resized:
+            x = F.interpolate(x, size=geom.oriented_shape, mode="trilinear", align_corners=False)
+        x = x[0].argmax(0).to(torch.uint8)
+        if any(geom.flip):
+            x = x.flip([d - 1 for d in fdims])
+        return x.permute(*geom.inverse).contiguous()
+
+    def report(case, ms, eager_ms, nbytes, naive_ms=None):
+        rec = {"case": case, "ms": round(ms, 4), "eager_ms": round(eager_ms, 4), "eager_over_kernel": round(eager_ms / ms, 2),
+               "bytes": nbytes, "hbm_fraction": round(nbytes / (ms * 1e-3) / HBM, 3)}
+        if naive_ms is not None:                                                    # the read path that is not the default
+            rec["other_path_ms"] = round(naive_ms, 4)
+            rec["other_over_default"] = round(naive_ms / ms, 2)
+        print(json.dumps(rec), flush=True)
+
+    t = lambda fn: timed(fn, a.calls, a.warmup)                                     # noqa: E731
+    # the results agree before anything is timed
+    assert torch.allclose(scan.prepare_scan(raw, moved), eager_prepare(moved), rtol=0, atol=1e-6)
+    assert torch.equal(scan.prepare_labels(seg, resized), eager_labels(resized))
+
+    for name, geom in (("identity", ident), ("moved", moved), ("moved+resize", resized)):
+        out = torch.empty((1, 1) + geom.size, dtype=torch.float32, device=dev)
+        n_out = out.numel()
+        ms = t(lambda: scan.prepare_scan(raw, geom, out=out))
+        naive = t(lambda: scan.prepare_scan(raw, geom, out=out, flags=scan.FLAG_DIRECT)) if geom is not ident else None
+        report(f"prepare {name}", ms, t(lambda: eager_prepare(geom)), 2 * nvox + 4 * n_out, naive)
+
+    for name, geom in (("moved", moved), ("moved+resize", resized)):
+        n_out = geom.size[0] * geom.size[1] * geom.size[2]
+        lab = scan.prepare_labels(seg, geom)
+        ms = t(lambda: scan.prepare_labels(seg, geom, check=False))
+        naive = t(lambda: scan.prepare_labels(seg, geom, check=False, flags=scan.FLAG_STAGED))
+        report(f"prepare_labels {name}", ms, t(lambda: eager_labels(geom)), nvox + n_out, naive)
+        out = torch.empty(SHAPE, dtype=torch.uint8, device=dev)
+        ms = t(lambda: scan.restore_labels(lab, geom, out=out))
+        naive = t(lambda: scan.restore_labels(lab, geom, out=out, flags=scan.FLAG_STAGED))
+        report(f"restore_labels {name}", ms, t(lambda: eager_restore(lab, geom)), nvox + n_out, naive)
+        lg = torch.randn((1, 2) + geom.size, generator=g, device=dev)
+        ms = t(lambda: scan.restore_labels_from_logits(lg, geom, out=out))
+        naive = t(lambda: scan.restore_labels_from_logits(lg, geom, out=out, flags=scan.FLAG_STAGED))
+        report(f"restore_from_logits C=2 {name}", ms, t(lambda: eager_restore_logits(lg, geom)), 8 * n_out + nvox, naive)
+
+
+if __name__ == "__main__":
+    main()
