@@ -673,6 +673,34 @@ int mivp_stitch_finalize(const float* acc, const float* wsum, int32_t C, const i
                          mivp_stream_t stream);
 int mivp_window_advance(int32_t* sub_idx, mivp_stream_t stream);
 
+/* Mirror test-time augmentation and probability maps (ABI 18, csrc/stitch.hip; SlidingWindowPredictor(mirror_axes=...)).
+ * The _tta entries take the arguments of mivp_window_gather / mivp_window_blend; word 3 of a table entry is
+ * valid | code << 1, bit a of the 3-bit code flipping roi axis a (0 = H, 1 = W, 2 = D).  The table lists every window under
+ * every code, window-major (entry w * F + j = window w under the j-th code), and must be 16-byte aligned.  s_a(i) = r_a - 1 - i
+ * where bit a is set, else i:
+ *   mivp_window_gather_tta: out[b][c][i0][i1][i2] = padded volume[c][o + s(i)] (zero outside the image and for invalid
+ *     entries); a D flip loads the mirrored 16-byte quad and reverses it in registers where rows are aligned.
+ *   mivp_window_blend_tta: voxel o + p of the padded volume receives w(p) * logits[slot][c][s(p)] and w(p), w as in
+ *     mivp_window_blend, indexed by the UNFLIPPED position p; contributions add in increasing entry index (bitwise
+ *     independent of B).  comp: NULL, or f32 [pdims][C + 1] zeroed with acc / wsum: the sums are then compensated (Kahan),
+ *     comp carrying each accumulator word's and the weight sum's running rounding error between launches, so F times as many
+ *     contributions round like a few; acc / wsum remain the values to finalize.  With comp NULL and code 0 everywhere the
+ *     result is bitwise that of mivp_window_blend.  The sub-batch's entries and union box are staged in LDS once per
+ *     workgroup.  ubox: the largest union box over the sub-batches of THIS table.
+ *   mivp_stitch_finalize_probs: mivp_stitch_finalize (the same labels, logits and counts, bit for bit) plus, each when
+ *     non-NULL: probs f32 [C][H][W][D] = softmax over classes of acc / wsum (max-subtracted), confidence f32 [H][W][D] = the
+ *     maximum probability, entropy f32 [H][W][D] = -sum p ln p / ln C in [0, 1] (0 when C == 1).  C <= 16. */
+int mivp_window_gather_tta(const float* vol, int32_t Cin, const int32_t* dims, const int32_t* pad, const int32_t* pdims,
+                           const int32_t* roi, const int32_t* table, int32_t n_entries, const int32_t* sub_idx, int32_t B,
+                           float* out, mivp_stream_t stream);
+int mivp_window_blend_tta(const float* logits, int32_t channels_last, int32_t C, const int32_t* pdims, const int32_t* roi,
+                          const int32_t* table, int32_t n_entries, const int32_t* sub_idx, int32_t B, const int32_t* ubox,
+                          const float* w0, const float* w1, const float* w2, float w_floor, float* acc, float* wsum,
+                          float* comp, mivp_stream_t stream);
+int mivp_stitch_finalize_probs(const float* acc, const float* wsum, int32_t C, const int32_t* dims, const int32_t* pad,
+                               const int32_t* pdims, uint8_t* labels, float* logits, float* probs, float* confidence,
+                               float* entropy, const float* target, void* counts, mivp_stream_t stream);
+
 /* Surface-distance metrics (ABI 15, csrc/surface.hip; mivp_amd/surface.py).  dims = {H, W, D} (host), volumes
  * [H][W][D] row-major, fewer than 2^31 voxels.
  *   mivp_surface_map: pred / target class maps (dtype 0 uint8, 1 int32, 2 int64, 3 float32; values outside [0, C) and

@@ -171,6 +171,40 @@ def window_table(origins: np.ndarray, sub_batch: int) -> np.ndarray:
     return t
 
 
+def flip_codes(mirror_axes: Sequence[int] = ()) -> Tuple[int, ...]:
+    """The flip codes of mirror test-time augmentation: every subset of ``mirror_axes`` (distinct spatial axes out of
+    0 = H, 1 = W, 2 = D) as a 3-bit mask, bit ``a`` set = axis ``a`` flipped, in increasing numeric order from 0."""
+    try:
+        axes = [int(a) for a in mirror_axes]
+        exact = all(int(a) == a for a in mirror_axes)
+    except (TypeError, ValueError):
+        raise ValueError(f"mirror_axes must be a sequence of axes out of 0, 1, 2, got {mirror_axes!r}") from None
+    if not exact or any(a < 0 or a > 2 for a in axes):
+        raise ValueError(f"mirror_axes must be spatial axes out of 0 (H), 1 (W), 2 (D), got {tuple(mirror_axes)}")
+    if len(set(axes)) != len(axes):
+        raise ValueError(f"mirror_axes must be distinct, got {tuple(mirror_axes)}")
+    mask = sum(1 << a for a in axes)
+    return tuple(m for m in range(8) if m & ~mask == 0)
+
+
+def tta_table(origins: np.ndarray, sub_batch: int, codes: Sequence[int]) -> np.ndarray:
+    """The device work list under mirror augmentation: int32 [ceil(N F / sub_batch) * sub_batch, 4] =
+    (o0, o1, o2, valid | code << 1), entry ``w * F + j`` = window ``w`` under ``codes[j]`` (window-major, flip-minor);
+    padding entries are invalid.  ``codes == (0,)`` gives ``window_table(origins, sub_batch)``."""
+    if int(sub_batch) < 1:
+        raise ValueError("sub_batch must be >= 1")
+    codes = [int(m) for m in codes]
+    if not codes or any(m < 0 or m > 7 for m in codes) or len(set(codes)) != len(codes):
+        raise ValueError(f"codes must be distinct 3-bit flip masks, got {codes}")
+    f = len(codes)
+    n = origins.shape[0] * f
+    total = -(-n // int(sub_batch)) * int(sub_batch)
+    t = np.zeros((total, 4), dtype=np.int32)
+    t[:n, :3] = np.repeat(origins, f, axis=0)
+    t[:n, 3] = 1 + 2 * np.tile(np.asarray(codes, dtype=np.int32), origins.shape[0])
+    return t
+
+
 def importance_tables(roi: Sequence[int], mode: str = "gaussian", sigma_scale: float = 0.125):
     """The separable importance map as three 1-D float64 tables and the floor it is clamped at from below:
     w(i, j, k) = max(t0[i] * t1[j] * t2[k], floor).  ``"constant"``: all ones.  ``"gaussian"``:
@@ -212,16 +246,26 @@ class SlidingWindowPredictor:
     one blend launch adds ``w * logits`` and ``w`` into the accumulators (gather form, no float atomics: bitwise
     independent of ``sub_batch``), one launch advances the index.  One finalize launch writes the labels.
 
+    ``mirror_axes`` (distinct axes out of 0 = H, 1 = W, 2 = D) turns on mirror test-time augmentation: every window is
+    predicted under each of the ``2 ** len(mirror_axes)`` combinations of flips (``flip_codes``), the logits are flipped back
+    and all of them take part in the same weighted mean (logits are averaged, not probabilities; the importance map is
+    not flipped).  The work list is window-major, flip-minor (``tta_table``), its sub-batches are ``sub_batch`` consecutive
+    entries, and every voxel still sums in increasing entry index (with compensated fp32 sums, whose state is kept per
+    voxel between launches), so the result stays bitwise independent of ``sub_batch`` and of the graph form.
+
     ``graph=True`` records gather -> model -> blend -> advance once (after two eager sub-batches that pack the weight
-    caches) and replays it ``ceil(N / sub_batch)`` times with no host work in between: bitwise equal to eager.  The graph
+    caches) and replays it ``ceil(N F / sub_batch)`` times with no host work in between: bitwise equal to eager.  The graph
     holds the model's weights as they were when it was recorded; build a new predictor after changing them."""
 
     def __init__(self, model, image_size: Sequence[int], in_channels: int, num_classes: int, roi: Sequence[int],
                  overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                 graph: bool = False):
+                 graph: bool = False, mirror_axes: Sequence[int] = ()):
         self.image_size = _check_shape3("image_size", image_size)
         self.roi = _check_shape3("roi", roi)
         _check_overlap(overlap)
+        self.flip_codes = flip_codes(mirror_axes)
+        self.mirror_axes = tuple(int(a) for a in mirror_axes)
+        self.n_flips = len(self.flip_codes)
         if int(sub_batch) < 1:
             raise ValueError("sub_batch must be >= 1")
         if not 1 <= int(in_channels) <= 4:
@@ -251,12 +295,15 @@ class SlidingWindowPredictor:
         self.pad, self.pdims = window_padding(self.image_size, self.roi)
         self.origins = window_origins(self.image_size, self.roi, overlap)
         self.n_windows = int(self.origins.shape[0])
-        table = window_table(self.origins, self.sub_batch)
+        self.n_entries = self.n_windows * self.n_flips
+        table = tta_table(self.origins, self.sub_batch, self.flip_codes)
         self.n_sub = table.shape[0] // self.sub_batch
-        # grid of the blend: the largest union box of one sub-batch's windows
+        # the flip-aware kernels run when there is a flip; a plain predictor keeps the plain entry points
+        self._tta_kernels = self.n_flips > 1
+        # grid of the blend: the largest union box of one sub-batch's entries (the flips of a window share its box)
         ubox = [0, 0, 0]
         for s in range(self.n_sub):
-            o = self.origins[s * self.sub_batch:(s + 1) * self.sub_batch]
+            o = table[s * self.sub_batch:min((s + 1) * self.sub_batch, self.n_entries), :3]
             for a in range(3):
                 ubox[a] = max(ubox[a], int(o[:, a].max() - o[:, a].min()) + self.roi[a])
         self.ubox = tuple(ubox)
@@ -268,6 +315,10 @@ class SlidingWindowPredictor:
         self.acc = torch.zeros(self.pdims + (self.ncls,), dtype=torch.float32, device=dev)
         self.wsum = torch.zeros(self.pdims, dtype=torch.float32, device=dev)
         self.counts = torch.zeros((self.ncls, 3), dtype=torch.int64, device=dev)
+        # under augmentation a voxel adds F times as many contributions: the blend then carries the rounding error of acc
+        # and wsum along (compensated sums, in the same order), so that they round like the plain prediction's
+        self.comp = (torch.zeros(self.pdims + (self.ncls + 1,), dtype=torch.float32, device=dev)
+                     if self.n_flips > 1 else None)
         self._a = dict(dims=_i3(self.image_size), pad=_i3(self.pad), pdims=_i3(self.pdims), roi=_i3(self.roi),
                        ubox=_i3(self.ubox))
         self.vol = None          # graph mode: the resident volume the recorded gather reads
@@ -277,7 +328,7 @@ class SlidingWindowPredictor:
     # ------------------------------------------------------------------ per sub-batch launches
     def _gather(self, vol):
         a = self._a
-        L.call("mivp_window_gather", L.ptr(vol), C.c_int32(self.cin), a["dims"], a["pad"], a["pdims"], a["roi"],
+        L.call("mivp_window_gather_tta" if self._tta_kernels else "mivp_window_gather", L.ptr(vol), C.c_int32(self.cin), a["dims"], a["pad"], a["pdims"], a["roi"],
                L.ptr(self.table), C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch),
                L.ptr(self.xb), L.stream())
 
@@ -290,10 +341,14 @@ class SlidingWindowPredictor:
         else:
             src, clast = out.float().contiguous(), 0
         a = self._a
-        L.call("mivp_window_blend", L.ptr(src), C.c_int32(clast), C.c_int32(self.ncls), a["pdims"], a["roi"],
-               L.ptr(self.table), C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch),
-               a["ubox"], L.ptr(self.w[0]), L.ptr(self.w[1]), L.ptr(self.w[2]), C.c_float(self.w_floor),
-               L.ptr(self.acc), L.ptr(self.wsum), L.stream())
+        args = (L.ptr(src), C.c_int32(clast), C.c_int32(self.ncls), a["pdims"], a["roi"], L.ptr(self.table),
+                C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch), a["ubox"],
+                L.ptr(self.w[0]), L.ptr(self.w[1]), L.ptr(self.w[2]), C.c_float(self.w_floor), L.ptr(self.acc),
+                L.ptr(self.wsum))
+        if self._tta_kernels:
+            L.call("mivp_window_blend_tta", *args, L.ptr(self.comp), L.stream())
+        else:
+            L.call("mivp_window_blend", *args, L.stream())
 
     def _step(self, vol):
         self._gather(vol)
@@ -305,6 +360,8 @@ class SlidingWindowPredictor:
     def _reset(self):
         self.acc.zero_()
         self.wsum.zero_()
+        if self.comp is not None:
+            self.comp.zero_()
         self.sub_idx.zero_()
 
     def _record(self):
@@ -334,7 +391,8 @@ class SlidingWindowPredictor:
             raise ValueError(f"{name} is on {x.device}, the model on {self.dev}")
 
     @torch.no_grad()
-    def _run(self, x, want_logits, seg, post=None):
+    def _run(self, x, want_logits, seg, post=None, maps=()):
+        """-> (labels, logits or None, {name: map} for the names in ``maps`` out of probs / confidence / entropy)."""
         self._check_input(x)
         if self.graph_mode and self.model.training:
             raise RuntimeError("graph=True needs the model in eval() mode")
@@ -361,34 +419,46 @@ class SlidingWindowPredictor:
             self.counts.zero_()
         a = self._a
         counts = self.counts if seg is not None else None
-        if post is None:
-            L.call("mivp_stitch_finalize", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"], a["pad"],
-                   a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(tgt), L.ptr(counts), L.stream())
+        extra = {k: torch.empty((1, self.ncls if k == "probs" else 1) + self.image_size, dtype=torch.float32,
+                                device=self.dev) for k in maps}
+        # the post-processing rewrites the labels in place; its filter pass, not the finalize, counts them against seg
+        f_tgt, f_counts = (tgt, counts) if post is None else (None, None)
+        if extra:
+            L.call("mivp_stitch_finalize_probs", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"],
+                   a["pad"], a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(extra.get("probs")),
+                   L.ptr(extra.get("confidence")), L.ptr(extra.get("entropy")), L.ptr(f_tgt), L.ptr(f_counts), L.stream())
         else:
-            # the post-processing rewrites the labels in place; its filter pass, not the finalize, counts them against seg
-            from . import components
             L.call("mivp_stitch_finalize", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"], a["pad"],
-                   a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(None), L.ptr(None), L.stream())
+                   a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(f_tgt), L.ptr(f_counts), L.stream())
+        if post is not None:
+            from . import components
             lab = labels[0, 0]
             self.cc_ws = components._postprocess_launch(lab, lab, post, self.cc_ws,
                                                         tgt[0, 0] if tgt is not None else None, counts)
-        return labels, logits
+        return labels, logits, extra
 
     def _post(self, postprocess):
         from . import components
         return components.postprocess_kwargs(postprocess, self.ncls)
 
-    def predict(self, x: torch.Tensor, return_logits: bool = False,
-                postprocess: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
+    def predict(self, x: torch.Tensor, return_logits: bool = False, postprocess: Optional[Dict] = None,
+                return_probs: bool = False, return_confidence: bool = False,
+                return_entropy: bool = False) -> Dict[str, torch.Tensor]:
         """``x [1, Cin, H, W, D]`` -> ``{"labels": uint8 [1, 1, H, W, D]}`` (+ ``"logits"``: the blended fp32 logits
         ``[1, C, H, W, D]``).  ``postprocess``: a dict of ``mivp_amd.components.postprocess_labels`` keyword arguments
         (``largest``, ``min_size``, ``classes``, ``connectivity``) applied to the labels on the device; ``"logits"``
-        stays the blend before post-processing."""
+        stays the blend before post-processing.  On request, from the same finalize launch and like ``"logits"`` of the
+        blend before post-processing: ``"probs"`` fp32 ``[1, C, H, W, D]``, the softmax of the blended logits over the
+        classes; ``"confidence"`` fp32 ``[1, 1, H, W, D]``, the maximum probability; ``"entropy"`` fp32
+        ``[1, 1, H, W, D]``, ``-sum p ln p / ln C`` in [0, 1] (0 for one class)."""
         post = self._post(postprocess)
-        labels, logits = self._run(x, return_logits, None, post)
+        maps = [k for k, on in (("probs", return_probs), ("confidence", return_confidence), ("entropy", return_entropy))
+                if on]
+        labels, logits, extra = self._run(x, return_logits, None, post, maps)
         out = {"labels": labels}
         if return_logits:
             out["logits"] = logits
+        out.update(extra)
         return out
 
     def evaluate(self, x: torch.Tensor, seg: torch.Tensor, postprocess: Optional[Dict] = None) -> Tuple[float, float]:
@@ -415,7 +485,7 @@ class SlidingWindowPredictor:
         post = self._post(postprocess)
         self._check_input(seg, "seg", channels=1)
         ncls, sp, pc, tol = S._check_metric_args(self.ncls, spacing, percentile, tolerance)
-        labels, _ = self._run(x, False, seg, post)
+        labels, _, _ = self._run(x, False, seg, post)
         scount, recs = S._metrics_launch(labels, seg, ncls, sp, pc, tol, include_background)
         host = torch.cat([self.counts.reshape(-1), scount.reshape(-1), recs.reshape(-1)]).cpu()
         c = host[:3 * ncls].reshape(ncls, 3).to(torch.float64)
@@ -456,7 +526,7 @@ class SlidingWindowPredictor:
         from . import scan
         post = self._post(postprocess)
         x = self._prepare_scan(raw, geom, restore, postprocess, intensity)
-        labels, logits = self._run(x, restore == "logits", None, post)
+        labels, logits, _ = self._run(x, restore == "logits", None, post)
         native = scan.restore_labels(labels, geom) if restore == "labels" else scan.restore_labels_from_logits(logits, geom)
         return {"labels": native, "labels_oriented": labels}
 
@@ -475,7 +545,8 @@ class SlidingWindowPredictor:
 def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], num_classes: int, out_size=None,
                         axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
                         sub_batch: int = 10, graph: bool = False, restore: str = "labels",
-                        postprocess: Optional[Dict] = None, **intensity) -> Dict[str, torch.Tensor]:
+                        postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                        **intensity) -> Dict[str, torch.Tensor]:
     """One-shot ``SlidingWindowPredictor(...).predict_scan(raw, geom, restore, postprocess, **intensity)`` with
     ``geom = ScanGeometry.from_affine(raw's spatial shape, affine, axcodes, out_size)``; also returns ``"geometry"``."""
     from . import scan
@@ -483,7 +554,8 @@ def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], nu
         raise ValueError("raw must be a [C, H, W, D] (or [H, W, D] / [1, C, H, W, D]) tensor")
     geom = scan.ScanGeometry.from_affine(tuple(raw.shape[-3:]), affine, axcodes, out_size)
     cin = 1 if raw.dim() == 3 else int(raw.shape[-4])
-    p = SlidingWindowPredictor(model, geom.size, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph)
+    p = SlidingWindowPredictor(model, geom.size, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph,
+                               mirror_axes)
     out = p.predict_scan(raw, geom, restore, postprocess, **intensity)
     out["geometry"] = geom
     return out
@@ -491,23 +563,27 @@ def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], nu
 
 def predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10, graph: bool = False,
-                   return_logits: bool = False, postprocess: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
-    """One-shot ``SlidingWindowPredictor(...).predict(x, return_logits, postprocess)`` for ``x [1, Cin, H, W, D]``."""
+                   return_logits: bool = False, postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                   return_probs: bool = False, return_confidence: bool = False,
+                   return_entropy: bool = False) -> Dict[str, torch.Tensor]:
+    """One-shot ``SlidingWindowPredictor(..., mirror_axes=mirror_axes).predict(x, return_logits, postprocess, ...)`` for
+    ``x [1, Cin, H, W, D]``."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph)
-    return p.predict(x, return_logits, postprocess)
+                               graph, mirror_axes)
+    return p.predict(x, return_logits, postprocess, return_probs, return_confidence, return_entropy)
 
 
 def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
                     mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                    graph: bool = False, postprocess: Optional[Dict] = None) -> Tuple[float, float]:
+                    graph: bool = False, postprocess: Optional[Dict] = None,
+                    mirror_axes: Sequence[int] = ()) -> Tuple[float, float]:
     """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg, postprocess)``: whole-volume (mean IoU, mean Dice)."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph)
+                               graph, mirror_axes)
     return p.evaluate(x, seg, postprocess)
 
 
@@ -515,10 +591,10 @@ def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequ
                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0), percentile: float = 95.0,
                             tolerance: float = 1.0, include_background: bool = False,
-                            postprocess: Optional[Dict] = None) -> Dict[str, object]:
+                            postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = ()) -> Dict[str, object]:
     """One-shot ``SlidingWindowPredictor(...).evaluate_surface(x, seg, ...)``: whole-volume surface metrics + IoU / Dice."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph)
+                               graph, mirror_axes)
     return p.evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)

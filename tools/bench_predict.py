@@ -4,16 +4,20 @@ recorded graph per sub-batch, timed on device events after a warm-up volume.  Tw
   cfg1_96  : the cfg1 model (window 7^3), roi 96^3, a 1x1x256x256x160 volume, overlap 0.5, sub-batch 4
   yml_128x8: window (8, 8, 4), roi 128x128x8, a 1x1x512x512x96 volume, overlap 0.5, sub-batch 10
 One JSON line per (shape, mode): windows/s, volumes/s, ms per volume, and the algorithmic bytes of gather + blend +
-finalize per volume (from the shapes, below).
+finalize per volume (from the shapes, below).  ``--mirror-axes 0,1,2`` turns on mirror test-time augmentation (the line
+then also gives windows x flips per second), ``--maps`` asks for the probability, confidence and entropy maps (the
+probability finalize instead of the plain one).
 
 Kernel shares come from a run under the kernel tracer:
     rocprofv3 --kernel-trace --stats -d OUT -o pred -- python tools/bench_predict.py --volumes 2
 then ``python tools/bench_predict.py --stats OUT/.../pred_kernel_stats.csv --volumes 2`` prints the stitching kernels'
-share of kernel time and their bytes / time against 6.3 TB/s (bytes of that run, from the traffic model below)."""
+share of kernel time and their bytes / time against 6.3 TB/s (bytes of that run, from the traffic model below).  Give
+``--stats`` the ``--mirror-axes`` / ``--maps`` / ``--shape`` of the profiled run."""
 import argparse
 import csv
 import json
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,17 +31,24 @@ SHAPES = {
 NCLS, CIN = 2, 1
 
 
-def traffic(name):
+def parse_axes(text):
+    return tuple(int(a) for a in text.split(",") if a.strip() != "")
+
+
+def traffic(name, mirror_axes=(), maps=False):
     """Algorithmic bytes of one predicted volume per kernel family: gather reads and writes every window element of each
-    sub-batch (tail slots included); blend reads the logits of the valid windows and reads + writes the accumulator and
+    sub-batch (tail slots included); blend reads the logits of the valid entries and reads + writes the accumulator and
     weight sum over each sub-batch's union box; finalize reads the accumulator and weight sum of every image voxel and
-    writes one label byte."""
+    writes one label byte (with ``maps``: plus the C + 2 fp32 maps).  Under augmentation the entries are every window
+    under every flip code, window-major, and the blend also reads + writes the compensation words over the box."""
     import numpy as np
-    from mivp_amd.inference import window_origins
+    from mivp_amd.inference import flip_codes, window_origins
     s = SHAPES[name]
     roi, B = s["roi"], s["sub_batch"]
     rvol = int(np.prod(roi))
-    o = window_origins(s["image"], roi, 0.5)
+    flips = len(flip_codes(mirror_axes))
+    windows = window_origins(s["image"], roi, 0.5).shape[0]
+    o = np.repeat(window_origins(s["image"], roi, 0.5), flips, axis=0)
     n = o.shape[0]
     n_sub = -(-n // B)
     box = 0
@@ -45,13 +56,13 @@ def traffic(name):
         w = o[k * B:(k + 1) * B]
         box += int(np.prod([w[:, a].max() - w[:, a].min() + roi[a] for a in range(3)]))
     nvox = int(np.prod(s["image"]))
-    return {"windows": n, "sub_batches": n_sub,
+    return {"windows": windows, "flips": flips, "sub_batches": n_sub,
             "gather": 2 * n_sub * B * CIN * rvol * 4,
-            "blend": n * rvol * NCLS * 4 + 2 * box * (NCLS + 1) * 4,
-            "finalize": nvox * ((NCLS + 1) * 4 + 1)}
+            "blend": n * rvol * NCLS * 4 + 2 * box * (NCLS + 1) * 4 * (2 if flips > 1 else 1),
+            "finalize": nvox * ((NCLS + 1) * 4 + 1 + ((NCLS + 2) * 4 if maps else 0))}
 
 
-def run(name, volumes, warmup):
+def run(name, volumes, warmup, mirror_axes=(), maps=False):
     import torch
     from mivp_amd import train
     from mivp_amd.inference import SlidingWindowPredictor
@@ -62,49 +73,57 @@ def run(name, volumes, warmup):
     torch.manual_seed(0)
     model = SwinUnetR(conf).to(dev).eval()
     x = torch.rand((1, CIN) + s["image"], generator=torch.Generator().manual_seed(1)).to(dev)
-    t = traffic(name)
+    t = traffic(name, mirror_axes, maps)
     algo = t["gather"] + t["blend"] + t["finalize"]
+    kw = dict(return_probs=True, return_confidence=True, return_entropy=True) if maps else {}
     out = []
     for mode in ("eager", "graph"):
         p = SlidingWindowPredictor(model, s["image"], CIN, NCLS, s["roi"], overlap=0.5, mode="gaussian",
-                                   sub_batch=s["sub_batch"], graph=(mode == "graph"))
+                                   sub_batch=s["sub_batch"], graph=(mode == "graph"), mirror_axes=mirror_axes)
         for _ in range(warmup):
-            labels = p.predict(x)["labels"]
+            labels = p.predict(x, **kw)["labels"]
         torch.cuda.synchronize()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         for _ in range(volumes):
-            labels = p.predict(x)["labels"]
+            labels = p.predict(x, **kw)["labels"]
         b.record()
         torch.cuda.synchronize()
         ms = a.elapsed_time(b) / volumes
         out.append({"shape": name, "mode": mode, "image": list(s["image"]), "roi": list(s["roi"]),
-                    "sub_batch": s["sub_batch"], "windows": t["windows"], "ms_per_volume": round(ms, 3),
+                    "sub_batch": s["sub_batch"], "windows": t["windows"], "mirror_axes": list(mirror_axes),
+                    "flips": t["flips"], "maps": bool(maps), "ms_per_volume": round(ms, 3),
                     "volumes_per_s": round(1e3 / ms, 3), "windows_per_s": round(t["windows"] * 1e3 / ms, 1),
+                    "window_flips_per_s": round(t["windows"] * t["flips"] * 1e3 / ms, 1),
                     "stitch_bytes_per_volume": algo, "label_hist": torch.bincount(labels.reshape(-1).long()).tolist()})
         del p
         torch.cuda.empty_cache()
     return out
 
 
-def stats(path, volumes, warmup):
-    """Share of kernel time and bytes / time of the stitching kernels in a profiled run of both shapes."""
-    fam = {"gather": "k_window_gather", "blend": "k_window_blend", "finalize": "k_stitch_finalize",
-           "advance": "k_window_advance"}
+def stats(path, volumes, warmup, shapes, mirror_axes=(), maps=False):
+    """Share of kernel time and bytes / time of the stitching kernels in a profiled run of ``shapes``.  The flip-aware
+    gather / blend and the probability finalize are the kernels of a run with ``mirror_axes`` / ``maps``."""
+    tta = len(mirror_axes) > 0
+    fam = {"gather": "k_window_gather_tta" if tta else "k_window_gather",
+           "blend": "k_window_blend_tta" if tta else "k_window_blend",
+           "finalize": "k_stitch_finalize_probs" if maps else "k_stitch_finalize", "advance": "k_window_advance"}
     total_ns, fam_ns, fam_calls = 0.0, {k: 0.0 for k in fam}, {k: 0 for k in fam}
     with open(path) as f:
         for row in csv.DictReader(f):
             ns = float(row.get("TotalDurationNs", 0) or 0)
             total_ns += ns
+            m = re.search(r"\bk_[a-z_]+", row.get("Name", ""))
+            kernel = m.group(0) if m else ""
             for k, kname in fam.items():
-                if kname in row.get("Name", ""):
+                if kernel == kname:
                     fam_ns[k] += ns
                     fam_calls[k] += int(row.get("Calls", 0) or 0)
     # predicts per shape and mode: warm-up + timed volumes; graph recording adds two eager sub-batches (not counted)
     nvol = 2 * (volumes + warmup)
     byts = {k: 0 for k in ("gather", "blend", "finalize")}
-    for name in SHAPES:
-        t = traffic(name)
+    for name in shapes:
+        t = traffic(name, mirror_axes, maps)
         for k in byts:
             byts[k] += nvol * t[k]
     for k in fam:
@@ -125,15 +144,20 @@ def main():
     ap.add_argument("--volumes", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--shape", choices=list(SHAPES) + ["all"], default="all")
-    ap.add_argument("--stats", help="kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of this tool (all shapes)")
+    ap.add_argument("--mirror-axes", type=parse_axes, default=(), metavar="A[,A..]",
+                    help="mirror test-time augmentation over these spatial axes (0 = H, 1 = W, 2 = D), e.g. 0,1,2")
+    ap.add_argument("--maps", action="store_true", help="also return probs / confidence / entropy (probability finalize)")
+    ap.add_argument("--stats", help="kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of this tool with the same "
+                                    "--shape / --mirror-axes / --maps")
     a = ap.parse_args()
     import mivp_amd  # noqa: F401
+    shapes = list(SHAPES) if a.shape == "all" else [a.shape]
     if a.stats:
-        stats(a.stats, a.volumes, a.warmup)
+        stats(a.stats, a.volumes, a.warmup, shapes, a.mirror_axes, a.maps)
         return
-    for name in (SHAPES if a.shape == "all" else [a.shape]):
+    for name in shapes:
         try:
-            lines = run(name, a.volumes, a.warmup)
+            lines = run(name, a.volumes, a.warmup, a.mirror_axes, a.maps)
         except (RuntimeError, ValueError) as exc:                # a shape the model cannot run: say so, go on
             lines = [{"shape": name, "error": str(exc)[:300]}]
         for line in lines:
