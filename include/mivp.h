@@ -777,6 +777,64 @@ int mivp_scan_restore_argmax(const float* logits, int32_t C, const int32_t* src_
                              const int32_t* axes, const int32_t* tables, int32_t interp, int32_t flags, uint8_t* out,
                              mivp_stream_t stream);
 
+/* Per-lesion region statistics and lesion-wise detection metrics (csrc/regions.hip; mivp_amd/regions.py).
+ * These entry points joined ABI 18 without a bump: they are additive and no earlier signature changed.  dims = {H, W, D}
+ * (host), volumes [H][W][D] row-major, fewer than 2^31 voxels; connectivity as mivp_label_components.  No host
+ * synchronisation: every count stays on the device.  Integer results are exact and bitwise reproducible.
+ *   MivpRegionTable: DEVICE arrays of `capacity` entries, entry r describes the component labelled r + 1.  n[0] = the number
+ *     of components (it may exceed capacity; entries at and above min(n, capacity) are zero), overflow[0] = (n > capacity).
+ *     cls = the class, size = voxels, first = linear index of the first voxel in raster order, bbox [6] = minimum h, w, d
+ *     and maximum h, w, d (inclusive), coord_sum [3] = sums of h, w, d.  image_dtype: -1 no image (vmin, vmax, vsum, vsqsum
+ *     may be NULL), else the dtype of mivp_scan_prepare (0 uint8, 1 int32, 3 float32, 4 int16): vmin / vmax are int32
+ *     (float32 for a float image), vsum / vsqsum int64 and exact while they fit (int64 arithmetic wraps modulo 2^64, which
+ *     only the sum of squares of an int32 image with values beyond about 2^31 / sqrt(voxels) can reach) (float64 for a float image: added with hardware float64
+ *     atomics, so these two alone depend on the order of arrival in their last bits).
+ *   mivp_region_stats: x (dtype 0 uint8, 1 int32, 2 int64, 3 float32) is a class map; the voxels whose class (value in
+ *     [0, C), integer for floats) is a set bit of class_mask (bits 1..C-1 only, not empty) are labelled as
+ *     mivp_label_components labels them: labels int32 [H][W][D], 16-byte aligned, numbered 1..n in the raster order of first
+ *     voxels.  One pass over labels (and image, of table->image_dtype, same shape) fills the table: runs along D per lane,
+ *     one LDS table per workgroup, one set of global atomics per (workgroup, region).  C <= 16.  workspace:
+ *     mivp_region_stats_ws(dims) bytes.
+ *   mivp_region_overlap: the sparse table of n_pt = |p and t| over the pairs (p of labels_pred, t of labels_target) of one
+ *     class with p <= pred->capacity and t <= target->capacity: an open-addressing hash table in `pairs`
+ *     (mivp_region_overlap_ws(max_pairs) bytes, 8-byte aligned) of int64 words: [0] the number of distinct pairs, [1] the
+ *     overflow flag (more than max_pairs distinct pairs; the table is then incomplete), then keys [S] = (p << 32) | t,
+ *     0 = empty, then counts [S], S = the smallest power of two >= max(64, 2 * max_pairs).  Probing is bounded: a full table
+ *     sets the flag and the launch ends.
+ *   mivp_lesion_match: components smaller than min_size are ignored on both sides.  Per reference lesion t (arrays of
+ *     target->capacity entries): overlap = sum_p n_pt, touching = sum of |p| over the p with n_pt > 0, best_pred = the p
+ *     with the largest n_pt (ties: the smaller label; 0 when none), best_overlap = its n_pt, detected = 1 iff some pair
+ *     (p, t) matches: IoU = (double)n_pt / (double)(|p| + |t| - n_pt) > 0 when iou_threshold == 0, else >= iou_threshold.
+ *     matched [pred->capacity] = 1 iff p has a match.  counts int64 [C][4] = (reference lesions, predicted lesions,
+ *     detected reference lesions, matched predictions) per class. */
+typedef struct {
+    int32_t capacity;
+    int32_t image_dtype;
+    int32_t* n;
+    int32_t* overflow;
+    int32_t* cls;
+    int64_t* size;
+    int64_t* first;
+    int32_t* bbox;
+    int64_t* coord_sum;
+    void* vmin;
+    void* vmax;
+    void* vsum;
+    void* vsqsum;
+} MivpRegionTable;
+size_t mivp_region_stats_ws(const int32_t* dims);
+int mivp_region_stats(const void* x, int32_t dtype, const int32_t* dims, int32_t C, uint32_t class_mask,
+                      int32_t connectivity, const void* image, int32_t* labels, const MivpRegionTable* table,
+                      void* workspace, mivp_stream_t stream);
+size_t mivp_region_overlap_ws(int64_t max_pairs);
+int mivp_region_overlap(const int32_t* labels_pred, const int32_t* labels_target, const int32_t* dims,
+                        const MivpRegionTable* pred, const MivpRegionTable* target, int64_t max_pairs, void* pairs,
+                        mivp_stream_t stream);
+int mivp_lesion_match(const MivpRegionTable* pred, const MivpRegionTable* target, const void* pairs, int64_t max_pairs,
+                      int32_t C, int64_t min_size, double iou_threshold, int64_t* counts, int64_t* overlap,
+                      int64_t* touching, int64_t* best_overlap, int32_t* best_pred, int32_t* detected, int32_t* matched,
+                      mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

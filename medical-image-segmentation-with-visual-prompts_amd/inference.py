@@ -461,6 +461,33 @@ class SlidingWindowPredictor:
         out.update(extra)
         return out
 
+    def predict_regions(self, x: torch.Tensor, return_logits: bool = False, postprocess: Optional[Dict] = None,
+                        return_probs: bool = False, return_confidence: bool = False, return_entropy: bool = False,
+                        spacing: Sequence[float] = (1.0, 1.0, 1.0), **region_kwargs) -> Dict[str, object]:
+        """``predict(x, ...)`` plus ``"regions"``: the ``mivp_amd.regions.RegionTable`` of the returned labels
+        (``region_kwargs``: ``connectivity``, ``classes``, ``max_regions`` of ``region_stats``), with the confidence map
+        as its image when ``return_confidence`` is set (``vmean`` is then the mean confidence per lesion).  No host read."""
+        from . import regions
+        regions.check_region_kwargs(self.ncls, spacing, **region_kwargs)
+        out = self.predict(x, return_logits, postprocess, return_probs, return_confidence, return_entropy)
+        out["regions"] = regions.region_stats(out["labels"], self.ncls, image=out.get("confidence"), spacing=spacing,
+                                              **region_kwargs)
+        return out
+
+    def evaluate_lesions(self, x: torch.Tensor, seg: torch.Tensor, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                         postprocess: Optional[Dict] = None, **lesion_kwargs):
+        """Lesion-wise detection metrics of the whole-volume prediction against ``seg [1, 1, H, W, D]``: the
+        ``mivp_amd.regions.LesionReport`` of ``lesion_metrics(predict(x, postprocess=postprocess)["labels"], seg,
+        num_classes, spacing, **lesion_kwargs)`` (``connectivity``, ``iou_threshold``, ``min_size``, ``classes``,
+        ``max_regions``, ``max_pairs``).  Prediction, post-processing and the metrics run with no host read in between;
+        ``LesionReport.cpu()`` synchronises."""
+        from . import regions
+        post = self._post(postprocess)
+        self._check_input(seg, "seg", channels=1)
+        regions.check_lesion_kwargs(self.ncls, spacing, **lesion_kwargs)
+        labels, _, _ = self._run(x, False, None, post)
+        return regions.lesion_metrics(labels, seg, self.ncls, spacing, **lesion_kwargs)
+
     def evaluate(self, x: torch.Tensor, seg: torch.Tensor, postprocess: Optional[Dict] = None) -> Tuple[float, float]:
         """(mean IoU, mean Dice) of the whole-volume prediction against ``seg [1, 1, H, W, D]`` (class indices), with the
         formulas of ``SegMetrics.compute``; the per-class counts stay in ``self.counts``.  One host read.  With
@@ -598,3 +625,16 @@ def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequ
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
                                graph, mirror_axes)
     return p.evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)
+
+
+def evaluate_volume_lesions(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
+                            overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                            graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                            postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (), **lesion_kwargs):
+    """One-shot ``SlidingWindowPredictor(...).evaluate_lesions(x, seg, spacing, postprocess, **lesion_kwargs)``: the
+    lesion-wise ``mivp_amd.regions.LesionReport`` of the whole-volume prediction."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        raise ValueError("x must be a [1, C, H, W, D] tensor")
+    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
+                               graph, mirror_axes)
+    return p.evaluate_lesions(x, seg, spacing, postprocess, **lesion_kwargs)

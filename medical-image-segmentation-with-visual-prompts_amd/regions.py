@@ -1,0 +1,389 @@
+"""Per-lesion region statistics and lesion-wise detection metrics on the GPU (csrc/regions.hip).
+
+Definitions (written out, as in ``mivp_amd.components``; ``tests/regions_ref.py`` restates them in numpy / scipy):
+
+- **Layout.**  Class maps are ``[1, 1, H, W, D]`` or ``[H, W, D]`` GPU tensors, uint8, int32, int64, float32 or bool, with
+  the layout and class rules of ``mivp_amd.components`` (a value outside ``[0, C)`` or a non-integer float belongs to no
+  class).  ``image`` has the same spatial shape and is int16, uint8, int32 or float32 (finite values).
+- **Regions.**  The voxels whose class is in ``classes`` (default ``1..C-1``) are labelled per class value with the
+  adjacency rule and numbering of ``components.label_components``: 1..n in the raster order of each region's first voxel,
+  over all listed classes together.  Regions of other classes are not listed and take no number.
+- **RegionTable.**  Device tensors of ``max_regions`` entries, entry ``r`` describing the region labelled ``r + 1``:
+  ``cls`` int32, ``size`` int64 (voxels), ``first`` int64 (linear index of the first voxel), ``bbox`` int32 ``[6]`` (minimum
+  h, w, d then maximum h, w, d, inclusive), ``coord_sum`` int64 ``[3]``; with an image ``vmin`` / ``vmax`` (int32, or
+  float32 for a float image) and ``vsum`` / ``vsqsum`` (int64, or float64 for a float image; the int64 sums are exact
+  while they fit: only the squares of an int32 image with values beyond about 2^31 / sqrt(voxels) can wrap).  ``n`` (device int32) is the
+  number of regions, ``overflow`` (device int32) says that it exceeds ``max_regions``; ``labels`` is the dense int32 label
+  map.  Derived values are properties computed with torch in float64 from the integer fields: ``volume_mm3`` = size *
+  prod(spacing); ``centroid`` = coord_sum / size; ``centroid_mm`` = centroid * spacing; ``extent`` = bbox max - min + 1;
+  ``vmean`` = vsum / size; ``vstd`` = sqrt(max(vsqsum / size - vmean^2, 0)) (the population deviation).
+- **Lesion matching.**  Prediction and reference are both labelled as above.  Regions smaller than ``min_size`` voxels are
+  ignored on both sides.  For a predicted region p and a reference region t of the same class n_pt = |p and t|.  The pair is
+  a *match* when n_pt > 0 and IoU(p, t) = n_pt / (|p| + |t| - n_pt) meets the threshold: ``> 0`` when ``iou_threshold ==
+  0``, else ``>= iou_threshold``, the division being one float64 division.  t is *detected* iff it has a match; p is a
+  *true positive* iff it has a match, else a false positive.  ``counts`` int64 ``[C, 4]`` = (n_ref, n_pred, detected,
+  true-positive predictions) per class; ``sensitivity`` = detected / n_ref, ``precision`` = tp / n_pred, ``f1`` =
+  2 tp' / (2 tp' + fn + fp) with tp' = detected, fn = n_ref - detected, fp = n_pred - tp; each NaN where its denominator
+  is 0.  Per reference lesion: ``size``, ``overlap`` = sum_p n_pt, ``touching`` = sum of |p| over the p with n_pt > 0,
+  ``best_pred`` = the p with the largest n_pt (ties to the smaller label, 0 when none), ``best_overlap`` its n_pt,
+  ``best_iou``, ``dice_t`` = 2 overlap / (size + touching), ``detected``; ``valid`` marks the lesions of at least
+  ``min_size`` voxels (the others hold zeros).  ``lesion_dice[c]`` = sum_t dice_t / (n_ref + false positives), NaN when
+  that is 0: the lesion-wise Dice of the multi-lesion benchmarks **without their dilation of the reference** (they
+  dilate the reference before the components are taken, so that nearby lesions merge; here they do not).
+
+Numerics: every integer field is exact and bitwise reproducible, and so is everything derived from integers.  For float32
+images ``vmin`` / ``vmax`` are exact, and ``vsum`` / ``vsqsum`` are float64 sums added with hardware atomics: **these two
+(and ``vmean`` / ``vstd`` from them) are the one pair of fields that is not bitwise reproducible**; their error is within
+``size * 2^-53 * sum|x|`` (``sum x^2``) of any other float64 summation order.
+
+Nothing here reads back to the host, so ``region_stats`` and ``lesion_metrics`` can be recorded in a ``torch.cuda.graph``.
+``RegionTable.cpu()`` and ``LesionReport.cpu()`` are the synchronising calls; they raise ``RuntimeError`` on overflow.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import numbers
+from typing import Dict, Iterable, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .components import _check_connectivity, _prepare
+from .surface import _DTYPES, _check_classes, _check_gpu, _check_spacing, _i3
+
+_IMAGE_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.float32: 3, torch.int16: 4}
+
+
+class _CTable(C.Structure):
+    _fields_ = [("capacity", C.c_int32), ("image_dtype", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("n", "overflow", "cls", "size", "first", "bbox", "coord_sum", "vmin", "vmax", "vsum",
+                                  "vsqsum")]
+
+
+def _check_region_args(num_classes, connectivity=26, classes: Optional[Iterable[int]] = None, max_regions=4096,
+                       spacing=(1.0, 1.0, 1.0)):
+    """-> (num_classes, class bit mask, connectivity, max_regions, spacing)."""
+    ncls = _check_classes(num_classes)
+    conn = _check_connectivity(connectivity)
+    cls = list(range(1, ncls)) if classes is None else list(classes)
+    if not cls:
+        raise ValueError("classes is empty" + (" (num_classes=1 has no foreground class)" if classes is None else ""))
+    for c in cls:
+        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 1 <= c < ncls:
+            raise ValueError(f"classes must be ints in 1..{ncls - 1}, got {c!r}")
+    if len(set(cls)) != len(cls):
+        raise ValueError(f"classes has duplicates: {cls}")
+    mask = 0
+    for c in cls:
+        mask |= 1 << int(c)
+    if isinstance(max_regions, bool) or not isinstance(max_regions, numbers.Integral) or not 1 <= max_regions <= 2 ** 24:
+        raise ValueError(f"max_regions must be an int in 1..2^24, got {max_regions!r}")
+    return ncls, mask, conn, int(max_regions), _check_spacing(spacing)
+
+
+def _check_lesion_args(iou_threshold=0.0, min_size=0, max_regions=4096, max_pairs=None):
+    """-> (iou_threshold, min_size, max_pairs)."""
+    if isinstance(iou_threshold, bool) or not isinstance(iou_threshold, numbers.Real) or \
+            not (math.isfinite(iou_threshold) and 0.0 <= iou_threshold <= 1.0):
+        raise ValueError(f"iou_threshold must be in [0, 1], got {iou_threshold!r}")
+    if isinstance(min_size, bool) or not isinstance(min_size, numbers.Integral) or min_size < 0:
+        raise ValueError(f"min_size must be a non-negative int, got {min_size!r}")
+    if max_pairs is None:
+        max_pairs = 4 * int(max_regions)
+    if isinstance(max_pairs, bool) or not isinstance(max_pairs, numbers.Integral) or not 1 <= max_pairs <= 2 ** 28:
+        raise ValueError(f"max_pairs must be an int in 1..2^28, got {max_pairs!r}")
+    return float(iou_threshold), min(int(min_size), 2 ** 31 - 1), int(max_pairs)
+
+
+REGION_KWARGS = ("connectivity", "classes", "max_regions")
+LESION_KWARGS = ("connectivity", "iou_threshold", "min_size", "classes", "max_regions", "max_pairs")
+
+
+def check_region_kwargs(num_classes, spacing=(1.0, 1.0, 1.0), **kwargs):
+    """Validate the keyword arguments a caller will forward to ``region_stats`` (``REGION_KWARGS``), before it spends
+    time on anything else; raises ``ValueError`` like ``region_stats`` would."""
+    unknown = set(kwargs) - set(REGION_KWARGS)
+    if unknown:
+        raise ValueError(f"unknown region_stats arguments {sorted(unknown)}")
+    _check_region_args(num_classes, spacing=spacing, **kwargs)
+
+
+def check_lesion_kwargs(num_classes, spacing=(1.0, 1.0, 1.0), **kwargs):
+    """The same for ``lesion_metrics`` (``LESION_KWARGS``)."""
+    unknown = set(kwargs) - set(LESION_KWARGS)
+    if unknown:
+        raise ValueError(f"unknown lesion_metrics arguments {sorted(unknown)}")
+    r = _check_region_args(num_classes, spacing=spacing, **{k: v for k, v in kwargs.items() if k in REGION_KWARGS})
+    _check_lesion_args(kwargs.get("iou_threshold", 0.0), kwargs.get("min_size", 0), r[3], kwargs.get("max_pairs"))
+
+
+def _check_image(image, dims, device) -> torch.Tensor:
+    _check_gpu("image", image)
+    if image.device != device:
+        raise ValueError(f"image is on {image.device}, labels on {device}")
+    if image.dim() == 5 and image.shape[0] == 1 and image.shape[1] == 1:
+        image = image[0, 0]
+    if image.dim() != 3 or tuple(image.shape) != tuple(dims):
+        raise ValueError(f"image must have the labels' spatial shape {tuple(dims)}, got {tuple(image.shape)}")
+    if image.dtype not in _IMAGE_DTYPES:
+        raise ValueError(f"image must be int16, uint8, int32 or float32, got {image.dtype}")
+    return image.contiguous()
+
+
+class RegionTable:
+    """The regions of one class map (the module docstring has every field).  All tensors live on the device."""
+
+    _FIELDS = ("cls", "size", "first", "bbox", "coord_sum")
+    _IMAGE_FIELDS = ("vmin", "vmax", "vsum", "vsqsum")
+
+    def __init__(self, dims, max_regions: int, spacing, device, image_dtype: Optional[torch.dtype]):
+        m = int(max_regions)
+        self.dims, self.max_regions, self.spacing = tuple(int(d) for d in dims), m, tuple(spacing)
+        self.n = torch.empty(1, dtype=torch.int32, device=device)
+        self.overflow = torch.empty(1, dtype=torch.int32, device=device)
+        self.labels = torch.empty(self.dims, dtype=torch.int32, device=device)
+        self.cls = torch.empty(m, dtype=torch.int32, device=device)
+        self.size = torch.empty(m, dtype=torch.int64, device=device)
+        self.first = torch.empty(m, dtype=torch.int64, device=device)
+        self.bbox = torch.empty((m, 6), dtype=torch.int32, device=device)
+        self.coord_sum = torch.empty((m, 3), dtype=torch.int64, device=device)
+        self.image_dtype = image_dtype
+        self.vmin = self.vmax = self.vsum = self.vsqsum = None
+        if image_dtype is not None:
+            isf = image_dtype == torch.float32
+            self.vmin = torch.empty(m, dtype=torch.float32 if isf else torch.int32, device=device)
+            self.vmax = torch.empty_like(self.vmin)
+            self.vsum = torch.empty(m, dtype=torch.float64 if isf else torch.int64, device=device)
+            self.vsqsum = torch.empty_like(self.vsum)
+        self._c = _CTable(m, -1 if image_dtype is None else _IMAGE_DTYPES[image_dtype],
+                          *[None if t is None else t.data_ptr()
+                            for t in (self.n, self.overflow, self.cls, self.size, self.first, self.bbox, self.coord_sum,
+                                      self.vmin, self.vmax, self.vsum, self.vsqsum)])
+
+    # ---- derived, float64, from the integer fields
+    def _per(self, a: torch.Tensor) -> torch.Tensor:
+        size = self.size.to(torch.float64)
+        return a.to(torch.float64) / (size if a.dim() == 1 else size[:, None])
+
+    @property
+    def volume_mm3(self) -> torch.Tensor:
+        return self.size.to(torch.float64) * (self.spacing[0] * self.spacing[1] * self.spacing[2])
+
+    @property
+    def centroid(self) -> torch.Tensor:
+        return self._per(self.coord_sum)
+
+    @property
+    def centroid_mm(self) -> torch.Tensor:
+        return self.centroid * torch.tensor(self.spacing, dtype=torch.float64, device=self.size.device)
+
+    @property
+    def extent(self) -> torch.Tensor:
+        return self.bbox[:, 3:] - self.bbox[:, :3] + (self.size > 0).to(torch.int32)[:, None]
+
+    def _need_image(self):
+        if self.vsum is None:
+            raise RuntimeError("this RegionTable was computed without an image")
+
+    @property
+    def vmean(self) -> torch.Tensor:
+        self._need_image()
+        return self._per(self.vsum)
+
+    @property
+    def vstd(self) -> torch.Tensor:
+        self._need_image()
+        m = self.vmean
+        return torch.sqrt(torch.clamp(self._per(self.vsqsum) - m * m, min=0.0))
+
+    def _device_fields(self) -> Dict[str, torch.Tensor]:
+        out = {k: getattr(self, k) for k in self._FIELDS}
+        out.update(volume_mm3=self.volume_mm3, centroid=self.centroid, centroid_mm=self.centroid_mm, extent=self.extent)
+        if self.vsum is not None:
+            out.update({k: getattr(self, k) for k in self._IMAGE_FIELDS})
+            out.update(vmean=self.vmean, vstd=self.vstd)
+        return out
+
+    def check_overflow(self, n: int, overflow: int, what: str = "region table"):
+        if overflow:
+            raise RuntimeError(f"{what} overflow: {n} components, capacity {self.max_regions} (raise max_regions)")
+
+    def cpu(self) -> Dict[str, np.ndarray]:
+        """The one synchronising call: every field and derived value as a numpy array trimmed to ``n`` (plus ``"n"``).
+        Raises ``RuntimeError`` when the map has more regions than ``max_regions``."""
+        fields = self._device_fields()
+        head = torch.stack([self.n[0], self.overflow[0]]).cpu()
+        n, overflow = int(head[0]), int(head[1])
+        self.check_overflow(n, overflow)
+        out = {k: v[:n].cpu().numpy() for k, v in fields.items()}
+        out["n"] = n
+        return out
+
+
+def _stats_launch(v: torch.Tensor, args, image: Optional[torch.Tensor], ws: Optional[torch.Tensor] = None) -> RegionTable:
+    ncls, mask, conn, max_regions, spacing = args
+    dims = tuple(v.shape)
+    tab = RegionTable(dims, max_regions, spacing, v.device, None if image is None else image.dtype)
+    if ws is None:
+        ws = torch.empty(max(int(L.lib().mivp_region_stats_ws(_i3(dims))), 1), dtype=torch.uint8, device=v.device)
+    L.call("mivp_region_stats", L.ptr(v), C.c_int32(_DTYPES[v.dtype]), _i3(dims), C.c_int32(ncls), C.c_uint32(mask),
+           C.c_int32(conn), L.ptr(image), L.ptr(tab.labels), C.byref(tab._c), L.ptr(ws), L.stream())
+    return tab
+
+
+def region_stats(labels: torch.Tensor, num_classes: int, image: Optional[torch.Tensor] = None,
+                 spacing: Sequence[float] = (1.0, 1.0, 1.0), connectivity: int = 26,
+                 classes: Optional[Iterable[int]] = None, max_regions: int = 4096) -> RegionTable:
+    """The connected regions of the class map ``labels`` with their size, first voxel, bounding box and coordinate sums,
+    and with ``image`` their minimum, maximum, sum and sum of squares (the module docstring has the definitions).  No host
+    read: ``RegionTable.cpu()`` synchronises."""
+    _check_gpu("labels", labels)
+    args = _check_region_args(num_classes, connectivity, classes, max_regions, spacing)
+    v = _prepare("labels", labels)
+    img = None if image is None else _check_image(image, v.shape, v.device)
+    return _stats_launch(v, args, img)
+
+
+class LesionReport:
+    """Lesion-wise detection metrics of a prediction against a reference (the module docstring has every field)."""
+
+    def __init__(self, pred_regions: RegionTable, target_regions: RegionTable, num_classes: int, min_size: int,
+                 iou_threshold: float, max_pairs: int):
+        dev = pred_regions.size.device
+        self.pred_regions, self.target_regions = pred_regions, target_regions
+        self.num_classes, self.min_size, self.iou_threshold, self.max_pairs = num_classes, min_size, iou_threshold, max_pairs
+        mt, mp = target_regions.max_regions, pred_regions.max_regions
+        self.pairs = torch.empty(int(L.lib().mivp_region_overlap_ws(C.c_int64(max_pairs))) // 8, dtype=torch.int64, device=dev)
+        self.counts = torch.empty((num_classes, 4), dtype=torch.int64, device=dev)
+        self.overlap = torch.empty(mt, dtype=torch.int64, device=dev)
+        self.touching = torch.empty(mt, dtype=torch.int64, device=dev)
+        self.best_overlap = torch.empty(mt, dtype=torch.int64, device=dev)
+        self.best_pred = torch.empty(mt, dtype=torch.int32, device=dev)
+        self.detected = torch.empty(mt, dtype=torch.int32, device=dev)
+        self.matched = torch.empty(mp, dtype=torch.int32, device=dev)
+
+    @property
+    def size(self) -> torch.Tensor:
+        return self.target_regions.size
+
+    @property
+    def valid(self) -> torch.Tensor:
+        t = self.target_regions
+        return (torch.arange(t.max_regions, device=t.size.device) < t.n) & (t.size >= self.min_size) & (t.size > 0)
+
+    @property
+    def n_pairs(self) -> torch.Tensor:
+        return self.pairs[0]
+
+    @property
+    def pair_overflow(self) -> torch.Tensor:
+        return self.pairs[1]
+
+    @property
+    def best_iou(self) -> torch.Tensor:
+        n = self.best_overlap.to(torch.float64)
+        sp = self.pred_regions.size[(self.best_pred.long() - 1).clamp(min=0)].to(torch.float64)
+        iou = n / (sp + self.size.to(torch.float64) - n)
+        return torch.where(self.best_pred > 0, iou, torch.zeros_like(iou))
+
+    @property
+    def dice_t(self) -> torch.Tensor:
+        d = 2.0 * self.overlap.to(torch.float64) / (self.size + self.touching).to(torch.float64)
+        return torch.where(self.valid, d, torch.zeros_like(d))
+
+    def _ratio(self, num, den):
+        num, den = num.to(torch.float64), den.to(torch.float64)
+        return torch.where(den > 0, num / den, torch.full_like(den, float("nan")))
+
+    @property
+    def sensitivity(self) -> torch.Tensor:
+        return self._ratio(self.counts[:, 2], self.counts[:, 0])
+
+    @property
+    def precision(self) -> torch.Tensor:
+        return self._ratio(self.counts[:, 3], self.counts[:, 1])
+
+    @property
+    def f1(self) -> torch.Tensor:
+        c = self.counts
+        det, fn, fp = c[:, 2], c[:, 0] - c[:, 2], c[:, 1] - c[:, 3]
+        return self._ratio(2 * det, 2 * det + fn + fp)
+
+    @property
+    def lesion_dice(self) -> torch.Tensor:
+        cls = self.target_regions.cls
+        onehot = cls[None, :] == torch.arange(self.num_classes, device=cls.device, dtype=cls.dtype)[:, None]
+        total = torch.where(onehot, self.dice_t[None, :], torch.zeros((), dtype=torch.float64, device=cls.device)).sum(1)
+        c = self.counts
+        return self._ratio(total, c[:, 0] + c[:, 1] - c[:, 3])
+
+    def cpu(self) -> Dict[str, object]:
+        """The one synchronising call: ``counts`` and the per-class values, the per-lesion arrays trimmed to the number
+        of reference lesions, ``pairs`` (int64 ``[K, 3]`` rows (p, t, n_pt) sorted by p then t) and the two region tables
+        (``pred_regions`` / ``target_regions``, as ``RegionTable.cpu()``).  Raises ``RuntimeError`` when either region
+        table or the pair table overflowed."""
+        per_class = dict(counts=self.counts, sensitivity=self.sensitivity, precision=self.precision, f1=self.f1,
+                         lesion_dice=self.lesion_dice)
+        per_lesion = dict(size=self.size, valid=self.valid, overlap=self.overlap, touching=self.touching,
+                          best_pred=self.best_pred, best_overlap=self.best_overlap, best_iou=self.best_iou,
+                          dice_t=self.dice_t, detected=self.detected)
+        matched = self.matched
+        pred, target = self.pred_regions, self.target_regions
+        pf, tf = pred._device_fields(), target._device_fields()
+        head = torch.stack([pred.n[0].long(), pred.overflow[0].long(), target.n[0].long(), target.overflow[0].long(),
+                            self.pairs[0], self.pairs[1]]).cpu()
+        np_, po, nt, to, nk, ko = (int(a) for a in head)
+        pred.check_overflow(np_, po, "predicted region table")
+        target.check_overflow(nt, to, "reference region table")
+        if ko:
+            raise RuntimeError(f"pair table overflow: more than {self.max_pairs} distinct (prediction, reference) pairs "
+                               f"(raise max_pairs)")
+        out = {k: v.cpu().numpy() for k, v in per_class.items()}
+        out.update({k: v[:nt].cpu().numpy() for k, v in per_lesion.items()})
+        out["matched"] = matched[:np_].cpu().numpy()
+        slots = (self.pairs.numel() - 2) // 2
+        keys, cnt = self.pairs[2:2 + slots], self.pairs[2 + slots:]
+        used = keys != 0
+        keys, cnt = keys[used], cnt[used]
+        order = torch.argsort(keys)
+        keys, cnt = keys[order], cnt[order]
+        out["pairs"] = torch.stack([keys >> 32, keys & 0xFFFFFFFF, cnt], 1).cpu().numpy()
+        out["pred_regions"] = {**{k: v[:np_].cpu().numpy() for k, v in pf.items()}, "n": np_}
+        out["target_regions"] = {**{k: v[:nt].cpu().numpy() for k, v in tf.items()}, "n": nt}
+        return out
+
+
+def _lesion_launch(pv: torch.Tensor, tv: torch.Tensor, rargs, largs) -> LesionReport:
+    ncls = rargs[0]
+    thr, min_size, max_pairs = largs
+    pred = _stats_launch(pv, rargs, None)
+    target = _stats_launch(tv, rargs, None)
+    rep = LesionReport(pred, target, ncls, min_size, thr, max_pairs)
+    L.call("mivp_region_overlap", L.ptr(pred.labels), L.ptr(target.labels), _i3(pv.shape), C.byref(pred._c),
+           C.byref(target._c), C.c_int64(max_pairs), L.ptr(rep.pairs), L.stream())
+    L.call("mivp_lesion_match", C.byref(pred._c), C.byref(target._c), L.ptr(rep.pairs), C.c_int64(max_pairs),
+           C.c_int32(ncls), C.c_int64(min_size), C.c_double(thr), L.ptr(rep.counts), L.ptr(rep.overlap),
+           L.ptr(rep.touching), L.ptr(rep.best_overlap), L.ptr(rep.best_pred), L.ptr(rep.detected), L.ptr(rep.matched),
+           L.stream())
+    return rep
+
+
+def lesion_metrics(pred: torch.Tensor, target: torch.Tensor, num_classes: int,
+                   spacing: Sequence[float] = (1.0, 1.0, 1.0), connectivity: int = 26, iou_threshold: float = 0.0,
+                   min_size: int = 0, classes: Optional[Iterable[int]] = None, max_regions: int = 4096,
+                   max_pairs: Optional[int] = None) -> LesionReport:
+    """Lesion-wise detection metrics of the class map ``pred`` against the class map ``target`` (the module docstring has
+    the definitions): per-class counts, sensitivity, precision, F1 and lesion-wise Dice, the per-lesion table and both
+    ``RegionTable``s.  ``max_pairs`` defaults to ``4 * max_regions``.  No host read: ``LesionReport.cpu()`` synchronises."""
+    _check_gpu("pred", pred)
+    _check_gpu("target", target)
+    rargs = _check_region_args(num_classes, connectivity, classes, max_regions, spacing)
+    largs = _check_lesion_args(iou_threshold, min_size, max_regions, max_pairs)
+    pv, tv = _prepare("pred", pred), _prepare("target", target)
+    if pv.shape != tv.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
+    if pv.device != tv.device:
+        raise ValueError(f"pred is on {pv.device}, target on {tv.device}")
+    return _lesion_launch(pv, tv, rargs, largs)
