@@ -326,14 +326,21 @@ def bn_finalize(part, nblk, Cc, count, weight, bias, eps, running_mean, running_
     return scale, shift, mean_rstd
 
 
-def bn_batch_stats(x, weight, bias, eps, running_mean=None, running_var=None, momentum=0.1):
-    """Batch statistics of a bf16 channels-last tensor -> (scale, shift, mean_rstd); running stats updated in place."""
+def bn_partial_sums(x):
+    """Per-block partial sums of a bf16 channels-last tensor: (part [nblk, 2*C] = sum x | sum x^2, nblk, n_vox), the form
+    bn_finalize reduces (upcat_stats returns the same triple)."""
     Cc = x.shape[-1]
     n_vox = x.numel() // Cc
     nblk = _nblk(n_vox * (Cc // 8), Cc // 8)
     part = torch.empty((nblk, 2 * Cc), dtype=torch.float32, device=x.device)
     L.call("mivp_bn_stats", L.ptr(x), C.c_int64(n_vox), C.c_int32(Cc), C.c_int32(nblk), L.ptr(part), L.stream())
-    return bn_finalize(part, nblk, Cc, n_vox, weight, bias, eps, running_mean, running_var, momentum)
+    return part, nblk, n_vox
+
+
+def bn_batch_stats(x, weight, bias, eps, running_mean=None, running_var=None, momentum=0.1):
+    """Batch statistics of a bf16 channels-last tensor -> (scale, shift, mean_rstd); running stats updated in place."""
+    part, nblk, n_vox = bn_partial_sums(x)
+    return bn_finalize(part, nblk, x.shape[-1], n_vox, weight, bias, eps, running_mean, running_var, momentum)
 
 
 def bn_eval_affine(weight, bias, running_mean, running_var, eps):
