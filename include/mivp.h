@@ -835,6 +835,27 @@ int mivp_lesion_match(const MivpRegionTable* pred, const MivpRegionTable* target
                       int64_t* touching, int64_t* best_overlap, int32_t* best_pred, int32_t* detected, int32_t* matched,
                       mivp_stream_t stream);
 
+/* Random intensity augmentation of a resident batch (csrc/intensity.hip; mivp_amd/augment.py).  These entry
+ * points joined ABI 18 without a bump: they are additive and no earlier signature changed.  x: contiguous fp32
+ * [B][C][H][W][D], dims = {H, W, D} (host), fewer than 2^31 voxels per sample, B <= 65535.  slot: DEVICE int32 [B][40], one
+ * record per sample (fp32 values as their bits): [0] flags (bit 0 bias field, 1 std shift, 2 gamma contrast, 3 scale,
+ * 4 histogram shift), [1] n control points (2..12), [2] shift factor, [3] gamma, [4] scale factor, [5..24] the bias
+ * coefficients c[i][j][k] of the Legendre degree-3 field (i + j + k <= 3; i outer, k inner), [25..36] the floating control
+ * points, [37..39] unused.  The steps run in bit order; a sample's statistics run over all of its channels.
+ *   mivp_intensity_ws(B, voxels_per_sample): bytes of the partials workspace (never more than B * 256 * 32).
+ *   mivp_intensity_stats: per-workgroup (min, max, count, mean, M2) partials of v = x * exp(field) (v = x without the bias
+ *     flag) of every sample whose flags need statistics (shift, contrast, histogram); the others are not read.
+ *   mivp_intensity_apply: merges a sample's partials in a fixed order, derives the scalar plan (std, contrast min / range,
+ *     the histogram knots on the tracked extremes) and streams x to out.  out may be x.  A sample without flags is copied
+ *     bit for bit.  Results are bitwise reproducible.
+ * No host synchronisation and no host-side parameter other than the shape: both launches record into a graph and a replay
+ * uses whatever the slot holds then. */
+size_t mivp_intensity_ws(int32_t B, int64_t voxels_per_sample);
+int mivp_intensity_stats(const float* x, int32_t B, int32_t C, const int32_t* dims, const int32_t* slot, void* workspace,
+                         size_t workspace_bytes, mivp_stream_t stream);
+int mivp_intensity_apply(const float* x, int32_t B, int32_t C, const int32_t* dims, const int32_t* slot,
+                         const void* workspace, size_t workspace_bytes, float* out, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

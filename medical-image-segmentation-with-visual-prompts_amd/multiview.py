@@ -326,12 +326,17 @@ def multiview_forward_backward(model, opt, conf, x: torch.Tensor, slot: ViewSlot
     return vec
 
 
-def multiview_step(model, opt, sched, conf, x: torch.Tensor, draws: ViewDraws, slot: Optional[ViewSlot] = None):
+def multiview_step(model, opt, sched, conf, x: torch.Tensor, draws: ViewDraws, slot: Optional[ViewSlot] = None,
+                   augment=None):
     """One eager phase-1 step (multi_view.py:115-176): load the draws, forward / backward, ``opt.step()``, ``sched.step()``.
-    Returns the loss vector [rec, rot, con, mut, total] on the device."""
+    Returns the loss vector [rec, rot, con, mut, total] on the device.  ``augment``: ``augment.IntensityDraws`` (or an
+    ``IntensitySlot`` with draws loaded): the random intensity chain runs on ``x`` before the views are built."""
     check_shapes(tuple(x.shape[2:]), conf.masking_shape, bool(conf.use_mutual_learning))
     slot = slot if slot is not None else make_slot(conf, x)
     slot.load(draws)
+    if augment is not None:
+        from .augment import as_slot, augment_intensity
+        x = augment_intensity(x, as_slot(augment, x))
     vec = multiview_forward_backward(model, opt, conf, x, slot)
     opt.step()
     if sched is not None:
@@ -339,23 +344,32 @@ def multiview_step(model, opt, sched, conf, x: torch.Tensor, draws: ViewDraws, s
     return vec
 
 
-def graphed_multiview_step(model, opt, sched, conf, x: torch.Tensor, draws, warmup: int = 2):
+def graphed_multiview_step(model, opt, sched, conf, x: torch.Tensor, draws, warmup: int = 2, augment=None):
     """``multiview_step`` as a recorded graph (``train.GraphedStep``).  ``x`` is the fixed input tensor (copy new volumes
     into it); ``draws`` is a ViewDraws used for every step or a callable returning the next step's ViewDraws -- the
     step's ``refresh`` loads them into the slot before each warm-up step and replay.  The result's ``loss`` is the loss
     vector [rec, rot, con, mut, total] of the last replay (read it after the replay); ``views`` holds the recorded view
-    buffers."""
+    buffers.  ``augment``: ``augment.IntensityDraws`` used for every step, a callable returning the next step's, or an
+    ``IntensitySlot`` the caller reloads; ``refresh`` loads the draws into the slot (``step.augment_slot``) and the two
+    intensity launches are recorded in front of the view builder (``x`` itself is left as it is)."""
     from .train import GraphedStep
     check_shapes(tuple(x.shape[2:]), conf.masking_shape, bool(conf.use_mutual_learning))
     slot = make_slot(conf, x)
     views = {}
+    aug = None
+    if augment is not None:
+        from . import augment as A
+        aug = augment if isinstance(augment, A.IntensitySlot) else A.IntensitySlot(x.shape[0], x.device)
 
     def refresh():
         slot.load(draws() if callable(draws) else draws)
+        if aug is not None and aug is not augment:
+            aug.load(augment() if callable(augment) else augment)
 
     def forward_backward():
-        return multiview_forward_backward(model, opt, conf, x, slot, keep_views=views)
+        xa = x if aug is None else A.augment_intensity(x, aug)
+        return multiview_forward_backward(model, opt, conf, xa, slot, keep_views=views)
 
     step = GraphedStep(forward_backward, opt, sched, refresh, warmup)
-    step.slot, step.views = slot, views
+    step.slot, step.views, step.augment_slot = slot, views, aug
     return step

@@ -78,11 +78,17 @@ def synthetic_views(conf: Namespace, batch: int, size: int, device, rank: int = 
 
 
 def students_teacher_forward_backward(model: MomentumModel, optimizer, loss_prt: ClusteredPrototypeLoss, conf: Namespace,
-                                      batch: dict, jitters=None) -> torch.Tensor:
+                                      batch: dict, jitters=None, augment=None) -> torch.Tensor:
     """students_teacher.py:150-205 up to (not including) the optimizer step: EMA teacher update, students + teacher forward,
-    prototype loss (+ Dice on student 0 in the supervised modes with real labels), backward."""
+    prototype loss (+ Dice on student 0 in the supervised modes with real labels), backward.  ``augment``: an
+    ``augment.IntensitySlot`` with draws loaded: the random intensity chain runs on the teacher view (the reference augments
+    ``image``, not the ``image_st_i`` copies)."""
     model.update_teacher()
-    out_sts, out_tch = model(batch["image_st"], batch["image"])
+    x_teacher = batch["image"]
+    if augment is not None:
+        from .augment import augment_intensity
+        x_teacher = augment_intensity(x_teacher, augment)
+    out_sts, out_tch = model(batch["image_st"], x_teacher)
     total = torch.zeros((), dtype=torch.float32, device=batch["image"].device)
     if getattr(conf, "use_prototype_assignment", True):
         total = total + loss_prt([o["latent_outputs"] for o in out_sts], out_tch["latent_outputs"], batch["coord_st"],
@@ -96,10 +102,14 @@ def students_teacher_forward_backward(model: MomentumModel, optimizer, loss_prt:
 
 
 def students_teacher_step(model: MomentumModel, optimizer, scheduler, loss_prt: ClusteredPrototypeLoss, conf: Namespace,
-                          batch: dict, jitters=None) -> torch.Tensor:
+                          batch: dict, jitters=None, augment=None) -> torch.Tensor:
     """One iteration of students_teacher.py:150-207: EMA teacher update, students + teacher forward, prototype loss
-    (+ Dice on student 0 in the supervised modes with real labels), backward, optimizer and per-step scheduler."""
-    total = students_teacher_forward_backward(model, optimizer, loss_prt, conf, batch, jitters)
+    (+ Dice on student 0 in the supervised modes with real labels), backward, optimizer and per-step scheduler.
+    ``augment``: ``augment.IntensityDraws`` (or an ``IntensitySlot`` with draws loaded) for the teacher view."""
+    if augment is not None:
+        from .augment import as_slot
+        augment = as_slot(augment, batch["image"])
+    total = students_teacher_forward_backward(model, optimizer, loss_prt, conf, batch, jitters, augment)
     optimizer.step()
     if scheduler is not None:
         scheduler.step()
@@ -107,24 +117,35 @@ def students_teacher_step(model: MomentumModel, optimizer, scheduler, loss_prt: 
 
 
 def graphed_students_teacher_step(model: MomentumModel, optimizer, scheduler, loss_prt: ClusteredPrototypeLoss, conf: Namespace,
-                                  batch: dict, jitters=None, warmup: int = 2):
+                                  batch: dict, jitters=None, warmup: int = 2, augment=None):
     """``students_teacher_step`` recorded in a HIP graph (train.GraphedStep): EMA update, three forwards, prototype loss,
     backward and the optimizer launch replay as one launch; per replay the host draws the students' jitter like the
     reference (``loss_prt.draw_jitters``, or ``jitters()`` if given: a callable returning one list per student), refreshes the
     sampling tables, advances the optimizer's step counts / hyper-parameters and steps the scheduler.  ``batch`` holds the
-    fixed input tensors.  ``loss_prt`` must have been built with ``static_jitter=True``."""
+    fixed input tensors.  ``loss_prt`` must have been built with ``static_jitter=True``.  ``augment``:
+    ``augment.IntensityDraws`` used for every step, a callable returning the next step's, or an ``IntensitySlot`` the caller
+    reloads: the intensity chain on the teacher view, its slot (``step.augment_slot``) refreshed before every replay and its
+    two launches recorded in the graph (``batch["image"]`` itself is left as it is)."""
     from . import train
     if not loss_prt.static_jitter:
         raise ValueError("graph mode needs ClusteredPrototypeLoss(static_jitter=True)")
     n_st = len(batch["image_st"])
     state = {"j": None}
+    aug = None
+    if augment is not None:
+        from .augment import IntensitySlot
+        aug = augment if isinstance(augment, IntensitySlot) else IntensitySlot(batch["image"].shape[0], batch["image"].device)
 
     def refresh():
         state["j"] = jitters() if jitters is not None else loss_prt.draw_jitters(n_st)
         if loss_prt._slots:                                    # (the first eager warm-up step creates and loads the slots itself)
             loss_prt.load_jitters(state["j"])
+        if aug is not None and aug is not augment:
+            aug.load(augment() if callable(augment) else augment)
 
     def forward_backward():
-        return students_teacher_forward_backward(model, optimizer, loss_prt, conf, batch, jitters=state["j"])
+        return students_teacher_forward_backward(model, optimizer, loss_prt, conf, batch, jitters=state["j"], augment=aug)
 
-    return train.GraphedStep(forward_backward, optimizer, scheduler, refresh, warmup)
+    step = train.GraphedStep(forward_backward, optimizer, scheduler, refresh, warmup)
+    step.augment_slot = aug
+    return step
