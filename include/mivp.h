@@ -834,6 +834,31 @@ int mivp_lesion_match(const MivpRegionTable* pred, const MivpRegionTable* target
                       int32_t C, int64_t min_size, double iou_threshold, int64_t* counts, int64_t* overlap,
                       int64_t* touching, int64_t* best_overlap, int32_t* best_pred, int32_t* detected, int32_t* matched,
                       mivp_stream_t stream);
+/* Lesion scores for FROC (additive, ABI 18).  pred must carry a float32 image (image_dtype 3).  One pass over
+ * the pair table with the pair rules of mivp_lesion_match (one device function serves both): best_score [target->capacity]
+ * = the largest pred->vmax over the predictions that match the reference lesion, -inf where none does; score
+ * [pred->capacity] = a copy of pred->vmax.  vmax is exact, so both are bitwise reproducible. */
+int mivp_lesion_best_score(const MivpRegionTable* pred, const MivpRegionTable* target, const void* pairs,
+                           int64_t max_pairs, int64_t min_size, double iou_threshold, float* best_score, float* score,
+                           mivp_stream_t stream);
+
+/* Calibration and threshold-sweep tables (csrc/calibration.hip; mivp_amd/calibration.py).  These entry points
+ * joined ABI 18 without a bump: they are additive and no earlier signature changed.  probs: contiguous fp32 [C][H][W][D],
+ * target: a class map [H][W][D] of target_dtype (0 uint8, 1 int32, 2 int64, 3 float32), dims = {H, W, D} (host), fewer
+ * than 2^31 voxels, 1 <= C <= 16, 1 <= n_bins <= 1024.  With Q = 2^20, q = rint(p * Q) and bin = min(n_bins - 1,
+ * q * n_bins >> 20), a voxel whose C probabilities are all in [0, 1] and whose reference value is a class adds to C + 1
+ * rows: rows 0..C-1 one-vs-rest (p = p_c, y = [target == c]), row C top-label (p = max p_c, y = [argmax == target], the
+ * lowest index among equals).  A voxel with a probability outside [0, 1] (or NaN) only adds 1 to n_invalid; otherwise one
+ * whose reference value is no class only adds 1 to n_ignored.
+ *   tables: DEVICE int64 block of mivp_calibration_ws(C, n_bins) bytes, with R = C + 1: count [R][n_bins], pos [R][n_bins]
+ *     (sum of y), qsum [R][n_bins] (sum of q), n [R], n_pos [R], sq_hi [R], sq_lo [R] (sums of e^2 >> 20 and e^2 & (Q - 1)
+ *     for e = |q - y Q|), n_ignored, n_invalid.  The launch ADDS to the block: zero it first, or pool volumes in it.
+ *   flags: bit 0 sums the lanes of a wave that hit the same cell before the atomic (measured slower than plain adds,
+ *     DESIGN 4.22; tools/bench_calibration.py times both).  0 is the default path.
+ * One launch, no host synchronisation, integer atomics only: the result is exact and bitwise reproducible. */
+size_t mivp_calibration_ws(int32_t C, int32_t n_bins);
+int mivp_calibration_hist(const float* probs, const void* target, int32_t target_dtype, const int32_t* dims, int32_t C,
+                          int32_t n_bins, int32_t flags, int64_t* tables, mivp_stream_t stream);
 
 /* Random intensity augmentation of a resident batch (csrc/intensity.hip; mivp_amd/augment.py).  These entry
  * points joined ABI 18 without a bump: they are additive and no earlier signature changed.  x: contiguous fp32

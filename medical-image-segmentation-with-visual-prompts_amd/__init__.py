@@ -15,14 +15,14 @@ __all__ = ["_lib", "geometry"]
 def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
-                "components", "scan", "regions", "augment"):
+                "components", "scan", "regions", "augment", "calibration"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
         from .swin_unetr import SwinUnetR
         return SwinUnetR
     if name in ("SlidingWindowPredictor", "predict_volume", "evaluate_volume", "evaluate_volume_surface",
-                "predict_scan_volume", "evaluate_volume_lesions"):
+                "predict_scan_volume", "evaluate_volume_lesions", "evaluate_volume_calibration"):
         from . import inference
         return getattr(inference, name)
     if name in ("surface_map", "distance_transform_sq", "surface_metrics"):
@@ -31,9 +31,12 @@ def __getattr__(name):
     if name in ("label_components", "postprocess_labels"):
         from . import components
         return getattr(components, name)
-    if name in ("region_stats", "lesion_metrics", "RegionTable", "LesionReport"):
+    if name in ("region_stats", "lesion_metrics", "lesion_score_metrics", "RegionTable", "LesionReport"):
         from . import regions
         return getattr(regions, name)
+    if name in ("calibration_tables", "CalibrationReport"):
+        from . import calibration
+        return getattr(calibration, name)
     if name in ("ScanGeometry", "prepare_scan", "prepare_labels", "restore_labels", "restore_labels_from_logits"):
         from . import scan
         return getattr(scan, name)

@@ -80,6 +80,7 @@ def lib():
         _lib.mivp_region_stats_ws.restype = C.c_size_t
         _lib.mivp_region_overlap_ws.restype = C.c_size_t
         _lib.mivp_intensity_ws.restype = C.c_size_t
+        _lib.mivp_calibration_ws.restype = C.c_size_t
         ver = _lib.mivp_abi_version()
         if ver != ABI_VERSION:
             raise RuntimeError(f"mivp_amd: ABI version mismatch: library {ver}, binding {ABI_VERSION}")

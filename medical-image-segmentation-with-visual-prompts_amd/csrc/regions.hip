@@ -19,6 +19,8 @@
 //   match     one thread per hash slot: per reference lesion overlap, touching and a packed 64-bit atomicMax
 //             (n_pt << 32 | ~p) for best_pred (ties to the smaller label whatever the arrival order), detection flags by
 //             one float64 division per pair; then one thread per region: the per-class counts.  Integer atomics only.
+//   score      one more pass over the hash slots with the same pair rules (pair_counts / pair_matches): per
+//             reference lesion the largest vmax of its matching predictions, an atomicMax on order-preserving keys.
 // Labels above a table's capacity are skipped everywhere (the table's overflow flag says so).
 #include "common.hpp"
 #include <limits.h>
@@ -418,6 +420,16 @@ __global__ __launch_bounds__(TPB) void k_mt_init(Match m, int cap_p, int cap_t, 
     for (int i = i0; i < cap_p; i += gridDim.x * TPB) m.matched[i] = 0;
 }
 
+// The pair rules of DESIGN 4.20, shared by k_mt_pairs and k_bs_pairs.  A pair counts when it overlaps and neither region is
+// below min_size; it is a match when its IoU (one float64 division) meets the threshold.
+MIVP_DEV bool pair_counts(long long n, long long sp, long long st, long long min_size) {
+    return n > 0 && sp >= min_size && st >= min_size;
+}
+MIVP_DEV bool pair_matches(long long n, long long sp, long long st, double thr) {
+    const double iou = (double)n / (double)(sp + st - n);
+    return thr == 0.0 ? iou > 0.0 : iou >= thr;
+}
+
 __global__ __launch_bounds__(TPB) void k_mt_pairs(Pairs p, const long long* __restrict__ size_p,
                                                   const long long* __restrict__ size_t_, long long min_size, double thr,
                                                   Match m) {
@@ -426,16 +438,40 @@ __global__ __launch_bounds__(TPB) void k_mt_pairs(Pairs p, const long long* __re
         if (key == 0ull) continue;
         const int pp = (int)(key >> 32), tt = (int)(unsigned)key;
         const long long n = p.counts[i], sp = size_p[pp - 1], st = size_t_[tt - 1];
-        if (n <= 0 || sp < min_size || st < min_size) continue;
+        if (!pair_counts(n, sp, st, min_size)) continue;
         atomicAdd((u64*)m.overlap + (tt - 1), (u64)n);
         atomicAdd((u64*)m.touching + (tt - 1), (u64)sp);
         atomicMax((u64*)m.best + (tt - 1), ((u64)n << 32) | (u64)(0xFFFFFFFFu - (unsigned)pp));
-        const double iou = (double)n / (double)(sp + st - n);
-        if (thr == 0.0 ? iou > 0.0 : iou >= thr) {
+        if (pair_matches(n, sp, st, thr)) {
             atomicMax(m.detected + (tt - 1), 1);
             atomicMax(m.matched + (pp - 1), 1);
         }
     }
+}
+
+// best_score: per reference lesion the largest vmax over its matching predictions, as order-preserving keys until
+// k_bs_finish decodes them (-inf where there is no match); score: a copy of the predictions' vmax
+__global__ __launch_bounds__(TPB) void k_bs_init(unsigned* __restrict__ best, float* __restrict__ score,
+                                                 const float* __restrict__ vmax_p, int cap_p, int cap_t) {
+    const int i0 = blockIdx.x * TPB + threadIdx.x;
+    for (int i = i0; i < cap_t; i += gridDim.x * TPB) best[i] = okey(-INFINITY);
+    for (int i = i0; i < cap_p; i += gridDim.x * TPB) score[i] = vmax_p[i];
+}
+
+__global__ __launch_bounds__(TPB) void k_bs_pairs(Pairs p, const long long* __restrict__ size_p,
+                                                  const long long* __restrict__ size_t_, const float* __restrict__ vmax_p,
+                                                  long long min_size, double thr, unsigned* __restrict__ best) {
+    for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < p.slots; i += (long)gridDim.x * TPB) {
+        const u64 key = p.keys[i];
+        if (key == 0ull) continue;
+        const int pp = (int)(key >> 32), tt = (int)(unsigned)key;
+        const long long n = p.counts[i], sp = size_p[pp - 1], st = size_t_[tt - 1];
+        if (pair_counts(n, sp, st, min_size) && pair_matches(n, sp, st, thr)) atomicMax(best + (tt - 1), okey(vmax_p[pp - 1]));
+    }
+}
+
+__global__ __launch_bounds__(TPB) void k_bs_finish(unsigned* __restrict__ best, int cap_t) {
+    for (int i = blockIdx.x * TPB + threadIdx.x; i < cap_t; i += gridDim.x * TPB) best[i] = okey_decode_float(best[i]);
 }
 
 __global__ __launch_bounds__(TPB) void k_mt_finish(Tab tp, Tab tt, long long min_size, int C, Match m) {
@@ -556,4 +592,24 @@ extern "C" int mivp_lesion_match(const MivpRegionTable* pred, const MivpRegionTa
                        (const long long*)tt.size, (long long)min_size, iou_threshold, m);
     hipLaunchKernelGGL(k_mt_finish, dim3(stride_grid(cap)), dim3(TPB), 0, st, tp, tt, (long long)min_size, (int)C, m);
     return mivp_check_launch("lesion_match");
+}
+
+extern "C" int mivp_lesion_best_score(const MivpRegionTable* pred, const MivpRegionTable* target, const void* pairs,
+                                      int64_t max_pairs, int64_t min_size, double iou_threshold, float* best_score,
+                                      float* score, mivp_stream_t stream) {
+    MIVP_REQUIRE(tab_ok(pred) && tab_ok(target) && pairs && best_score && score);
+    MIVP_REQUIRE(pred->image_dtype == 3 && pred->vmax);
+    MIVP_REQUIRE(max_pairs >= 1 && max_pairs <= (1LL << 28) && min_size >= 0);
+    MIVP_REQUIRE(iou_threshold >= 0.0 && iou_threshold <= 1.0);
+    hipStream_t st = (hipStream_t)stream;
+    const Pairs p = pairs_view(const_cast<void*>(pairs), (long)max_pairs);
+    const Tab tp = view(pred), tt = view(target);
+    const int cap = tp.cap > tt.cap ? tp.cap : tt.cap;
+    hipLaunchKernelGGL(k_bs_init, dim3(stride_grid(cap)), dim3(TPB), 0, st, (unsigned*)best_score, score,
+                       (const float*)tp.vmax, tp.cap, tt.cap);
+    hipLaunchKernelGGL(k_bs_pairs, dim3(stride_grid(p.slots)), dim3(TPB), 0, st, p, (const long long*)tp.size,
+                       (const long long*)tt.size, (const float*)tp.vmax, (long long)min_size, iou_threshold,
+                       (unsigned*)best_score);
+    hipLaunchKernelGGL(k_bs_finish, dim3(stride_grid(tt.cap)), dim3(TPB), 0, st, (unsigned*)best_score, tt.cap);
+    return mivp_check_launch("lesion_best_score");
 }

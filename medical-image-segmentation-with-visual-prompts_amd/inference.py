@@ -475,18 +475,35 @@ class SlidingWindowPredictor:
         return out
 
     def evaluate_lesions(self, x: torch.Tensor, seg: torch.Tensor, spacing: Sequence[float] = (1.0, 1.0, 1.0),
-                         postprocess: Optional[Dict] = None, **lesion_kwargs):
+                         postprocess: Optional[Dict] = None, with_scores: bool = False, **lesion_kwargs):
         """Lesion-wise detection metrics of the whole-volume prediction against ``seg [1, 1, H, W, D]``: the
         ``mivp_amd.regions.LesionReport`` of ``lesion_metrics(predict(x, postprocess=postprocess)["labels"], seg,
         num_classes, spacing, **lesion_kwargs)`` (``connectivity``, ``iou_threshold``, ``min_size``, ``classes``,
-        ``max_regions``, ``max_pairs``).  Prediction, post-processing and the metrics run with no host read in between;
-        ``LesionReport.cpu()`` synchronises."""
+        ``max_regions``, ``max_pairs``).  ``with_scores``: the prediction also writes its confidence map and the report is
+        built with it as ``pred_image`` (lesion scores, ``froc()``).  Prediction, post-processing and the metrics run with
+        no host read in between; ``LesionReport.cpu()`` synchronises."""
         from . import regions
         post = self._post(postprocess)
         self._check_input(seg, "seg", channels=1)
         regions.check_lesion_kwargs(self.ncls, spacing, **lesion_kwargs)
-        labels, _, _ = self._run(x, False, None, post)
-        return regions.lesion_metrics(labels, seg, self.ncls, spacing, **lesion_kwargs)
+        if not with_scores:
+            labels, _, _ = self._run(x, False, None, post)
+            return regions.lesion_metrics(labels, seg, self.ncls, spacing, **lesion_kwargs)
+        labels, _, extra = self._run(x, False, None, post, ["confidence"])
+        return regions.lesion_score_metrics(labels, seg, self.ncls, extra["confidence"], spacing, **lesion_kwargs)
+
+    def evaluate_calibration(self, x: torch.Tensor, seg: torch.Tensor, n_bins: int = 15, out=None):
+        """Calibration and threshold-sweep tables of the whole-volume prediction against ``seg [1, 1, H, W, D]``: the
+        ``mivp_amd.calibration.CalibrationReport`` of ``calibration_tables(predict(x, return_probs=True)["probs"], seg,
+        num_classes, n_bins, out)``.  ``out``: an earlier report to pool into.  No host read;
+        ``CalibrationReport.cpu()`` synchronises."""
+        from . import calibration
+        self._check_input(seg, "seg", channels=1)
+        shape = (1, self.ncls) + self.image_size
+        calibration._check_calibration_args(torch.empty(shape, dtype=torch.float32, device="meta"), seg, self.ncls, n_bins,
+                                            out)
+        _, _, extra = self._run(x, False, None, None, ["probs"])
+        return calibration.calibration_tables(extra["probs"], seg, self.ncls, n_bins, out)
 
     def evaluate(self, x: torch.Tensor, seg: torch.Tensor, postprocess: Optional[Dict] = None) -> Tuple[float, float]:
         """(mean IoU, mean Dice) of the whole-volume prediction against ``seg [1, 1, H, W, D]`` (class indices), with the
@@ -630,11 +647,25 @@ def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequ
 def evaluate_volume_lesions(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0),
-                            postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (), **lesion_kwargs):
-    """One-shot ``SlidingWindowPredictor(...).evaluate_lesions(x, seg, spacing, postprocess, **lesion_kwargs)``: the
-    lesion-wise ``mivp_amd.regions.LesionReport`` of the whole-volume prediction."""
+                            postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                            with_scores: bool = False, **lesion_kwargs):
+    """One-shot ``SlidingWindowPredictor(...).evaluate_lesions(x, seg, spacing, postprocess, with_scores,
+    **lesion_kwargs)``: the lesion-wise ``mivp_amd.regions.LesionReport`` of the whole-volume prediction."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
                                graph, mirror_axes)
-    return p.evaluate_lesions(x, seg, spacing, postprocess, **lesion_kwargs)
+    return p.evaluate_lesions(x, seg, spacing, postprocess, with_scores, **lesion_kwargs)
+
+
+def evaluate_volume_calibration(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
+                                overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
+                                sub_batch: int = 10, graph: bool = False, mirror_axes: Sequence[int] = (),
+                                n_bins: int = 15, out=None):
+    """One-shot ``SlidingWindowPredictor(...).evaluate_calibration(x, seg, n_bins, out)``: the
+    ``mivp_amd.calibration.CalibrationReport`` of the whole-volume prediction."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        raise ValueError("x must be a [1, C, H, W, D] tensor")
+    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
+                               graph, mirror_axes)
+    return p.evaluate_calibration(x, seg, n_bins, out)

@@ -30,6 +30,14 @@ Definitions (written out, as in ``mivp_amd.components``; ``tests/regions_ref.py`
   ``min_size`` voxels (the others hold zeros).  ``lesion_dice[c]`` = sum_t dice_t / (n_ref + false positives), NaN when
   that is 0: the lesion-wise Dice of the multi-lesion benchmarks **without their dilation of the reference** (they
   dilate the reference before the components are taken, so that nearby lesions merge; here they do not).
+- **Lesion scores and FROC** (``lesion_score_metrics``, a float32 image such as the confidence map).
+  ``score[p]`` = the predicted region's ``vmax``; ``best_score[t]`` = the largest score over the predictions that match t
+  (the match rule above), ``-inf`` where there is none.  Per class the thresholds are the distinct scores of the valid
+  predictions (at least ``min_size`` voxels), descending; at tau: det = #{valid t : best_score >= tau}, fp = #{valid p :
+  not matched, score >= tau}, tp_pred = #{valid p : matched, score >= tau}; ``sensitivity`` = det / n_ref, ``precision``
+  = tp_pred / (tp_pred + fp), ``average_precision`` = sum_i (S_i - S_{i-1}) P_i along the thresholds; ``froc_score`` =
+  the mean over the fp levels of the largest sensitivity among the thresholds with fp <= level, 0 where none.  ``vmax`` is
+  exact, so all of this is bitwise reproducible (``vmean`` comes from float64 atomics and is not the score).
 
 Numerics: every integer field is exact and bitwise reproducible, and so is everything derived from integers.  For float32
 images ``vmin`` / ``vmax`` are exact, and ``vsum`` / ``vsqsum`` are float64 sums added with hardware atomics: **these two
@@ -263,6 +271,7 @@ class LesionReport:
         self.best_pred = torch.empty(mt, dtype=torch.int32, device=dev)
         self.detected = torch.empty(mt, dtype=torch.int32, device=dev)
         self.matched = torch.empty(mp, dtype=torch.int32, device=dev)
+        self.score = self.best_score = None                 # float32, with lesion_score_metrics only
 
     @property
     def size(self) -> torch.Tensor:
@@ -319,11 +328,77 @@ class LesionReport:
         c = self.counts
         return self._ratio(total, c[:, 0] + c[:, 1] - c[:, 3])
 
+    # ---- FROC (with lesion_score_metrics)
+    def _need_scores(self):
+        if self.score is None:
+            raise RuntimeError("this LesionReport was computed without pred_image (lesion_score_metrics): it has no lesion scores")
+
+    @property
+    def valid_pred(self) -> torch.Tensor:
+        p = self.pred_regions
+        return (torch.arange(p.max_regions, device=p.size.device) < p.n) & (p.size >= self.min_size) & (p.size > 0)
+
+    def froc(self) -> Dict[str, torch.Tensor]:
+        """The free-response curve per class, on the device and with no host read: ``thresholds`` float32 ``[C, M]``
+        (``M`` = the prediction table's ``max_regions``; the first ``n_thresholds[c]`` entries of a row are the distinct
+        scores of the class's valid predictions, descending, the rest NaN) and, at each of them, ``sensitivity`` =
+        det / n_ref, ``fp`` (int64, -1 in the padding), ``precision`` = tp_pred / (tp_pred + fp); ``average_precision``
+        ``[C]`` = sum_i (S_i - S_{i-1}) P_i over the thresholds in that order, S_{-1} = 0 (0 without predictions).
+        Values with n_ref = 0 are NaN."""
+        self._need_scores()
+        p, t = self.pred_regions, self.target_regions
+        dev, ncls, mp, mt = p.size.device, self.num_classes, p.max_regions, t.max_regions
+        classes = torch.arange(ncls, device=dev, dtype=p.cls.dtype)[:, None]
+        vp = self.valid_pred[None, :] & (p.cls[None, :] == classes)
+        vt = self.valid[None, :] & (t.cls[None, :] == classes)
+        ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
+        idx = torch.arange(mp, device=dev)[None, :]
+        srt = torch.where(vp, self.score[None, :], ninf).sort(1, descending=True).values
+        first = (idx < vp.sum(1)[:, None]) & ((idx == 0) | (srt != srt.roll(1, 1)))
+        k = first.sum(1)
+        live = idx < k[:, None]
+        thr = torch.where(first, srt, ninf).sort(1, descending=True).values
+        probe = torch.where(live, thr, -ninf).contiguous()          # +inf in the padding: nothing reaches it
+
+        def at_least(values, mask):                                  # per class and threshold: #{mask : value >= tau}
+            asc = torch.where(mask, values[None, :], ninf).sort(1).values.contiguous()
+            return asc.shape[1] - torch.searchsorted(asc, probe)
+
+        hit = self.matched[None, :] > 0
+        det = at_least(self.best_score, vt)
+        fp = at_least(self.score, vp & ~hit)
+        tpp = at_least(self.score, vp & hit)
+        n_ref = self.counts[:, 0]
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        sens = torch.where(live, self._ratio(det, n_ref[:, None].expand_as(det)), nan)
+        prec = torch.where(live, self._ratio(tpp, tpp + fp), nan)
+        step = det - torch.cat([torch.zeros_like(det[:, :1]), det[:, :-1]], 1)
+        term = torch.where(live, step.to(torch.float64) * prec, torch.zeros((), dtype=torch.float64, device=dev))
+        return dict(thresholds=torch.where(live, thr, torch.full_like(thr, float("nan"))), n_thresholds=k,
+                    sensitivity=sens, fp=torch.where(live, fp, torch.full_like(fp, -1)), precision=prec,
+                    average_precision=self._ratio(term.sum(1), n_ref))
+
+    def froc_score(self, fp_levels: Sequence[float] = (0.125, 0.25, 0.5, 1, 2, 4, 8)) -> torch.Tensor:
+        """Per class, the mean over ``fp_levels`` of the largest sensitivity among the thresholds with ``fp <= level``
+        (0 where there is none); NaN for a class without reference lesions.  No host read."""
+        levels = [float(a) for a in fp_levels]
+        if not levels or not all(math.isfinite(a) and a >= 0 for a in levels):
+            raise ValueError(f"fp_levels must be a non-empty sequence of non-negative numbers, got {fp_levels!r}")
+        f = self.froc()
+        sens, fp = f["sensitivity"], f["fp"]
+        zero = torch.zeros((), dtype=torch.float64, device=sens.device)
+        total = torch.zeros(self.num_classes, dtype=torch.float64, device=sens.device)
+        for a in levels:
+            total = total + torch.where((fp >= 0) & (fp <= a), sens, zero).max(1).values
+        return torch.where(self.counts[:, 0] > 0, total / len(levels), torch.full_like(total, float("nan")))
+
     def cpu(self) -> Dict[str, object]:
         """The one synchronising call: ``counts`` and the per-class values, the per-lesion arrays trimmed to the number
         of reference lesions, ``pairs`` (int64 ``[K, 3]`` rows (p, t, n_pt) sorted by p then t) and the two region tables
-        (``pred_regions`` / ``target_regions``, as ``RegionTable.cpu()``).  Raises ``RuntimeError`` when either region
-        table or the pair table overflowed."""
+        (``pred_regions`` / ``target_regions``, as ``RegionTable.cpu()``).  With lesion scores also ``score`` (per
+        prediction), ``best_score`` (per reference lesion), ``froc`` (the arrays of ``froc()``, trimmed to the longest
+        curve) and ``froc_score``.  Raises ``RuntimeError`` when either region table or the pair table overflowed."""
+        curve = None if self.score is None else dict(self.froc(), froc_score=self.froc_score())
         per_class = dict(counts=self.counts, sensitivity=self.sensitivity, precision=self.precision, f1=self.f1,
                          lesion_dice=self.lesion_dice)
         per_lesion = dict(size=self.size, valid=self.valid, overlap=self.overlap, touching=self.touching,
@@ -343,6 +418,13 @@ class LesionReport:
         out = {k: v.cpu().numpy() for k, v in per_class.items()}
         out.update({k: v[:nt].cpu().numpy() for k, v in per_lesion.items()})
         out["matched"] = matched[:np_].cpu().numpy()
+        if curve is not None:
+            out["score"] = self.score[:np_].cpu().numpy()
+            out["best_score"] = self.best_score[:nt].cpu().numpy()
+            out["froc_score"] = curve.pop("froc_score").cpu().numpy()
+            host = {k: v.cpu().numpy() for k, v in curve.items()}
+            kmax = int(host["n_thresholds"].max()) if host["n_thresholds"].size else 0
+            out["froc"] = {k: (v[:, :kmax] if v.ndim == 2 else v) for k, v in host.items()}
         slots = (self.pairs.numel() - 2) // 2
         keys, cnt = self.pairs[2:2 + slots], self.pairs[2 + slots:]
         used = keys != 0
@@ -355,10 +437,10 @@ class LesionReport:
         return out
 
 
-def _lesion_launch(pv: torch.Tensor, tv: torch.Tensor, rargs, largs) -> LesionReport:
+def _lesion_launch(pv: torch.Tensor, tv: torch.Tensor, rargs, largs, pred_image: Optional[torch.Tensor] = None) -> LesionReport:
     ncls = rargs[0]
     thr, min_size, max_pairs = largs
-    pred = _stats_launch(pv, rargs, None)
+    pred = _stats_launch(pv, rargs, pred_image)
     target = _stats_launch(tv, rargs, None)
     rep = LesionReport(pred, target, ncls, min_size, thr, max_pairs)
     L.call("mivp_region_overlap", L.ptr(pred.labels), L.ptr(target.labels), _i3(pv.shape), C.byref(pred._c),
@@ -367,6 +449,11 @@ def _lesion_launch(pv: torch.Tensor, tv: torch.Tensor, rargs, largs) -> LesionRe
            C.c_int32(ncls), C.c_int64(min_size), C.c_double(thr), L.ptr(rep.counts), L.ptr(rep.overlap),
            L.ptr(rep.touching), L.ptr(rep.best_overlap), L.ptr(rep.best_pred), L.ptr(rep.detected), L.ptr(rep.matched),
            L.stream())
+    if pred_image is not None:
+        rep.score = torch.empty(pred.max_regions, dtype=torch.float32, device=pv.device)
+        rep.best_score = torch.empty(target.max_regions, dtype=torch.float32, device=pv.device)
+        L.call("mivp_lesion_best_score", C.byref(pred._c), C.byref(target._c), L.ptr(rep.pairs), C.c_int64(max_pairs),
+               C.c_int64(min_size), C.c_double(thr), L.ptr(rep.best_score), L.ptr(rep.score), L.stream())
     return rep
 
 
@@ -376,7 +463,19 @@ def lesion_metrics(pred: torch.Tensor, target: torch.Tensor, num_classes: int,
                    max_pairs: Optional[int] = None) -> LesionReport:
     """Lesion-wise detection metrics of the class map ``pred`` against the class map ``target`` (the module docstring has
     the definitions): per-class counts, sensitivity, precision, F1 and lesion-wise Dice, the per-lesion table and both
-    ``RegionTable``s.  ``max_pairs`` defaults to ``4 * max_regions``.  No host read: ``LesionReport.cpu()`` synchronises."""
+    ``RegionTable``s.  ``max_pairs`` defaults to ``4 * max_regions``.  No host read: ``LesionReport.cpu()`` synchronises.
+    ``lesion_score_metrics`` is the same with a score per lesion."""
+    return lesion_score_metrics(pred, target, num_classes, None, spacing, connectivity, iou_threshold, min_size, classes,
+                                max_regions, max_pairs)
+
+
+def lesion_score_metrics(pred: torch.Tensor, target: torch.Tensor, num_classes: int, pred_image: Optional[torch.Tensor],
+                         spacing: Sequence[float] = (1.0, 1.0, 1.0), connectivity: int = 26, iou_threshold: float = 0.0,
+                         min_size: int = 0, classes: Optional[Iterable[int]] = None, max_regions: int = 4096,
+                         max_pairs: Optional[int] = None) -> LesionReport:
+    """``lesion_metrics`` with lesion scores: ``pred_image`` (float32, the spatial shape of ``pred``; a confidence map) is
+    the image of the predicted ``RegionTable``, and the report carries ``score`` / ``best_score``, ``froc()`` and
+    ``froc_score()`` (the module docstring has the definitions).  ``pred_image=None`` is ``lesion_metrics``."""
     _check_gpu("pred", pred)
     _check_gpu("target", target)
     rargs = _check_region_args(num_classes, connectivity, classes, max_regions, spacing)
@@ -386,4 +485,9 @@ def lesion_metrics(pred: torch.Tensor, target: torch.Tensor, num_classes: int,
         raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
     if pv.device != tv.device:
         raise ValueError(f"pred is on {pv.device}, target on {tv.device}")
-    return _lesion_launch(pv, tv, rargs, largs)
+    img = None
+    if pred_image is not None:
+        img = _check_image(pred_image, pv.shape, pv.device)
+        if img.dtype != torch.float32:
+            raise ValueError(f"pred_image must be float32, got {img.dtype}")
+    return _lesion_launch(pv, tv, rargs, largs, img)
