@@ -777,6 +777,37 @@ int mivp_scan_restore_argmax(const float* logits, int32_t C, const int32_t* src_
                              const int32_t* axes, const int32_t* tables, int32_t interp, int32_t flags, uint8_t* out,
                              mivp_stream_t stream);
 
+/* Scan statistics and data-driven intensity windows (csrc/scanstats.hip, csrc/scan.hip; mivp_amd/scanstats.py, DESIGN
+ * 4.23).  These entry points joined ABI 18 without a bump: they are additive and no earlier signature changed.
+ *   mivp_scan_hist: raw [C][H][W][D] (C <= 4) of dtype 0 uint8 or 4 int16, dims = {H, W, D} (host), fewer than 2^31 voxels
+ *     per channel.  hist: DEVICE int64 [C][65536], 8-byte aligned; the bin of value v is v + 32768 for both dtypes.  The
+ *     launch ADDS to hist: zero it first, or pool scans in it.  A voxel counts when mask (DEVICE uint8 [H][W][D] shared by
+ *     the channels, or NULL) is non-zero there and, with use_above, v > above.  base: the lowest value of the 16384
+ *     consecutive values a workgroup counts in LDS; a value outside them adds to hist directly, so any base gives the same
+ *     table and a base near the scan's minimum gives it fastest.  flags: bit 0 adds every value on its own, 0 (the
+ *     default) merges the equal consecutive values of a lane's 16-byte load first (tools/bench_scanstats.py times both).
+ *     Integer atomics only: exact, bitwise reproducible, independent of the launch shape.
+ *   mivp_scan_window_plan: hist [C][65536] -> slot: DEVICE f32 [C][8], one workgroup per channel.  With N the count,
+ *     a_lo / a_hi the k-th smallest counted values for k = max(1, ceil(q * (double)N)), q = q_lo / q_hi (0 <= q_lo <= q_hi
+ *     <= 1; nearest rank, not an interpolating percentile), mean = S1 / N and std = sqrt(max(0, S2 / N - mean^2)) in
+ *     float64 from the int64 sums S1 = sum v n_v, S2 = sum v^2 n_v (exact while S2 < 2^63: always for N < 2^33):
+ *       slot[c] = {s, t, lo, hi, a_lo, a_hi, mean, std}, every word rounded from float64 to float32 once.
+ *       mode 0 (percentile): s = (b_max - b_min) / (a_hi - a_lo), t = b_min - a_lo * s, lo = b_min, hi = b_max: the map of
+ *         a_min = a_lo, a_max = a_hi, bit for bit; a_hi == a_lo (a constant scan, N == 0): s = 0, t = b_min.  clip unused.
+ *       mode 1 (z-score): s = 1 / std, t = -mean / std (std == 0 or N == 0: s = 1, t = -mean; N == 0: mean = 0, a_lo =
+ *         a_hi = 0); with clip lo = fmaf(a_lo, s, t), hi = fmaf(a_hi, s, t) in float32 from the rounded s and t, else
+ *         -FLT_MAX and FLT_MAX.  b_min / b_max unused.
+ *   mivp_scan_prepare_dev: mivp_scan_prepare with the map in DEVICE memory and per channel: channel c applies words 0..3
+ *     of slot[c] (f32 [C][8], what mivp_scan_window_plan wrote).  The same kernels, staging choices and flag bits.
+ * No workspace, no host synchronisation: histogram -> plan -> prepare record into a graph as a linear chain. */
+int mivp_scan_hist(const void* raw, int32_t dtype, int32_t C, const int32_t* dims, const uint8_t* mask, int32_t use_above,
+                   int32_t above, int32_t base, int32_t flags, int64_t* hist, mivp_stream_t stream);
+int mivp_scan_window_plan(const int64_t* hist, int32_t C, int32_t mode, double q_lo, double q_hi, double b_min, double b_max,
+                          int32_t clip, float* slot, mivp_stream_t stream);
+int mivp_scan_prepare_dev(const void* raw, int32_t dtype, int32_t C, const int32_t* src_dims, const int32_t* out_dims,
+                          const int32_t* axes, const int32_t* tables, int32_t interp, const float* slot, int32_t clip,
+                          int32_t flags, float* out, mivp_stream_t stream);
+
 /* Per-lesion region statistics and lesion-wise detection metrics (csrc/regions.hip; mivp_amd/regions.py).
  * These entry points joined ABI 18 without a bump: they are additive and no earlier signature changed.  dims = {H, W, D}
  * (host), volumes [H][W][D] row-major, fewer than 2^31 voxels; connectivity as mivp_label_components.  No host

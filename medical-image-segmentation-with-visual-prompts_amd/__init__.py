@@ -15,7 +15,7 @@ __all__ = ["_lib", "geometry"]
 def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
-                "components", "scan", "regions", "augment", "calibration"):
+                "components", "scan", "regions", "augment", "calibration", "scanstats"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -40,6 +40,9 @@ def __getattr__(name):
     if name in ("ScanGeometry", "prepare_scan", "prepare_labels", "restore_labels", "restore_labels_from_logits"):
         from . import scan
         return getattr(scan, name)
+    if name in ("scan_histogram", "window_slot", "IntensityWindow", "ScanHistogram", "WindowSlot", "ScanReport"):
+        from . import scanstats
+        return getattr(scanstats, name)
     if name in ("IntensityDraws", "IntensitySlot", "draw_intensity", "augment_intensity"):
         from . import augment
         return getattr(augment, name)

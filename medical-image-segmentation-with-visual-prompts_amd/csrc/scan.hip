@@ -1,11 +1,12 @@
 // Scan preparation and native-grid restore around whole-volume prediction (ABI 17, mivp_amd/scan.py).
 //
-// All four entries are one "resample-gather": out[k0][k1][k2] = F(src at the taps of (k0, k1, k2)).  Output axis a walks
+// All entries are one "resample-gather": out[k0][k1][k2] = F(src at the taps of (k0, k1, k2)).  Output axis a walks
 // ONE source axis, axes[a] (a permutation), through per-axis tables built on the host:
 //     tables int32 [3][K], K = k0 + k1 + k2, axis a at offset k0 + .. + k(a-1) of each section:
 //       section 0: lower source index, section 1: upper source index, section 2: bits of the fp32 weight of the upper one.
 // Flips, the resize and its rounding all live in the tables; a pure gather (interp = 0) reads section 0 only.
-//   image   (prepare):          v = clip(fma(x, scale, shift)) per SOURCE voxel, then the eight-point blend
+//   image   (prepare):          v = clip(fma(x, scale, shift)) per SOURCE voxel, then the eight-point blend; the map is a
+//                               launch argument, or per channel words 0..3 of a DEVICE slot (mivp_scan_prepare_dev)
 //   labels  (prepare / restore): nearest, uint8 out; a value outside 0..255 (or a non-integer float) sets *bad
 //   arg-max (restore):          the blend of every class, first maximum wins; the resized logits are never stored
 // The blend is three levels of fma(w, hi - lo, lo): output axis 2 first, then 1, then 0, in both read paths below, so
@@ -42,12 +43,18 @@ struct Plan {
     long nvox;      // output voxels per channel
 };
 
-struct Map { float s, t, lo, hi; int clip; };
+struct Map { float s, t, lo, hi; int clip; const float* dev; };   // dev: [C][8] slot words on the device, or nullptr
 
 struct Taps { long ol[3], oh[3]; float w[3]; };
 
 __device__ inline int clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 __device__ inline float lerp(float a, float b, float w) { return fmaf(w, b - a, a); }
+// the image map of channel ch: the launch's own, or what a window-plan launch left in the channel's slot
+__device__ inline Map channel_map(const Map& mp, int ch) {
+    if (!mp.dev) return mp;
+    const float* __restrict__ w = mp.dev + 8 * ch;
+    return Map{w[0], w[1], w[2], w[3], mp.clip, nullptr};
+}
 
 template <int MODE, typename T>
 __device__ inline float value(const T* __restrict__ p, long i, const Map& mp, int& bad) {
@@ -115,7 +122,8 @@ __global__ __launch_bounds__(TPB) void k_scan_direct(const T* __restrict__ src, 
     int bad = 0;
     if (MODE == MODE_IMAGE) {
         const int ch = blockIdx.y;
-        static_cast<float*>(out)[(long)ch * P.nvox + t] = sample<MODE, T, INTERP>(src + (long)ch * P.msz, tp, mp, bad);
+        static_cast<float*>(out)[(long)ch * P.nvox + t] =
+            sample<MODE, T, INTERP>(src + (long)ch * P.msz, tp, channel_map(mp, ch), bad);
     } else if (MODE == MODE_LABELS) {
         static_cast<uint8_t*>(out)[t] = (uint8_t)sample<MODE, T, false>(src, tp, mp, bad);
         if (bad && flag) flag[0] = 1;
@@ -181,12 +189,13 @@ __global__ __launch_bounds__(TPB) void k_scan_staged(const T* __restrict__ src, 
     const int ch1 = MODE == MODE_ARGMAX ? Cn : ch0 + 1;
     for (int ch = ch0; ch < ch1; ++ch) {
         const T* __restrict__ srcc = src + (long)ch * P.msz;
+        const Map cm = MODE == MODE_IMAGE ? channel_map(mp, ch) : mp;
         if (fits) {
             if (ch != ch0) __syncthreads();                       // the previous class has been read
             for (int row = wv; row < np * len2; row += TPB / 64) {
                 const int p = row >= len2 ? 1 : 0;
                 const long base = (long)pc[p] * P.ss[c] + (long)(lo2 + row - p * len2) * P.ss[2] + lob;
-                for (int q = lane; q < lenb; q += 64) S[row * pitch + q] = value<MODE>(srcc, base + q, mp, bad);
+                for (int q = lane; q < lenb; q += 64) S[row * pitch + q] = value<MODE>(srcc, base + q, cm, bad);
             }
             __syncthreads();
         }
@@ -220,7 +229,7 @@ __global__ __launch_bounds__(TPB) void k_scan_staged(const T* __restrict__ src, 
                 }
             } else {
                 const Taps tp = get_taps<INTERP>(P, tab, k0, k1, k2);
-                v = sample<MODE, T, INTERP>(srcc, tp, mp, bad);
+                v = sample<MODE, T, INTERP>(srcc, tp, cm, bad);
             }
             const long o = ((long)k0 * P.k[1] + k1) * P.k[2] + k2;
             if (MODE == MODE_IMAGE) static_cast<float*>(out)[(long)ch * P.nvox + o] = v;
@@ -306,18 +315,34 @@ int launch_dtype(int32_t dtype, const void* src, const Plan& P, int32_t axes2, c
     mivp_set_error("scan: dtype must be 0 (uint8), 1 (int32), 3 (float32) or 4 (int16)");
     return MIVP_EINVAL;
 }
+
+int prepare(const void* raw, int32_t dtype, int32_t C, const int32_t* src_dims, const int32_t* out_dims, const int32_t* axes,
+            const int32_t* tables, int32_t interp, const Map& mp, int32_t flags, float* out, mivp_stream_t stream,
+            const char* what) {
+    Plan P;
+    MIVP_REQUIRE(fill_plan(P, src_dims, out_dims, axes));
+    if (interp)
+        return launch_dtype<MODE_IMAGE, true>(dtype, raw, P, axes[2], tables, mp, C, flags, out, nullptr, stream, what);
+    return launch_dtype<MODE_IMAGE, false>(dtype, raw, P, axes[2], tables, mp, C, flags, out, nullptr, stream, what);
+}
 }  // namespace
 
 extern "C" int mivp_scan_prepare(const void* raw, int32_t dtype, int32_t C, const int32_t* src_dims, const int32_t* out_dims,
                                  const int32_t* axes, const int32_t* tables, int32_t interp, const float* map, int32_t clip,
                                  int32_t flags, float* out, mivp_stream_t stream) {
     MIVP_REQUIRE(raw && out && src_dims && out_dims && axes && tables && map && C >= 1 && C <= 4);
-    Plan P;
-    MIVP_REQUIRE(fill_plan(P, src_dims, out_dims, axes));
-    const Map mp = {map[0], map[1], map[2], map[3], clip != 0};
-    if (interp)
-        return launch_dtype<MODE_IMAGE, true>(dtype, raw, P, axes[2], tables, mp, C, flags, out, nullptr, stream, "scan_prepare");
-    return launch_dtype<MODE_IMAGE, false>(dtype, raw, P, axes[2], tables, mp, C, flags, out, nullptr, stream, "scan_prepare");
+    const Map mp = {map[0], map[1], map[2], map[3], clip != 0, nullptr};
+    return prepare(raw, dtype, C, src_dims, out_dims, axes, tables, interp, mp, flags, out, stream, "scan_prepare");
+}
+
+// the same launch with the map in DEVICE memory: channel ch reads words 0..3 of slot[ch][8] (mivp_scan_window_plan)
+extern "C" int mivp_scan_prepare_dev(const void* raw, int32_t dtype, int32_t C, const int32_t* src_dims,
+                                     const int32_t* out_dims, const int32_t* axes, const int32_t* tables, int32_t interp,
+                                     const float* slot, int32_t clip, int32_t flags, float* out, mivp_stream_t stream) {
+    MIVP_REQUIRE(raw && out && src_dims && out_dims && axes && tables && slot && C >= 1 && C <= 4);
+    MIVP_REQUIRE(((uintptr_t)slot & 3u) == 0);
+    const Map mp = {1.f, 0.f, 0.f, 0.f, clip != 0, slot};
+    return prepare(raw, dtype, C, src_dims, out_dims, axes, tables, interp, mp, flags, out, stream, "scan_prepare_dev");
 }
 
 extern "C" int mivp_scan_prepare_labels(const void* seg, int32_t dtype, const int32_t* src_dims, const int32_t* out_dims,

@@ -545,9 +545,10 @@ class SlidingWindowPredictor:
     # ------------------------------------------------------------------ raw scans (mivp_amd.scan)
     def _prepare_scan(self, raw, geom, restore, postprocess, intensity):
         """Checked raw scan -> the model's input on the device: the predictor's resident volume in graph mode, so that the
-        recorded gather reads what the prepare launch wrote."""
+        recorded gather reads what the prepare launch wrote (with ``window=`` the histogram and plan launches run eagerly
+        in front of it, like the prepare launch itself)."""
         from . import scan
-        unknown = set(intensity) - {"a_min", "a_max", "b_min", "b_max", "clip"}
+        unknown = set(intensity) - {"a_min", "a_max", "b_min", "b_max", "clip", "window", "mask"}
         if unknown:
             raise ValueError(f"unknown intensity arguments {sorted(unknown)}")
         r = scan.check_predict_args(self.image_size, self.cin, raw, geom, restore, postprocess)
@@ -566,7 +567,9 @@ class SlidingWindowPredictor:
         ``prepare_scan`` -> the sliding-window prediction -> optional post-processing on the model grid -> restore, with
         no host read.  ``restore="labels"`` resizes the label map back (nearest); ``restore="logits"`` interpolates the
         blended logits on the native grid and takes the arg-max there (``restore_labels_from_logits``).  ``intensity``:
-        ``a_min``, ``a_max``, ``b_min``, ``b_max``, ``clip`` of ``prepare_scan``."""
+        ``a_min``, ``a_max``, ``b_min``, ``b_max``, ``clip`` of ``prepare_scan``, or its ``window`` (and ``mask``): a
+        data-driven window (``mivp_amd.scanstats``) adds two launches in front of the prepare launch and no host read,
+        in graph mode too, where the prepare launch writes the predictor's resident volume as before."""
         from . import scan
         post = self._post(postprocess)
         x = self._prepare_scan(raw, geom, restore, postprocess, intensity)

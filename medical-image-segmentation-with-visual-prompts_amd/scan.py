@@ -19,6 +19,7 @@ are not dependencies here, so the conventions are written out rather than pinned
 
 Four launches, all GPU tensors in and out with no CPU fallback: ``prepare_scan``, ``prepare_labels``, ``restore_labels``
 and ``restore_labels_from_logits``.  ``ScanGeometry`` holds what both directions need and is plain numpy.
+``prepare_scan(window=...)`` takes the window from the scan's own histogram instead (``mivp_amd.scanstats``).
 """
 from __future__ import annotations
 
@@ -268,15 +269,37 @@ def _raw_view(raw, geom: ScanGeometry) -> torch.Tensor:
     return raw
 
 
-def prepare_scan(raw: torch.Tensor, geom: ScanGeometry, a_min: float = -1000.0, a_max: float = 1000.0, b_min: float = 0.0,
-                 b_max: float = 1.0, clip: bool = True, out: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+def prepare_scan(raw: torch.Tensor, geom: ScanGeometry, a_min: Optional[float] = None, a_max: Optional[float] = None,
+                 b_min: float = 0.0, b_max: float = 1.0, clip: bool = True, out: Optional[torch.Tensor] = None, flags: int = 0,
+                 window=None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A raw scan on its native grid -> the model's input, in one launch: intensity map (with clip), orientation and,
     when ``geom.out_size`` is set, the trilinear resize.  ``raw``: ``[C, H, W, D]`` (or ``[H, W, D]`` /
     ``[1, C, H, W, D]``), C <= 4, int16, uint8, int32 or float32.  Returns fp32 ``[1, C, H', W', D']`` (``out`` when
-    given).  Without a resize the result is bit-equal to the intensity map of the transposed and flipped scan."""
+    given).  Without a resize the result is bit-equal to the intensity map of the transposed and flipped scan.
+    ``a_min`` / ``a_max`` default to the reference's CT window, -1000 and 1000.
+
+    ``window=`` replaces the fixed window by one that follows from the data (``mivp_amd.scanstats``, int16 / uint8 scans
+    only), per channel and with no host read.  An ``IntensityWindow`` is computed on the scan itself: histogram -> plan ->
+    this launch reading the plan from the device, three launches that record into a graph (the spec keeps the buffers:
+    after one eager call nothing is allocated); ``mask`` (uint8 on the native grid) and the spec's ``above`` select the
+    voxels it counts.  A ``WindowSlot`` -- ``window_slot`` of a histogram pooled over a data set -- is applied as it is.
+    ``a_min`` / ``a_max`` must then be left out, and so must ``b_min`` / ``b_max``, which belong to the spec
+    (``ValueError`` otherwise); ``clip`` holds for a percentile window (a z-score window clamps by its own ``clip=``
+    percentiles)."""
     geom = _check_geom(geom)
     r = _raw_view(raw, geom)
-    mp = intensity_map(a_min, a_max, b_min, b_max)
+    if window is None:
+        if mask is not None:
+            raise ValueError("mask selects the voxels a data-driven window counts: it needs window=")
+        mp = intensity_map(-1000.0 if a_min is None else a_min, 1000.0 if a_max is None else a_max, b_min, b_max)
+    else:
+        from . import scanstats
+        if a_min is not None or a_max is not None:
+            raise ValueError("window= takes the place of a_min / a_max: pass one or the other")
+        if (b_min, b_max) != (0.0, 1.0):
+            raise ValueError("with window= the output range belongs to the window: pass b_min / b_max to "
+                             "IntensityWindow.percentile, not to prepare_scan")
+        scanstats.check_window_args(window, r, mask, geom.shape)
     shape = (1, r.shape[0]) + geom.size
     out = _check_out(out, shape, torch.float32, r)
     _check_gpu("raw", r)
@@ -284,6 +307,13 @@ def prepare_scan(raw: torch.Tensor, geom: ScanGeometry, a_min: float = -1000.0, 
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=r.device)
     src, dst, axes, interp, _ = geom.tables("image")
+    if window is not None:
+        slot = scanstats.resolve_window(window, r, mask)
+        dev_clip = bool(clip) if slot.mode == scanstats.MODE_PERCENTILE else True
+        L.call("mivp_scan_prepare_dev", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(r.shape[0]), _i3(src), _i3(dst),
+               _i3(axes), L.ptr(geom.device_tables("image", r.device)), C.c_int32(int(interp)), L.ptr(slot.words),
+               C.c_int32(int(dev_clip)), C.c_int32(int(flags)), L.ptr(out), L.stream())
+        return out
     L.call("mivp_scan_prepare", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(r.shape[0]), _i3(src), _i3(dst), _i3(axes),
            L.ptr(geom.device_tables("image", r.device)), C.c_int32(int(interp)), (C.c_float * 4)(*mp),
            C.c_int32(int(bool(clip))), C.c_int32(int(flags)), L.ptr(out), L.stream())
