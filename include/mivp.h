@@ -912,6 +912,39 @@ int mivp_intensity_stats(const float* x, int32_t B, int32_t C, const int32_t* di
 int mivp_intensity_apply(const float* x, int32_t B, int32_t C, const int32_t* dims, const int32_t* slot,
                          const void* workspace, size_t workspace_bytes, float* out, mivp_stream_t stream);
 
+/* Skipping all-background windows in whole-volume prediction (csrc/window_skip.hip; SlidingWindowPredictor(skip=...),
+ * DESIGN 4.24).  These entry points joined the current ABI without a bump: they are additive and no earlier signature
+ * changed.  dims / pad / pdims / roi as for mivp_window_gather (host int32 [3]).
+ *   mivp_window_occupancy: counts int32 [n_windows] = foreground voxels of each window; the call zeroes counts itself.
+ *     Exactly one source: vol f32 [Cin][H][W][D] with channel and threshold (foreground: vol[channel] > threshold, strict
+ *     fp32, so NaN is not foreground), or mask uint8 [H][W][D] (foreground: mask != 0; vol NULL, Cin / channel / threshold
+ *     ignored).  Voxels of the zero padding are never foreground.  origins: DEVICE int32 [n_windows][origin_stride],
+ *     origin_stride 3 or 4, padded-volume coordinates; a window that does not lie in the padded volume counts 0.  The grid
+ *     is (window, slab of rows), four D voxels per load where D % 4 == 0 and the base is aligned, one integer atomic per
+ *     workgroup: exact and bitwise reproducible.
+ *   mivp_window_compact: full_table int32 [n_entries][4] (the immutable work list, entry e = window e / n_flips, never
+ *     written) -> table int32 [n_entries][4]: the valid entries of the windows with counts[w] >= min_voxels first, in their
+ *     original order and with word 3 unchanged, every later row zero (invalid); meta int32 [2] = (kept windows, kept
+ *     entries).  One workgroup, an ordered block prefix scan: deterministic.  table != full_table, both 16-byte aligned.
+ *   mivp_window_blend_any: the arguments and the per-voxel arithmetic of mivp_window_blend_tta (comp NULL: that of
+ *     mivp_window_blend; bitwise the same sums for the same entries), for a table whose sub-batches can have ANY union box
+ *     inside the padded volume: ubox only sizes the launch grid (the recorded graph's is fixed), a larger box is walked
+ *     with a grid stride and never dropped.
+ *   mivp_stitch_fill: every voxel of the padded volume with wsum == 0 gets acc[v][c] = +fill_logit at fill_class and
+ *     -fill_logit elsewhere and wsum = 1, so that mivp_stitch_finalize(_probs) returns exactly those logits there. */
+int mivp_window_occupancy(const float* vol, int32_t Cin, int32_t channel, float threshold, const uint8_t* mask,
+                          const int32_t* dims, const int32_t* pad, const int32_t* pdims, const int32_t* roi,
+                          const int32_t* origins, int32_t origin_stride, int32_t n_windows, int32_t* counts,
+                          mivp_stream_t stream);
+int mivp_window_compact(const int32_t* full_table, int32_t n_entries, int32_t n_windows, int32_t n_flips,
+                        const int32_t* counts, int32_t min_voxels, int32_t* table, int32_t* meta, mivp_stream_t stream);
+int mivp_window_blend_any(const float* logits, int32_t channels_last, int32_t C, const int32_t* pdims, const int32_t* roi,
+                          const int32_t* table, int32_t n_entries, const int32_t* sub_idx, int32_t B, const int32_t* ubox,
+                          const float* w0, const float* w1, const float* w2, float w_floor, float* acc, float* wsum,
+                          float* comp, mivp_stream_t stream);
+int mivp_stitch_fill(float* acc, float* wsum, int32_t C, const int32_t* pdims, int32_t fill_class, float fill_logit,
+                     mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

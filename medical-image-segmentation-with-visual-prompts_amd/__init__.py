@@ -22,7 +22,7 @@ def __getattr__(name):
         from .swin_unetr import SwinUnetR
         return SwinUnetR
     if name in ("SlidingWindowPredictor", "predict_volume", "evaluate_volume", "evaluate_volume_surface",
-                "predict_scan_volume", "evaluate_volume_lesions", "evaluate_volume_calibration"):
+                "predict_scan_volume", "evaluate_volume_lesions", "evaluate_volume_calibration", "WindowSkip"):
         from . import inference
         return getattr(inference, name)
     if name in ("surface_map", "distance_transform_sq", "surface_metrics"):

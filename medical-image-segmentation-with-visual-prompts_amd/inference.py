@@ -229,6 +229,51 @@ def _i3(v):
     return (C.c_int32 * 3)(*[int(a) for a in v])
 
 
+def _plain_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+class WindowSkip:
+    """Which windows a ``SlidingWindowPredictor(skip=...)`` leaves out.  A voxel of the prepared volume is
+    foreground iff ``vol[channel] > threshold`` (strict fp32: NaN is not foreground; the default threshold is the
+    reference's ``LoadPseudoBgMaskd`` rule, transforms.py:363); a window is kept iff it holds at least ``min_voxels``
+    foreground voxels.  Voxels no kept window covers get the label ``fill_class`` and the blended logits ``+fill_logit``
+    at ``fill_class``, ``-fill_logit`` elsewhere.  ``channel`` and ``fill_class`` are checked against the predictor's
+    channel and class counts when it is built.  Immutable."""
+
+    __slots__ = ("threshold", "channel", "min_voxels", "fill_class", "fill_logit")
+
+    def __init__(self, threshold: float = 0.0025, channel: int = 0, min_voxels: int = 1, fill_class: int = 0,
+                 fill_logit: float = 10.0):
+        for name, v in (("threshold", threshold), ("fill_logit", fill_logit)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) \
+                    or not math.isfinite(float(v)):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+        if not 0 < float(fill_logit) <= float(np.finfo(np.float32).max):
+            raise ValueError(f"fill_logit must be > 0 and finite in fp32, got {fill_logit!r}")
+        for name, v, lo in (("channel", channel, 0), ("min_voxels", min_voxels, 1), ("fill_class", fill_class, 0)):
+            if not _plain_int(v) or int(v) < lo or int(v) >= 2 ** 31:
+                raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+        object.__setattr__(self, "threshold", float(threshold))
+        object.__setattr__(self, "channel", int(channel))
+        object.__setattr__(self, "min_voxels", int(min_voxels))
+        object.__setattr__(self, "fill_class", int(fill_class))
+        object.__setattr__(self, "fill_logit", float(fill_logit))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("WindowSkip is immutable")
+
+    def __repr__(self):
+        return (f"WindowSkip(threshold={self.threshold}, channel={self.channel}, min_voxels={self.min_voxels}, "
+                f"fill_class={self.fill_class}, fill_logit={self.fill_logit})")
+
+    def __eq__(self, other):
+        return isinstance(other, WindowSkip) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
 def _model_factor(conf) -> Tuple[int, int, int]:
     """Per-axis size multiple the SwinUnetR accepts: the patch embedding times the encoder's patch mergings (every stage
     halves H and W, only the first one D: swin_unetr.py merge_last_dim)."""
@@ -255,11 +300,27 @@ class SlidingWindowPredictor:
 
     ``graph=True`` records gather -> model -> blend -> advance once (after two eager sub-batches that pack the weight
     caches) and replays it ``ceil(N F / sub_batch)`` times with no host work in between: bitwise equal to eager.  The graph
-    holds the model's weights as they were when it was recorded; build a new predictor after changing them."""
+    holds the model's weights as they were when it was recorded; build a new predictor after changing them.
+
+    ``skip`` (a ``WindowSkip``; ``None``, the default, launches what the predictor always launched and reads nothing
+    back) leaves the windows without foreground out.  Per volume: reset -> one occupancy launch (foreground voxels per
+    window, ``self.occupancy``) -> one compact launch that writes the kept entries of the immutable full work list
+    (``self.table_full``), in their original order, into ``self.table`` -- the buffer the gather, the blend and the
+    recorded graph read -- and zeroes the rest -> ``ceil(n_kept F / sub_batch)`` sub-batches -> one fill launch (voxels no
+    kept window covered get the fill logits) -> finalize.  The number of sub-batches is ONE 8-BYTE HOST READ of the
+    compact launch's (kept windows, kept entries) word, the only synchronisation ``skip`` adds: without it the empty
+    sub-batches would still run the model.  Entry order is preserved, so every voxel still sums in increasing entry
+    index: the result stays bitwise independent of ``sub_batch`` and of the graph form, a voxel all of whose covering
+    windows are kept (with ``min_voxels=1``: every foreground voxel) gets the logits of the unfiltered prediction bit
+    for bit, and the graph is recorded once (with the full table) and replayed for every volume whatever its kept set.
+    A compacted sub-batch can span any union box, so the blend is then ``mivp_window_blend_any``: the unfiltered launch
+    grid, walked with a stride over a larger box (the same sums per voxel).  After a run
+    ``n_kept`` is the number of windows kept and ``n_sub_run`` the number of sub-batches run.  ``set_region(mask)``
+    replaces the threshold rule by a resident uint8 ``[H, W, D]`` mask (foreground: ``mask != 0``)."""
 
     def __init__(self, model, image_size: Sequence[int], in_channels: int, num_classes: int, roi: Sequence[int],
                  overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                 graph: bool = False, mirror_axes: Sequence[int] = ()):
+                 graph: bool = False, mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None):
         self.image_size = _check_shape3("image_size", image_size)
         self.roi = _check_shape3("roi", roi)
         _check_overlap(overlap)
@@ -272,6 +333,14 @@ class SlidingWindowPredictor:
             raise ValueError("in_channels must be in 1..4")
         if not 1 <= int(num_classes) <= 16:
             raise ValueError("num_classes must be in 1..16")
+        if skip is not None:
+            if not isinstance(skip, WindowSkip):
+                raise ValueError(f"skip must be a WindowSkip or None, got {type(skip).__name__}")
+            if skip.channel >= int(in_channels):
+                raise ValueError(f"skip.channel {skip.channel} is not a channel of a {int(in_channels)}-channel volume")
+            if skip.fill_class >= int(num_classes):
+                raise ValueError(f"skip.fill_class {skip.fill_class} is not one of {int(num_classes)} classes")
+        self.skip = skip
         conf = getattr(model, "conf", None)
         if conf is not None:
             if getattr(conf, "training_mode", "downstream") != "downstream":
@@ -306,6 +375,7 @@ class SlidingWindowPredictor:
             o = table[s * self.sub_batch:min((s + 1) * self.sub_batch, self.n_entries), :3]
             for a in range(3):
                 ubox[a] = max(ubox[a], int(o[:, a].max() - o[:, a].min()) + self.roi[a])
+        # (with skip a compacted sub-batch can have any union box: the grid stays this one, mivp_window_blend_any strides)
         self.ubox = tuple(ubox)
         tabs, self.w_floor = importance_tables(self.roi, mode, sigma_scale)
         self.w = [torch.tensor(t, dtype=torch.float32, device=dev) for t in tabs]
@@ -324,6 +394,14 @@ class SlidingWindowPredictor:
         self.vol = None          # graph mode: the resident volume the recorded gather reads
         self.graph = None
         self.cc_ws = None        # post-processing workspace (8 bytes per voxel), allocated on first use
+        # window skipping: the full work list stays as built; self.table is the active (compacted) list of the volume
+        self.occupancy, self.region = None, None
+        self.n_kept, self.n_sub_run = self.n_windows, self.n_sub
+        if skip is not None:
+            self.table_full = self.table.clone()
+            self.origins_dev = torch.from_numpy(np.ascontiguousarray(self.origins)).to(dev)
+            self.occupancy = torch.zeros(self.n_windows, dtype=torch.int32, device=dev)
+            self.meta = torch.zeros(2, dtype=torch.int32, device=dev)
 
     # ------------------------------------------------------------------ per sub-batch launches
     def _gather(self, vol):
@@ -345,7 +423,9 @@ class SlidingWindowPredictor:
                 C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch), a["ubox"],
                 L.ptr(self.w[0]), L.ptr(self.w[1]), L.ptr(self.w[2]), C.c_float(self.w_floor), L.ptr(self.acc),
                 L.ptr(self.wsum))
-        if self._tta_kernels:
+        if self.skip is not None:                                # any union box on the unfiltered grid (comp None: plain sums)
+            L.call("mivp_window_blend_any", *args, L.ptr(self.comp), L.stream())
+        elif self._tta_kernels:
             L.call("mivp_window_blend_tta", *args, L.ptr(self.comp), L.stream())
         else:
             L.call("mivp_window_blend", *args, L.stream())
@@ -363,6 +443,45 @@ class SlidingWindowPredictor:
         if self.comp is not None:
             self.comp.zero_()
         self.sub_idx.zero_()
+
+    # ------------------------------------------------------------------ window skipping (csrc/window_skip.hip)
+    def set_region(self, mask: Optional[torch.Tensor]):
+        """While a resident uint8 ``[H, W, D]`` GPU tensor is set, foreground means ``mask != 0`` (a body or lung mask
+        from ``mivp_amd.components``) and the threshold is ignored; ``None`` returns to the threshold rule.  The tensor
+        is read at every run, not copied."""
+        if self.skip is None:
+            raise ValueError("set_region needs a predictor built with skip=WindowSkip(...)")
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+                raise ValueError("the region mask must be a GPU tensor (no CPU fallback)")
+            if mask.dtype != torch.uint8 or tuple(mask.shape) != self.image_size:
+                raise ValueError(f"the region mask must be uint8 {self.image_size}, got {mask.dtype} {tuple(mask.shape)}")
+            if mask.device != self.dev or not mask.is_contiguous():
+                raise ValueError("the region mask must be contiguous and on the model's device")
+        self.region = mask
+
+    def _select(self, vol):
+        """occupancy -> compact into ``self.table``; no host read."""
+        a, k = self._a, self.skip
+        src = (L.ptr(vol), C.c_int32(self.cin), C.c_int32(k.channel), C.c_float(k.threshold), L.ptr(None)) \
+            if self.region is None else (L.ptr(None), C.c_int32(0), C.c_int32(0), C.c_float(0.0), L.ptr(self.region))
+        L.call("mivp_window_occupancy", *src, a["dims"], a["pad"], a["pdims"], a["roi"], L.ptr(self.origins_dev),
+               C.c_int32(3), C.c_int32(self.n_windows), L.ptr(self.occupancy), L.stream())
+        L.call("mivp_window_compact", L.ptr(self.table_full), C.c_int32(self.table.shape[0]), C.c_int32(self.n_windows),
+               C.c_int32(self.n_flips), L.ptr(self.occupancy), C.c_int32(k.min_voxels), L.ptr(self.table),
+               L.ptr(self.meta), L.stream())
+
+    def _kept(self) -> int:
+        """The one host read of a skipping run: (kept windows, kept entries) -> the number of sub-batches to run."""
+        kept_windows, kept_entries = self.meta.tolist()
+        self.n_kept = int(kept_windows)
+        self.n_sub_run = -(-int(kept_entries) // self.sub_batch)
+        return self.n_sub_run
+
+    def _fill(self):
+        k = self.skip
+        L.call("mivp_stitch_fill", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), self._a["pdims"],
+               C.c_int32(k.fill_class), C.c_float(k.fill_logit), L.stream())
 
     def _record(self):
         """Warm up two sub-batches eagerly on a side stream, then record one sub-batch step."""
@@ -403,14 +522,26 @@ class SlidingWindowPredictor:
             if vol.data_ptr() != self.vol.data_ptr():            # predict_scan prepares straight into the resident volume
                 self.vol.copy_(vol)
             if self.graph is None:
+                if self.skip is not None:                        # warm up and record with the full work list
+                    self.table.copy_(self.table_full)
                 self._record()
             self._reset()
-            for _ in range(self.n_sub):
+            n_sub = self.n_sub
+            if self.skip is not None:
+                self._select(self.vol)
+                n_sub = self._kept()
+            for _ in range(n_sub):
                 self.graph.replay()
         else:
             self._reset()
-            for _ in range(self.n_sub):
+            n_sub = self.n_sub
+            if self.skip is not None:
+                self._select(vol)
+                n_sub = self._kept()
+            for _ in range(n_sub):
                 self._step(vol)
+        if self.skip is not None:
+            self._fill()
         labels = torch.empty((1, 1) + self.image_size, dtype=torch.uint8, device=self.dev)
         logits = torch.empty((1, self.ncls) + self.image_size, dtype=torch.float32, device=self.dev) if want_logits else None
         tgt = None
@@ -593,7 +724,7 @@ def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], nu
                         axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
                         sub_batch: int = 10, graph: bool = False, restore: str = "labels",
                         postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                        **intensity) -> Dict[str, torch.Tensor]:
+                        skip: Optional[WindowSkip] = None, **intensity) -> Dict[str, torch.Tensor]:
     """One-shot ``SlidingWindowPredictor(...).predict_scan(raw, geom, restore, postprocess, **intensity)`` with
     ``geom = ScanGeometry.from_affine(raw's spatial shape, affine, axcodes, out_size)``; also returns ``"geometry"``."""
     from . import scan
@@ -602,7 +733,7 @@ def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], nu
     geom = scan.ScanGeometry.from_affine(tuple(raw.shape[-3:]), affine, axcodes, out_size)
     cin = 1 if raw.dim() == 3 else int(raw.shape[-4])
     p = SlidingWindowPredictor(model, geom.size, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph,
-                               mirror_axes)
+                               mirror_axes, skip)
     out = p.predict_scan(raw, geom, restore, postprocess, **intensity)
     out["geometry"] = geom
     return out
@@ -612,25 +743,25 @@ def predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int,
                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10, graph: bool = False,
                    return_logits: bool = False, postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
                    return_probs: bool = False, return_confidence: bool = False,
-                   return_entropy: bool = False) -> Dict[str, torch.Tensor]:
-    """One-shot ``SlidingWindowPredictor(..., mirror_axes=mirror_axes).predict(x, return_logits, postprocess, ...)`` for
+                   return_entropy: bool = False, skip: Optional[WindowSkip] = None) -> Dict[str, torch.Tensor]:
+    """One-shot ``SlidingWindowPredictor(..., mirror_axes=mirror_axes, skip=skip).predict(x, return_logits, postprocess, ...)`` for
     ``x [1, Cin, H, W, D]``."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes)
+                               graph, mirror_axes, skip)
     return p.predict(x, return_logits, postprocess, return_probs, return_confidence, return_entropy)
 
 
 def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
                     mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                     graph: bool = False, postprocess: Optional[Dict] = None,
-                    mirror_axes: Sequence[int] = ()) -> Tuple[float, float]:
+                    mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None) -> Tuple[float, float]:
     """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg, postprocess)``: whole-volume (mean IoU, mean Dice)."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes)
+                               graph, mirror_axes, skip)
     return p.evaluate(x, seg, postprocess)
 
 
@@ -638,12 +769,13 @@ def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequ
                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0), percentile: float = 95.0,
                             tolerance: float = 1.0, include_background: bool = False,
-                            postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = ()) -> Dict[str, object]:
+                            postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                            skip: Optional[WindowSkip] = None) -> Dict[str, object]:
     """One-shot ``SlidingWindowPredictor(...).evaluate_surface(x, seg, ...)``: whole-volume surface metrics + IoU / Dice."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes)
+                               graph, mirror_axes, skip)
     return p.evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)
 
 
@@ -651,24 +783,24 @@ def evaluate_volume_lesions(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequ
                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0),
                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                            with_scores: bool = False, **lesion_kwargs):
+                            with_scores: bool = False, skip: Optional[WindowSkip] = None, **lesion_kwargs):
     """One-shot ``SlidingWindowPredictor(...).evaluate_lesions(x, seg, spacing, postprocess, with_scores,
     **lesion_kwargs)``: the lesion-wise ``mivp_amd.regions.LesionReport`` of the whole-volume prediction."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes)
+                               graph, mirror_axes, skip)
     return p.evaluate_lesions(x, seg, spacing, postprocess, with_scores, **lesion_kwargs)
 
 
 def evaluate_volume_calibration(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
                                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
                                 sub_batch: int = 10, graph: bool = False, mirror_axes: Sequence[int] = (),
-                                n_bins: int = 15, out=None):
+                                n_bins: int = 15, out=None, skip: Optional[WindowSkip] = None):
     """One-shot ``SlidingWindowPredictor(...).evaluate_calibration(x, seg, n_bins, out)``: the
     ``mivp_amd.calibration.CalibrationReport`` of the whole-volume prediction."""
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise ValueError("x must be a [1, C, H, W, D] tensor")
     p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes)
+                               graph, mirror_axes, skip)
     return p.evaluate_calibration(x, seg, n_bins, out)

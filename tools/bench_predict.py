@@ -8,6 +8,12 @@ finalize per volume (from the shapes, below).  ``--mirror-axes 0,1,2`` turns on 
 then also gives windows x flips per second), ``--maps`` asks for the probability, confidence and entropy maps (the
 probability finalize instead of the plain one).
 
+``--skip-background`` times window skipping (``SlidingWindowPredictor(skip=WindowSkip())``) instead: a
+synthetic volume that is exactly 0 (air) outside an ellipsoid "body" filling ``1 - --air-fraction`` of the voxels, the
+same volume predicted without and with skipping by graph predictors, alternating, on device events.  One JSON line per
+shape: ms per volume without and with skipping, kept and total windows, and the time of the occupancy + compact + fill
+launches on their own.
+
 Kernel shares come from a run under the kernel tracer:
     rocprofv3 --kernel-trace --stats -d OUT -o pred -- python tools/bench_predict.py --volumes 2
 then ``python tools/bench_predict.py --stats OUT/.../pred_kernel_stats.csv --volumes 2`` prints the stitching kernels'
@@ -101,6 +107,71 @@ def run(name, volumes, warmup, mirror_axes=(), maps=False):
     return out
 
 
+def body_volume(image, air_fraction, dev):
+    """fp32 [1, 1, image]: values in (0.1, 1] inside a centred ellipsoid with the image's aspect that holds
+    ``1 - air_fraction`` of the voxels (clipped by the volume's faces when it must be larger than the inscribed one),
+    exactly 0 outside it."""
+    import torch
+    ax = [((torch.arange(n, dtype=torch.float32, device=dev) + 0.5) / n * 2 - 1) ** 2 for n in image]
+    rho = ax[0][:, None, None] + ax[1][None, :, None] + ax[2][None, None, :]
+    nvox = rho.numel()
+    nbody = min(nvox, max(0, int(round((1.0 - air_fraction) * nvox))))
+    x = 0.1 + 0.9 * torch.rand(image, generator=torch.Generator().manual_seed(1)).to(dev)
+    if nbody < nvox:
+        cut = torch.sort(rho.reshape(-1)).values[nbody] if nbody > 0 else -1.0
+        x = torch.where(rho < cut, x, torch.zeros_like(x))
+    return x[None, None].contiguous()
+
+
+def run_skip(name, volumes, warmup, air_fraction, mirror_axes=()):
+    import torch
+    from mivp_amd import train
+    from mivp_amd.inference import SlidingWindowPredictor, WindowSkip
+    from mivp_amd.swin_unetr import SwinUnetR
+    s = SHAPES[name]
+    conf, _, _ = train.make_conf("cfg1", window=s["window"])
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = SwinUnetR(conf).to(dev).eval()
+    x = body_volume(s["image"], air_fraction, dev)
+    air = float((x == 0).double().mean())
+    kw = dict(overlap=0.5, mode="gaussian", sub_batch=s["sub_batch"], graph=True, mirror_axes=mirror_axes)
+    preds = {"full": SlidingWindowPredictor(model, s["image"], CIN, NCLS, s["roi"], **kw),
+             "skip": SlidingWindowPredictor(model, s["image"], CIN, NCLS, s["roi"], skip=WindowSkip(), **kw)}
+    for p in preds.values():
+        for _ in range(warmup):
+            p.predict(x)
+    torch.cuda.synchronize()
+    ms = {k: [] for k in preds}
+    for _ in range(volumes):                                     # alternate the two, one event pair per volume
+        for k, p in preds.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            labels = p.predict(x)["labels"]
+            b.record()
+            torch.cuda.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    p = preds["skip"]
+    # the feature's own launches: occupancy + compact + fill (the fill finds nothing to write after a finished volume)
+    reps = 20
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        p._select(p.vol)
+        p._fill()
+    b.record()
+    torch.cuda.synchronize()
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    return [{"shape": name, "mode": "graph", "image": list(s["image"]), "roi": list(s["roi"]), "sub_batch": s["sub_batch"],
+             "mirror_axes": list(mirror_axes), "air_fraction": round(air, 4), "windows": p.n_windows, "kept": p.n_kept,
+             "kept_over_windows": round(p.n_kept / p.n_windows, 4), "sub_batches": p.n_sub, "sub_batches_run": p.n_sub_run,
+             "ms_per_volume_full": round(med["full"], 3), "ms_per_volume_skip": round(med["skip"], 3),
+             "skip_over_full": round(med["skip"] / med["full"], 4),
+             "ms_min_full": round(min(ms["full"]), 3), "ms_min_skip": round(min(ms["skip"]), 3),
+             "occupancy_compact_fill_ms": round(a.elapsed_time(b) / reps, 4),
+             "label_hist": torch.bincount(labels.reshape(-1).long()).tolist()}]
+
+
 def stats(path, volumes, warmup, shapes, mirror_axes=(), maps=False):
     """Share of kernel time and bytes / time of the stitching kernels in a profiled run of ``shapes``.  The flip-aware
     gather / blend and the probability finalize are the kernels of a run with ``mirror_axes`` / ``maps``."""
@@ -147,9 +218,15 @@ def main():
     ap.add_argument("--mirror-axes", type=parse_axes, default=(), metavar="A[,A..]",
                     help="mirror test-time augmentation over these spatial axes (0 = H, 1 = W, 2 = D), e.g. 0,1,2")
     ap.add_argument("--maps", action="store_true", help="also return probs / confidence / entropy (probability finalize)")
+    ap.add_argument("--skip-background", action="store_true",
+                    help="time window skipping against the unfiltered prediction on a synthetic body-in-air volume")
+    ap.add_argument("--air-fraction", type=float, default=0.5,
+                    help="with --skip-background: the fraction of voxels that are air (exactly 0), in [0, 1]")
     ap.add_argument("--stats", help="kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of this tool with the same "
                                     "--shape / --mirror-axes / --maps")
     a = ap.parse_args()
+    if not 0.0 <= a.air_fraction <= 1.0:
+        ap.error("--air-fraction must be in [0, 1]")
     import mivp_amd  # noqa: F401
     shapes = list(SHAPES) if a.shape == "all" else [a.shape]
     if a.stats:
@@ -157,7 +234,8 @@ def main():
         return
     for name in shapes:
         try:
-            lines = run(name, a.volumes, a.warmup, a.mirror_axes, a.maps)
+            lines = (run_skip(name, a.volumes, a.warmup, a.air_fraction, a.mirror_axes) if a.skip_background
+                     else run(name, a.volumes, a.warmup, a.mirror_axes, a.maps))
         except (RuntimeError, ValueError) as exc:                # a shape the model cannot run: say so, go on
             lines = [{"shape": name, "error": str(exc)[:300]}]
         for line in lines:
