@@ -1,0 +1,109 @@
+"""Host-side argument checks and small helpers shared by the evaluation modules (``inference``, ``surface``,
+``components``, ``regions``, ``calibration``, ``scan``, ``scanstats``).  One definition each: a module that needs one
+imports it from here, not from a sibling.  Nothing here launches a kernel except ``workspace``'s size query."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import numbers
+from typing import Iterable, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+LABEL_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}    # dtype codes of the label kernels
+CONNECTIVITY = (6, 18, 26)
+
+
+def i3(v):
+    """Three sizes as the ``int32[3]`` the C ABI takes."""
+    return (C.c_int32 * 3)(*[int(a) for a in v])
+
+
+def plain_int(v) -> bool:
+    """An int or a numpy integer, but not a bool."""
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def check_gpu(name: str, t):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a GPU tensor (no CPU fallback)")
+
+
+def check_classes(num_classes: int) -> int:
+    if not 1 <= int(num_classes) <= 16:
+        raise ValueError(f"num_classes must be in 1..16, got {num_classes}")
+    return int(num_classes)
+
+
+def check_spacing(spacing: Sequence[float]) -> Tuple[float, float, float]:
+    s = tuple(float(a) for a in spacing)
+    if len(s) != 3 or not all(math.isfinite(a) and a > 0 for a in s):
+        raise ValueError(f"spacing must be three positive sizes in mm, got {tuple(spacing)}")
+    return s
+
+
+def check_connectivity(connectivity) -> int:
+    if isinstance(connectivity, bool) or connectivity not in CONNECTIVITY:
+        raise ValueError(f"connectivity must be one of {CONNECTIVITY}, got {connectivity!r}")
+    return int(connectivity)
+
+
+def class_mask(ncls: int, classes: Optional[Iterable[int]]) -> int:
+    """``classes`` (default ``1..ncls-1``; distinct ints, 0 is rejected) as a bit mask."""
+    cls = list(range(1, ncls)) if classes is None else list(classes)
+    if not cls:
+        raise ValueError("classes is empty" + (" (num_classes=1 has no foreground class)" if classes is None else ""))
+    for c in cls:
+        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 1 <= c < ncls:
+            raise ValueError(f"classes must be ints in 1..{ncls - 1}, got {c!r}")
+    if len(set(cls)) != len(cls):
+        raise ValueError(f"classes has duplicates: {cls}")
+    mask = 0
+    for c in cls:
+        mask |= 1 << int(c)
+    return mask
+
+
+def check_min_size(min_size) -> int:
+    """Component sizes are below 2^31: a larger ``min_size`` removes every component, as 2^31 - 1 does."""
+    if isinstance(min_size, bool) or not isinstance(min_size, numbers.Integral) or min_size < 0:
+        raise ValueError(f"min_size must be a non-negative int, got {min_size!r}")
+    return min(int(min_size), 2 ** 31 - 1)
+
+
+def label_volume(name: str, t: torch.Tensor) -> torch.Tensor:
+    """``[1, 1, H, W, D]`` (or ``[H, W, D]``) GPU class map -> contiguous ``[H, W, D]`` of a dtype in ``LABEL_DTYPES``
+    (bool is read as uint8, any other dtype is converted to float32)."""
+    check_gpu(name, t)
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dim() == 5:
+        if t.shape[0] != 1 or t.shape[1] != 1:
+            raise ValueError(f"{name} must be [1, 1, H, W, D] (one volume of class indices), got {tuple(t.shape)}")
+        t = t[0, 0]
+    elif t.dim() != 3:
+        raise ValueError(f"{name} must be [1, 1, H, W, D] or [H, W, D], got {tuple(t.shape)}")
+    if t.numel() >= 2 ** 31:
+        raise ValueError(f"{name} has {t.numel()} voxels, the kernels take fewer than 2^31")
+    if t.dtype not in LABEL_DTYPES:
+        t = t.float()
+    return t.contiguous()
+
+
+def workspace(kind: str, dims, device) -> torch.Tensor:
+    """The uint8 workspace ``mivp_<kind>_ws(dims)`` asks for (at least one byte)."""
+    nbytes = int(getattr(L.lib(), f"mivp_{kind}_ws")(i3(dims)))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
+def iou_dice(counts: torch.Tensor) -> Tuple[float, float]:
+    """(mean IoU, mean Dice) in float64 from a ``[C, 3]`` table of (intersection, predicted, target) counts (utils.py:14-64);
+    a device table costs the one host read."""
+    c = counts.to(torch.float64).cpu()
+    inter, psum, tsum = c[:, 0], c[:, 1], c[:, 2]
+    iou = (inter / (psum + tsum - inter + 1e-6)).mean()
+    dice = (2 * inter / (psum + tsum + 1e-6)).mean()
+    return float(iou), float(dice)

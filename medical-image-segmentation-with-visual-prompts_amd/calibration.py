@@ -48,8 +48,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .components import _prepare
-from .surface import _DTYPES, _check_classes, _check_gpu, _i3
+from ._host import LABEL_DTYPES, check_classes, check_gpu, i3, label_volume
 
 QBITS = 20
 Q = 1 << QBITS
@@ -198,7 +197,7 @@ def _check_calibration_args(probs, target, num_classes, n_bins=15, out=None) -> 
         raise TypeError("probs and target must be torch tensors")
     if probs.dtype != torch.float32:
         raise TypeError(f"probs must be float32, got {probs.dtype}")
-    ncls = _check_classes(num_classes)
+    ncls = check_classes(num_classes)
     if isinstance(n_bins, bool) or not isinstance(n_bins, numbers.Integral) or not 1 <= n_bins <= MAX_BINS:
         raise ValueError(f"n_bins must be an int in 1..{MAX_BINS}, got {n_bins!r}")
     if probs.dim() == 5 and probs.shape[0] == 1:
@@ -230,16 +229,16 @@ def calibration_tables(probs: torch.Tensor, target: torch.Tensor, num_classes: i
     definitions): the ``CalibrationReport`` of their tables.  With ``out=`` the counts are added to that report, which is
     how scans are pooled.  No host read: ``CalibrationReport.cpu()`` synchronises."""
     ncls, nb, dims = _check_calibration_args(probs, target, num_classes, n_bins, out)
-    _check_gpu("probs", probs)
-    _check_gpu("target", target)
+    check_gpu("probs", probs)
+    check_gpu("target", target)
     if probs.device != target.device:
         raise ValueError(f"probs is on {probs.device}, target on {target.device}")
     if out is not None and out.tables.device != probs.device:
         raise ValueError(f"out is on {out.tables.device}, probs on {probs.device}")
     p = (probs[0] if probs.dim() == 5 else probs).contiguous()
-    t = _prepare("target", target)
+    t = label_volume("target", target)
     rep = CalibrationReport(ncls, nb, p.device) if out is None else out
     assert rep.tables.numel() * 8 == int(L.lib().mivp_calibration_ws(C.c_int32(ncls), C.c_int32(nb)))
-    L.call("mivp_calibration_hist", L.ptr(p), L.ptr(t), C.c_int32(_DTYPES[t.dtype]), _i3(dims), C.c_int32(ncls),
+    L.call("mivp_calibration_hist", L.ptr(p), L.ptr(t), C.c_int32(LABEL_DTYPES[t.dtype]), i3(dims), C.c_int32(ncls),
            C.c_int32(nb), C.c_int32(int(flags)), L.ptr(rep.tables), L.stream())
     return rep

@@ -26,59 +26,29 @@ root and one filter pass (post-processing).  ``postprocess_labels`` makes no hos
 from __future__ import annotations
 
 import ctypes as C
-import numbers
 from typing import Dict, Iterable, Optional, Tuple
 
 import torch
 
 from . import _lib as L
-from .surface import _DTYPES, _check_classes, _check_gpu, _i3, _volume
+from ._host import CONNECTIVITY  # noqa: F401  (public here since the module was written)
+from ._host import (LABEL_DTYPES, check_classes, check_connectivity, check_gpu, check_min_size, class_mask, i3,
+                    label_volume, workspace)
 
-CONNECTIVITY = (6, 18, 26)
-
-
-def _check_connectivity(connectivity) -> int:
-    if isinstance(connectivity, bool) or connectivity not in CONNECTIVITY:
-        raise ValueError(f"connectivity must be one of {CONNECTIVITY}, got {connectivity!r}")
-    return int(connectivity)
+_check_connectivity = check_connectivity      # the name tests/test_components_host.py imports
 
 
 def _check_post_args(num_classes, largest=True, min_size=0, classes: Optional[Iterable[int]] = None,
                      connectivity=26) -> Tuple[int, int, int, bool, int]:
     """Validate the post-processing arguments -> (num_classes, class bit mask, min_size, largest, connectivity)."""
-    ncls = _check_classes(num_classes)
-    if isinstance(min_size, bool) or not isinstance(min_size, numbers.Integral) or min_size < 0:
-        raise ValueError(f"min_size must be a non-negative int, got {min_size!r}")
+    ncls = check_classes(num_classes)
+    min_size = check_min_size(min_size)
     if not isinstance(largest, bool):
         raise ValueError(f"largest must be a bool, got {largest!r}")
     if not largest and min_size == 0:
         raise ValueError("largest=False with min_size=0 keeps every component: nothing to do")
-    conn = _check_connectivity(connectivity)
-    cls = list(range(1, ncls)) if classes is None else list(classes)
-    if not cls:
-        raise ValueError("classes is empty" + (" (num_classes=1 has no foreground class)" if classes is None else ""))
-    for c in cls:
-        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 1 <= c < ncls:
-            raise ValueError(f"classes must be ints in 1..{ncls - 1}, got {c!r}")
-    if len(set(cls)) != len(cls):
-        raise ValueError(f"classes has duplicates: {cls}")
-    mask = 0
-    for c in cls:
-        mask |= 1 << int(c)
-    # sizes are below 2^31: a larger min_size removes every component, as 2^31 - 1 does
-    return ncls, mask, min(int(min_size), 2 ** 31 - 1), largest, conn
-
-
-def _prepare(name: str, x: torch.Tensor) -> torch.Tensor:
-    _check_gpu(name, x)
-    if x.dtype == torch.bool:
-        x = x.view(torch.uint8)
-    return _volume(name, x)
-
-
-def _workspace(kind: str, dims, device) -> torch.Tensor:
-    nbytes = int(getattr(L.lib(), f"mivp_{kind}_ws")(_i3(dims)))
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+    conn = check_connectivity(connectivity)
+    return ncls, class_mask(ncls, classes), min_size, largest, conn
 
 
 def label_components(x: torch.Tensor, connectivity: int = 6) -> Tuple[torch.Tensor, int]:
@@ -86,13 +56,13 @@ def label_components(x: torch.Tensor, connectivity: int = 6) -> Tuple[torch.Tens
     nonzero value are joined): ``(labels, n)`` with ``labels`` int32 of x's shape numbered 1..n as
     ``scipy.ndimage.label`` numbers them (the module docstring), 0 on background.  ``n`` is a Python int: reading it is
     the one host synchronisation of this call."""
-    conn = _check_connectivity(connectivity)
-    v = _prepare("x", x)
+    conn = check_connectivity(connectivity)
+    v = label_volume("x", x)
     dims = tuple(v.shape)
     labels = torch.empty(dims, dtype=torch.int32, device=v.device)
     n = torch.empty(1, dtype=torch.int32, device=v.device)
-    ws = _workspace("label", dims, v.device)
-    L.call("mivp_label_components", L.ptr(v), C.c_int32(_DTYPES[v.dtype]), _i3(dims), C.c_int32(conn), L.ptr(labels),
+    ws = workspace("label", dims, v.device)
+    L.call("mivp_label_components", L.ptr(v), C.c_int32(LABEL_DTYPES[v.dtype]), i3(dims), C.c_int32(conn), L.ptr(labels),
            L.ptr(n), L.ptr(ws), L.stream())
     return labels.reshape(x.shape), int(n.item())
 
@@ -105,8 +75,8 @@ def _postprocess_launch(v: torch.Tensor, out: torch.Tensor, args, ws: Optional[t
     ncls, mask, min_size, largest, conn = args
     dims = tuple(v.shape)
     if ws is None:
-        ws = _workspace("postprocess", dims, v.device)
-    L.call("mivp_postprocess_labels", L.ptr(v), C.c_int32(_DTYPES[v.dtype]), _i3(dims), C.c_int32(ncls),
+        ws = workspace("postprocess", dims, v.device)
+    L.call("mivp_postprocess_labels", L.ptr(v), C.c_int32(LABEL_DTYPES[v.dtype]), i3(dims), C.c_int32(ncls),
            C.c_uint32(mask), C.c_int64(min_size), C.c_int32(int(largest)), C.c_int32(conn), L.ptr(out), L.ptr(target),
            L.ptr(counts), L.ptr(ws), L.stream())
     return ws
@@ -117,9 +87,9 @@ def postprocess_labels(labels: torch.Tensor, num_classes: int, largest: bool = T
     """Keep the largest connected component of each class in ``classes`` and / or remove its components smaller than
     ``min_size`` voxels (the module docstring has the exact rule).  ``labels`` is a ``[1, 1, H, W, D]`` or ``[H, W, D]``
     GPU class map; the result is a new tensor of its dtype and shape.  No host synchronisation (graph-capturable)."""
-    _check_gpu("labels", labels)
+    check_gpu("labels", labels)
     args = _check_post_args(num_classes, largest, min_size, classes, connectivity)
-    v = _prepare("labels", labels)
+    v = label_volume("labels", labels)
     out = torch.empty_like(v)
     _postprocess_launch(v, out, args)
     if labels.dtype == torch.bool:

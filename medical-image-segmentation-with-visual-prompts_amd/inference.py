@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._host import check_classes, check_gpu, i3, iou_dice, plain_int
 
 
 def window_grid(image_size: Sequence[int], roi: Sequence[int]) -> Tuple[List[slice], List[int], List[int]]:
@@ -88,11 +89,7 @@ class SegMetrics:
 
     def compute(self) -> Tuple[float, float]:
         """(mean IoU, mean Dice) -- the one host read."""
-        c = self.counts.to(torch.float64).cpu()
-        inter, psum, tsum = c[:, 0], c[:, 1], c[:, 2]
-        iou = (inter / (psum + tsum - inter + 1e-6)).mean()
-        dice = (2 * inter / (psum + tsum + 1e-6)).mean()
-        return float(iou), float(dice)
+        return iou_dice(self.counts)
 
 
 @torch.no_grad()
@@ -126,6 +123,7 @@ def _check_overlap(overlap: float):
         raise ValueError(f"overlap must be in [0, 1), got {overlap}")
 
 
+# truncates non-integer sizes, unlike scan._shape3, which rejects them
 def _check_shape3(name: str, v: Sequence[int]) -> Tuple[int, int, int]:
     t = tuple(int(a) for a in v)
     if len(t) != 3 or min(t) < 1:
@@ -163,12 +161,7 @@ def window_table(origins: np.ndarray, sub_batch: int) -> np.ndarray:
     """The device table: int32 [ceil(N / sub_batch) * sub_batch, 4] = (o0, o1, o2, valid); padding entries are invalid."""
     if int(sub_batch) < 1:
         raise ValueError("sub_batch must be >= 1")
-    n = origins.shape[0]
-    total = -(-n // int(sub_batch)) * int(sub_batch)
-    t = np.zeros((total, 4), dtype=np.int32)
-    t[:n, :3] = origins
-    t[:n, 3] = 1
-    return t
+    return tta_table(origins, sub_batch, (0,))
 
 
 def flip_codes(mirror_axes: Sequence[int] = ()) -> Tuple[int, ...]:
@@ -225,14 +218,6 @@ def importance_tables(roi: Sequence[int], mode: str = "gaussian", sigma_scale: f
     return tabs, floor
 
 
-def _i3(v):
-    return (C.c_int32 * 3)(*[int(a) for a in v])
-
-
-def _plain_int(v) -> bool:
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-
-
 class WindowSkip:
     """Which windows a ``SlidingWindowPredictor(skip=...)`` leaves out.  A voxel of the prepared volume is
     foreground iff ``vol[channel] > threshold`` (strict fp32: NaN is not foreground; the default threshold is the
@@ -252,7 +237,7 @@ class WindowSkip:
         if not 0 < float(fill_logit) <= float(np.finfo(np.float32).max):
             raise ValueError(f"fill_logit must be > 0 and finite in fp32, got {fill_logit!r}")
         for name, v, lo in (("channel", channel, 0), ("min_voxels", min_voxels, 1), ("fill_class", fill_class, 0)):
-            if not _plain_int(v) or int(v) < lo or int(v) >= 2 ** 31:
+            if not plain_int(v) or int(v) < lo or int(v) >= 2 ** 31:
                 raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
         object.__setattr__(self, "threshold", float(threshold))
         object.__setattr__(self, "channel", int(channel))
@@ -331,8 +316,7 @@ class SlidingWindowPredictor:
             raise ValueError("sub_batch must be >= 1")
         if not 1 <= int(in_channels) <= 4:
             raise ValueError("in_channels must be in 1..4")
-        if not 1 <= int(num_classes) <= 16:
-            raise ValueError("num_classes must be in 1..16")
+        check_classes(num_classes)
         if skip is not None:
             if not isinstance(skip, WindowSkip):
                 raise ValueError(f"skip must be a WindowSkip or None, got {type(skip).__name__}")
@@ -389,8 +373,8 @@ class SlidingWindowPredictor:
         # and wsum along (compensated sums, in the same order), so that they round like the plain prediction's
         self.comp = (torch.zeros(self.pdims + (self.ncls + 1,), dtype=torch.float32, device=dev)
                      if self.n_flips > 1 else None)
-        self._a = dict(dims=_i3(self.image_size), pad=_i3(self.pad), pdims=_i3(self.pdims), roi=_i3(self.roi),
-                       ubox=_i3(self.ubox))
+        self._a = dict(dims=i3(self.image_size), pad=i3(self.pad), pdims=i3(self.pdims), roi=i3(self.roi),
+                       ubox=i3(self.ubox))
         self.vol = None          # graph mode: the resident volume the recorded gather reads
         self.graph = None
         self.cc_ws = None        # post-processing workspace (8 bytes per voxel), allocated on first use
@@ -499,8 +483,7 @@ class SlidingWindowPredictor:
 
     # ------------------------------------------------------------------ whole volume
     def _check_input(self, x, name="x", channels=None):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError(f"{name} must be a GPU tensor (no CPU fallback)")
+        check_gpu(name, x)
         if x.dim() != 5 or x.shape[0] != 1:
             raise ValueError(f"{name} must be [1, C, H, W, D] (one volume at a time), got {tuple(x.shape)}")
         ch = self.cin if channels is None else channels
@@ -525,19 +508,16 @@ class SlidingWindowPredictor:
                 if self.skip is not None:                        # warm up and record with the full work list
                     self.table.copy_(self.table_full)
                 self._record()
-            self._reset()
-            n_sub = self.n_sub
-            if self.skip is not None:
-                self._select(self.vol)
-                n_sub = self._kept()
+            vol = self.vol                                       # what the launches below and the recorded gather read
+        self._reset()
+        n_sub = self.n_sub
+        if self.skip is not None:
+            self._select(vol)
+            n_sub = self._kept()
+        if self.graph_mode:
             for _ in range(n_sub):
                 self.graph.replay()
         else:
-            self._reset()
-            n_sub = self.n_sub
-            if self.skip is not None:
-                self._select(vol)
-                n_sub = self._kept()
             for _ in range(n_sub):
                 self._step(vol)
         if self.skip is not None:
@@ -554,13 +534,13 @@ class SlidingWindowPredictor:
                                 device=self.dev) for k in maps}
         # the post-processing rewrites the labels in place; its filter pass, not the finalize, counts them against seg
         f_tgt, f_counts = (tgt, counts) if post is None else (None, None)
+        # a call that asks for no maps keeps the plain finalize; the probability one takes the three maps in the middle
+        name, map_ptrs = "mivp_stitch_finalize", ()
         if extra:
-            L.call("mivp_stitch_finalize_probs", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"],
-                   a["pad"], a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(extra.get("probs")),
-                   L.ptr(extra.get("confidence")), L.ptr(extra.get("entropy")), L.ptr(f_tgt), L.ptr(f_counts), L.stream())
-        else:
-            L.call("mivp_stitch_finalize", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"], a["pad"],
-                   a["pdims"], L.ptr(labels), L.ptr(logits), L.ptr(f_tgt), L.ptr(f_counts), L.stream())
+            name = "mivp_stitch_finalize_probs"
+            map_ptrs = tuple(L.ptr(extra.get(k)) for k in ("probs", "confidence", "entropy"))
+        L.call(name, L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"], a["pad"], a["pdims"],
+               L.ptr(labels), L.ptr(logits), *map_ptrs, L.ptr(f_tgt), L.ptr(f_counts), L.stream())
         if post is not None:
             from . import components
             lab = labels[0, 0]
@@ -643,11 +623,7 @@ class SlidingWindowPredictor:
         post = self._post(postprocess)
         self._check_input(seg, "seg", channels=1)
         self._run(x, False, seg, post)
-        c = self.counts.to(torch.float64).cpu()
-        inter, psum, tsum = c[:, 0], c[:, 1], c[:, 2]
-        iou = (inter / (psum + tsum - inter + 1e-6)).mean()
-        dice = (2 * inter / (psum + tsum + 1e-6)).mean()
-        return float(iou), float(dice)
+        return iou_dice(self.counts)
 
     def evaluate_surface(self, x: torch.Tensor, seg: torch.Tensor, spacing: Sequence[float] = (1.0, 1.0, 1.0),
                          percentile: float = 95.0, tolerance: float = 1.0, include_background: bool = False,
@@ -663,14 +639,10 @@ class SlidingWindowPredictor:
         labels, _, _ = self._run(x, False, seg, post)
         scount, recs = S._metrics_launch(labels, seg, ncls, sp, pc, tol, include_background)
         host = torch.cat([self.counts.reshape(-1), scount.reshape(-1), recs.reshape(-1)]).cpu()
-        c = host[:3 * ncls].reshape(ncls, 3).to(torch.float64)
-        inter, psum, tsum = c[:, 0], c[:, 1], c[:, 2]
-        iou = (inter / (psum + tsum - inter + 1e-6)).mean()
-        dice = (2 * inter / (psum + tsum + 1e-6)).mean()
         rest = host[3 * ncls:].numpy()
         out = S._metrics_finish(rest[:2 * ncls].reshape(ncls, 2), rest[2 * ncls:].reshape(ncls, 2, S._REC), ncls, pc,
                                 include_background)
-        out["iou"], out["dice"] = float(iou), float(dice)
+        out["iou"], out["dice"] = iou_dice(host[:3 * ncls].reshape(ncls, 3))
         return out
 
     # ------------------------------------------------------------------ raw scans (mivp_amd.scan)
@@ -720,6 +692,17 @@ class SlidingWindowPredictor:
         return self.evaluate(x, seg, postprocess)
 
 
+def _one_shot(model, x_or_shape, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes, skip):
+    """The predictor behind a one-shot wrapper: built for the volume ``x [1, Cin, H, W, D]`` (``cin`` None), or for an
+    image size and its ``cin``."""
+    if cin is None:
+        if not isinstance(x_or_shape, torch.Tensor) or x_or_shape.dim() != 5:
+            raise ValueError("x must be a [1, C, H, W, D] tensor")
+        x_or_shape, cin = x_or_shape.shape[2:], x_or_shape.shape[1]
+    return SlidingWindowPredictor(model, x_or_shape, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph,
+                                  mirror_axes, skip)
+
+
 def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], num_classes: int, out_size=None,
                         axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
                         sub_batch: int = 10, graph: bool = False, restore: str = "labels",
@@ -732,9 +715,8 @@ def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], nu
         raise ValueError("raw must be a [C, H, W, D] (or [H, W, D] / [1, C, H, W, D]) tensor")
     geom = scan.ScanGeometry.from_affine(tuple(raw.shape[-3:]), affine, axcodes, out_size)
     cin = 1 if raw.dim() == 3 else int(raw.shape[-4])
-    p = SlidingWindowPredictor(model, geom.size, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph,
-                               mirror_axes, skip)
-    out = p.predict_scan(raw, geom, restore, postprocess, **intensity)
+    out = _one_shot(model, geom.size, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
+                    skip).predict_scan(raw, geom, restore, postprocess, **intensity)
     out["geometry"] = geom
     return out
 
@@ -746,11 +728,8 @@ def predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int,
                    return_entropy: bool = False, skip: Optional[WindowSkip] = None) -> Dict[str, torch.Tensor]:
     """One-shot ``SlidingWindowPredictor(..., mirror_axes=mirror_axes, skip=skip).predict(x, return_logits, postprocess, ...)`` for
     ``x [1, Cin, H, W, D]``."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 5:
-        raise ValueError("x must be a [1, C, H, W, D] tensor")
-    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes, skip)
-    return p.predict(x, return_logits, postprocess, return_probs, return_confidence, return_entropy)
+    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
+                     skip).predict(x, return_logits, postprocess, return_probs, return_confidence, return_entropy)
 
 
 def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
@@ -758,11 +737,8 @@ def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int
                     graph: bool = False, postprocess: Optional[Dict] = None,
                     mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None) -> Tuple[float, float]:
     """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg, postprocess)``: whole-volume (mean IoU, mean Dice)."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 5:
-        raise ValueError("x must be a [1, C, H, W, D] tensor")
-    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes, skip)
-    return p.evaluate(x, seg, postprocess)
+    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
+                     skip).evaluate(x, seg, postprocess)
 
 
 def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
@@ -772,11 +748,8 @@ def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequ
                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
                             skip: Optional[WindowSkip] = None) -> Dict[str, object]:
     """One-shot ``SlidingWindowPredictor(...).evaluate_surface(x, seg, ...)``: whole-volume surface metrics + IoU / Dice."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 5:
-        raise ValueError("x must be a [1, C, H, W, D] tensor")
-    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes, skip)
-    return p.evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)
+    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
+                     skip).evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)
 
 
 def evaluate_volume_lesions(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
@@ -786,11 +759,8 @@ def evaluate_volume_lesions(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequ
                             with_scores: bool = False, skip: Optional[WindowSkip] = None, **lesion_kwargs):
     """One-shot ``SlidingWindowPredictor(...).evaluate_lesions(x, seg, spacing, postprocess, with_scores,
     **lesion_kwargs)``: the lesion-wise ``mivp_amd.regions.LesionReport`` of the whole-volume prediction."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 5:
-        raise ValueError("x must be a [1, C, H, W, D] tensor")
-    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes, skip)
-    return p.evaluate_lesions(x, seg, spacing, postprocess, with_scores, **lesion_kwargs)
+    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
+                     skip).evaluate_lesions(x, seg, spacing, postprocess, with_scores, **lesion_kwargs)
 
 
 def evaluate_volume_calibration(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
@@ -799,8 +769,5 @@ def evaluate_volume_calibration(model, x: torch.Tensor, seg: torch.Tensor, roi: 
                                 n_bins: int = 15, out=None, skip: Optional[WindowSkip] = None):
     """One-shot ``SlidingWindowPredictor(...).evaluate_calibration(x, seg, n_bins, out)``: the
     ``mivp_amd.calibration.CalibrationReport`` of the whole-volume prediction."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 5:
-        raise ValueError("x must be a [1, C, H, W, D] tensor")
-    p = SlidingWindowPredictor(model, x.shape[2:], x.shape[1], num_classes, roi, overlap, mode, sigma_scale, sub_batch,
-                               graph, mirror_axes, skip)
-    return p.evaluate_calibration(x, seg, n_bins, out)
+    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
+                     skip).evaluate_calibration(x, seg, n_bins, out)

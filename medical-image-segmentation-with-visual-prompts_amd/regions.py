@@ -58,8 +58,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .components import _check_connectivity, _prepare
-from .surface import _DTYPES, _check_classes, _check_gpu, _check_spacing, _i3
+from ._host import (LABEL_DTYPES, check_classes, check_connectivity, check_gpu, check_min_size, check_spacing, class_mask,
+                    i3, label_volume, workspace)
 
 _IMAGE_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.float32: 3, torch.int16: 4}
 
@@ -73,22 +73,12 @@ class _CTable(C.Structure):
 def _check_region_args(num_classes, connectivity=26, classes: Optional[Iterable[int]] = None, max_regions=4096,
                        spacing=(1.0, 1.0, 1.0)):
     """-> (num_classes, class bit mask, connectivity, max_regions, spacing)."""
-    ncls = _check_classes(num_classes)
-    conn = _check_connectivity(connectivity)
-    cls = list(range(1, ncls)) if classes is None else list(classes)
-    if not cls:
-        raise ValueError("classes is empty" + (" (num_classes=1 has no foreground class)" if classes is None else ""))
-    for c in cls:
-        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 1 <= c < ncls:
-            raise ValueError(f"classes must be ints in 1..{ncls - 1}, got {c!r}")
-    if len(set(cls)) != len(cls):
-        raise ValueError(f"classes has duplicates: {cls}")
-    mask = 0
-    for c in cls:
-        mask |= 1 << int(c)
+    ncls = check_classes(num_classes)
+    conn = check_connectivity(connectivity)
+    mask = class_mask(ncls, classes)
     if isinstance(max_regions, bool) or not isinstance(max_regions, numbers.Integral) or not 1 <= max_regions <= 2 ** 24:
         raise ValueError(f"max_regions must be an int in 1..2^24, got {max_regions!r}")
-    return ncls, mask, conn, int(max_regions), _check_spacing(spacing)
+    return ncls, mask, conn, int(max_regions), check_spacing(spacing)
 
 
 def _check_lesion_args(iou_threshold=0.0, min_size=0, max_regions=4096, max_pairs=None):
@@ -96,13 +86,12 @@ def _check_lesion_args(iou_threshold=0.0, min_size=0, max_regions=4096, max_pair
     if isinstance(iou_threshold, bool) or not isinstance(iou_threshold, numbers.Real) or \
             not (math.isfinite(iou_threshold) and 0.0 <= iou_threshold <= 1.0):
         raise ValueError(f"iou_threshold must be in [0, 1], got {iou_threshold!r}")
-    if isinstance(min_size, bool) or not isinstance(min_size, numbers.Integral) or min_size < 0:
-        raise ValueError(f"min_size must be a non-negative int, got {min_size!r}")
+    min_size = check_min_size(min_size)
     if max_pairs is None:
         max_pairs = 4 * int(max_regions)
     if isinstance(max_pairs, bool) or not isinstance(max_pairs, numbers.Integral) or not 1 <= max_pairs <= 2 ** 28:
         raise ValueError(f"max_pairs must be an int in 1..2^28, got {max_pairs!r}")
-    return float(iou_threshold), min(int(min_size), 2 ** 31 - 1), int(max_pairs)
+    return float(iou_threshold), min_size, int(max_pairs)
 
 
 REGION_KWARGS = ("connectivity", "classes", "max_regions")
@@ -128,7 +117,7 @@ def check_lesion_kwargs(num_classes, spacing=(1.0, 1.0, 1.0), **kwargs):
 
 
 def _check_image(image, dims, device) -> torch.Tensor:
-    _check_gpu("image", image)
+    check_gpu("image", image)
     if image.device != device:
         raise ValueError(f"image is on {image.device}, labels on {device}")
     if image.dim() == 5 and image.shape[0] == 1 and image.shape[1] == 1:
@@ -235,8 +224,8 @@ def _stats_launch(v: torch.Tensor, args, image: Optional[torch.Tensor], ws: Opti
     dims = tuple(v.shape)
     tab = RegionTable(dims, max_regions, spacing, v.device, None if image is None else image.dtype)
     if ws is None:
-        ws = torch.empty(max(int(L.lib().mivp_region_stats_ws(_i3(dims))), 1), dtype=torch.uint8, device=v.device)
-    L.call("mivp_region_stats", L.ptr(v), C.c_int32(_DTYPES[v.dtype]), _i3(dims), C.c_int32(ncls), C.c_uint32(mask),
+        ws = workspace("region_stats", dims, v.device)
+    L.call("mivp_region_stats", L.ptr(v), C.c_int32(LABEL_DTYPES[v.dtype]), i3(dims), C.c_int32(ncls), C.c_uint32(mask),
            C.c_int32(conn), L.ptr(image), L.ptr(tab.labels), C.byref(tab._c), L.ptr(ws), L.stream())
     return tab
 
@@ -247,9 +236,9 @@ def region_stats(labels: torch.Tensor, num_classes: int, image: Optional[torch.T
     """The connected regions of the class map ``labels`` with their size, first voxel, bounding box and coordinate sums,
     and with ``image`` their minimum, maximum, sum and sum of squares (the module docstring has the definitions).  No host
     read: ``RegionTable.cpu()`` synchronises."""
-    _check_gpu("labels", labels)
+    check_gpu("labels", labels)
     args = _check_region_args(num_classes, connectivity, classes, max_regions, spacing)
-    v = _prepare("labels", labels)
+    v = label_volume("labels", labels)
     img = None if image is None else _check_image(image, v.shape, v.device)
     return _stats_launch(v, args, img)
 
@@ -443,7 +432,7 @@ def _lesion_launch(pv: torch.Tensor, tv: torch.Tensor, rargs, largs, pred_image:
     pred = _stats_launch(pv, rargs, pred_image)
     target = _stats_launch(tv, rargs, None)
     rep = LesionReport(pred, target, ncls, min_size, thr, max_pairs)
-    L.call("mivp_region_overlap", L.ptr(pred.labels), L.ptr(target.labels), _i3(pv.shape), C.byref(pred._c),
+    L.call("mivp_region_overlap", L.ptr(pred.labels), L.ptr(target.labels), i3(pv.shape), C.byref(pred._c),
            C.byref(target._c), C.c_int64(max_pairs), L.ptr(rep.pairs), L.stream())
     L.call("mivp_lesion_match", C.byref(pred._c), C.byref(target._c), L.ptr(rep.pairs), C.c_int64(max_pairs),
            C.c_int32(ncls), C.c_int64(min_size), C.c_double(thr), L.ptr(rep.counts), L.ptr(rep.overlap),
@@ -476,11 +465,11 @@ def lesion_score_metrics(pred: torch.Tensor, target: torch.Tensor, num_classes: 
     """``lesion_metrics`` with lesion scores: ``pred_image`` (float32, the spatial shape of ``pred``; a confidence map) is
     the image of the predicted ``RegionTable``, and the report carries ``score`` / ``best_score``, ``froc()`` and
     ``froc_score()`` (the module docstring has the definitions).  ``pred_image=None`` is ``lesion_metrics``."""
-    _check_gpu("pred", pred)
-    _check_gpu("target", target)
+    check_gpu("pred", pred)
+    check_gpu("target", target)
     rargs = _check_region_args(num_classes, connectivity, classes, max_regions, spacing)
     largs = _check_lesion_args(iou_threshold, min_size, max_regions, max_pairs)
-    pv, tv = _prepare("pred", pred), _prepare("target", target)
+    pv, tv = label_volume("pred", pred), label_volume("target", target)
     if pv.shape != tv.shape:
         raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
     if pv.device != tv.device:

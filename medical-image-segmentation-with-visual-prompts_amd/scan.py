@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._host import check_gpu, i3
 
 _DTYPES = {torch.uint8: 0, torch.int32: 1, torch.float32: 3, torch.int16: 4}
 _CODES = {"L": (0, -1), "R": (0, 1), "P": (1, -1), "A": (1, 1), "I": (2, -1), "S": (2, 1)}
@@ -38,10 +39,7 @@ FLAG_DIRECT = 1          # read the source directly even when the innermost axis
 FLAG_STAGED = 2          # stage tiles through LDS where the default reads directly (labels, arg-max)
 
 
-def _i3(v):
-    return (C.c_int32 * 3)(*[int(a) for a in v])
-
-
+# rejects non-integer sizes, unlike inference._check_shape3, which truncates them
 def _shape3(name: str, v) -> Tuple[int, int, int]:
     try:
         t = tuple(int(a) for a in v)
@@ -225,11 +223,6 @@ def _check_tensor(name: str, t, dims: Sequence[int], dtypes) -> None:
         raise ValueError(f"{name} must be one of {[str(d).replace('torch.', '') for d in dtypes]}, got {t.dtype}")
 
 
-def _check_gpu(name: str, t: torch.Tensor) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a GPU tensor (no CPU fallback)")
-
-
 def _check_out(out, shape, dtype, like: torch.Tensor):
     if out is None:
         return None
@@ -302,7 +295,7 @@ def prepare_scan(raw: torch.Tensor, geom: ScanGeometry, a_min: Optional[float] =
         scanstats.check_window_args(window, r, mask, geom.shape)
     shape = (1, r.shape[0]) + geom.size
     out = _check_out(out, shape, torch.float32, r)
-    _check_gpu("raw", r)
+    check_gpu("raw", r)
     r = r.contiguous()
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=r.device)
@@ -310,11 +303,11 @@ def prepare_scan(raw: torch.Tensor, geom: ScanGeometry, a_min: Optional[float] =
     if window is not None:
         slot = scanstats.resolve_window(window, r, mask)
         dev_clip = bool(clip) if slot.mode == scanstats.MODE_PERCENTILE else True
-        L.call("mivp_scan_prepare_dev", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(r.shape[0]), _i3(src), _i3(dst),
-               _i3(axes), L.ptr(geom.device_tables("image", r.device)), C.c_int32(int(interp)), L.ptr(slot.words),
+        L.call("mivp_scan_prepare_dev", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(r.shape[0]), i3(src), i3(dst),
+               i3(axes), L.ptr(geom.device_tables("image", r.device)), C.c_int32(int(interp)), L.ptr(slot.words),
                C.c_int32(int(dev_clip)), C.c_int32(int(flags)), L.ptr(out), L.stream())
         return out
-    L.call("mivp_scan_prepare", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(r.shape[0]), _i3(src), _i3(dst), _i3(axes),
+    L.call("mivp_scan_prepare", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(r.shape[0]), i3(src), i3(dst), i3(axes),
            L.ptr(geom.device_tables("image", r.device)), C.c_int32(int(interp)), (C.c_float * 4)(*mp),
            C.c_int32(int(bool(clip))), C.c_int32(int(flags)), L.ptr(out), L.stream())
     return out
@@ -331,13 +324,13 @@ def prepare_labels(seg: torch.Tensor, geom: ScanGeometry, out: Optional[torch.Te
     s = _volume3("seg", seg, geom.shape)
     shape = (1, 1) + geom.size
     out = _check_out(out, shape, torch.uint8, s)
-    _check_gpu("seg", s)
+    check_gpu("seg", s)
     s = s.contiguous()
     if out is None:
         out = torch.empty(shape, dtype=torch.uint8, device=s.device)
     bad = torch.zeros(1, dtype=torch.int32, device=s.device)
     src, dst, axes, _, _ = geom.tables("labels")
-    L.call("mivp_scan_prepare_labels", L.ptr(s), C.c_int32(_DTYPES[s.dtype]), _i3(src), _i3(dst), _i3(axes),
+    L.call("mivp_scan_prepare_labels", L.ptr(s), C.c_int32(_DTYPES[s.dtype]), i3(src), i3(dst), i3(axes),
            L.ptr(geom.device_tables("labels", s.device)), C.c_int32(int(flags)), L.ptr(out), L.ptr(bad), L.stream())
     if check and int(bad.item()) != 0:
         raise ValueError("seg holds values outside 0..255 (or non-integer values): they do not fit a uint8 label map")
@@ -353,12 +346,12 @@ def restore_labels(labels: torch.Tensor, geom: ScanGeometry, out: Optional[torch
     _check_tensor("labels", labels, (3, 5), (torch.uint8,))
     v = _volume3("labels", labels, geom.size)
     out = _check_out(out, geom.shape, torch.uint8, v)
-    _check_gpu("labels", v)
+    check_gpu("labels", v)
     v = v.contiguous()
     if out is None:
         out = torch.empty(geom.shape, dtype=torch.uint8, device=v.device)
     src, dst, axes, _, _ = geom.tables("restore_labels")
-    L.call("mivp_scan_restore_labels", L.ptr(v), _i3(src), _i3(dst), _i3(axes),
+    L.call("mivp_scan_restore_labels", L.ptr(v), i3(src), i3(dst), i3(axes),
            L.ptr(geom.device_tables("restore_labels", v.device)), C.c_int32(int(flags)), L.ptr(out), L.stream())
     return out
 
@@ -381,12 +374,12 @@ def restore_labels_from_logits(logits: torch.Tensor, geom: ScanGeometry, out: Op
     if tuple(v.shape[1:]) != geom.size:
         raise ValueError(f"logits have spatial size {tuple(v.shape[1:])}, the geometry's model grid is {geom.size}")
     out = _check_out(out, geom.shape, torch.uint8, v)
-    _check_gpu("logits", v)
+    check_gpu("logits", v)
     v = v.contiguous()
     if out is None:
         out = torch.empty(geom.shape, dtype=torch.uint8, device=v.device)
     src, dst, axes, interp, _ = geom.tables("restore_logits")
-    L.call("mivp_scan_restore_argmax", L.ptr(v), C.c_int32(v.shape[0]), _i3(src), _i3(dst), _i3(axes),
+    L.call("mivp_scan_restore_argmax", L.ptr(v), C.c_int32(v.shape[0]), i3(src), i3(dst), i3(axes),
            L.ptr(geom.device_tables("restore_logits", v.device)), C.c_int32(int(interp)), C.c_int32(int(flags)), L.ptr(out),
            L.stream())
     return out

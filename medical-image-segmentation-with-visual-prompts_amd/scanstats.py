@@ -47,6 +47,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._host import check_gpu, i3
 
 NBINS = 65536
 OFFSET = 32768                # bin of value 0
@@ -55,10 +56,6 @@ FLAG_PER_VALUE = 1            # one atomic per value instead of one per run of e
 MODE_PERCENTILE, MODE_ZSCORE = 0, 1
 _DTYPES = {torch.uint8: 0, torch.int16: 4}
 _BASE = {torch.uint8: 0, torch.int16: -4096}
-
-
-def _i3(v):
-    return (C.c_int32 * 3)(*[int(a) for a in v])
 
 
 def _check_q(name: str, q) -> float:
@@ -252,8 +249,7 @@ def scan_histogram(raw: torch.Tensor, mask: Optional[torch.Tensor] = None, above
             raise ValueError(f"out must be a ScanHistogram, got {type(out).__name__}")
         if out.channels != channels:
             raise ValueError(f"out was made for {out.channels} channels, raw has {channels}")
-    if not raw.is_cuda:
-        raise RuntimeError("raw must be a GPU tensor (no CPU fallback)")
+    check_gpu("raw", raw)
     if mask is not None and mask.device != raw.device:
         raise ValueError(f"mask is on {mask.device}, raw on {raw.device}")
     if out is not None and out.table.device != raw.device:
@@ -261,7 +257,7 @@ def scan_histogram(raw: torch.Tensor, mask: Optional[torch.Tensor] = None, above
     r = raw.contiguous()
     m = None if mask is None else mask.contiguous()
     hist = ScanHistogram(channels, r.device) if out is None else out
-    L.call("mivp_scan_hist", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(channels), _i3(shape), L.ptr(m),
+    L.call("mivp_scan_hist", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(channels), i3(shape), L.ptr(m),
            C.c_int32(int(above is not None)), C.c_int32(above or 0), C.c_int32(_BASE[r.dtype] if base is None else int(base)),
            C.c_int32(int(flags)), L.ptr(hist.table), L.stream())
     return hist

@@ -26,53 +26,15 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Sequence, Tuple
+from typing import Dict, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from ._host import LABEL_DTYPES, check_classes, check_gpu, check_spacing, i3, label_volume, workspace
 
-_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
 _REC = 8          # record int64 [8] per (class, direction): see include/mivp.h, mivp_surface_stats
-
-
-def _i3(v):
-    return (C.c_int32 * 3)(*[int(a) for a in v])
-
-
-def _check_gpu(name: str, t):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name} must be a GPU tensor (no CPU fallback)")
-
-
-def _check_classes(num_classes: int) -> int:
-    if not 1 <= int(num_classes) <= 16:
-        raise ValueError(f"num_classes must be in 1..16, got {num_classes}")
-    return int(num_classes)
-
-
-def _check_spacing(spacing: Sequence[float]) -> Tuple[float, float, float]:
-    s = tuple(float(a) for a in spacing)
-    if len(s) != 3 or not all(math.isfinite(a) and a > 0 for a in s):
-        raise ValueError(f"spacing must be three positive sizes in mm, got {tuple(spacing)}")
-    return s
-
-
-def _volume(name: str, t: torch.Tensor) -> torch.Tensor:
-    """[1, 1, H, W, D] (or [H, W, D]) class map -> contiguous [H, W, D] of a dtype the kernel reads."""
-    _check_gpu(name, t)
-    if t.dim() == 5:
-        if t.shape[0] != 1 or t.shape[1] != 1:
-            raise ValueError(f"{name} must be [1, 1, H, W, D] (one volume of class indices), got {tuple(t.shape)}")
-        t = t[0, 0]
-    elif t.dim() != 3:
-        raise ValueError(f"{name} must be [1, 1, H, W, D] or [H, W, D], got {tuple(t.shape)}")
-    if t.numel() >= 2 ** 31:
-        raise ValueError(f"{name} has {t.numel()} voxels, the kernels take fewer than 2^31")
-    if t.dtype not in _DTYPES:
-        t = t.float()
-    return t.contiguous()
 
 
 def _surface_launch(pred: torch.Tensor, target, num_classes: int):
@@ -81,35 +43,31 @@ def _surface_launch(pred: torch.Tensor, target, num_classes: int):
     sp = torch.empty(dims, dtype=torch.uint8, device=pred.device)
     st = torch.empty(dims, dtype=torch.uint8, device=pred.device) if target is not None else None
     counts = torch.zeros((num_classes, 2), dtype=torch.int64, device=pred.device)
-    L.call("mivp_surface_map", L.ptr(pred), L.ptr(target), C.c_int32(_DTYPES[pred.dtype]), C.c_int32(num_classes),
-           _i3(dims), L.ptr(sp), L.ptr(st), L.ptr(counts), L.stream())
+    L.call("mivp_surface_map", L.ptr(pred), L.ptr(target), C.c_int32(LABEL_DTYPES[pred.dtype]), C.c_int32(num_classes),
+           i3(dims), L.ptr(sp), L.ptr(st), L.ptr(counts), L.stream())
     return sp, st, counts
 
 
 def surface_map(labels: torch.Tensor, num_classes: int) -> torch.Tensor:
     """``labels [1, 1, H, W, D]`` (uint8, int32, int64 or float class indices) -> uint8 ``[1, 1, H, W, D]``: the class on
     its surface voxels, 255 elsewhere."""
-    ncls = _check_classes(num_classes)
-    lab = _volume("labels", labels)
+    ncls = check_classes(num_classes)
+    lab = label_volume("labels", labels)
     sp, _, _ = _surface_launch(lab, None, ncls)
     return sp.reshape((1, 1) + tuple(lab.shape))
 
 
 def _edt_launch(seeds: torch.Tensor, cls: int, spacing, out: torch.Tensor, ws: torch.Tensor):
-    L.call("mivp_edt_sq", L.ptr(seeds), C.c_int32(cls), _i3(seeds.shape), (C.c_float * 3)(*spacing), L.ptr(out),
+    L.call("mivp_edt_sq", L.ptr(seeds), C.c_int32(cls), i3(seeds.shape), (C.c_float * 3)(*spacing), L.ptr(out),
            L.ptr(ws), L.stream())
-
-
-def _edt_workspace(dims, device):
-    return torch.empty(int(L.lib().mivp_edt_ws(_i3(dims))), dtype=torch.uint8, device=device)
 
 
 def distance_transform_sq(seeds: torch.Tensor, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> torch.Tensor:
     """Exact squared Euclidean distance transform: ``seeds [H, W, D]`` (or ``[1, 1, H, W, D]``; non-zero = seed) ->
     float32 ``[H, W, D]``, the squared distance in mm^2 from every voxel to the nearest seed, ``inf`` where there is no
     seed.  With ``spacing == (1, 1, 1)`` the values are the exact integers ``rint(distance_transform_edt(~seeds)^2)``."""
-    sp = _check_spacing(spacing)
-    _check_gpu("seeds", seeds)
+    sp = check_spacing(spacing)
+    check_gpu("seeds", seeds)
     s = seeds[0, 0] if seeds.dim() == 5 and seeds.shape[:2] == (1, 1) else seeds
     if s.dim() != 3:
         raise ValueError(f"seeds must be [H, W, D] or [1, 1, H, W, D], got {tuple(seeds.shape)}")
@@ -117,13 +75,13 @@ def distance_transform_sq(seeds: torch.Tensor, spacing: Sequence[float] = (1.0, 
         raise ValueError(f"seeds of shape {tuple(s.shape)}: H and W must be <= 65535 and the volume < 2^31 voxels")
     s = (s != 0).to(torch.uint8).contiguous()
     out = torch.empty(tuple(s.shape), dtype=torch.float32, device=s.device)
-    _edt_launch(s, 1, sp, out, _edt_workspace(s.shape, s.device))
+    _edt_launch(s, 1, sp, out, workspace("edt", s.shape, s.device))
     return out
 
 
 def _check_metric_args(num_classes, spacing, percentile, tolerance):
-    ncls = _check_classes(num_classes)
-    sp = _check_spacing(spacing)
+    ncls = check_classes(num_classes)
+    sp = check_spacing(spacing)
     if not 0.0 <= float(percentile) <= 100.0:
         raise ValueError(f"percentile must be in [0, 100], got {percentile}")
     if not float(tolerance) >= 0.0 or not math.isfinite(float(tolerance)):
@@ -133,7 +91,7 @@ def _check_metric_args(num_classes, spacing, percentile, tolerance):
 
 def _metrics_launch(pred, target, ncls, spacing, percentile, tolerance, include_background):
     """All device work of ``surface_metrics``; returns (counts int64 [C, 2], records int64 [C, 2, 8]) on the device."""
-    p, t = _volume("pred", pred), _volume("target", target)
+    p, t = label_volume("pred", pred), label_volume("target", target)
     if p.shape != t.shape:
         raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
     if p.device != t.device:
@@ -146,9 +104,9 @@ def _metrics_launch(pred, target, ncls, spacing, percentile, tolerance, include_
     sp, st, counts = _surface_launch(p, t, ncls)
     recs = torch.zeros((ncls, 2, _REC), dtype=torch.int64, device=p.device)
     dist = torch.empty(dims, dtype=torch.float32, device=p.device)
-    ews = _edt_workspace(dims, p.device)
-    sws = torch.empty(int(L.lib().mivp_surface_stats_ws(_i3(dims))), dtype=torch.uint8, device=p.device)
-    q, a = percentile / 100.0, _i3(dims)
+    ews = workspace("edt", dims, p.device)
+    sws = workspace("surface_stats", dims, p.device)
+    q, a = percentile / 100.0, i3(dims)
     for c in range(0 if include_background else 1, ncls):
         # direction 0: pred's surface sampled in the EDT of target's; direction 1: the other way round
         for m, (seeds, sampled) in enumerate(((st, sp), (sp, st))):
@@ -207,8 +165,8 @@ def surface_metrics(pred: torch.Tensor, target: torch.Tensor, num_classes: int, 
 
     Returns float64 CPU tensors ``[num_classes]`` ``hd``, ``hd_p``, ``assd``, ``nsd`` and int64 ``surface_voxels
     [num_classes, 2]`` (pred, target).  One host read."""
-    _check_gpu("pred", pred)
-    _check_gpu("target", target)
+    check_gpu("pred", pred)
+    check_gpu("target", target)
     ncls, sp, pc, tol = _check_metric_args(num_classes, spacing, percentile, tolerance)
     counts, recs = _metrics_launch(pred, target, ncls, sp, pc, tol, include_background)
     host = torch.cat([counts.reshape(-1), recs.reshape(-1)]).cpu().numpy()

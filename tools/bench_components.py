@@ -94,12 +94,12 @@ def label_device(x, conn):
     import ctypes as C
     import torch
     from mivp_amd import _lib as L
-    from mivp_amd.components import _DTYPES, _i3, _workspace
+    from mivp_amd._host import LABEL_DTYPES, i3, workspace
     v = x[0, 0]
     labels = torch.empty(tuple(v.shape), dtype=torch.int32, device=v.device)
     n = torch.empty(1, dtype=torch.int32, device=v.device)
-    ws = _workspace("label", v.shape, v.device)
-    L.call("mivp_label_components", L.ptr(v), C.c_int32(_DTYPES[v.dtype]), _i3(v.shape), C.c_int32(conn), L.ptr(labels),
+    ws = workspace("label", v.shape, v.device)
+    L.call("mivp_label_components", L.ptr(v), C.c_int32(LABEL_DTYPES[v.dtype]), i3(v.shape), C.c_int32(conn), L.ptr(labels),
            L.ptr(n), L.ptr(ws), L.stream())
     return labels, n
 

@@ -86,11 +86,11 @@ def label_device(x, conn):
     import ctypes as C
     import torch
     from mivp_amd import _lib as L
-    from mivp_amd.components import _DTYPES, _i3, _workspace
+    from mivp_amd._host import LABEL_DTYPES, i3, workspace
     labels = torch.empty(tuple(x.shape), dtype=torch.int32, device=x.device)
     n = torch.empty(1, dtype=torch.int32, device=x.device)
-    ws = _workspace("label", x.shape, x.device)
-    L.call("mivp_label_components", L.ptr(x), C.c_int32(_DTYPES[x.dtype]), _i3(x.shape), C.c_int32(conn), L.ptr(labels),
+    ws = workspace("label", x.shape, x.device)
+    L.call("mivp_label_components", L.ptr(x), C.c_int32(LABEL_DTYPES[x.dtype]), i3(x.shape), C.c_int32(conn), L.ptr(labels),
            L.ptr(n), L.ptr(ws), L.stream())
     return labels, n
 
