@@ -32,7 +32,6 @@
 //   lse_s, del_s [nq] f32, ridq [nq] bytes
 // Every reduction has a fixed order: results are bit-reproducible.
 #include "common.hpp"
-#include <cstdlib>
 
 int mivp_attn_tile_config(const MivpSwinDesc* d, int* dks, int* nt);
 
@@ -152,10 +151,7 @@ MIVP_DEV void stage_query_side(const QSide& s, char* Qimg, char* Oimg, float* de
 
 }  // namespace
 
-// ABL: timing ablations (results are WRONG for ABL != 0; selected by MIVP_ATTN_BWD_ABL for cost breakdowns, tools/ab_attn_bwd.sh):
-//   1 no dQ reduce / store   2 no barrier in the tile loop   3 no dS exchange and dQ products   4 at most three key tiles per wave
-//   5 no exponentials / products / conversions (P = dS = S bits)
-template <int NW, bool DROP, bool MASKED, bool DMA = false, int ABL = 0>
+template <int NW, bool DROP, bool MASKED, bool DMA = false>
 __global__ __launch_bounds__(64 * NW, 4) void k_win_attn_bwd_fused(
     MivpSwinDesc d, const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ kp, const bf16_t* __restrict__ vp, const bf16_t* __restrict__ qa,
@@ -404,7 +400,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_win_attn_bwd_fused(
         constexpr int NT = decltype(nt_c)::value;
         constexpr bool CUT = decltype(cut_c)::value;
         for (int t = 0; t < nqt; ++t) {
-            if (ABL != 1 && t > 0 && wave == reducer_of(t - 1)) dq_store(t - 1);
+            if (t > 0 && wave == reducer_of(t - 1)) dq_store(t - 1);
             const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + 16 * t + 4 * g);
             const f32x4 n4 = *reinterpret_cast<const f32x4*>(del_s + 16 * t + 4 * g);
             const bf16x8 qf = *reinterpret_cast<const bf16x8*>(q_rd + 1024 * t);
@@ -445,9 +441,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_win_attn_bwd_fused(
                     if (DROP) keep = drop_keep(hj[j], r & 1, d.attn_drop_thr) ? d.attn_drop_scale : 0.f;
                     const float dpe = DROP ? dp[j] * keep + n4[j] : dp[j];
                     float pe, dsv;
-                    if (ABL == 5) {
-                        pe = s[j]; dsv = dpe;
-                    } else if (CUT) {
+                    if (CUT) {
                         // a masked logit is the constant 0 (accumulator value l4[j]): it keeps its P, carries no gradient
                         const bool live = never | (rqs[j] == kcls);
                         pe = __builtin_amdgcn_exp2f(live ? s[j] : l4[j]);
@@ -460,9 +454,9 @@ __global__ __launch_bounds__(64 * NW, 4) void k_win_attn_bwd_fused(
                     ds[j] = dsv;
                 }
                 if (i == NT - 1) dsum = dsum + (f32x2{ds[0], ds[1]} + f32x2{ds[2], ds[3]});   // (used if that tile holds prompt keys)
-                const u32x2 pb = ABL == 5 ? u32x2{__builtin_bit_cast(unsigned, pv[0]), __builtin_bit_cast(unsigned, pv[1])} : pack4_pk(pv);
-                const u32x2 sb = ABL == 5 ? u32x2{__builtin_bit_cast(unsigned, ds[0]), __builtin_bit_cast(unsigned, ds[1])} : pack4_pk(ds);
-                if (ABL != 3) *reinterpret_cast<u32x2*>(ex_wr + 4096 * i) = sb;            // this wave's private slot
+                const u32x2 pb = pack4_pk(pv);
+                const u32x2 sb = pack4_pk(ds);
+                *reinterpret_cast<u32x2*>(ex_wr + 4096 * i) = sb;            // this wave's private slot
                 dkacc[i] = mfma16k16(qt, sb, dkacc[i]);
                 dvacc[i] = mfma16k16(ot, pb, dvacc[i]);
             }
@@ -472,27 +466,25 @@ __global__ __launch_bounds__(64 * NW, 4) void k_win_attn_bwd_fused(
             // what a 16x16x32 one does (tools/ubench/valu_rates.hip), and the chain of dependent accumulations in front of the
             // barrier is half as long
             f32x4 dqa = fzero4();
-            constexpr int NTQ = ABL == 3 ? 0 : NT;
 #pragma unroll
-            for (int i = 0; i + 1 < NTQ; i += 2) {
+            for (int i = 0; i + 1 < NT; i += 2) {
                 const bf16x8 b = cat44(tr_read(ex_tr + 4096 * i), tr_read(ex_tr + 4096 * (i + 1)));
                 const bf16x8 a = DMA ? cat44(tr_read(kt_rd + 4096 * i), tr_read(kt_rd + 4096 * (i + 1)))
                                      : cat44(*reinterpret_cast<const bf16x4*>(kt_rd + 256 * i), *reinterpret_cast<const bf16x4*>(kt_rd + 256 * (i + 1)));
                 dqa = mfma16(a, b, dqa);
             }
-            if (NTQ & 1) {
-                constexpr int i = NTQ > 0 ? NTQ - 1 : 0;
+            if (NT & 1) {
+                constexpr int i = NT > 0 ? NT - 1 : 0;
                 const bf16x4 b = tr_read(ex_tr + 4096 * i);
                 const bf16x4 a = DMA ? tr_read(kt_rd + 4096 * i) : *reinterpret_cast<const bf16x4*>(kt_rd + 256 * i);
                 dqa = mfma16k16(a, b, dqa);
             }
             *reinterpret_cast<f32x4*>(dqp_wr + (t & 1) * NW * 256) = dqa;
-            if (ABL != 2) __syncthreads();
+            __syncthreads();
         }
-        if (ABL != 1 && wave == reducer_of(nqt - 1)) dq_store(nqt - 1);      // (a phantom tile stores nothing)
+        if (wave == reducer_of(nqt - 1)) dq_store(nqt - 1);      // (a phantom tile stores nothing)
     };
-    int my_nt = wave < nt ? (nt - wave + NW - 1) / NW : 0;         // scalar
-    if (ABL == 4 && my_nt > 3) my_nt = 3;
+    const int my_nt = wave < nt ? (nt - wave + NW - 1) / NW : 0;         // scalar
     auto walk_nt = [&](auto cut_c) {
         switch (my_nt) {
             case 0: walk(std::integral_constant<int, 0>{}, cut_c); break;
@@ -686,10 +678,9 @@ static size_t fused_lds_bytes(const MivpSwinDesc* d, bool dma) {
     const size_t kimg = dma ? (size_t)d->Nkp * 32 : hd * (size_t)(d->Nkp + 8) * 2;
     return nq * 64 + nq * 32 + kimg + nt * 512 + 2 * 8 * 256 * sizeof(float) + 2 * nq * sizeof(float) + ((nq + 15) & ~(size_t)15);
 }
-// LDS-DMA staged images unless MIVP_ATTN_BWD_REG_STAGING is set (A/B runs) or they would cost the second workgroup per CU
+// LDS-DMA staged images unless the call has dropout or they would cost the second workgroup per CU
 static bool fused_use_dma(const MivpSwinDesc* d) {
-    static const bool reg_staging = getenv("MIVP_ATTN_BWD_REG_STAGING") != nullptr;
-    if (reg_staging || d->attn_drop_thr) return false;
+    if (d->attn_drop_thr) return false;
     const size_t a = fused_lds_bytes(d, true), b = fused_lds_bytes(d, false);
     return a <= 80 * 1024 || b > 80 * 1024;
 }
@@ -721,14 +712,8 @@ extern "C" int mivp_win_attn_bwd_fused(const MivpSwinDesc* d, const void* q, con
     const bool dma = fused_use_dma(d);
     const size_t lds = fused_lds_bytes(d, dma);
     constexpr int NW = 8;
-    static const int abl = getenv("MIVP_ATTN_BWD_ABL") ? atoi(getenv("MIVP_ATTN_BWD_ABL")) : 0;
     const bool msk = d->has_mask != 0;
     auto kern = d->attn_drop_thr ? (msk ? k_win_attn_bwd_fused<NW, true, true> : k_win_attn_bwd_fused<NW, true, false>)
-              : (dma && abl == 1) ? (msk ? k_win_attn_bwd_fused<NW, false, true, true, 1> : k_win_attn_bwd_fused<NW, false, false, true, 1>)
-              : (dma && abl == 2) ? (msk ? k_win_attn_bwd_fused<NW, false, true, true, 2> : k_win_attn_bwd_fused<NW, false, false, true, 2>)
-              : (dma && abl == 3) ? (msk ? k_win_attn_bwd_fused<NW, false, true, true, 3> : k_win_attn_bwd_fused<NW, false, false, true, 3>)
-              : (dma && abl == 4) ? (msk ? k_win_attn_bwd_fused<NW, false, true, true, 4> : k_win_attn_bwd_fused<NW, false, false, true, 4>)
-              : (dma && abl == 5) ? (msk ? k_win_attn_bwd_fused<NW, false, true, true, 5> : k_win_attn_bwd_fused<NW, false, false, true, 5>)
               : dma ? (msk ? k_win_attn_bwd_fused<NW, false, true, true> : k_win_attn_bwd_fused<NW, false, false, true>)
                     : (msk ? k_win_attn_bwd_fused<NW, false, true> : k_win_attn_bwd_fused<NW, false, false>);
     MIVP_LDS_OPT_IN(kern, lds);

@@ -2,7 +2,6 @@
 // proj+MLP+scatter.  Reference semantics: swin_transformer/swin_block.py:145-255,
 // multi_head_attention/window_attention.py:35-61, relative_positional_encoding.py:99-142.
 #include "common.hpp"
-#include <cstdlib>
 
 // swin_tok_wide.hip: the column-split token kernels of the wide stages
 int mivp_tok_wide_supported(const MivpSwinDesc* d);
@@ -413,19 +412,18 @@ MIVP_DEV bf16x4 attn_tr_read(const char* p) {
 
 // waves per SIMD asked of the register allocator: the one-k-step kernels hold four workgroups per CU (34 KB of LDS each at 7^3
 // windows) when they fit 64 VGPRs
-template <int DKS, bool DROP, bool MASKED, bool ZREF, bool DMA, bool BITS>
+template <int DKS, bool DROP, bool MASKED>
 constexpr int attn_fwd_occupancy() {
     if (DKS != 1) return 2;
-    if (DROP) return DMA ? 6 : 2;            // (dropout kernels: ~90-115 VGPRs left alone = two workgroups per CU; 80 = three)
+    if (DROP) return 6;                      // (dropout kernels: ~90-115 VGPRs left alone = two workgroups per CU; 80 = three)
     // (the masked kernels need 68-72 VGPRs, with byte classes and with mask words: capped at 64 they spill around every tile)
-    if (DMA) return MASKED ? 6 : 8;
-    return (MASKED && ZREF) ? 8 : 2;
+    return MASKED ? 6 : 8;
 }
 //   BITS (shifted blocks, mivp.h "mask words"): the shift mask of a (query tile, key tile) pair comes as four 64-bit lane
 //   masks from a per-geometry table (scalar loads -> v_cndmask on an SGPR pair: ONE vector instruction per logit) instead of
 //   byte classes compared per logit (extract + compare + select); cut windows cost ~2x an uncut one with the compares.
-template <int DKS, int DVT, int NW, int QT, bool DROP, bool ONES, bool MASKED, bool ZREF = false, bool DMA = false, bool BITS = false>
-__global__ __launch_bounds__(64 * NW, (attn_fwd_occupancy<DKS, DROP, MASKED, ZREF, DMA, BITS>())) void k_win_attn_fwd(MivpSwinDesc d, const bf16_t* __restrict__ q,
+template <int DKS, int DVT, int NW, int QT, bool DROP, bool ONES, bool MASKED, bool ZREF = false, bool BITS = false>
+__global__ __launch_bounds__(64 * NW, (attn_fwd_occupancy<DKS, DROP, MASKED>())) void k_win_attn_fwd(MivpSwinDesc d, const bf16_t* __restrict__ q,
                                                          const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                          const bf16_t* __restrict__ kp, const bf16_t* __restrict__ vp,
                                                          const bf16_t* __restrict__ qa, const bf16_t* __restrict__ ka,
@@ -445,9 +443,10 @@ __global__ __launch_bounds__(64 * NW, (attn_fwd_occupancy<DKS, DROP, MASKED, ZRE
     // dropout, row head_dim of V^T is set to one, so O's row head_dim accumulates sum_k P -- of the same bf16-rounded P
     // the numerator uses -- and the eight adds per 32 keys leave the (binding) VALU stream.  (ONES is picked at launch.)
     const int Nkp = d.Nkp, Nqp = d.Nqp;
-    // DMA form (DKS == DVT == 1): V stays ROW-major [Nkp][16] (32-byte rows) and the PV product's A operand comes out of
-    // transposing reads; the classic form keeps a V^T image [16 DVT][Nkp + 8]
-    static_assert(!DMA || (DKS == 1 && DVT == 1), "the DMA-staged images are laid out for one k-step / one value tile");
+    // DMA form (DKS == DVT == 1, always LDS-DMA staged): V stays ROW-major [Nkp][16] (32-byte rows) and the PV product's A
+    // operand comes out of transposing reads; the classic form (DKS 2 and 3) keeps a V^T image [16 DVT][Nkp + 8]
+    constexpr bool DMA = DKS == 1;
+    static_assert(!DMA || DVT == 1, "the DMA-staged images are laid out for one k-step / one value tile");
     const int VROW = DMA ? 32 : (Nkp + 8) * 2;               // bytes
     char* Kimg = smem;
     char* Vt = Kimg + (size_t)Nkp * KROW;
@@ -1191,11 +1190,12 @@ extern "C" int mivp_relbias_aug(const MivpSwinDesc* d, const float* t_h, const f
     return mivp_check_launch("relbias_aug");
 }
 
-template <int DKS, int DVT, int NW, int QT, bool DMA, bool BITS>
+template <int DKS, int DVT, int NW, int QT, bool BITS>
 static int launch_attn_fwd_cfg(const MivpSwinDesc* d, const void* q, const void* k, const void* v, const void* kp,
                                const void* vp, const void* qa, const void* ka, const int32_t* tok_rid, void* o, float* lse,
                                const unsigned long long* mask_words, const unsigned char* cut_flags, hipStream_t st) {
     const size_t krow = OperandRows<32 * DKS>::ROW, vrow = (d->Nkp + 8) * 2;
+    constexpr bool DMA = DKS == 1;                           // (kernel: the one-k-step form stages by LDS-DMA)
     const size_t lds = (size_t)d->Nkp * krow + (DMA ? (size_t)d->Nkp * 32 : (size_t)16 * DVT * vrow) + (size_t)d->Nkp;
     if (lds > 160 * 1024) { mivp_set_error("win_attn_fwd: LDS image exceeds 160 KiB"); return MIVP_EUNSUPPORTED; }
     const bool ones = !d->attn_drop_thr && (d->C / d->heads) < 16 * DVT;
@@ -1203,18 +1203,17 @@ static int launch_attn_fwd_cfg(const MivpSwinDesc* d, const void* q, const void*
     const bool zref = lse == nullptr && !d->attn_drop_thr;      // forward only (kernel header: ZREF)
     // (BITS only ever instantiates masked kernels: the un-masked arms below pass false)
     auto kern = d->attn_drop_thr
-        ? (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, true, false, true, false, DMA, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, true, false, false, false, DMA, false>)
-        : ones ? (zref ? (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, false, true, true, true, DMA, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, false, true, false, true, DMA, false>)
-                       : (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, false, true, true, false, DMA, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, false, true, false, false, DMA, false>))
-               : (zref ? (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, false, false, true, true, DMA, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, false, false, false, true, DMA, false>)
-                       : (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, false, false, true, false, DMA, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, false, false, false, false, DMA, false>));
+        ? (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, true, false, true, false, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, true, false, false, false, false>)
+        : ones ? (zref ? (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, false, true, true, true, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, false, true, false, true, false>)
+                       : (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, false, true, true, false, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, false, true, false, false, false>))
+               : (zref ? (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, false, false, true, true, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, false, false, false, true, false>)
+                       : (msk ? k_win_attn_fwd<DKS, DVT, NW, QT, false, false, true, false, BITS> : k_win_attn_fwd<DKS, DVT, NW, QT, false, false, false, false, false>));
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) { mivp_set_error(hipGetErrorString(e)); return MIVP_ELAUNCH; }
     }
     const unsigned grid = (unsigned)((long)d->B * d->P * d->heads);
-    static const bool no_remap = getenv("MIVP_ATTN_NO_XCD_REMAP") != nullptr;
-    const int xcd_remap = (!no_remap && grid % 8 == 0 && grid >= 64) ? 1 : 0;
+    const int xcd_remap = (grid % 8 == 0 && grid >= 64) ? 1 : 0;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, st, *d, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
                        (const bf16_t*)kp, (const bf16_t*)vp, (const bf16_t*)qa, (const bf16_t*)ka, tok_rid, (bf16_t*)o, lse, xcd_remap,
                        mask_words, cut_flags);
@@ -1227,20 +1226,12 @@ static int launch_attn_fwd(const MivpSwinDesc* d, const void* q, const void* k, 
                            const unsigned long long* mw, const unsigned char* cf, hipStream_t st) {
     // (NW, QT) = (4, 2) -- two query tiles per wave sharing every K' / V^T fragment -- measures the same as (8, 1) at 7^3
     // windows (87.5 vs 87.2 us per stage-1 block): the kernel is bound by VALU issue, not by the LDS pipe
-    static const bool no_bits = getenv("MIVP_ATTN_MASK_CLASSES") != nullptr;       // A/B: byte classes instead of mask words
-    const bool bits = d->has_mask && mw != nullptr && cf != nullptr && !no_bits;
-    // one k-step / one value tile (head_dim <= 16: the encoder stages and the last decoder stage): LDS-DMA staged images
-    // (MIVP_ATTN_FWD_REG_STAGING=1 keeps the register-path staging for A/B runs)
-    if constexpr (DKS == 1 && DVT == 1) {
-        static const bool reg_staging = getenv("MIVP_ATTN_FWD_REG_STAGING") != nullptr;
-        // (the masked kernels need ~72 VGPRs in this form with byte classes: three workgroups per CU)
-        if (!reg_staging && d->Nqp % 8 == 0) {
-            if (bits) return launch_attn_fwd_cfg<DKS, DVT, 8, 1, true, true>(d, q, k, v, kp, vp, qa, ka, tok_rid, o, lse, mw, cf, st);
-            return launch_attn_fwd_cfg<DKS, DVT, 8, 1, true, false>(d, q, k, v, kp, vp, qa, ka, tok_rid, o, lse, mw, cf, st);
-        }
-    }
-    if (bits) return launch_attn_fwd_cfg<DKS, DVT, 8, 1, false, true>(d, q, k, v, kp, vp, qa, ka, tok_rid, o, lse, mw, cf, st);
-    return launch_attn_fwd_cfg<DKS, DVT, 8, 1, false, false>(d, q, k, v, kp, vp, qa, ka, tok_rid, o, lse, mw, cf, st);
+    // byte classes instead of mask words when the caller passes no table
+    const bool bits = d->has_mask && mw != nullptr && cf != nullptr;
+    // (one k-step / one value tile -- head_dim <= 16: the encoder stages and the last decoder stage -- is the LDS-DMA staged
+    // form; its masked kernels need ~72 VGPRs with byte classes: three workgroups per CU)
+    if (bits) return launch_attn_fwd_cfg<DKS, DVT, 8, 1, true>(d, q, k, v, kp, vp, qa, ka, tok_rid, o, lse, mw, cf, st);
+    return launch_attn_fwd_cfg<DKS, DVT, 8, 1, false>(d, q, k, v, kp, vp, qa, ka, tok_rid, o, lse, mw, cf, st);
 }
 
 // shared by forward and backward dispatch: which (NT, DKS=DVT) instantiation covers this shape

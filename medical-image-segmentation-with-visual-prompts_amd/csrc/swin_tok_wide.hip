@@ -18,7 +18,6 @@
 //   * every global load is unconditional (common.hpp "Branch-free loads").
 // The launchers at the bottom are called by the C entries of swin_fwd.hip / swin_bwd.hip when mivp_tok_wide_supported().
 #include "common.hpp"
-#include <cstdlib>
 
 namespace {
 
@@ -1008,19 +1007,14 @@ extern "C" int mivp_pack_weight_frags(const void* w, int32_t rows, int32_t cols,
 // C = 96 / 192 / 384, windows of a multiple of 32 slots (a 32-token granule then never leaves its window)
 int mivp_tok_wide_supported(const MivpSwinDesc* d) {
     const int hd = d->C / d->heads;
-    if (!(d->C == 48 || d->C == 96 || d->C == 192 || d->C == 384)) return 0;
-    static const bool off = getenv("MIVP_NO_WIDE_TOKEN_KERNELS") != nullptr;     // A/B switch for profiling and tests
-    if (off) return 0;
     // C = 48: the QKV pair measured SLOWER in this form (forward 55 vs 50 us, backward 88 vs 77 us at 48^3 x 4: the
-    // head-major piece decode, the LDS round trip and half the occupancy cost more than the contiguous stores save); opt-in
-    if (d->C == 48 && !getenv("MIVP_C48_QKV_ROW_KERNELS")) return 0;
+    // head-major piece decode, the LDS round trip and half the occupancy cost more than the contiguous stores save)
+    if (!(d->C == 96 || d->C == 192 || d->C == 384)) return 0;
     return (hd % 4 == 0 && d->Nqp % 32 == 0 && 8 * hd < 65536 && 72 * d->C < 65536) ? 1 : 0;
 }
 // the proj / MLP pair in the same form also at C = 48 (one column group: a wave owns its 32 tokens' three column tiles)
 int mivp_tok_rows_supported(const MivpSwinDesc* d) {
-    if (mivp_tok_wide_supported(d)) return 1;
-    static const bool off = getenv("MIVP_NO_WIDE_TOKEN_KERNELS") != nullptr;
-    return (!off && d->C == 48) ? 1 : 0;
+    return (d->C == 48 || mivp_tok_wide_supported(d)) ? 1 : 0;
 }
 // element offset of the natural-order image behind the paired one (swin_ops.paired_and_natural)
 long mivp_tok_natural_offset(int C) { return (long)(C / 16) * ((C + 31) / 32) * 512; }
@@ -1052,9 +1046,8 @@ int mivp_tok_wide_qkv_fwd(const MivpSwinDesc* d, const void* x, const int32_t* t
         hipLaunchKernelGGL((k_qkv_fwd_wide<CTV>), WIDE_GRID(CTV), dim3(256), lds, st, *d, (const bf16_t*)x, tok_src, ln_w,   \
                            ln_b, (const bf16_t*)wqkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v);                                   \
     } while (0)
-    static const bool no_ws = getenv("MIVP_QKV_FWD_STREAMED_WEIGHTS") != nullptr;      // A/B switch: the round-2 work split
     const int hd = d->C / d->heads;
-    if (!no_ws && (d->C == 96 || d->C == 192) && hd % 4 == 0 && d->Nqp % 16 == 0 && d->Nqp >= 64) {
+    if ((d->C == 96 || d->C == 192) && hd % 4 == 0 && d->Nqp % 16 == 0 && d->Nqp >= 64) {
 #define L_WS(CTV)                                                                                                            \
     do {                                                                                                                     \
         const size_t lds = (size_t)64 * RowImg<WideGeom<CTV>::KP>::ROWB;                                                     \
@@ -1065,7 +1058,7 @@ int mivp_tok_wide_qkv_fwd(const MivpSwinDesc* d, const void* x, const int32_t* t
 #undef L_WS
         return mivp_check_launch("swin_qkv_fwd(weight-stationary)");
     }
-    ROWS_SWITCH(L_W)
+    WIDE_SWITCH(L_W)
 #undef L_W
     return mivp_check_launch("swin_qkv_fwd(wide)");
 }
@@ -1114,7 +1107,7 @@ int mivp_tok_wide_qkv_bwd(const MivpSwinDesc* d, const void* dq, const void* dk,
                            (const bf16_t*)dv, (const bf16_t*)x, tok_src, ln_w, (const bf16_t*)wqkv_t, (const bf16_t*)d_t1,   \
                            (bf16_t*)dx, (bf16_t*)dn_out);                                                                    \
     } while (0)
-    ROWS_SWITCH(L_W)
+    WIDE_SWITCH(L_W)
 #undef L_W
     return mivp_check_launch("swin_qkv_bwd(wide)");
 }

@@ -266,8 +266,6 @@ class GraphedStep:
         self._fn = Fn
         self.optimizer, self.scheduler, self.refresh = optimizer, scheduler, refresh
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
-        if os.environ.get("MIVP_GRAPH_FORCE_SINGLE"):             # (debug: the single-graph path under an initialised process group)
-            self.world = 1
         params = [p for g in optimizer.param_groups for p in g["params"] if p.requires_grad]
         self.params = params
         dev = params[0].device
