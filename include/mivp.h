@@ -945,6 +945,34 @@ int mivp_window_blend_any(const float* logits, int32_t channels_last, int32_t C,
 int mivp_stitch_fill(float* acc, float* wsum, int32_t C, const int32_t* pdims, int32_t fill_class, float fill_logit,
                      mivp_stream_t stream);
 
+/* Fitting the prediction windows to the foreground bounding box (csrc/window_fit.hip; SlidingWindowPredictor(fit=...),
+ * DESIGN 4.25).  These entry points joined the current ABI without a bump: they are additive and no earlier signature
+ * changed.
+ *   mivp_foreground_box: box DEVICE int32 [6] = (lo0, lo1, lo2, hi0, hi1, hi2), the inclusive bounding box of the
+ *     foreground in image coordinates; no foreground gives lo = dims and hi = -1.  Exactly one source, as for
+ *     mivp_window_occupancy: vol f32 [Cin][H][W][D] with channel and threshold (vol[channel] > threshold, strict fp32, so
+ *     NaN is not foreground), or mask uint8 [H][W][D] (mask != 0; vol NULL, Cin / channel / threshold ignored).  dims =
+ *     {H, W, D} (host), fewer than 2^31 voxels.  Two launches on the stream: one initialises the six words, one reads the
+ *     channel (or the mask) once, four D voxels per load where D % 4 == 0 and the base is aligned, and issues six integer
+ *     atomicMin / atomicMax per workgroup that saw foreground.  No host synchronisation; exact and bitwise reproducible.
+ *   mivp_window_fit_plan: the work list of the windows that tile the box.  Per axis, with p = pdims, r = roi, m = margin,
+ *     the box [lo, hi]: b0 = max(lo + pad - m, 0), b1 = min(hi + pad + m + 1, p), n = b1 - b0; if n < r then
+ *     b0 = clamp(b0 - (r - n) / 2, 0, p - r) and n = r; count = ceil((n - r) / interval) + 1 and window i starts at
+ *     b0 + min(i * interval, n - r).  interval: host int32 [3], max(int(r * (1 - overlap)), 1), in 1..r.  margin: host
+ *     int32 [3], 0..2^30.  codes: host int32 [n_flips], the 3-bit flip codes (n_flips in 1..8).  table: DEVICE int32
+ *     [n_entries][4], 16-byte aligned: entry w * n_flips + j = window w (row-major over the three counts) under codes[j],
+ *     word 3 = 1 | code << 1; every remaining row is zero.  origins: DEVICE int32 [n_origins][3], the origins of the
+ *     windows, zero behind them.  meta: DEVICE int32 [2] = (windows, entries).  An empty box (hi < lo on an axis, or a box
+ *     outside the image) plans zero windows.  A plan of more than n_entries entries or n_origins windows writes an
+ *     all-zero table and meta = (-1, -1); with the capacities of the full tiling it cannot happen (n <= p per axis).  One
+ *     workgroup, no host synchronisation, nothing is written outside the capacities given. */
+int mivp_foreground_box(const float* vol, int32_t Cin, int32_t channel, float threshold, const uint8_t* mask,
+                        const int32_t* dims, int32_t* box, mivp_stream_t stream);
+int mivp_window_fit_plan(const int32_t* box, const int32_t* dims, const int32_t* pad, const int32_t* pdims,
+                         const int32_t* roi, const int32_t* interval, const int32_t* margin, const int32_t* codes,
+                         int32_t n_flips, int32_t* table, int32_t n_entries, int32_t* origins, int32_t n_origins,
+                         int32_t* meta, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,14 +15,15 @@ __all__ = ["_lib", "geometry"]
 def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
-                "components", "scan", "regions", "augment", "calibration", "scanstats"):
+                "components", "scan", "regions", "augment", "calibration", "scanstats", "window_fit"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
         from .swin_unetr import SwinUnetR
         return SwinUnetR
     if name in ("SlidingWindowPredictor", "predict_volume", "evaluate_volume", "evaluate_volume_surface",
-                "predict_scan_volume", "evaluate_volume_lesions", "evaluate_volume_calibration", "WindowSkip"):
+                "predict_scan_volume", "evaluate_volume_lesions", "evaluate_volume_calibration", "WindowSkip", "WindowFit",
+                "foreground_box"):
         from . import inference
         return getattr(inference, name)
     if name in ("surface_map", "distance_transform_sq", "surface_metrics"):

@@ -27,6 +27,39 @@ def plain_int(v) -> bool:
     return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
+def check_finite(name: str, v) -> float:
+    """A finite int or float (numpy scalars included), but not a bool."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(float(v)):
+        raise ValueError(f"{name} must be a finite number, got {v!r}")
+    return float(v)
+
+
+def check_int_from(name: str, v, lo: int) -> int:
+    """A ``plain_int`` in ``lo .. 2^31 - 1``."""
+    if not plain_int(v) or int(v) < lo or int(v) >= 2 ** 31:
+        raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+    return int(v)
+
+
+def check_fill_logit(v) -> float:
+    """The logit magnitude of filled voxels: finite, > 0 and finite in fp32."""
+    check_finite("fill_logit", v)
+    if not 0 < float(v) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"fill_logit must be > 0 and finite in fp32, got {v!r}")
+    return float(v)
+
+
+def check_region_mask(mask, image_size, device):
+    """A resident foreground mask of the predictors: a contiguous uint8 ``[H, W, D]`` GPU tensor on ``device``."""
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+        raise ValueError("the region mask must be a GPU tensor (no CPU fallback)")
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(image_size):
+        raise ValueError(f"the region mask must be uint8 {tuple(image_size)}, got {mask.dtype} {tuple(mask.shape)}")
+    if mask.device != device or not mask.is_contiguous():
+        raise ValueError("the region mask must be contiguous and on the model's device")
+
+
 def check_gpu(name: str, t):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError(f"{name} must be a GPU tensor (no CPU fallback)")

@@ -5,6 +5,7 @@ and the metric counts accumulated by one kernel per sub-batch (no ``.item()`` in
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -12,7 +13,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._host import check_classes, check_gpu, i3, iou_dice, plain_int
+from ._host import (check_classes, check_fill_logit, check_finite, check_gpu, check_int_from, check_region_mask, i3,
+                    iou_dice)
+from .window_fit import WindowFit, foreground_box
 
 
 def window_grid(image_size: Sequence[int], roi: Sequence[int]) -> Tuple[List[slice], List[int], List[int]]:
@@ -230,15 +233,10 @@ class WindowSkip:
 
     def __init__(self, threshold: float = 0.0025, channel: int = 0, min_voxels: int = 1, fill_class: int = 0,
                  fill_logit: float = 10.0):
-        for name, v in (("threshold", threshold), ("fill_logit", fill_logit)):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) \
-                    or not math.isfinite(float(v)):
-                raise ValueError(f"{name} must be a finite number, got {v!r}")
-        if not 0 < float(fill_logit) <= float(np.finfo(np.float32).max):
-            raise ValueError(f"fill_logit must be > 0 and finite in fp32, got {fill_logit!r}")
+        check_finite("threshold", threshold)
+        check_fill_logit(fill_logit)
         for name, v, lo in (("channel", channel, 0), ("min_voxels", min_voxels, 1), ("fill_class", fill_class, 0)):
-            if not plain_int(v) or int(v) < lo or int(v) >= 2 ** 31:
-                raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+            check_int_from(name, v, lo)
         object.__setattr__(self, "threshold", float(threshold))
         object.__setattr__(self, "channel", int(channel))
         object.__setattr__(self, "min_voxels", int(min_voxels))
@@ -257,6 +255,25 @@ class WindowSkip:
 
     def __hash__(self):
         return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def _fit_intervals(roi: Sequence[int], overlap: float) -> Tuple[int, int, int]:
+    """Per axis ``max(int(r * (1 - overlap)), 1)``, the window step of ``window_origins`` (and of the fitted tiling,
+    which takes it from the host so that the float arithmetic is done once)."""
+    _check_overlap(overlap)
+    return tuple(max(int(r * (1.0 - float(overlap))), 1) for r in _check_shape3("roi", roi))
+
+
+def _fit_keyword(impl):
+    """Decorator of the predictor's entry points that take ``fit``.  The decorated function is the declaration -- the
+    positional signature that existing callers and ``inspect.signature`` see, and the docstring; its body is ``impl``,
+    which has the same parameters plus ``fit``.  The result takes ``fit`` as a keyword only."""
+    def declare(fn):
+        @functools.wraps(fn)
+        def entry(*args, fit=None, **kwargs):
+            return impl(*args, fit=fit, **kwargs)
+        return entry
+    return declare
 
 
 def _model_factor(conf) -> Tuple[int, int, int]:
@@ -301,11 +318,26 @@ class SlidingWindowPredictor:
     A compacted sub-batch can span any union box, so the blend is then ``mivp_window_blend_any``: the unfiltered launch
     grid, walked with a stride over a larger box (the same sums per voxel).  After a run
     ``n_kept`` is the number of windows kept and ``n_sub_run`` the number of sub-batches run.  ``set_region(mask)``
-    replaces the threshold rule by a resident uint8 ``[H, W, D]`` mask (foreground: ``mask != 0``)."""
+    replaces the threshold rule by a resident uint8 ``[H, W, D]`` mask (foreground: ``mask != 0``).
 
-    def __init__(self, model, image_size: Sequence[int], in_channels: int, num_classes: int, roi: Sequence[int],
-                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                 graph: bool = False, mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None):
+    ``fit`` (a ``WindowFit``; ``None``, the default, launches what the predictor always launched and reads nothing back;
+    not together with ``skip``) tiles the foreground's bounding box instead of the whole volume, so windows are removed
+    where ``skip`` could only drop the ones that hold no foreground at all.  Per volume: reset -> the box
+    (``foreground_box`` into ``self.box``; of ``mask != 0`` after ``set_region(mask)``) -> one plan launch that writes
+    the fitted work list into ``self.table`` and its origins into ``self.fit_origins`` -> the one 8-byte host read of
+    (windows, entries) -> ``ceil(entries / sub_batch)`` sub-batches -> the fill launch -> finalize.  Per axis on the
+    padded volume (p = padded size, r = roi, m = margin, [lo, hi] the box): ``b0 = max(lo + pad - m, 0)``,
+    ``b1 = min(hi + pad + m + 1, p)``, ``n = b1 - b0``; if ``n < r`` then ``b0 = clamp(b0 - (r - n) // 2, 0, p - r)`` and
+    ``n = r``; ``count = ceil((n - r) / interval) + 1`` with ``window_origins``' interval, window i starts at
+    ``b0 + min(i * interval, n - r)``.  ``n <= p``, so no axis has more windows than the full tiling: the table, the
+    input batch, the accumulators and the graph (recorded once with the full table) are reused as built, and a box that
+    is the whole volume gives the full tiling and the prediction without ``fit`` bit for bit.  After a run ``n_kept`` is
+    the number of fitted windows and ``n_sub_run`` the number of sub-batches run."""
+
+    def _init(self, model, image_size: Sequence[int], in_channels: int, num_classes: int, roi: Sequence[int],
+              overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+              graph: bool = False, mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None,
+              fit: Optional[WindowFit] = None):
         self.image_size = _check_shape3("image_size", image_size)
         self.roi = _check_shape3("roi", roi)
         _check_overlap(overlap)
@@ -324,7 +356,16 @@ class SlidingWindowPredictor:
                 raise ValueError(f"skip.channel {skip.channel} is not a channel of a {int(in_channels)}-channel volume")
             if skip.fill_class >= int(num_classes):
                 raise ValueError(f"skip.fill_class {skip.fill_class} is not one of {int(num_classes)} classes")
-        self.skip = skip
+        if fit is not None:
+            if not isinstance(fit, WindowFit):
+                raise ValueError(f"fit must be a WindowFit or None, got {type(fit).__name__}")
+            if skip is not None:
+                raise ValueError("fit and skip cannot be combined: build the predictor with one of them")
+            if fit.channel >= int(in_channels):
+                raise ValueError(f"fit.channel {fit.channel} is not a channel of a {int(in_channels)}-channel volume")
+            if fit.fill_class >= int(num_classes):
+                raise ValueError(f"fit.fill_class {fit.fill_class} is not one of {int(num_classes)} classes")
+        self.skip, self.fit = skip, fit
         conf = getattr(model, "conf", None)
         if conf is not None:
             if getattr(conf, "training_mode", "downstream") != "downstream":
@@ -381,11 +422,26 @@ class SlidingWindowPredictor:
         # window skipping: the full work list stays as built; self.table is the active (compacted) list of the volume
         self.occupancy, self.region = None, None
         self.n_kept, self.n_sub_run = self.n_windows, self.n_sub
+        self.box = None
+        if fit is not None:
+            # the fitted tiling never has more windows per axis than the full one: table, xb, accumulators, graph as built
+            self.table_full = self.table.clone()
+            self.box = torch.zeros(6, dtype=torch.int32, device=dev)
+            self.fit_origins = torch.zeros((self.n_windows, 3), dtype=torch.int32, device=dev)
+            self.meta = torch.zeros(2, dtype=torch.int32, device=dev)
+            self._fit_args = (i3(_fit_intervals(self.roi, overlap)), i3([min(m, 2 ** 30) for m in fit.margin]),
+                              (C.c_int32 * self.n_flips)(*self.flip_codes))
         if skip is not None:
             self.table_full = self.table.clone()
             self.origins_dev = torch.from_numpy(np.ascontiguousarray(self.origins)).to(dev)
             self.occupancy = torch.zeros(self.n_windows, dtype=torch.int32, device=dev)
             self.meta = torch.zeros(2, dtype=torch.int32, device=dev)
+
+    @_fit_keyword(_init)
+    def __init__(self, model, image_size: Sequence[int], in_channels: int, num_classes: int, roi: Sequence[int],
+                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                 graph: bool = False, mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None):
+        """The class docstring describes the arguments; ``fit`` is keyword-only."""
 
     # ------------------------------------------------------------------ per sub-batch launches
     def _gather(self, vol):
@@ -407,7 +463,7 @@ class SlidingWindowPredictor:
                 C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch), a["ubox"],
                 L.ptr(self.w[0]), L.ptr(self.w[1]), L.ptr(self.w[2]), C.c_float(self.w_floor), L.ptr(self.acc),
                 L.ptr(self.wsum))
-        if self.skip is not None:                                # any union box on the unfiltered grid (comp None: plain sums)
+        if self.skip is not None or self.fit is not None:        # any union box on the unfiltered grid (comp None: plain sums)
             L.call("mivp_window_blend_any", *args, L.ptr(self.comp), L.stream())
         elif self._tta_kernels:
             L.call("mivp_window_blend_tta", *args, L.ptr(self.comp), L.stream())
@@ -433,15 +489,10 @@ class SlidingWindowPredictor:
         """While a resident uint8 ``[H, W, D]`` GPU tensor is set, foreground means ``mask != 0`` (a body or lung mask
         from ``mivp_amd.components``) and the threshold is ignored; ``None`` returns to the threshold rule.  The tensor
         is read at every run, not copied."""
-        if self.skip is None:
+        if self.skip is None and self.fit is None:
             raise ValueError("set_region needs a predictor built with skip=WindowSkip(...)")
         if mask is not None:
-            if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-                raise ValueError("the region mask must be a GPU tensor (no CPU fallback)")
-            if mask.dtype != torch.uint8 or tuple(mask.shape) != self.image_size:
-                raise ValueError(f"the region mask must be uint8 {self.image_size}, got {mask.dtype} {tuple(mask.shape)}")
-            if mask.device != self.dev or not mask.is_contiguous():
-                raise ValueError("the region mask must be contiguous and on the model's device")
+            check_region_mask(mask, self.image_size, self.dev)
         self.region = mask
 
     def _select(self, vol):
@@ -455,15 +506,28 @@ class SlidingWindowPredictor:
                C.c_int32(self.n_flips), L.ptr(self.occupancy), C.c_int32(k.min_voxels), L.ptr(self.table),
                L.ptr(self.meta), L.stream())
 
+    def _plan(self, vol):
+        """box -> the fitted work list into ``self.table`` (csrc/window_fit.hip); no host read."""
+        a, k = self._a, self.fit
+        src = self.region if self.region is not None else vol
+        foreground_box(src, k.channel, k.threshold, out=self.box)
+        step, margin, codes = self._fit_args
+        L.call("mivp_window_fit_plan", L.ptr(self.box), a["dims"], a["pad"], a["pdims"], a["roi"], step, margin, codes,
+               C.c_int32(self.n_flips), L.ptr(self.table), C.c_int32(self.table.shape[0]), L.ptr(self.fit_origins),
+               C.c_int32(self.n_windows), L.ptr(self.meta), L.stream())
+
     def _kept(self) -> int:
-        """The one host read of a skipping run: (kept windows, kept entries) -> the number of sub-batches to run."""
+        """The one host read of a skipping or fitting run: (windows, entries) of the volume's work list -> the number of
+        sub-batches to run."""
         kept_windows, kept_entries = self.meta.tolist()
+        if kept_entries < 0:
+            raise RuntimeError("mivp_amd: the fitted tiling does not fit the predictor's work list")
         self.n_kept = int(kept_windows)
-        self.n_sub_run = -(-int(kept_entries) // self.sub_batch)
+        self.n_sub_run = min(-(-int(kept_entries) // self.sub_batch), self.n_sub)
         return self.n_sub_run
 
     def _fill(self):
-        k = self.skip
+        k = self.skip if self.skip is not None else self.fit
         L.call("mivp_stitch_fill", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), self._a["pdims"],
                C.c_int32(k.fill_class), C.c_float(k.fill_logit), L.stream())
 
@@ -505,7 +569,7 @@ class SlidingWindowPredictor:
             if vol.data_ptr() != self.vol.data_ptr():            # predict_scan prepares straight into the resident volume
                 self.vol.copy_(vol)
             if self.graph is None:
-                if self.skip is not None:                        # warm up and record with the full work list
+                if self.skip is not None or self.fit is not None:   # warm up and record with the full work list
                     self.table.copy_(self.table_full)
                 self._record()
             vol = self.vol                                       # what the launches below and the recorded gather read
@@ -514,13 +578,16 @@ class SlidingWindowPredictor:
         if self.skip is not None:
             self._select(vol)
             n_sub = self._kept()
+        elif self.fit is not None:
+            self._plan(vol)
+            n_sub = self._kept()
         if self.graph_mode:
             for _ in range(n_sub):
                 self.graph.replay()
         else:
             for _ in range(n_sub):
                 self._step(vol)
-        if self.skip is not None:
+        if self.skip is not None or self.fit is not None:
             self._fill()
         labels = torch.empty((1, 1) + self.image_size, dtype=torch.uint8, device=self.dev)
         logits = torch.empty((1, self.ncls) + self.image_size, dtype=torch.float32, device=self.dev) if want_logits else None
@@ -692,7 +759,8 @@ class SlidingWindowPredictor:
         return self.evaluate(x, seg, postprocess)
 
 
-def _one_shot(model, x_or_shape, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes, skip):
+def _one_shot(model, x_or_shape, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes, skip,
+              fit=None):
     """The predictor behind a one-shot wrapper: built for the volume ``x [1, Cin, H, W, D]`` (``cin`` None), or for an
     image size and its ``cin``."""
     if cin is None:
@@ -700,74 +768,132 @@ def _one_shot(model, x_or_shape, cin, num_classes, roi, overlap, mode, sigma_sca
             raise ValueError("x must be a [1, C, H, W, D] tensor")
         x_or_shape, cin = x_or_shape.shape[2:], x_or_shape.shape[1]
     return SlidingWindowPredictor(model, x_or_shape, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph,
-                                  mirror_axes, skip)
+                                  mirror_axes, skip, fit=fit)
 
 
-def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], num_classes: int, out_size=None,
-                        axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
-                        sub_batch: int = 10, graph: bool = False, restore: str = "labels",
-                        postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                        skip: Optional[WindowSkip] = None, **intensity) -> Dict[str, torch.Tensor]:
-    """One-shot ``SlidingWindowPredictor(...).predict_scan(raw, geom, restore, postprocess, **intensity)`` with
-    ``geom = ScanGeometry.from_affine(raw's spatial shape, affine, axcodes, out_size)``; also returns ``"geometry"``."""
+def _predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], num_classes: int, out_size=None,
+                         axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
+                         sub_batch: int = 10, graph: bool = False, restore: str = "labels",
+                         postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                         skip: Optional[WindowSkip] = None, fit: Optional[WindowFit] = None,
+                         **intensity) -> Dict[str, torch.Tensor]:
     from . import scan
     if not isinstance(raw, torch.Tensor) or raw.dim() not in (3, 4, 5):
         raise ValueError("raw must be a [C, H, W, D] (or [H, W, D] / [1, C, H, W, D]) tensor")
     geom = scan.ScanGeometry.from_affine(tuple(raw.shape[-3:]), affine, axcodes, out_size)
     cin = 1 if raw.dim() == 3 else int(raw.shape[-4])
     out = _one_shot(model, geom.size, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                    skip).predict_scan(raw, geom, restore, postprocess, **intensity)
+                    skip, fit).predict_scan(raw, geom, restore, postprocess, **intensity)
     out["geometry"] = geom
     return out
 
 
+@_fit_keyword(_predict_scan_volume)
+def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], num_classes: int, out_size=None,
+                        axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
+                        sub_batch: int = 10, graph: bool = False, restore: str = "labels",
+                        postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                        skip: Optional[WindowSkip] = None, **intensity) -> Dict[str, torch.Tensor]:
+    """One-shot ``SlidingWindowPredictor(...).predict_scan(raw, geom, restore, postprocess, **intensity)`` with
+    ``geom = ScanGeometry.from_affine(raw's spatial shape, affine, axcodes, out_size)``; also returns ``"geometry"``.
+    Keyword-only ``fit``: the predictor's ``fit=``."""
+
+
+def _predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
+                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10, graph: bool = False,
+                    return_logits: bool = False, postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                    return_probs: bool = False, return_confidence: bool = False,
+                    return_entropy: bool = False, skip: Optional[WindowSkip] = None,
+                    fit: Optional[WindowFit] = None) -> Dict[str, torch.Tensor]:
+    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
+                     skip, fit).predict(x, return_logits, postprocess, return_probs, return_confidence, return_entropy)
+
+
+@_fit_keyword(_predict_volume)
 def predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10, graph: bool = False,
                    return_logits: bool = False, postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
                    return_probs: bool = False, return_confidence: bool = False,
                    return_entropy: bool = False, skip: Optional[WindowSkip] = None) -> Dict[str, torch.Tensor]:
     """One-shot ``SlidingWindowPredictor(..., mirror_axes=mirror_axes, skip=skip).predict(x, return_logits, postprocess, ...)`` for
-    ``x [1, Cin, H, W, D]``."""
+    ``x [1, Cin, H, W, D]``.
+    Keyword-only ``fit``: the predictor's ``fit=``."""
+
+
+def _evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
+                     mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                     graph: bool = False, postprocess: Optional[Dict] = None,
+                     mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None,
+                     fit: Optional[WindowFit] = None) -> Tuple[float, float]:
     return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                     skip).predict(x, return_logits, postprocess, return_probs, return_confidence, return_entropy)
+                     skip, fit).evaluate(x, seg, postprocess)
 
 
+@_fit_keyword(_evaluate_volume)
 def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
                     mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                     graph: bool = False, postprocess: Optional[Dict] = None,
                     mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None) -> Tuple[float, float]:
-    """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg, postprocess)``: whole-volume (mean IoU, mean Dice)."""
+    """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg, postprocess)``: whole-volume (mean IoU, mean Dice).
+    Keyword-only ``fit``: the predictor's ``fit=``."""
+
+
+def _evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
+                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0), percentile: float = 95.0,
+                             tolerance: float = 1.0, include_background: bool = False,
+                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                             skip: Optional[WindowSkip] = None, fit: Optional[WindowFit] = None) -> Dict[str, object]:
     return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                     skip).evaluate(x, seg, postprocess)
+                     skip, fit).evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)
 
 
+@_fit_keyword(_evaluate_volume_surface)
 def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0), percentile: float = 95.0,
                             tolerance: float = 1.0, include_background: bool = False,
                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
                             skip: Optional[WindowSkip] = None) -> Dict[str, object]:
-    """One-shot ``SlidingWindowPredictor(...).evaluate_surface(x, seg, ...)``: whole-volume surface metrics + IoU / Dice."""
+    """One-shot ``SlidingWindowPredictor(...).evaluate_surface(x, seg, ...)``: whole-volume surface metrics + IoU / Dice.
+    Keyword-only ``fit``: the predictor's ``fit=``."""
+
+
+def _evaluate_volume_lesions(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
+                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                             with_scores: bool = False, skip: Optional[WindowSkip] = None,
+                             fit: Optional[WindowFit] = None, **lesion_kwargs):
     return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                     skip).evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)
+                     skip, fit).evaluate_lesions(x, seg, spacing, postprocess, with_scores, **lesion_kwargs)
 
 
+@_fit_keyword(_evaluate_volume_lesions)
 def evaluate_volume_lesions(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0),
                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
                             with_scores: bool = False, skip: Optional[WindowSkip] = None, **lesion_kwargs):
     """One-shot ``SlidingWindowPredictor(...).evaluate_lesions(x, seg, spacing, postprocess, with_scores,
-    **lesion_kwargs)``: the lesion-wise ``mivp_amd.regions.LesionReport`` of the whole-volume prediction."""
+    **lesion_kwargs)``: the lesion-wise ``mivp_amd.regions.LesionReport`` of the whole-volume prediction.
+    Keyword-only ``fit``: the predictor's ``fit=``."""
+
+
+def _evaluate_volume_calibration(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
+                                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
+                                 sub_batch: int = 10, graph: bool = False, mirror_axes: Sequence[int] = (),
+                                 n_bins: int = 15, out=None, skip: Optional[WindowSkip] = None,
+                                 fit: Optional[WindowFit] = None):
     return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                     skip).evaluate_lesions(x, seg, spacing, postprocess, with_scores, **lesion_kwargs)
+                     skip, fit).evaluate_calibration(x, seg, n_bins, out)
 
 
+@_fit_keyword(_evaluate_volume_calibration)
 def evaluate_volume_calibration(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
                                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
                                 sub_batch: int = 10, graph: bool = False, mirror_axes: Sequence[int] = (),
                                 n_bins: int = 15, out=None, skip: Optional[WindowSkip] = None):
     """One-shot ``SlidingWindowPredictor(...).evaluate_calibration(x, seg, n_bins, out)``: the
-    ``mivp_amd.calibration.CalibrationReport`` of the whole-volume prediction."""
-    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                     skip).evaluate_calibration(x, seg, n_bins, out)
+    ``mivp_amd.calibration.CalibrationReport`` of the whole-volume prediction.
+    Keyword-only ``fit``: the predictor's ``fit=``."""

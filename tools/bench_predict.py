@@ -14,6 +14,12 @@ same volume predicted without and with skipping by graph predictors, alternating
 shape: ms per volume without and with skipping, kept and total windows, and the time of the occupancy + compact + fill
 launches on their own.
 
+``--fit-foreground [--margin M]`` times fitting the windows to the foreground bounding box
+(``SlidingWindowPredictor(fit=WindowFit(margin=M))``) on the same synthetic volume: predicted without either,
+with skipping and with fitting by graph predictors, alternating, on device events.  One JSON line per shape: ms per volume
+of the three, the windows each ran, the box, and the time of the box + plan + fill launches on their own.
+``--air-fraction 0`` makes the box the whole volume: the line then shows what the feature costs when it removes nothing.
+
 Kernel shares come from a run under the kernel tracer:
     rocprofv3 --kernel-trace --stats -d OUT -o pred -- python tools/bench_predict.py --volumes 2
 then ``python tools/bench_predict.py --stats OUT/.../pred_kernel_stats.csv --volumes 2`` prints the stitching kernels'
@@ -172,6 +178,57 @@ def run_skip(name, volumes, warmup, air_fraction, mirror_axes=()):
              "label_hist": torch.bincount(labels.reshape(-1).long()).tolist()}]
 
 
+def run_fit(name, volumes, warmup, air_fraction, margin, mirror_axes=()):
+    import torch
+    from mivp_amd import train
+    from mivp_amd.inference import SlidingWindowPredictor, WindowFit, WindowSkip
+    from mivp_amd.swin_unetr import SwinUnetR
+    s = SHAPES[name]
+    conf, _, _ = train.make_conf("cfg1", window=s["window"])
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = SwinUnetR(conf).to(dev).eval()
+    x = body_volume(s["image"], air_fraction, dev)
+    air = float((x == 0).double().mean())
+    kw = dict(overlap=0.5, mode="gaussian", sub_batch=s["sub_batch"], graph=True, mirror_axes=mirror_axes)
+    preds = {"full": SlidingWindowPredictor(model, s["image"], CIN, NCLS, s["roi"], **kw),
+             "skip": SlidingWindowPredictor(model, s["image"], CIN, NCLS, s["roi"], skip=WindowSkip(), **kw),
+             "fit": SlidingWindowPredictor(model, s["image"], CIN, NCLS, s["roi"], fit=WindowFit(margin=margin), **kw)}
+    for p in preds.values():
+        for _ in range(warmup):
+            p.predict(x)
+    torch.cuda.synchronize()
+    ms = {k: [] for k in preds}
+    for _ in range(volumes):                                     # alternate the three, one event pair per volume
+        for k, p in preds.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            labels = p.predict(x)["labels"]
+            b.record()
+            torch.cuda.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    p = preds["fit"]
+    # the feature's own launches: box + plan + fill (the fill finds nothing to write after a finished volume)
+    reps = 20
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        p._plan(p.vol)
+        p._fill()
+    b.record()
+    torch.cuda.synchronize()
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    return [{"shape": name, "mode": "graph", "image": list(s["image"]), "roi": list(s["roi"]), "sub_batch": s["sub_batch"],
+             "mirror_axes": list(mirror_axes), "air_fraction": round(air, 4), "margin": margin, "box": p.box.tolist(),
+             "windows": p.n_windows, "windows_skip": preds["skip"].n_kept, "windows_fit": p.n_kept,
+             "sub_batches": p.n_sub, "sub_batches_skip": preds["skip"].n_sub_run, "sub_batches_fit": p.n_sub_run,
+             "ms_per_volume_full": round(med["full"], 3), "ms_per_volume_skip": round(med["skip"], 3),
+             "ms_per_volume_fit": round(med["fit"], 3), "fit_over_full": round(med["fit"] / med["full"], 4),
+             "ms_min_full": round(min(ms["full"]), 3), "ms_min_skip": round(min(ms["skip"]), 3),
+             "ms_min_fit": round(min(ms["fit"]), 3), "box_plan_fill_ms": round(a.elapsed_time(b) / reps, 4),
+             "label_hist": torch.bincount(labels.reshape(-1).long()).tolist()}]
+
+
 def stats(path, volumes, warmup, shapes, mirror_axes=(), maps=False):
     """Share of kernel time and bytes / time of the stitching kernels in a profiled run of ``shapes``.  The flip-aware
     gather / blend and the probability finalize are the kernels of a run with ``mirror_axes`` / ``maps``."""
@@ -220,13 +277,21 @@ def main():
     ap.add_argument("--maps", action="store_true", help="also return probs / confidence / entropy (probability finalize)")
     ap.add_argument("--skip-background", action="store_true",
                     help="time window skipping against the unfiltered prediction on a synthetic body-in-air volume")
+    ap.add_argument("--fit-foreground", action="store_true",
+                    help="time fitting the windows to the foreground box against the unfiltered and the skipping prediction")
+    ap.add_argument("--margin", type=int, default=0, help="with --fit-foreground: voxels added around the box per axis")
     ap.add_argument("--air-fraction", type=float, default=0.5,
-                    help="with --skip-background: the fraction of voxels that are air (exactly 0), in [0, 1]")
+                    help="with --skip-background / --fit-foreground: the fraction of voxels that are air (exactly 0), in "
+                         "[0, 1]")
     ap.add_argument("--stats", help="kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of this tool with the same "
                                     "--shape / --mirror-axes / --maps")
     a = ap.parse_args()
     if not 0.0 <= a.air_fraction <= 1.0:
         ap.error("--air-fraction must be in [0, 1]")
+    if a.margin < 0:
+        ap.error("--margin must be >= 0")
+    if a.fit_foreground and a.skip_background:
+        ap.error("--fit-foreground already times skipping next to fitting: give one of the two")
     import mivp_amd  # noqa: F401
     shapes = list(SHAPES) if a.shape == "all" else [a.shape]
     if a.stats:
@@ -234,8 +299,11 @@ def main():
         return
     for name in shapes:
         try:
-            lines = (run_skip(name, a.volumes, a.warmup, a.air_fraction, a.mirror_axes) if a.skip_background
-                     else run(name, a.volumes, a.warmup, a.mirror_axes, a.maps))
+            if a.fit_foreground:
+                lines = run_fit(name, a.volumes, a.warmup, a.air_fraction, a.margin, a.mirror_axes)
+            else:
+                lines = (run_skip(name, a.volumes, a.warmup, a.air_fraction, a.mirror_axes) if a.skip_background
+                         else run(name, a.volumes, a.warmup, a.mirror_axes, a.maps))
         except (RuntimeError, ValueError) as exc:                # a shape the model cannot run: say so, go on
             lines = [{"shape": name, "error": str(exc)[:300]}]
         for line in lines:
