@@ -1,6 +1,8 @@
 """Host-side argument checks and small helpers shared by the evaluation modules (``inference``, ``surface``,
 ``components``, ``regions``, ``calibration``, ``scan``, ``scanstats``).  One definition each: a module that needs one
-imports it from here, not from a sibling.  Nothing here launches a kernel except ``workspace``'s size query."""
+imports it from here, not from a sibling.  Also the two things the predictor's pieces share that are not checks: the
+``ImmutableValue`` base of ``WindowSkip`` / ``WindowFit`` and ``channels_last_or_copy``, the layout in which the kernels
+read a model's logits.  Nothing here launches a kernel except ``workspace``'s size query."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,6 +19,15 @@ LABEL_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3
 CONNECTIVITY = (6, 18, 26)
 
 
+def channels_last_or_copy(t: torch.Tensor):
+    """``[B, C, ...]`` logits as the kernels read them -> (tensor, channels_last flag): the channels-last view when the
+    storage is fp32 channels-last (what the model returns), else an fp32 contiguous channels-first copy."""
+    base = t.permute(0, *range(2, t.dim()), 1)
+    if base.is_contiguous() and t.dtype == torch.float32:
+        return base, 1
+    return t.float().contiguous(), 0
+
+
 def i3(v):
     """Three sizes as the ``int32[3]`` the C ABI takes."""
     return (C.c_int32 * 3)(*[int(a) for a in v])
@@ -25,6 +36,29 @@ def i3(v):
 def plain_int(v) -> bool:
     """An int or a numpy integer, but not a bool."""
     return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+class ImmutableValue:
+    """Base of the small value objects (``WindowSkip``, ``WindowFit``): the fields are the subclass's ``__slots__``, set
+    once by ``_set`` in its ``__init__``; immutability, ``repr``, equality and hashing follow from them."""
+
+    __slots__ = ()
+
+    def _set(self, **fields):
+        for k in self.__slots__:
+            object.__setattr__(self, k, fields[k])
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"{type(self).__name__} is immutable")
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(f'{k}={getattr(self, k)}' for k in self.__slots__)})"
+
+    def __eq__(self, other):
+        return isinstance(other, type(self)) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
 
 
 def check_finite(name: str, v) -> float:

@@ -18,20 +18,14 @@
 // 3-bit code flips roi axis a.  The work list holds every window under every code, window-major; the gather hands the model
 // the flipped window, the blend reads the logits through the same flip and weights them by the UNFLIPPED importance map, in
 // increasing entry index.  With code 0 everywhere both kernels compute what the plain ones compute, bit for bit.
-#include "common.hpp"
-#include <limits.h>
+//
+// The window geometry (Geo, fill_geo, MAXC, TPB) and the plain accumulation of one contribution (add_weighted) are
+// csrc/window_common.hpp's, shared with window_skip.hip and window_fit.hip.
+// In this file the two finalize kernels share padded_index / count_voxel and their entry points finalize_setup; the two
+// gather entry points share launch_gather.
+#include "window_common.hpp"
 
 namespace {
-constexpr int MAXC = 16;
-constexpr int TPB = 256;
-
-struct Geo {
-    int n[3];      // image size
-    int pad[3];    // zeros in front of the image (padded volume coordinates = image coordinates + pad)
-    int p[3];      // padded size, max(n, roi)
-    int r[3];      // roi
-};
-
 // one thread = four consecutive D outputs of one (window, channel, i, j) row
 __global__ __launch_bounds__(TPB) void k_window_gather(const float* __restrict__ vol, int Cin, Geo g,
                                                        const int* __restrict__ table, int n_entries,
@@ -122,9 +116,7 @@ __global__ __launch_bounds__(TPB) void k_window_blend(const float* __restrict__ 
         const long lv = ((long)i * g.r[1] + j) * g.r[2] + k;
         const float* src = channels_last ? logits + ((long)b * rvol + lv) * C : logits + (long)b * C * rvol + lv;
         const long cs = channels_last ? 1 : rvol;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c)
-            if (c < C) a[c] += wt * src[c * cs];
+        add_weighted(a, C, wt, src, cs);
         s += wt;
         any = true;
     }
@@ -133,6 +125,21 @@ __global__ __launch_bounds__(TPB) void k_window_blend(const float* __restrict__ 
     for (int c = 0; c < MAXC; ++c)
         if (c < C) acc[v * C + c] = a[c];
     wsum[v] = s;
+}
+
+// What k_stitch_finalize and k_stitch_finalize_probs share.  Image voxel v -> its index in the padded volume:
+MIVP_DEV long padded_index(long v, const Geo& g) {
+    const int d = (int)(v % g.n[2]);
+    const long r = v / g.n[2];
+    const int x1 = (int)(r % g.n[1]);
+    const int h = (int)(r / g.n[1]);
+    return ((long)(h + g.pad[0]) * g.p[1] + (x1 + g.pad[1])) * g.p[2] + (d + g.pad[2]);
+}
+// the workgroup's Dice / IoU counts in LDS, sm[class][intersection, predicted, target]: one voxel
+MIVP_DEV void count_voxel(unsigned int* sm, int best, float tv, int C) {
+    atomicAdd(&sm[best * 3 + 1], 1u);
+    for (int c = 0; c < C; ++c)
+        if (tv == (float)c) { atomicAdd(&sm[c * 3 + 2], 1u); if (best == c) atomicAdd(&sm[c * 3 + 0], 1u); }
 }
 
 // acc / wsum over the image (cropped out of the padded volume), first arg-max, optional logits and counts
@@ -145,11 +152,7 @@ __global__ __launch_bounds__(TPB) void k_stitch_finalize(const float* __restrict
     __syncthreads();
     const long nvox = (long)g.n[0] * g.n[1] * g.n[2];
     for (long v = (long)blockIdx.x * TPB + threadIdx.x; v < nvox; v += (long)gridDim.x * TPB) {
-        const int d = (int)(v % g.n[2]);
-        const long r = v / g.n[2];
-        const int x1 = (int)(r % g.n[1]);
-        const int h = (int)(r / g.n[1]);
-        const long pv = ((long)(h + g.pad[0]) * g.p[1] + (x1 + g.pad[1])) * g.p[2] + (d + g.pad[2]);
+        const long pv = padded_index(v, g);
         const float s = wsum[pv];
         int best = 0;
         float bv = 0.f;
@@ -161,12 +164,7 @@ __global__ __launch_bounds__(TPB) void k_stitch_finalize(const float* __restrict
             if (c == 0 || x > bv) { bv = x; best = c; }       // first maximum, like torch.argmax
         }
         labels[v] = (uint8_t)best;
-        if (target) {
-            const float tv = target[v];
-            atomicAdd(&sm[best * 3 + 1], 1u);
-            for (int c = 0; c < C; ++c)
-                if (tv == (float)c) { atomicAdd(&sm[c * 3 + 2], 1u); if (best == c) atomicAdd(&sm[c * 3 + 0], 1u); }
-        }
+        if (target) count_voxel(sm, best, target[v], C);
     }
     if (!target) return;                                       // (uniform: the whole grid returns together)
     __syncthreads();
@@ -321,9 +319,7 @@ __global__ __launch_bounds__(TPB) void k_window_blend_tta(const float* __restric
                 cw = __fsub_rn(__fsub_rn(tt, s), y);
                 s = tt;
             } else {
-#pragma unroll
-                for (int c = 0; c < MAXC; ++c)
-                    if (c < C) a[c] += wt * src[c * cs];
+                add_weighted(a, C, wt, src, cs);
                 s += wt;
             }
             any = true;
@@ -356,11 +352,7 @@ __global__ __launch_bounds__(TPB) void k_stitch_finalize_probs(const float* __re
     const long nvox = (long)g.n[0] * g.n[1] * g.n[2];
     const float inv_lnc = C > 1 ? 1.f / logf((float)C) : 0.f;
     for (long v = (long)blockIdx.x * TPB + threadIdx.x; v < nvox; v += (long)gridDim.x * TPB) {
-        const int d = (int)(v % g.n[2]);
-        const long r = v / g.n[2];
-        const int x1 = (int)(r % g.n[1]);
-        const int h = (int)(r / g.n[1]);
-        const long pv = ((long)(h + g.pad[0]) * g.p[1] + (x1 + g.pad[1])) * g.p[2] + (d + g.pad[2]);
+        const long pv = padded_index(v, g);
         const float s = wsum[pv];
         float x[MAXC];
         int best = 0;
@@ -390,12 +382,7 @@ __global__ __launch_bounds__(TPB) void k_stitch_finalize_probs(const float* __re
         if (conf) conf[v] = inv;                               // the maximum probability: exp(0) / den
         // -sum p ln p = ln den - sum p (x - max)
         if (entropy) entropy[v] = fminf(fmaxf((logf(den) - dot) * inv_lnc, 0.f), 1.f);
-        if (target) {
-            const float tv = target[v];
-            atomicAdd(&sm[best * 3 + 1], 1u);
-            for (int c = 0; c < C; ++c)
-                if (tv == (float)c) { atomicAdd(&sm[c * 3 + 2], 1u); if (best == c) atomicAdd(&sm[c * 3 + 0], 1u); }
-        }
+        if (target) count_voxel(sm, best, target[v], C);
     }
     if (!target) return;                                       // (uniform: the whole grid returns together)
     __syncthreads();
@@ -406,18 +393,10 @@ __global__ __launch_bounds__(TPB) void k_stitch_finalize_probs(const float* __re
 // a separate one-thread launch: the blend's workgroups all read the word, so none of them may bump it
 __global__ void k_window_advance(int* __restrict__ sub_idx) { sub_idx[0] = sub_idx[0] + 1; }
 
-bool fill_geo(Geo& g, const int32_t* dims, const int32_t* pad, const int32_t* pdims, const int32_t* roi) {
-    for (int a = 0; a < 3; ++a) {
-        g.n[a] = dims[a]; g.pad[a] = pad[a]; g.p[a] = pdims[a]; g.r[a] = roi[a];
-        if (g.n[a] < 1 || g.r[a] < 1 || g.pad[a] < 0 || g.pad[a] + g.n[a] > g.p[a] || g.r[a] > g.p[a]) return false;
-    }
-    return (long)g.p[0] * g.p[1] * g.p[2] < (1L << 31) / MAXC;
-}
-}  // namespace
-
-extern "C" int mivp_window_gather(const float* vol, int32_t Cin, const int32_t* dims, const int32_t* pad, const int32_t* pdims,
-                                  const int32_t* roi, const int32_t* table, int32_t n_entries, const int32_t* sub_idx,
-                                  int32_t B, float* out, mivp_stream_t stream) {
+// the one host-side launcher of the two gather kernels (they take the same arguments)
+int launch_gather(decltype(&k_window_gather) kern, const char* what, const float* vol, int32_t Cin, const int32_t* dims,
+                  const int32_t* pad, const int32_t* pdims, const int32_t* roi, const int32_t* table, int32_t n_entries,
+                  const int32_t* sub_idx, int32_t B, float* out, mivp_stream_t stream) {
     MIVP_REQUIRE(vol && out && table && sub_idx && dims && pad && pdims && roi);
     MIVP_REQUIRE(Cin >= 1 && Cin <= 4 && B >= 1 && n_entries >= B && n_entries % B == 0);
     Geo g;
@@ -425,9 +404,30 @@ extern "C" int mivp_window_gather(const float* vol, int32_t Cin, const int32_t* 
     const int vec_ok = (reinterpret_cast<uintptr_t>(vol) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) &&
                        g.n[2] % 4 == 0 && g.r[2] % 4 == 0;
     const long total = (long)B * Cin * g.r[0] * g.r[1] * ((g.r[2] + 3) / 4);
-    hipLaunchKernelGGL(k_window_gather, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, vol,
-                       (int)Cin, g, table, (int)n_entries, sub_idx, (int)B, vec_ok, out);
-    return mivp_check_launch("window_gather");
+    hipLaunchKernelGGL(kern, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, vol, (int)Cin, g,
+                       table, (int)n_entries, sub_idx, (int)B, vec_ok, out);
+    return mivp_check_launch(what);
+}
+
+// the argument checks of the two finalize entry points, and their (grid, Geo)
+int finalize_setup(const float* acc, const float* wsum, int32_t C, const int32_t* dims, const int32_t* pad,
+                    const int32_t* pdims, const uint8_t* labels, const float* target, const void* counts, Geo& g,
+                    unsigned& grid) {
+    MIVP_REQUIRE(acc && wsum && labels && dims && pad && pdims && C >= 1 && C <= MAXC);
+    MIVP_REQUIRE((target == nullptr) == (counts == nullptr));
+    const int32_t one[3] = {1, 1, 1};
+    MIVP_REQUIRE(fill_geo(g, dims, pad, pdims, one));
+    const long nvox = (long)g.n[0] * g.n[1] * g.n[2];
+    grid = (unsigned)((nvox + TPB - 1) / TPB > 2048 ? 2048 : (nvox + TPB - 1) / TPB);
+    return MIVP_OK;
+}
+}  // namespace
+
+extern "C" int mivp_window_gather(const float* vol, int32_t Cin, const int32_t* dims, const int32_t* pad, const int32_t* pdims,
+                                  const int32_t* roi, const int32_t* table, int32_t n_entries, const int32_t* sub_idx,
+                                  int32_t B, float* out, mivp_stream_t stream) {
+    return launch_gather(k_window_gather, "window_gather", vol, Cin, dims, pad, pdims, roi, table, n_entries, sub_idx, B, out,
+                         stream);
 }
 
 extern "C" int mivp_window_blend(const float* logits, int32_t channels_last, int32_t C, const int32_t* pdims,
@@ -450,13 +450,9 @@ extern "C" int mivp_window_blend(const float* logits, int32_t channels_last, int
 extern "C" int mivp_stitch_finalize(const float* acc, const float* wsum, int32_t C, const int32_t* dims, const int32_t* pad,
                                     const int32_t* pdims, uint8_t* labels, float* logits, const float* target, void* counts,
                                     mivp_stream_t stream) {
-    MIVP_REQUIRE(acc && wsum && labels && dims && pad && pdims && C >= 1 && C <= MAXC);
-    MIVP_REQUIRE((target == nullptr) == (counts == nullptr));
     Geo g;
-    const int32_t one[3] = {1, 1, 1};
-    MIVP_REQUIRE(fill_geo(g, dims, pad, pdims, one));
-    const long nvox = (long)g.n[0] * g.n[1] * g.n[2];
-    const unsigned grid = (unsigned)((nvox + TPB - 1) / TPB > 2048 ? 2048 : (nvox + TPB - 1) / TPB);
+    unsigned grid;
+    if (const int e = finalize_setup(acc, wsum, C, dims, pad, pdims, labels, target, counts, g, grid)) return e;
     hipLaunchKernelGGL(k_stitch_finalize, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, acc, wsum, (int)C, g, labels, logits,
                        target, (unsigned long long*)counts);
     return mivp_check_launch("stitch_finalize");
@@ -465,16 +461,8 @@ extern "C" int mivp_stitch_finalize(const float* acc, const float* wsum, int32_t
 extern "C" int mivp_window_gather_tta(const float* vol, int32_t Cin, const int32_t* dims, const int32_t* pad,
                                       const int32_t* pdims, const int32_t* roi, const int32_t* table, int32_t n_entries,
                                       const int32_t* sub_idx, int32_t B, float* out, mivp_stream_t stream) {
-    MIVP_REQUIRE(vol && out && table && sub_idx && dims && pad && pdims && roi);
-    MIVP_REQUIRE(Cin >= 1 && Cin <= 4 && B >= 1 && n_entries >= B && n_entries % B == 0);
-    Geo g;
-    MIVP_REQUIRE(fill_geo(g, dims, pad, pdims, roi));
-    const int vec_ok = (reinterpret_cast<uintptr_t>(vol) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) &&
-                       g.n[2] % 4 == 0 && g.r[2] % 4 == 0;
-    const long total = (long)B * Cin * g.r[0] * g.r[1] * ((g.r[2] + 3) / 4);
-    hipLaunchKernelGGL(k_window_gather_tta, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, vol,
-                       (int)Cin, g, table, (int)n_entries, sub_idx, (int)B, vec_ok, out);
-    return mivp_check_launch("window_gather_tta");
+    return launch_gather(k_window_gather_tta, "window_gather_tta", vol, Cin, dims, pad, pdims, roi, table, n_entries, sub_idx,
+                         B, out, stream);
 }
 
 extern "C" int mivp_window_blend_tta(const float* logits, int32_t channels_last, int32_t C, const int32_t* pdims,
@@ -500,13 +488,9 @@ extern "C" int mivp_stitch_finalize_probs(const float* acc, const float* wsum, i
                                           const int32_t* pad, const int32_t* pdims, uint8_t* labels, float* logits,
                                           float* probs, float* confidence, float* entropy, const float* target, void* counts,
                                           mivp_stream_t stream) {
-    MIVP_REQUIRE(acc && wsum && labels && dims && pad && pdims && C >= 1 && C <= MAXC);
-    MIVP_REQUIRE((target == nullptr) == (counts == nullptr));
     Geo g;
-    const int32_t one[3] = {1, 1, 1};
-    MIVP_REQUIRE(fill_geo(g, dims, pad, pdims, one));
-    const long nvox = (long)g.n[0] * g.n[1] * g.n[2];
-    const unsigned grid = (unsigned)((nvox + TPB - 1) / TPB > 2048 ? 2048 : (nvox + TPB - 1) / TPB);
+    unsigned grid;
+    if (const int e = finalize_setup(acc, wsum, C, dims, pad, pdims, labels, target, counts, g, grid)) return e;
     hipLaunchKernelGGL(k_stitch_finalize_probs, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, acc, wsum, (int)C, g, labels,
                        logits, probs, confidence, entropy, target, (unsigned long long*)counts);
     return mivp_check_launch("stitch_finalize_probs");

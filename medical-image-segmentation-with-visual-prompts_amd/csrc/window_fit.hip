@@ -5,11 +5,10 @@
 //   window_fit_plan: the window tiling of that box (the placement rule of window_origins on the box, widened to the roi
 //                    and clamped into the padded volume) written as the work list the gather / blend / recorded graph read
 // Integers only: every result is independent of the order of the atomics and bitwise reproducible.
-#include "common.hpp"
-#include <limits.h>
+// The plan's geometry arguments pass the check of the other window kernels (fill_geo of csrc/window_common.hpp).
+#include "window_common.hpp"
 
 namespace {
-constexpr int TPB = 256;
 constexpr int WAVES = TPB / 64;
 constexpr int MAXF = 8;                                        // flip codes of one window (3-bit masks)
 
@@ -176,15 +175,15 @@ extern "C" int mivp_window_fit_plan(const int32_t* box, const int32_t* dims, con
     MIVP_REQUIRE(n_flips >= 1 && n_flips <= MAXF && n_entries >= 1 && n_origins >= 1);
     MIVP_REQUIRE(n_entries <= (1 << 27) && n_origins <= (1 << 27));
     MIVP_REQUIRE(reinterpret_cast<uintptr_t>(table) % 16 == 0);
+    Geo geo;
+    MIVP_REQUIRE(fill_geo(geo, dims, pad, pdims, roi));
     Dims g;
     FitGeo f;
     for (int a = 0; a < 3; ++a) {
-        g.n[a] = dims[a]; f.pad[a] = pad[a]; f.p[a] = pdims[a]; f.r[a] = roi[a]; f.step[a] = interval[a];
+        g.n[a] = geo.n[a]; f.pad[a] = geo.pad[a]; f.p[a] = geo.p[a]; f.r[a] = geo.r[a]; f.step[a] = interval[a];
         f.margin[a] = margin[a];
-        MIVP_REQUIRE(g.n[a] >= 1 && f.r[a] >= 1 && f.pad[a] >= 0 && f.pad[a] + g.n[a] <= f.p[a] && f.r[a] <= f.p[a]);
         MIVP_REQUIRE(f.step[a] >= 1 && f.step[a] <= f.r[a] && f.margin[a] >= 0 && f.margin[a] <= (1 << 30));
     }
-    MIVP_REQUIRE((long)f.p[0] * f.p[1] * f.p[2] < (1L << 31) / 16);
     FlipCodes c;
     for (int j = 0; j < MAXF; ++j) {
         c.m[j] = j < n_flips ? codes[j] : 0;

@@ -7,20 +7,11 @@
 //   fill     : voxels no kept window covered (wsum == 0) get the fill logits and wsum = 1, so that the unchanged finalize
 //              kernels produce the fill result
 // Integer atomics and an ordered block scan only: every result is bitwise reproducible.
-#include "common.hpp"
-#include <limits.h>
+// The window geometry (Geo, fill_geo, MAXC, TPB) is csrc/window_common.hpp's, shared with stitch.hip and window_fit.hip.
+#include "window_common.hpp"
 
 namespace {
-constexpr int MAXC = 16;
-constexpr int TPB = 256;
 constexpr int WAVES = TPB / 64;
-
-struct Geo {
-    int n[3];      // image size
-    int pad[3];    // zeros in front of the image (padded volume coordinates = image coordinates + pad)
-    int p[3];      // padded size, max(n, roi)
-    int r[3];      // roi
-};
 
 MIVP_DEV int fg(float v, float thr) { return v > thr ? 1 : 0; }          // strict: NaN is not foreground
 MIVP_DEV int fg(uint8_t v, float) { return v != 0 ? 1 : 0; }
@@ -240,14 +231,6 @@ __global__ __launch_bounds__(TPB) void k_stitch_fill(float* __restrict__ acc, fl
         for (int c = 0; c < C; ++c) acc[v * C + c] = c == fill_class ? fill_logit : -fill_logit;
         wsum[v] = 1.f;
     }
-}
-
-bool fill_geo(Geo& g, const int32_t* dims, const int32_t* pad, const int32_t* pdims, const int32_t* roi) {
-    for (int a = 0; a < 3; ++a) {
-        g.n[a] = dims[a]; g.pad[a] = pad[a]; g.p[a] = pdims[a]; g.r[a] = roi[a];
-        if (g.n[a] < 1 || g.r[a] < 1 || g.pad[a] < 0 || g.pad[a] + g.n[a] > g.p[a] || g.r[a] > g.p[a]) return false;
-    }
-    return (long)g.p[0] * g.p[1] * g.p[2] < (1L << 31) / MAXC;
 }
 }  // namespace
 

@@ -5,7 +5,6 @@ and the metric counts accumulated by one kernel per sub-batch (no ``.item()`` in
 from __future__ import annotations
 
 import ctypes as C
-import functools
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -13,8 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._host import (check_classes, check_fill_logit, check_finite, check_gpu, check_int_from, check_region_mask, i3,
-                    iou_dice)
+from ._host import (ImmutableValue, channels_last_or_copy, check_classes, check_fill_logit, check_finite, check_gpu,
+                    check_int_from, check_region_mask, i3, iou_dice)
 from .window_fit import WindowFit, foreground_box
 
 
@@ -77,12 +76,7 @@ class SegMetrics:
         Cn = preds.shape[1]
         if Cn != self.num_classes:
             raise ValueError("class count mismatch")
-        nd = preds.dim()
-        base = preds.permute(0, *range(2, nd), 1)
-        if base.is_contiguous() and preds.dtype == torch.float32:
-            src, clast = base, 1
-        else:
-            src, clast = preds.float().contiguous(), 0
+        src, clast = channels_last_or_copy(preds)
         tgt = target.float().contiguous()
         vol = 1
         for n in preds.shape[2:]:
@@ -134,12 +128,25 @@ def _check_shape3(name: str, v: Sequence[int]) -> Tuple[int, int, int]:
     return t
 
 
+def _check_sub_batch(sub_batch) -> int:
+    if int(sub_batch) < 1:
+        raise ValueError("sub_batch must be >= 1")
+    return int(sub_batch)
+
+
 def window_padding(image_size: Sequence[int], roi: Sequence[int]) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
     """(zeros in front per axis, padded size per axis): an axis shorter than the roi is padded to the roi, (r - n) // 2
     in front and the rest behind; other axes are not padded."""
     n, r = _check_shape3("image_size", image_size), _check_shape3("roi", roi)
     pad = tuple((ri - ni) // 2 if ni < ri else 0 for ni, ri in zip(n, r))
     return pad, tuple(max(ni, ri) for ni, ri in zip(n, r))
+
+
+def _fit_intervals(roi: Sequence[int], overlap: float) -> Tuple[int, int, int]:
+    """Per axis ``max(int(r * (1 - overlap)), 1)``, the window step of ``window_origins`` (and of the fitted tiling,
+    which takes it from the host so that the float arithmetic is done once)."""
+    _check_overlap(overlap)
+    return tuple(max(int(r * (1.0 - float(overlap))), 1) for r in _check_shape3("roi", roi))
 
 
 def window_origins(image_size: Sequence[int], roi: Sequence[int], overlap: float) -> np.ndarray:
@@ -149,11 +156,10 @@ def window_origins(image_size: Sequence[int], roi: Sequence[int], overlap: float
     so parity with it is not pinned by a test): per axis, on the padded size n and roi r,
     ``interval = max(int(r * (1 - overlap)), 1)``, ``count = ceil((n - r) / interval) + 1`` and window i starts at
     ``min(i * interval, n - r)``, so the last window is flush with the end."""
-    _check_overlap(overlap)
+    _check_overlap(overlap)                                      # (refused before a bad shape, as always)
     _, p = window_padding(image_size, roi)
     axes = []
-    for n, r in zip(p, roi):
-        interval = max(int(r * (1.0 - float(overlap))), 1)
+    for n, r, interval in zip(p, roi, _fit_intervals(roi, overlap)):
         count = int(math.ceil((n - r) / interval)) + 1
         axes.append([min(i * interval, n - r) for i in range(count)])
     g = np.stack(np.meshgrid(*[np.asarray(a, dtype=np.int32) for a in axes], indexing="ij"), axis=-1)
@@ -162,8 +168,6 @@ def window_origins(image_size: Sequence[int], roi: Sequence[int], overlap: float
 
 def window_table(origins: np.ndarray, sub_batch: int) -> np.ndarray:
     """The device table: int32 [ceil(N / sub_batch) * sub_batch, 4] = (o0, o1, o2, valid); padding entries are invalid."""
-    if int(sub_batch) < 1:
-        raise ValueError("sub_batch must be >= 1")
     return tta_table(origins, sub_batch, (0,))
 
 
@@ -187,8 +191,7 @@ def tta_table(origins: np.ndarray, sub_batch: int, codes: Sequence[int]) -> np.n
     """The device work list under mirror augmentation: int32 [ceil(N F / sub_batch) * sub_batch, 4] =
     (o0, o1, o2, valid | code << 1), entry ``w * F + j`` = window ``w`` under ``codes[j]`` (window-major, flip-minor);
     padding entries are invalid.  ``codes == (0,)`` gives ``window_table(origins, sub_batch)``."""
-    if int(sub_batch) < 1:
-        raise ValueError("sub_batch must be >= 1")
+    _check_sub_batch(sub_batch)
     codes = [int(m) for m in codes]
     if not codes or any(m < 0 or m > 7 for m in codes) or len(set(codes)) != len(codes):
         raise ValueError(f"codes must be distinct 3-bit flip masks, got {codes}")
@@ -221,7 +224,7 @@ def importance_tables(roi: Sequence[int], mode: str = "gaussian", sigma_scale: f
     return tabs, floor
 
 
-class WindowSkip:
+class WindowSkip(ImmutableValue):
     """Which windows a ``SlidingWindowPredictor(skip=...)`` leaves out.  A voxel of the prepared volume is
     foreground iff ``vol[channel] > threshold`` (strict fp32: NaN is not foreground; the default threshold is the
     reference's ``LoadPseudoBgMaskd`` rule, transforms.py:363); a window is kept iff it holds at least ``min_voxels``
@@ -237,43 +240,8 @@ class WindowSkip:
         check_fill_logit(fill_logit)
         for name, v, lo in (("channel", channel, 0), ("min_voxels", min_voxels, 1), ("fill_class", fill_class, 0)):
             check_int_from(name, v, lo)
-        object.__setattr__(self, "threshold", float(threshold))
-        object.__setattr__(self, "channel", int(channel))
-        object.__setattr__(self, "min_voxels", int(min_voxels))
-        object.__setattr__(self, "fill_class", int(fill_class))
-        object.__setattr__(self, "fill_logit", float(fill_logit))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("WindowSkip is immutable")
-
-    def __repr__(self):
-        return (f"WindowSkip(threshold={self.threshold}, channel={self.channel}, min_voxels={self.min_voxels}, "
-                f"fill_class={self.fill_class}, fill_logit={self.fill_logit})")
-
-    def __eq__(self, other):
-        return isinstance(other, WindowSkip) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
-
-
-def _fit_intervals(roi: Sequence[int], overlap: float) -> Tuple[int, int, int]:
-    """Per axis ``max(int(r * (1 - overlap)), 1)``, the window step of ``window_origins`` (and of the fitted tiling,
-    which takes it from the host so that the float arithmetic is done once)."""
-    _check_overlap(overlap)
-    return tuple(max(int(r * (1.0 - float(overlap))), 1) for r in _check_shape3("roi", roi))
-
-
-def _fit_keyword(impl):
-    """Decorator of the predictor's entry points that take ``fit``.  The decorated function is the declaration -- the
-    positional signature that existing callers and ``inspect.signature`` see, and the docstring; its body is ``impl``,
-    which has the same parameters plus ``fit``.  The result takes ``fit`` as a keyword only."""
-    def declare(fn):
-        @functools.wraps(fn)
-        def entry(*args, fit=None, **kwargs):
-            return impl(*args, fit=fit, **kwargs)
-        return entry
-    return declare
+        self._set(threshold=float(threshold), channel=int(channel), min_voxels=int(min_voxels), fill_class=int(fill_class),
+                  fill_logit=float(fill_logit))
 
 
 def _model_factor(conf) -> Tuple[int, int, int]:
@@ -334,38 +302,34 @@ class SlidingWindowPredictor:
     is the whole volume gives the full tiling and the prediction without ``fit`` bit for bit.  After a run ``n_kept`` is
     the number of fitted windows and ``n_sub_run`` the number of sub-batches run."""
 
-    def _init(self, model, image_size: Sequence[int], in_channels: int, num_classes: int, roi: Sequence[int],
-              overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-              graph: bool = False, mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None,
-              fit: Optional[WindowFit] = None):
+    def __init__(self, model, image_size: Sequence[int], in_channels: int, num_classes: int, roi: Sequence[int],
+                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                 graph: bool = False, mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None, *,
+                 fit: Optional[WindowFit] = None):
+        """The class docstring describes the arguments; ``fit`` is keyword-only."""
         self.image_size = _check_shape3("image_size", image_size)
         self.roi = _check_shape3("roi", roi)
         _check_overlap(overlap)
         self.flip_codes = flip_codes(mirror_axes)
         self.mirror_axes = tuple(int(a) for a in mirror_axes)
         self.n_flips = len(self.flip_codes)
-        if int(sub_batch) < 1:
-            raise ValueError("sub_batch must be >= 1")
+        _check_sub_batch(sub_batch)
         if not 1 <= int(in_channels) <= 4:
             raise ValueError("in_channels must be in 1..4")
         check_classes(num_classes)
-        if skip is not None:
-            if not isinstance(skip, WindowSkip):
-                raise ValueError(f"skip must be a WindowSkip or None, got {type(skip).__name__}")
-            if skip.channel >= int(in_channels):
-                raise ValueError(f"skip.channel {skip.channel} is not a channel of a {int(in_channels)}-channel volume")
-            if skip.fill_class >= int(num_classes):
-                raise ValueError(f"skip.fill_class {skip.fill_class} is not one of {int(num_classes)} classes")
-        if fit is not None:
-            if not isinstance(fit, WindowFit):
-                raise ValueError(f"fit must be a WindowFit or None, got {type(fit).__name__}")
-            if skip is not None:
+        for name, rule, cls in (("skip", skip, WindowSkip), ("fit", fit, WindowFit)):
+            if rule is None:
+                continue
+            if not isinstance(rule, cls):
+                raise ValueError(f"{name} must be a {cls.__name__} or None, got {type(rule).__name__}")
+            if name == "fit" and skip is not None:
                 raise ValueError("fit and skip cannot be combined: build the predictor with one of them")
-            if fit.channel >= int(in_channels):
-                raise ValueError(f"fit.channel {fit.channel} is not a channel of a {int(in_channels)}-channel volume")
-            if fit.fill_class >= int(num_classes):
-                raise ValueError(f"fit.fill_class {fit.fill_class} is not one of {int(num_classes)} classes")
-        self.skip, self.fit = skip, fit
+            if rule.channel >= int(in_channels):
+                raise ValueError(f"{name}.channel {rule.channel} is not a channel of a {int(in_channels)}-channel volume")
+            if rule.fill_class >= int(num_classes):
+                raise ValueError(f"{name}.fill_class {rule.fill_class} is not one of {int(num_classes)} classes")
+        # the active selection rule, if any: it writes the volume's work list into self.table, then one 8-byte read
+        self.skip, self.fit, self._rule = skip, fit, skip if skip is not None else fit
         conf = getattr(model, "conf", None)
         if conf is not None:
             if getattr(conf, "training_mode", "downstream") != "downstream":
@@ -423,47 +387,36 @@ class SlidingWindowPredictor:
         self.occupancy, self.region = None, None
         self.n_kept, self.n_sub_run = self.n_windows, self.n_sub
         self.box = None
+        if self._rule is not None:
+            self.table_full = self.table.clone()
+            self.meta = torch.zeros(2, dtype=torch.int32, device=dev)
         if fit is not None:
             # the fitted tiling never has more windows per axis than the full one: table, xb, accumulators, graph as built
-            self.table_full = self.table.clone()
             self.box = torch.zeros(6, dtype=torch.int32, device=dev)
             self.fit_origins = torch.zeros((self.n_windows, 3), dtype=torch.int32, device=dev)
-            self.meta = torch.zeros(2, dtype=torch.int32, device=dev)
             self._fit_args = (i3(_fit_intervals(self.roi, overlap)), i3([min(m, 2 ** 30) for m in fit.margin]),
                               (C.c_int32 * self.n_flips)(*self.flip_codes))
         if skip is not None:
-            self.table_full = self.table.clone()
             self.origins_dev = torch.from_numpy(np.ascontiguousarray(self.origins)).to(dev)
             self.occupancy = torch.zeros(self.n_windows, dtype=torch.int32, device=dev)
-            self.meta = torch.zeros(2, dtype=torch.int32, device=dev)
-
-    @_fit_keyword(_init)
-    def __init__(self, model, image_size: Sequence[int], in_channels: int, num_classes: int, roi: Sequence[int],
-                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                 graph: bool = False, mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None):
-        """The class docstring describes the arguments; ``fit`` is keyword-only."""
 
     # ------------------------------------------------------------------ per sub-batch launches
     def _gather(self, vol):
         a = self._a
-        L.call("mivp_window_gather_tta" if self._tta_kernels else "mivp_window_gather", L.ptr(vol), C.c_int32(self.cin), a["dims"], a["pad"], a["pdims"], a["roi"],
-               L.ptr(self.table), C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch),
-               L.ptr(self.xb), L.stream())
+        L.call("mivp_window_gather_tta" if self._tta_kernels else "mivp_window_gather", L.ptr(vol), C.c_int32(self.cin),
+               a["dims"], a["pad"], a["pdims"], a["roi"], L.ptr(self.table), C.c_int32(self.table.shape[0]),
+               L.ptr(self.sub_idx), C.c_int32(self.sub_batch), L.ptr(self.xb), L.stream())
 
     def _blend(self, out):
         if tuple(out.shape) != (self.sub_batch, self.ncls) + self.roi:
             raise ValueError(f"the model returned {tuple(out.shape)}, expected {(self.sub_batch, self.ncls) + self.roi}")
-        base = out.permute(0, 2, 3, 4, 1)
-        if base.is_contiguous() and out.dtype == torch.float32:
-            src, clast = base, 1
-        else:
-            src, clast = out.float().contiguous(), 0
+        src, clast = channels_last_or_copy(out)
         a = self._a
         args = (L.ptr(src), C.c_int32(clast), C.c_int32(self.ncls), a["pdims"], a["roi"], L.ptr(self.table),
                 C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch), a["ubox"],
                 L.ptr(self.w[0]), L.ptr(self.w[1]), L.ptr(self.w[2]), C.c_float(self.w_floor), L.ptr(self.acc),
                 L.ptr(self.wsum))
-        if self.skip is not None or self.fit is not None:        # any union box on the unfiltered grid (comp None: plain sums)
+        if self._rule is not None:                               # any union box on the unfiltered grid (comp None: plain sums)
             L.call("mivp_window_blend_any", *args, L.ptr(self.comp), L.stream())
         elif self._tta_kernels:
             L.call("mivp_window_blend_tta", *args, L.ptr(self.comp), L.stream())
@@ -489,7 +442,7 @@ class SlidingWindowPredictor:
         """While a resident uint8 ``[H, W, D]`` GPU tensor is set, foreground means ``mask != 0`` (a body or lung mask
         from ``mivp_amd.components``) and the threshold is ignored; ``None`` returns to the threshold rule.  The tensor
         is read at every run, not copied."""
-        if self.skip is None and self.fit is None:
+        if self._rule is None:
             raise ValueError("set_region needs a predictor built with skip=WindowSkip(...)")
         if mask is not None:
             check_region_mask(mask, self.image_size, self.dev)
@@ -527,7 +480,7 @@ class SlidingWindowPredictor:
         return self.n_sub_run
 
     def _fill(self):
-        k = self.skip if self.skip is not None else self.fit
+        k = self._rule
         L.call("mivp_stitch_fill", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), self._a["pdims"],
                C.c_int32(k.fill_class), C.c_float(k.fill_logit), L.stream())
 
@@ -569,17 +522,14 @@ class SlidingWindowPredictor:
             if vol.data_ptr() != self.vol.data_ptr():            # predict_scan prepares straight into the resident volume
                 self.vol.copy_(vol)
             if self.graph is None:
-                if self.skip is not None or self.fit is not None:   # warm up and record with the full work list
+                if self._rule is not None:                       # warm up and record with the full work list
                     self.table.copy_(self.table_full)
                 self._record()
             vol = self.vol                                       # what the launches below and the recorded gather read
         self._reset()
         n_sub = self.n_sub
-        if self.skip is not None:
-            self._select(vol)
-            n_sub = self._kept()
-        elif self.fit is not None:
-            self._plan(vol)
+        if self._rule is not None:
+            (self._select if self.skip is not None else self._plan)(vol)
             n_sub = self._kept()
         if self.graph_mode:
             for _ in range(n_sub):
@@ -587,7 +537,7 @@ class SlidingWindowPredictor:
         else:
             for _ in range(n_sub):
                 self._step(vol)
-        if self.skip is not None or self.fit is not None:
+        if self._rule is not None:
             self._fill()
         labels = torch.empty((1, 1) + self.image_size, dtype=torch.uint8, device=self.dev)
         logits = torch.empty((1, self.ncls) + self.image_size, dtype=torch.float32, device=self.dev) if want_logits else None
@@ -771,12 +721,15 @@ def _one_shot(model, x_or_shape, cin, num_classes, roi, overlap, mode, sigma_sca
                                   mirror_axes, skip, fit=fit)
 
 
-def _predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], num_classes: int, out_size=None,
-                         axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
-                         sub_batch: int = 10, graph: bool = False, restore: str = "labels",
-                         postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                         skip: Optional[WindowSkip] = None, fit: Optional[WindowFit] = None,
-                         **intensity) -> Dict[str, torch.Tensor]:
+def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], num_classes: int, out_size=None,
+                        axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
+                        sub_batch: int = 10, graph: bool = False, restore: str = "labels",
+                        postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
+                        skip: Optional[WindowSkip] = None, *, fit: Optional[WindowFit] = None,
+                        **intensity) -> Dict[str, torch.Tensor]:
+    """One-shot ``SlidingWindowPredictor(...).predict_scan(raw, geom, restore, postprocess, **intensity)`` with
+    ``geom = ScanGeometry.from_affine(raw's spatial shape, affine, axcodes, out_size)``; also returns ``"geometry"``.
+    Keyword-only ``fit``: the predictor's ``fit=``."""
     from . import scan
     if not isinstance(raw, torch.Tensor) or raw.dim() not in (3, 4, 5):
         raise ValueError("raw must be a [C, H, W, D] (or [H, W, D] / [1, C, H, W, D]) tensor")
@@ -788,112 +741,62 @@ def _predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], n
     return out
 
 
-@_fit_keyword(_predict_scan_volume)
-def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], num_classes: int, out_size=None,
-                        axcodes: str = "RAS", overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
-                        sub_batch: int = 10, graph: bool = False, restore: str = "labels",
-                        postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                        skip: Optional[WindowSkip] = None, **intensity) -> Dict[str, torch.Tensor]:
-    """One-shot ``SlidingWindowPredictor(...).predict_scan(raw, geom, restore, postprocess, **intensity)`` with
-    ``geom = ScanGeometry.from_affine(raw's spatial shape, affine, axcodes, out_size)``; also returns ``"geometry"``.
-    Keyword-only ``fit``: the predictor's ``fit=``."""
-
-
-def _predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
-                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10, graph: bool = False,
-                    return_logits: bool = False, postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                    return_probs: bool = False, return_confidence: bool = False,
-                    return_entropy: bool = False, skip: Optional[WindowSkip] = None,
-                    fit: Optional[WindowFit] = None) -> Dict[str, torch.Tensor]:
-    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                     skip, fit).predict(x, return_logits, postprocess, return_probs, return_confidence, return_entropy)
-
-
-@_fit_keyword(_predict_volume)
 def predict_volume(model, x: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10, graph: bool = False,
                    return_logits: bool = False, postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
                    return_probs: bool = False, return_confidence: bool = False,
-                   return_entropy: bool = False, skip: Optional[WindowSkip] = None) -> Dict[str, torch.Tensor]:
+                   return_entropy: bool = False, skip: Optional[WindowSkip] = None, *,
+                   fit: Optional[WindowFit] = None) -> Dict[str, torch.Tensor]:
     """One-shot ``SlidingWindowPredictor(..., mirror_axes=mirror_axes, skip=skip).predict(x, return_logits, postprocess, ...)`` for
     ``x [1, Cin, H, W, D]``.
     Keyword-only ``fit``: the predictor's ``fit=``."""
+    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
+                     skip, fit).predict(x, return_logits, postprocess, return_probs, return_confidence, return_entropy)
 
 
-def _evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
-                     mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                     graph: bool = False, postprocess: Optional[Dict] = None,
-                     mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None,
-                     fit: Optional[WindowFit] = None) -> Tuple[float, float]:
+def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
+                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
+                    graph: bool = False, postprocess: Optional[Dict] = None,
+                    mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None, *,
+                    fit: Optional[WindowFit] = None) -> Tuple[float, float]:
+    """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg, postprocess)``: whole-volume (mean IoU, mean Dice).
+    Keyword-only ``fit``: the predictor's ``fit=``."""
     return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
                      skip, fit).evaluate(x, seg, postprocess)
 
 
-@_fit_keyword(_evaluate_volume)
-def evaluate_volume(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int, overlap: float = 0.5,
-                    mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                    graph: bool = False, postprocess: Optional[Dict] = None,
-                    mirror_axes: Sequence[int] = (), skip: Optional[WindowSkip] = None) -> Tuple[float, float]:
-    """One-shot ``SlidingWindowPredictor(...).evaluate(x, seg, postprocess)``: whole-volume (mean IoU, mean Dice).
-    Keyword-only ``fit``: the predictor's ``fit=``."""
-
-
-def _evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
-                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0), percentile: float = 95.0,
-                             tolerance: float = 1.0, include_background: bool = False,
-                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                             skip: Optional[WindowSkip] = None, fit: Optional[WindowFit] = None) -> Dict[str, object]:
-    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                     skip, fit).evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)
-
-
-@_fit_keyword(_evaluate_volume_surface)
 def evaluate_volume_surface(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0), percentile: float = 95.0,
                             tolerance: float = 1.0, include_background: bool = False,
                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                            skip: Optional[WindowSkip] = None) -> Dict[str, object]:
+                            skip: Optional[WindowSkip] = None, *, fit: Optional[WindowFit] = None) -> Dict[str, object]:
     """One-shot ``SlidingWindowPredictor(...).evaluate_surface(x, seg, ...)``: whole-volume surface metrics + IoU / Dice.
     Keyword-only ``fit``: the predictor's ``fit=``."""
-
-
-def _evaluate_volume_lesions(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
-                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
-                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0),
-                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                             with_scores: bool = False, skip: Optional[WindowSkip] = None,
-                             fit: Optional[WindowFit] = None, **lesion_kwargs):
     return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                     skip, fit).evaluate_lesions(x, seg, spacing, postprocess, with_scores, **lesion_kwargs)
+                     skip, fit).evaluate_surface(x, seg, spacing, percentile, tolerance, include_background, postprocess)
 
 
-@_fit_keyword(_evaluate_volume_lesions)
 def evaluate_volume_lesions(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
                             overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125, sub_batch: int = 10,
                             graph: bool = False, spacing: Sequence[float] = (1.0, 1.0, 1.0),
                             postprocess: Optional[Dict] = None, mirror_axes: Sequence[int] = (),
-                            with_scores: bool = False, skip: Optional[WindowSkip] = None, **lesion_kwargs):
+                            with_scores: bool = False, skip: Optional[WindowSkip] = None, *,
+                            fit: Optional[WindowFit] = None, **lesion_kwargs):
     """One-shot ``SlidingWindowPredictor(...).evaluate_lesions(x, seg, spacing, postprocess, with_scores,
     **lesion_kwargs)``: the lesion-wise ``mivp_amd.regions.LesionReport`` of the whole-volume prediction.
     Keyword-only ``fit``: the predictor's ``fit=``."""
-
-
-def _evaluate_volume_calibration(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
-                                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
-                                 sub_batch: int = 10, graph: bool = False, mirror_axes: Sequence[int] = (),
-                                 n_bins: int = 15, out=None, skip: Optional[WindowSkip] = None,
-                                 fit: Optional[WindowFit] = None):
     return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
-                     skip, fit).evaluate_calibration(x, seg, n_bins, out)
+                     skip, fit).evaluate_lesions(x, seg, spacing, postprocess, with_scores, **lesion_kwargs)
 
 
-@_fit_keyword(_evaluate_volume_calibration)
 def evaluate_volume_calibration(model, x: torch.Tensor, seg: torch.Tensor, roi: Sequence[int], num_classes: int,
                                 overlap: float = 0.5, mode: str = "gaussian", sigma_scale: float = 0.125,
                                 sub_batch: int = 10, graph: bool = False, mirror_axes: Sequence[int] = (),
-                                n_bins: int = 15, out=None, skip: Optional[WindowSkip] = None):
+                                n_bins: int = 15, out=None, skip: Optional[WindowSkip] = None, *,
+                                fit: Optional[WindowFit] = None):
     """One-shot ``SlidingWindowPredictor(...).evaluate_calibration(x, seg, n_bins, out)``: the
     ``mivp_amd.calibration.CalibrationReport`` of the whole-volume prediction.
     Keyword-only ``fit``: the predictor's ``fit=``."""
+    return _one_shot(model, x, None, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes,
+                     skip, fit).evaluate_calibration(x, seg, n_bins, out)

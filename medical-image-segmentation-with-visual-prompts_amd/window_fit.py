@@ -9,10 +9,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._host import check_fill_logit, check_finite, check_gpu, check_int_from, i3, plain_int
+from ._host import ImmutableValue, check_fill_logit, check_finite, check_gpu, check_int_from, i3, plain_int
 
 
-class WindowFit:
+class WindowFit(ImmutableValue):
     """How a ``SlidingWindowPredictor(fit=...)`` fits its windows to the foreground.  A voxel of the
     prepared volume is foreground iff ``vol[channel] > threshold`` (strict fp32: NaN is not foreground; the default is
     ``WindowSkip``'s).  The windows tile the foreground's bounding box, grown by ``margin`` voxels per axis (an integer
@@ -34,24 +34,8 @@ class WindowFit:
             m = tuple(margin)
         else:
             raise ValueError(f"margin must be a non-negative integer or three of them, got {margin!r}")
-        object.__setattr__(self, "threshold", float(threshold))
-        object.__setattr__(self, "channel", int(channel))
-        object.__setattr__(self, "margin", tuple(check_int_from("margin", v, 0) for v in m))
-        object.__setattr__(self, "fill_class", int(fill_class))
-        object.__setattr__(self, "fill_logit", float(fill_logit))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("WindowFit is immutable")
-
-    def __repr__(self):
-        return (f"WindowFit(threshold={self.threshold}, channel={self.channel}, margin={self.margin}, "
-                f"fill_class={self.fill_class}, fill_logit={self.fill_logit})")
-
-    def __eq__(self, other):
-        return isinstance(other, WindowFit) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(threshold=float(threshold), channel=int(channel), margin=tuple(check_int_from("margin", v, 0) for v in m),
+                  fill_class=int(fill_class), fill_logit=float(fill_logit))
 
 
 def foreground_box(vol_or_mask: torch.Tensor, channel: int = 0, threshold: float = 0.0025,

@@ -219,26 +219,28 @@ SURFACE = {
         "(model, x: 'torch.Tensor', seg: 'torch.Tensor', roi: 'Sequence[int]', num_classes: 'int', "
         "overlap: 'float' = 0.5, mode: 'str' = 'gaussian', sigma_scale: 'float' = 0.125, "
         "sub_batch: 'int' = 10, graph: 'bool' = False, postprocess: 'Optional[Dict]' = None, "
-        "mirror_axes: 'Sequence[int]' = (), skip: 'Optional[WindowSkip]' = None) -> 'Tuple[float, "
+        "mirror_axes: 'Sequence[int]' = (), skip: 'Optional[WindowSkip]' = None, *, "
+        "fit: 'Optional[WindowFit]' = None) -> 'Tuple[float, "
         "float]'",
     'inference.evaluate_volume_calibration':
         "(model, x: 'torch.Tensor', seg: 'torch.Tensor', roi: 'Sequence[int]', num_classes: 'int', "
         "overlap: 'float' = 0.5, mode: 'str' = 'gaussian', sigma_scale: 'float' = 0.125, "
         "sub_batch: 'int' = 10, graph: 'bool' = False, mirror_axes: 'Sequence[int]' = (), "
-        "n_bins: 'int' = 15, out=None, skip: 'Optional[WindowSkip]' = None)",
+        "n_bins: 'int' = 15, out=None, skip: 'Optional[WindowSkip]' = None, *, fit: 'Optional[WindowFit]' = None)",
     'inference.evaluate_volume_lesions':
         "(model, x: 'torch.Tensor', seg: 'torch.Tensor', roi: 'Sequence[int]', num_classes: 'int', "
         "overlap: 'float' = 0.5, mode: 'str' = 'gaussian', sigma_scale: 'float' = 0.125, "
         "sub_batch: 'int' = 10, graph: 'bool' = False, spacing: 'Sequence[float]' = (1.0, 1.0, 1.0), "
         "postprocess: 'Optional[Dict]' = None, mirror_axes: 'Sequence[int]' = (), "
-        "with_scores: 'bool' = False, skip: 'Optional[WindowSkip]' = None, **lesion_kwargs)",
+        "with_scores: 'bool' = False, skip: 'Optional[WindowSkip]' = None, *, "
+        "fit: 'Optional[WindowFit]' = None, **lesion_kwargs)",
     'inference.evaluate_volume_surface':
         "(model, x: 'torch.Tensor', seg: 'torch.Tensor', roi: 'Sequence[int]', num_classes: 'int', "
         "overlap: 'float' = 0.5, mode: 'str' = 'gaussian', sigma_scale: 'float' = 0.125, "
         "sub_batch: 'int' = 10, graph: 'bool' = False, spacing: 'Sequence[float]' = (1.0, 1.0, 1.0), "
         "percentile: 'float' = 95.0, tolerance: 'float' = 1.0, include_background: 'bool' = False, "
         "postprocess: 'Optional[Dict]' = None, mirror_axes: 'Sequence[int]' = (), "
-        "skip: 'Optional[WindowSkip]' = None) -> 'Dict[str, object]'",
+        "skip: 'Optional[WindowSkip]' = None, *, fit: 'Optional[WindowFit]' = None) -> 'Dict[str, object]'",
     'inference.flip_codes':
         "(mirror_axes: 'Sequence[int]' = ()) -> 'Tuple[int, ...]'",
     'inference.importance_tables':
@@ -248,15 +250,15 @@ SURFACE = {
         "axcodes: 'str' = 'RAS', overlap: 'float' = 0.5, mode: 'str' = 'gaussian', "
         "sigma_scale: 'float' = 0.125, sub_batch: 'int' = 10, graph: 'bool' = False, "
         "restore: 'str' = 'labels', postprocess: 'Optional[Dict]' = None, "
-        "mirror_axes: 'Sequence[int]' = (), skip: 'Optional[WindowSkip]' = None, "
-        "**intensity) -> 'Dict[str, torch.Tensor]'",
+        "mirror_axes: 'Sequence[int]' = (), skip: 'Optional[WindowSkip]' = None, *, "
+        "fit: 'Optional[WindowFit]' = None, **intensity) -> 'Dict[str, torch.Tensor]'",
     'inference.predict_volume':
         "(model, x: 'torch.Tensor', roi: 'Sequence[int]', num_classes: 'int', overlap: 'float' = 0.5, "
         "mode: 'str' = 'gaussian', sigma_scale: 'float' = 0.125, sub_batch: 'int' = 10, "
         "graph: 'bool' = False, return_logits: 'bool' = False, postprocess: 'Optional[Dict]' = None, "
         "mirror_axes: 'Sequence[int]' = (), return_probs: 'bool' = False, "
         "return_confidence: 'bool' = False, return_entropy: 'bool' = False, "
-        "skip: 'Optional[WindowSkip]' = None) -> 'Dict[str, torch.Tensor]'",
+        "skip: 'Optional[WindowSkip]' = None, *, fit: 'Optional[WindowFit]' = None) -> 'Dict[str, torch.Tensor]'",
     'inference.sliding_window_view':
         "(x: 'torch.Tensor', roi: 'Sequence[int]') -> 'torch.Tensor'",
     'inference.sliding_windows':
@@ -284,7 +286,7 @@ SURFACE = {
         "(self, model, image_size: 'Sequence[int]', in_channels: 'int', num_classes: 'int', "
         "roi: 'Sequence[int]', overlap: 'float' = 0.5, mode: 'str' = 'gaussian', "
         "sigma_scale: 'float' = 0.125, sub_batch: 'int' = 10, graph: 'bool' = False, "
-        "mirror_axes: 'Sequence[int]' = (), skip: 'Optional[WindowSkip]' = None)",
+        "mirror_axes: 'Sequence[int]' = (), skip: 'Optional[WindowSkip]' = None, *, fit: 'Optional[WindowFit]' = None)",
     'inference.SlidingWindowPredictor.evaluate':
         "(self, x: 'torch.Tensor', seg: 'torch.Tensor', "
         "postprocess: 'Optional[Dict]' = None) -> 'Tuple[float, float]'",
