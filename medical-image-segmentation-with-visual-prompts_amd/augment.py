@@ -122,7 +122,7 @@ class IntensitySlot:
         self.B = int(B)
         if self.B < 1:
             raise ValueError("IntensitySlot: B >= 1 expected")
-        self.ws_bytes = int(L.lib().mivp_intensity_ws(C.c_int32(self.B), C.c_int64(1 << 40)))
+        self.ws_bytes = int(L.lib().mivp_intensity_ws(self.B, 1 << 40))
         self.buf = torch.zeros(self.B * RECORD + self.ws_bytes // 4, dtype=torch.int32, device=device)
         self.records = self.buf[:self.B * RECORD]
         self.ws = self.buf[self.B * RECORD:]
@@ -164,10 +164,9 @@ def augment_intensity(x: torch.Tensor, slot: IntensitySlot, out: Optional[torch.
         out = torch.empty_like(x)
     B, Cn = x.shape[0], x.shape[1]
     dims = (C.c_int32 * 3)(*x.shape[2:])
-    L.call("mivp_intensity_stats", L.ptr(x), C.c_int32(B), C.c_int32(Cn), dims, L.ptr(slot.records), L.ptr(slot.ws),
-           C.c_size_t(slot.ws_bytes), L.stream())
-    L.call("mivp_intensity_apply", L.ptr(x), C.c_int32(B), C.c_int32(Cn), dims, L.ptr(slot.records), L.ptr(slot.ws),
-           C.c_size_t(slot.ws_bytes), L.ptr(out), L.stream())
+    L.call("mivp_intensity_stats", L.ptr(x), B, Cn, dims, L.ptr(slot.records), L.ptr(slot.ws), slot.ws_bytes, L.stream())
+    L.call("mivp_intensity_apply", L.ptr(x), B, Cn, dims, L.ptr(slot.records), L.ptr(slot.ws), slot.ws_bytes, L.ptr(out),
+           L.stream())
     return out
 
 

@@ -13,8 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmivp_hip.so")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
-         "-I" + os.path.join(os.path.dirname(HERE), "include")]
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
+HEADER = os.path.join(INCLUDE, "mivp.h")           # the C ABI; _lib.py binds its prototypes from the same file
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I" + INCLUDE]
 
 
 # swin_bwd_fused.hip: the SLP vectoriser packs the four dS = P * dP multiplies of a tile into two v_pk_mul_f32 and then
@@ -33,7 +34,7 @@ def _stale(out, deps):
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    hdrs = glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(os.path.dirname(HERE), "include", "mivp.h")]
+    hdrs = glob.glob(os.path.join(CSRC, "*.hpp")) + [HEADER]
     jobs = []
     for s in srcs:
         o = os.path.join(OBJ, os.path.basename(s)[:-4] + ".o")

@@ -40,7 +40,6 @@ whatever the order of arrival, and so is everything derived from them.
 """
 from __future__ import annotations
 
-import ctypes as C
 import numbers
 from typing import Dict, Optional, Tuple
 
@@ -238,7 +237,7 @@ def calibration_tables(probs: torch.Tensor, target: torch.Tensor, num_classes: i
     p = (probs[0] if probs.dim() == 5 else probs).contiguous()
     t = label_volume("target", target)
     rep = CalibrationReport(ncls, nb, p.device) if out is None else out
-    assert rep.tables.numel() * 8 == int(L.lib().mivp_calibration_ws(C.c_int32(ncls), C.c_int32(nb)))
-    L.call("mivp_calibration_hist", L.ptr(p), L.ptr(t), C.c_int32(LABEL_DTYPES[t.dtype]), i3(dims), C.c_int32(ncls),
-           C.c_int32(nb), C.c_int32(int(flags)), L.ptr(rep.tables), L.stream())
+    assert rep.tables.numel() * 8 == int(L.lib().mivp_calibration_ws(ncls, nb))
+    L.call("mivp_calibration_hist", L.ptr(p), L.ptr(t), LABEL_DTYPES[t.dtype], i3(dims), ncls, nb, int(flags),
+           L.ptr(rep.tables), L.stream())
     return rep

@@ -25,7 +25,6 @@ root and one filter pass (post-processing).  ``postprocess_labels`` makes no hos
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Iterable, Optional, Tuple
 
 import torch
@@ -62,8 +61,8 @@ def label_components(x: torch.Tensor, connectivity: int = 6) -> Tuple[torch.Tens
     labels = torch.empty(dims, dtype=torch.int32, device=v.device)
     n = torch.empty(1, dtype=torch.int32, device=v.device)
     ws = workspace("label", dims, v.device)
-    L.call("mivp_label_components", L.ptr(v), C.c_int32(LABEL_DTYPES[v.dtype]), i3(dims), C.c_int32(conn), L.ptr(labels),
-           L.ptr(n), L.ptr(ws), L.stream())
+    L.call("mivp_label_components", L.ptr(v), LABEL_DTYPES[v.dtype], i3(dims), conn, L.ptr(labels), L.ptr(n), L.ptr(ws),
+           L.stream())
     return labels.reshape(x.shape), int(n.item())
 
 
@@ -76,9 +75,8 @@ def _postprocess_launch(v: torch.Tensor, out: torch.Tensor, args, ws: Optional[t
     dims = tuple(v.shape)
     if ws is None:
         ws = workspace("postprocess", dims, v.device)
-    L.call("mivp_postprocess_labels", L.ptr(v), C.c_int32(LABEL_DTYPES[v.dtype]), i3(dims), C.c_int32(ncls),
-           C.c_uint32(mask), C.c_int64(min_size), C.c_int32(int(largest)), C.c_int32(conn), L.ptr(out), L.ptr(target),
-           L.ptr(counts), L.ptr(ws), L.stream())
+    L.call("mivp_postprocess_labels", L.ptr(v), LABEL_DTYPES[v.dtype], i3(dims), ncls, mask, min_size, int(largest), conn,
+           L.ptr(out), L.ptr(target), L.ptr(counts), L.ptr(ws), L.stream())
     return ws
 
 

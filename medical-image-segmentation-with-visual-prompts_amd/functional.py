@@ -245,8 +245,7 @@ class _TokenScoresFn(torch.autograd.Function):
         Wc, Ec = W.detach().float().contiguous(), E.detach().float().contiguous()
         heads, e = Wc.shape
         ts = torch.empty((heads, n_prompt), dtype=torch.float32, device=W.device)
-        L.call("mivp_token_scores_fwd", L.ptr(Wc), L.ptr(Ec), C.c_int32(heads), C.c_int32(n_prompt), C.c_int32(e),
-               C.c_float(scale), L.ptr(ts), L.stream())
+        L.call("mivp_token_scores_fwd", L.ptr(Wc), L.ptr(Ec), heads, n_prompt, e, scale, L.ptr(ts), L.stream())
         ctx.save_for_backward(Wc, Ec)
         ctx.meta = (n_prompt, scale)
         return ts
@@ -258,8 +257,8 @@ class _TokenScoresFn(torch.autograd.Function):
         heads, e = Wc.shape
         dW = torch.empty_like(Wc)
         dE = torch.zeros_like(Ec) if Ec.shape[0] != n_prompt else torch.empty_like(Ec)
-        L.call("mivp_token_scores_bwd", L.ptr(dts.contiguous().float()), L.ptr(Wc), L.ptr(Ec), C.c_int32(heads),
-               C.c_int32(n_prompt), C.c_int32(e), C.c_float(scale), L.ptr(dW), L.ptr(dE), L.stream())
+        L.call("mivp_token_scores_bwd", L.ptr(dts.contiguous().float()), L.ptr(Wc), L.ptr(Ec), heads, n_prompt, e, scale,
+               L.ptr(dW), L.ptr(dE), L.stream())
         return dW, dE, None, None
 
 
@@ -275,8 +274,8 @@ class _TokenScoresMultiFn(torch.autograd.Function):
         e = int(Ws[0].shape[1])
         ts = [torch.empty((Ws[i].shape[0], meta[i][0]), dtype=torch.float32, device=Ws[i].device) for i in range(n)]
         vp = lambda ts_: (C.c_void_p * n)(*[t.data_ptr() for t in ts_])
-        L.call("mivp_token_scores_fwd_multi", C.c_int32(n), vp(Ws), vp(Es), (C.c_int32 * n)(*[int(w_.shape[0]) for w_ in Ws]),
-               (C.c_int32 * n)(*[m[0] for m in meta]), C.c_int32(e), (C.c_float * n)(*[m[1] for m in meta]), vp(ts), L.stream())
+        L.call("mivp_token_scores_fwd_multi", n, vp(Ws), vp(Es), (C.c_int32 * n)(*[int(w_.shape[0]) for w_ in Ws]),
+               (C.c_int32 * n)(*[m[0] for m in meta]), e, (C.c_float * n)(*[m[1] for m in meta]), vp(ts), L.stream())
         ctx.save_for_backward(*Ws, *Es)
         ctx.meta = meta
         return tuple(ts)
@@ -291,9 +290,8 @@ class _TokenScoresMultiFn(torch.autograd.Function):
         dW = [torch.empty_like(w_) for w_ in Ws]
         dE = [torch.zeros_like(E_) if E_.shape[0] != meta[i][0] else torch.empty_like(E_) for i, E_ in enumerate(Es)]
         vp = lambda ts_: (C.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in ts_])
-        L.call("mivp_token_scores_bwd_multi", C.c_int32(n), vp(dts), vp(Ws), vp(Es),
-               (C.c_int32 * n)(*[int(w_.shape[0]) for w_ in Ws]), (C.c_int32 * n)(*[m[0] for m in meta]), C.c_int32(e),
-               (C.c_float * n)(*[m[1] for m in meta]), vp(dW), vp(dE), L.stream())
+        L.call("mivp_token_scores_bwd_multi", n, vp(dts), vp(Ws), vp(Es), (C.c_int32 * n)(*[int(w_.shape[0]) for w_ in Ws]),
+               (C.c_int32 * n)(*[m[0] for m in meta]), e, (C.c_float * n)(*[m[1] for m in meta]), vp(dW), vp(dE), L.stream())
         out = [None]
         for i in range(n):
             out += [dW[i], dE[i]]
@@ -368,7 +366,7 @@ def prepare_prompted_blocks(pairs):
         vps = [torch.empty_like(t) for t in kps]
         darr = (L.SwinDesc * n)(*descs)
         vp = lambda ts_: (C.c_void_p * n)(*[t.data_ptr() for t in ts_])
-        L.call("mivp_prompt_kv_fwd_multi", C.c_int32(n), darr, vp(prs), vp([w_.ln1_w for w_ in ws]), vp([w_.ln1_b for w_ in ws]),
+        L.call("mivp_prompt_kv_fwd_multi", n, darr, vp(prs), vp([w_.ln1_w for w_ in ws]), vp([w_.ln1_b for w_ in ws]),
                vp([w_.wqkv for w_ in ws]), vp([t.detach() for t in ts]), vp(kps), vp(vps), vp([a[1] for a in aug]), L.stream())
         for i, (blk, prm) in enumerate(chunk):
             key = (int(descs[i].Nqp), int(descs[i].Nkp), int(descs[i].augp), nps[i])

@@ -81,8 +81,7 @@ class SegMetrics:
         vol = 1
         for n in preds.shape[2:]:
             vol *= int(n)
-        L.call("mivp_seg_counts", L.ptr(src), L.ptr(tgt), C.c_int64(preds.shape[0] * vol), C.c_int32(Cn), C.c_int32(clast),
-               C.c_int64(vol), L.ptr(self.counts), L.stream())
+        L.call("mivp_seg_counts", L.ptr(src), L.ptr(tgt), preds.shape[0] * vol, Cn, clast, vol, L.ptr(self.counts), L.stream())
 
     def compute(self) -> Tuple[float, float]:
         """(mean IoU, mean Dice) -- the one host read."""
@@ -403,19 +402,18 @@ class SlidingWindowPredictor:
     # ------------------------------------------------------------------ per sub-batch launches
     def _gather(self, vol):
         a = self._a
-        L.call("mivp_window_gather_tta" if self._tta_kernels else "mivp_window_gather", L.ptr(vol), C.c_int32(self.cin),
-               a["dims"], a["pad"], a["pdims"], a["roi"], L.ptr(self.table), C.c_int32(self.table.shape[0]),
-               L.ptr(self.sub_idx), C.c_int32(self.sub_batch), L.ptr(self.xb), L.stream())
+        L.call("mivp_window_gather_tta" if self._tta_kernels else "mivp_window_gather", L.ptr(vol), self.cin, a["dims"],
+               a["pad"], a["pdims"], a["roi"], L.ptr(self.table), self.table.shape[0], L.ptr(self.sub_idx), self.sub_batch,
+               L.ptr(self.xb), L.stream())
 
     def _blend(self, out):
         if tuple(out.shape) != (self.sub_batch, self.ncls) + self.roi:
             raise ValueError(f"the model returned {tuple(out.shape)}, expected {(self.sub_batch, self.ncls) + self.roi}")
         src, clast = channels_last_or_copy(out)
         a = self._a
-        args = (L.ptr(src), C.c_int32(clast), C.c_int32(self.ncls), a["pdims"], a["roi"], L.ptr(self.table),
-                C.c_int32(self.table.shape[0]), L.ptr(self.sub_idx), C.c_int32(self.sub_batch), a["ubox"],
-                L.ptr(self.w[0]), L.ptr(self.w[1]), L.ptr(self.w[2]), C.c_float(self.w_floor), L.ptr(self.acc),
-                L.ptr(self.wsum))
+        args = (L.ptr(src), clast, self.ncls, a["pdims"], a["roi"], L.ptr(self.table), self.table.shape[0],
+                L.ptr(self.sub_idx), self.sub_batch, a["ubox"], L.ptr(self.w[0]), L.ptr(self.w[1]), L.ptr(self.w[2]),
+                self.w_floor, L.ptr(self.acc), L.ptr(self.wsum))
         if self._rule is not None:                               # any union box on the unfiltered grid (comp None: plain sums)
             L.call("mivp_window_blend_any", *args, L.ptr(self.comp), L.stream())
         elif self._tta_kernels:
@@ -451,13 +449,12 @@ class SlidingWindowPredictor:
     def _select(self, vol):
         """occupancy -> compact into ``self.table``; no host read."""
         a, k = self._a, self.skip
-        src = (L.ptr(vol), C.c_int32(self.cin), C.c_int32(k.channel), C.c_float(k.threshold), L.ptr(None)) \
-            if self.region is None else (L.ptr(None), C.c_int32(0), C.c_int32(0), C.c_float(0.0), L.ptr(self.region))
-        L.call("mivp_window_occupancy", *src, a["dims"], a["pad"], a["pdims"], a["roi"], L.ptr(self.origins_dev),
-               C.c_int32(3), C.c_int32(self.n_windows), L.ptr(self.occupancy), L.stream())
-        L.call("mivp_window_compact", L.ptr(self.table_full), C.c_int32(self.table.shape[0]), C.c_int32(self.n_windows),
-               C.c_int32(self.n_flips), L.ptr(self.occupancy), C.c_int32(k.min_voxels), L.ptr(self.table),
-               L.ptr(self.meta), L.stream())
+        src = (L.ptr(vol), self.cin, k.channel, k.threshold, None) if self.region is None else \
+            (None, 0, 0, 0.0, L.ptr(self.region))
+        L.call("mivp_window_occupancy", *src, a["dims"], a["pad"], a["pdims"], a["roi"], L.ptr(self.origins_dev), 3,
+               self.n_windows, L.ptr(self.occupancy), L.stream())
+        L.call("mivp_window_compact", L.ptr(self.table_full), self.table.shape[0], self.n_windows, self.n_flips,
+               L.ptr(self.occupancy), k.min_voxels, L.ptr(self.table), L.ptr(self.meta), L.stream())
 
     def _plan(self, vol):
         """box -> the fitted work list into ``self.table`` (csrc/window_fit.hip); no host read."""
@@ -466,8 +463,8 @@ class SlidingWindowPredictor:
         foreground_box(src, k.channel, k.threshold, out=self.box)
         step, margin, codes = self._fit_args
         L.call("mivp_window_fit_plan", L.ptr(self.box), a["dims"], a["pad"], a["pdims"], a["roi"], step, margin, codes,
-               C.c_int32(self.n_flips), L.ptr(self.table), C.c_int32(self.table.shape[0]), L.ptr(self.fit_origins),
-               C.c_int32(self.n_windows), L.ptr(self.meta), L.stream())
+               self.n_flips, L.ptr(self.table), self.table.shape[0], L.ptr(self.fit_origins), self.n_windows, L.ptr(self.meta),
+               L.stream())
 
     def _kept(self) -> int:
         """The one host read of a skipping or fitting run: (windows, entries) of the volume's work list -> the number of
@@ -481,8 +478,8 @@ class SlidingWindowPredictor:
 
     def _fill(self):
         k = self._rule
-        L.call("mivp_stitch_fill", L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), self._a["pdims"],
-               C.c_int32(k.fill_class), C.c_float(k.fill_logit), L.stream())
+        L.call("mivp_stitch_fill", L.ptr(self.acc), L.ptr(self.wsum), self.ncls, self._a["pdims"], k.fill_class, k.fill_logit,
+               L.stream())
 
     def _record(self):
         """Warm up two sub-batches eagerly on a side stream, then record one sub-batch step."""
@@ -552,12 +549,13 @@ class SlidingWindowPredictor:
         # the post-processing rewrites the labels in place; its filter pass, not the finalize, counts them against seg
         f_tgt, f_counts = (tgt, counts) if post is None else (None, None)
         # a call that asks for no maps keeps the plain finalize; the probability one takes the three maps in the middle
-        name, map_ptrs = "mivp_stitch_finalize", ()
         if extra:
-            name = "mivp_stitch_finalize_probs"
-            map_ptrs = tuple(L.ptr(extra.get(k)) for k in ("probs", "confidence", "entropy"))
-        L.call(name, L.ptr(self.acc), L.ptr(self.wsum), C.c_int32(self.ncls), a["dims"], a["pad"], a["pdims"],
-               L.ptr(labels), L.ptr(logits), *map_ptrs, L.ptr(f_tgt), L.ptr(f_counts), L.stream())
+            L.call("mivp_stitch_finalize_probs", L.ptr(self.acc), L.ptr(self.wsum), self.ncls, a["dims"], a["pad"], a["pdims"],
+                   L.ptr(labels), L.ptr(logits), L.ptr(extra.get("probs")), L.ptr(extra.get("confidence")),
+                   L.ptr(extra.get("entropy")), L.ptr(f_tgt), L.ptr(f_counts), L.stream())
+        else:
+            L.call("mivp_stitch_finalize", L.ptr(self.acc), L.ptr(self.wsum), self.ncls, a["dims"], a["pad"], a["pdims"],
+                   L.ptr(labels), L.ptr(logits), L.ptr(f_tgt), L.ptr(f_counts), L.stream())
         if post is not None:
             from . import components
             lab = labels[0, 0]

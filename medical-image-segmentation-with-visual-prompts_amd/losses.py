@@ -147,8 +147,7 @@ class _SamplePointsFn(torch.autograd.Function):
         od = (C.c_int32 * 3)(*[int(v) for v in out_dims])
         N = int(out_dims[0]) * int(out_dims[1]) * int(out_dims[2])
         out = torch.empty((B, N, Cc), dtype=torch.float32, device=vol.device)
-        L.call("mivp_sample_points_fwd", L.ptr(src), C.c_int32(1 if src.dtype == torch.bfloat16 else 0), C.c_int32(clast),
-               C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(D), C.c_int32(Cc), od,
+        L.call("mivp_sample_points_fwd", L.ptr(src), 1 if src.dtype == torch.bfloat16 else 0, clast, B, H, W, D, Cc, od,
                _ptr3([t[0] for t in tabs], C.c_int32), _ptr3([t[1] for t in tabs], C.c_int32),
                _ptr3([t[2] for t in tabs], C.c_float), L.ptr(out), L.stream())
         ctx.tabs = tabs
@@ -163,8 +162,8 @@ class _SamplePointsFn(torch.autograd.Function):
             raise NotImplementedError("sample_points backward needs a channel count that is a multiple of 8")
         g = torch.empty((B, H, W, D, Cc), dtype=torch.bfloat16, device=gout.device)
         od = (C.c_int32 * 3)(*out_dims)
-        L.call("mivp_sample_points_bwd", L.ptr(gout.contiguous().float()), C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(D),
-               C.c_int32(Cc), od, _ptr3([t[3] for t in tabs], C.c_int32), _ptr3([t[5] for t in tabs], C.c_int32),
+        L.call("mivp_sample_points_bwd", L.ptr(gout.contiguous().float()), B, H, W, D, Cc, od,
+               _ptr3([t[3] for t in tabs], C.c_int32), _ptr3([t[5] for t in tabs], C.c_int32),
                _ptr3([t[4] for t in tabs], C.c_float), _ptr3([t[6] for t in tabs], C.c_float), L.ptr(g), L.stream())
         g = g.permute(0, 4, 1, 2, 3)                            # channels-first view, like the forward's input
         return (g if dtype == torch.bfloat16 else g.float()), None, None, None

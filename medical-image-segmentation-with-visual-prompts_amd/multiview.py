@@ -153,8 +153,8 @@ def make_views(x: torch.Tensor, slot: ViewSlot):
     _check_input(x, slot)
     xi, xj = torch.empty_like(x), torch.empty_like(x)
     xk = torch.empty_like(x) if slot.mutual else None
-    L.call("mivp_mv_views", L.ptr(x), C.c_int32(x.shape[0]), C.c_int32(x.shape[1]), slot._dims, slot._mshape,
-           L.ptr(slot.codes), L.ptr(slot.keep), L.ptr(slot.perm), L.ptr(xi), L.ptr(xj), L.ptr(xk), L.stream())
+    L.call("mivp_mv_views", L.ptr(x), x.shape[0], x.shape[1], slot._dims, slot._mshape, L.ptr(slot.codes), L.ptr(slot.keep),
+           L.ptr(slot.perm), L.ptr(xi), L.ptr(xj), L.ptr(xk), L.stream())
     return xi, xj, xk
 
 
@@ -178,19 +178,17 @@ class _MultiViewLossFn(torch.autograd.Function):
         if has_rec and (do_rec or rec_k is not None):
             ws = torch.empty(L.lib().mivp_mv_rec_ws(), dtype=torch.float32, device=dev)
             L.call("mivp_mv_rec_loss", L.ptr(rec_i), L.ptr(rec_j if do_rec else None), L.ptr(x_i if do_rec else None),
-                   L.ptr(x_j if do_rec else None), L.ptr(rec_k), C.c_int32(slot.B), C.c_int32(rec_i.shape[1]), slot._dims,
-                   slot._mshape, L.ptr(slot.keep), L.ptr(slot.perm), C.c_int32(int(do_rec)), C.c_float(slot.ratio),
-                   L.ptr(ws), L.ptr(vec), L.stream())
+                   L.ptr(x_j if do_rec else None), L.ptr(rec_k), slot.B, rec_i.shape[1], slot._dims, slot._mshape,
+                   L.ptr(slot.keep), L.ptr(slot.perm), int(do_rec), slot.ratio, L.ptr(ws), L.ptr(vec), L.stream())
             has_recmut = 1
         else:
             has_recmut = 0
         dim = z_i.shape[1] if z_i is not None else 0
-        hws = torch.empty(max(1, L.lib().mivp_mv_heads_ws(C.c_int32(slot.B), C.c_int32(max(dim, 1)))), dtype=torch.float32,
+        hws = torch.empty(max(1, L.lib().mivp_mv_heads_ws(slot.B, max(dim, 1))), dtype=torch.float32,
                           device=dev)
-        L.call("mivp_mv_heads", L.ptr(z_i), L.ptr(z_j), C.c_int32(slot.B), C.c_int32(dim), C.c_float(temp), L.ptr(rot_i),
-               L.ptr(rot_j), L.ptr(slot.codes), C.c_float(w["rec"]), C.c_float(w["rot"]), C.c_float(w["con"]),
-               C.c_int32(has_recmut), L.ptr(hws), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(vec),
-               L.stream())
+        L.call("mivp_mv_heads", L.ptr(z_i), L.ptr(z_j), slot.B, dim, temp, L.ptr(rot_i), L.ptr(rot_j), L.ptr(slot.codes),
+               w["rec"], w["rot"], w["con"], has_recmut, L.ptr(hws), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(None),
+               L.ptr(None), L.ptr(vec), L.stream())
         ctx.save_for_backward(rec_i, rec_j, rec_k, rot_i, rot_j, z_i, z_j, x_i, x_j, hws)
         ctx.slot, ctx.w, ctx.temp, ctx.do_rec = slot, w, temp, do_rec
         ctx.mark_non_differentiable(vec)
@@ -208,19 +206,18 @@ class _MultiViewLossFn(torch.autograd.Function):
             d[1] = torch.empty_like(rec_j) if ctx.do_rec else None
             d[2] = torch.empty_like(rec_k) if rec_k is not None else None
             L.call("mivp_mv_rec_grad", L.ptr(rec_i), L.ptr(rec_j if ctx.do_rec else None), L.ptr(x_i if ctx.do_rec else None),
-                   L.ptr(x_j if ctx.do_rec else None), L.ptr(rec_k), C.c_int32(slot.B), C.c_int32(rec_i.shape[1]),
-                   slot._dims, slot._mshape, L.ptr(slot.keep), L.ptr(slot.perm), C.c_int32(int(ctx.do_rec)),
-                   C.c_float(slot.ratio), C.c_float(w["rec"]), L.ptr(g), L.ptr(d[0]), L.ptr(d[1]), L.ptr(d[2]), L.stream())
+                   L.ptr(x_j if ctx.do_rec else None), L.ptr(rec_k), slot.B, rec_i.shape[1], slot._dims, slot._mshape,
+                   L.ptr(slot.keep), L.ptr(slot.perm), int(ctx.do_rec), slot.ratio, w["rec"], L.ptr(g), L.ptr(d[0]),
+                   L.ptr(d[1]), L.ptr(d[2]), L.stream())
         if z_i is not None or rot_i is not None:
             if rot_i is not None:
                 d[3], d[4] = torch.empty_like(rot_i), torch.empty_like(rot_j)
             if z_i is not None:
                 d[5], d[6] = torch.empty_like(z_i), torch.empty_like(z_j)
             dim = z_i.shape[1] if z_i is not None else 0
-            L.call("mivp_mv_heads", L.ptr(z_i), L.ptr(z_j), C.c_int32(slot.B), C.c_int32(dim), C.c_float(ctx.temp),
-                   L.ptr(rot_i), L.ptr(rot_j), L.ptr(slot.codes), C.c_float(w["rec"]), C.c_float(w["rot"]),
-                   C.c_float(w["con"]), C.c_int32(0), L.ptr(hws), L.ptr(g), L.ptr(d[5]), L.ptr(d[6]), L.ptr(d[3]),
-                   L.ptr(d[4]), L.ptr(None), L.stream())
+            L.call("mivp_mv_heads", L.ptr(z_i), L.ptr(z_j), slot.B, dim, ctx.temp, L.ptr(rot_i), L.ptr(rot_j),
+                   L.ptr(slot.codes), w["rec"], w["rot"], w["con"], 0, L.ptr(hws), L.ptr(g), L.ptr(d[5]), L.ptr(d[6]),
+                   L.ptr(d[3]), L.ptr(d[4]), L.ptr(None), L.stream())
         return (*d, None, None, None, None, None)
 
 
@@ -282,10 +279,9 @@ class _ContrastiveFn(torch.autograd.Function):
     def forward(ctx, z_i, z_j, temp):
         B, dim = z_i.shape
         vec = torch.zeros(5, dtype=torch.float32, device=z_i.device)
-        ws = torch.empty(L.lib().mivp_mv_heads_ws(C.c_int32(B), C.c_int32(dim)), dtype=torch.float32, device=z_i.device)
-        L.call("mivp_mv_heads", L.ptr(z_i), L.ptr(z_j), C.c_int32(B), C.c_int32(dim), C.c_float(temp), L.ptr(None),
-               L.ptr(None), L.ptr(None), C.c_float(0.0), C.c_float(0.0), C.c_float(1.0), C.c_int32(0), L.ptr(ws), L.ptr(None),
-               L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(vec), L.stream())
+        ws = torch.empty(L.lib().mivp_mv_heads_ws(B, dim), dtype=torch.float32, device=z_i.device)
+        L.call("mivp_mv_heads", L.ptr(z_i), L.ptr(z_j), B, dim, temp, L.ptr(None), L.ptr(None), L.ptr(None), 0.0, 0.0, 1.0, 0,
+               L.ptr(ws), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(vec), L.stream())
         ctx.save_for_backward(z_i, z_j, ws)
         ctx.temp = temp
         return vec[2]
@@ -296,9 +292,8 @@ class _ContrastiveFn(torch.autograd.Function):
         B, dim = z_i.shape
         g = g.detach().to(torch.float32).reshape(1).contiguous()
         dzi, dzj = torch.empty_like(z_i), torch.empty_like(z_j)
-        L.call("mivp_mv_heads", L.ptr(z_i), L.ptr(z_j), C.c_int32(B), C.c_int32(dim), C.c_float(ctx.temp), L.ptr(None),
-               L.ptr(None), L.ptr(None), C.c_float(0.0), C.c_float(0.0), C.c_float(1.0), C.c_int32(0), L.ptr(ws), L.ptr(g),
-               L.ptr(dzi), L.ptr(dzj), L.ptr(None), L.ptr(None), L.ptr(None), L.stream())
+        L.call("mivp_mv_heads", L.ptr(z_i), L.ptr(z_j), B, dim, ctx.temp, L.ptr(None), L.ptr(None), L.ptr(None), 0.0, 0.0, 1.0,
+               0, L.ptr(ws), L.ptr(g), L.ptr(dzi), L.ptr(dzj), L.ptr(None), L.ptr(None), L.ptr(None), L.stream())
         return dzi, dzj, None
 
 

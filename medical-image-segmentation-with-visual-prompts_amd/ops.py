@@ -4,12 +4,14 @@ Everything here is plumbing: shape bookkeeping, buffer allocation through torch,
 weight re-layout (done once per weight version), one HIP launch per op.
 """
 import ctypes as C
+import math
 from typing import Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib as L
 from .geometry import round_up
+from .swin_ops import _colsum_bf16, ln_wgrad          # (swin_ops imports this module inside its functions only)
 
 BF16 = torch.bfloat16
 
@@ -18,7 +20,6 @@ def _nblk(items: int, groups: int, cap: int = 1024) -> int:
     """Number of 256-thread blocks for a grid-stride kernel whose threads keep a fixed
     channel group: (nblk*256) % groups == 0."""
     want = max(1, min(cap, (items + 255) // 256))
-    import math
     step = groups // math.gcd(groups, 256)
     return max(step, (want // step) * step)
 
@@ -140,13 +141,13 @@ def conv3d(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], cout
         # large volume, few output channels: the halo-brick kernel (each input voxel fetched once per workgroup)
         y = torch.empty((B, H, W, D, cout), dtype=BF16, device=x.device)
         L.call("mivp_conv3d_halo_fwd", C.byref(d), L.ptr(x), L.ptr(halo_pack(wp, cin, cout)), L.ptr(bias), L.ptr(scale),
-               L.ptr(shift), L.ptr(residual), L.ptr(y), C.c_int32(bw), L.stream())
+               L.ptr(shift), L.ptr(residual), L.ptr(y), bw, L.stream())
         return y
     y = torch.empty((B, H, W, D, cout), dtype=torch.float32 if out_f32 else BF16, device=x.device)
     ws_bytes = L.lib().mivp_conv3d_fwd_ws(C.byref(d))
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
-    L.call("mivp_conv3d_fwd", C.byref(d), L.ptr(x), L.ptr(wp), L.ptr(bias), L.ptr(scale), L.ptr(shift),
-           L.ptr(residual), L.ptr(y), L.ptr(ws), C.c_size_t(ws_bytes), L.stream())
+    L.call("mivp_conv3d_fwd", C.byref(d), L.ptr(x), L.ptr(wp), L.ptr(bias), L.ptr(scale), L.ptr(shift), L.ptr(residual),
+           L.ptr(y), L.ptr(ws), ws_bytes, L.stream())
     return y
 
 
@@ -178,10 +179,9 @@ def uphead_batch_stats(x, weight, bias, eps, running_mean=None, running_var=None
     ``keep_gx`` appends gx f32 [B,h,w,d,C] = U^T U x (the pass forms it anyway; uphead_dx reads it back)."""
     B, h, w, d, Cc = x.shape
     gx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if keep_gx else None
-    nblk = L.lib().mivp_uphead_nblk(C.c_int32(B), C.c_int32(h), C.c_int32(w), C.c_int32(d), C.c_int32(Cc))
+    nblk = L.lib().mivp_uphead_nblk(B, h, w, d, Cc)
     part = torch.empty((nblk, 2 * Cc), dtype=torch.float32, device=x.device)
-    L.call("mivp_uphead_stats", L.ptr(x), C.c_int32(B), C.c_int32(h), C.c_int32(w), C.c_int32(d), C.c_int32(Cc), L.ptr(part),
-           L.ptr(gx), L.stream())
+    L.call("mivp_uphead_stats", L.ptr(x), B, h, w, d, Cc, L.ptr(part), L.ptr(gx), L.stream())
     out = bn_finalize(part, nblk, Cc, 8 * B * h * w * d, weight, bias, eps, running_mean, running_var, momentum)
     return (*out, gx) if keep_gx else out
 
@@ -191,19 +191,19 @@ def uphead_fold(conv_w, scale, shift):
     (w*scale | sum_c w*shift | 0)."""
     cout, cin = conv_w.shape[0], conv_w.shape[1]
     wf = torch.empty((2, round_up(27 * cout, 16), 64), dtype=BF16, device=conv_w.device)
-    L.call("mivp_uphead_fold", L.ptr(conv_w.detach().float().contiguous()), L.ptr(scale), L.ptr(shift), C.c_int32(cout),
-           C.c_int32(cin), L.ptr(wf), L.stream())
+    L.call("mivp_uphead_fold", L.ptr(conv_w.detach().float().contiguous()), L.ptr(scale), L.ptr(shift), cout, cin, L.ptr(wf),
+           L.stream())
     return wf
 
 
 def uphead_forward(x, wf, conv_b, cout):
     """f32 logits [B,2h,2w,2d,cout] = bias + conv3x3x3(BN-affine(upsample_x2(x))) from the low-res x."""
     B, h, w, d, Cc = x.shape
-    ws_bytes = L.lib().mivp_uphead_fwd_ws(C.c_int32(B), C.c_int32(h), C.c_int32(w), C.c_int32(d), C.c_int32(cout))
+    ws_bytes = L.lib().mivp_uphead_fwd_ws(B, h, w, d, cout)
     ws = torch.empty(ws_bytes // 2, dtype=torch.float16, device=x.device)
     y = torch.empty((B, 2 * h, 2 * w, 2 * d, cout), dtype=torch.float32, device=x.device)
-    L.call("mivp_uphead_fwd", L.ptr(x), L.ptr(wf), L.ptr(conv_b.detach().float().contiguous()), C.c_int32(B), C.c_int32(h),
-           C.c_int32(w), C.c_int32(d), C.c_int32(Cc), C.c_int32(cout), L.ptr(ws), L.ptr(y), L.stream())
+    L.call("mivp_uphead_fwd", L.ptr(x), L.ptr(wf), L.ptr(conv_b.detach().float().contiguous()), B, h, w, d, Cc, cout, L.ptr(ws),
+           L.ptr(y), L.stream())
     return y
 
 
@@ -211,14 +211,12 @@ def uphead_gs(x, dy, cout, keep_d=False, raw=False):
     """(G, S) of the head as conv3d_wgrad_rows defines them, from the low-res x and dy [B,2h,2w,2d,cout] f32:
     G[co, tap, c] = sum_u dy[u - tap][co] * upsample(x)[u][c],  S[co, tap] = sum_{u in bounds} dy[u - tap][co].
     ``keep_d`` also returns the adjoint tensor D [T, 64] (for uphead_dx)."""
-    from .swin_ops import _colsum_bf16
     B, h, w, d, Cc = x.shape
     T = B * h * w * d
     ld = 64 if keep_d else round_up(27 * cout, 8)
     dy = dy.contiguous().float()
     D = torch.empty((T, ld), dtype=BF16, device=x.device)
-    L.call("mivp_uphead_adjoint", L.ptr(dy), C.c_int32(dy.shape[-1]), C.c_int32(B), C.c_int32(h), C.c_int32(w), C.c_int32(d),
-           C.c_int32(cout), L.ptr(D), C.c_int32(ld), L.stream())
+    L.call("mivp_uphead_adjoint", L.ptr(dy), dy.shape[-1], B, h, w, d, cout, L.ptr(D), ld, L.stream())
     G = gemm_tn(D, operand_rows(ld), x, operand_rows(Cc), T, 27 * cout, Cc)                 # [tap*cout + co][c]
     S = _colsum_bf16(D)
     if raw:                                                   # tap-major, as produced: for head_grads_fused
@@ -236,9 +234,9 @@ def head_grads_fused(G, S, conv_w, scale, shift, mean_rstd):
     db = torch.empty(cout, dtype=torch.float32, device=dev)
     dgamma = torch.empty(cin, dtype=torch.float32, device=dev)
     dbeta = torch.empty(cin, dtype=torch.float32, device=dev)
-    L.call("mivp_head_grads", L.ptr(G), C.c_int64(G.shape[1]), C.c_int64(cout * G.shape[1]), L.ptr(S), C.c_int64(1),
-           C.c_int64(cout), L.ptr(conv_w.detach().float().contiguous()), L.ptr(scale), L.ptr(shift), L.ptr(mean_rstd),
-           C.c_int32(cout), C.c_int32(cin), L.ptr(dW), L.ptr(db), L.ptr(dgamma), L.ptr(dbeta), L.stream())
+    L.call("mivp_head_grads", L.ptr(G), G.shape[1], cout * G.shape[1], L.ptr(S), 1, cout,
+           L.ptr(conv_w.detach().float().contiguous()), L.ptr(scale), L.ptr(shift), L.ptr(mean_rstd), cout, cin, L.ptr(dW),
+           L.ptr(db), L.ptr(dgamma), L.ptr(dbeta), L.stream())
     return dW, db, dgamma, dbeta
 
 
@@ -250,11 +248,10 @@ def uphead_dx(x, D, conv_w, scale, mean_rstd, dgamma, dbeta, training, gx=None):
     wc = torch.empty((round_up(Cc, 16), 64), dtype=BF16, device=x.device)
     coef = torch.empty((4, Cc), dtype=torch.float32, device=x.device)
     L.call("mivp_uphead_dx_prep", L.ptr(conv_w.detach().float().contiguous()), L.ptr(scale), L.ptr(mean_rstd),
-           L.ptr(dgamma if training else None), L.ptr(dbeta if training else None), C.c_double(8.0 * B * h * w * d),
-           C.c_int32(1 if training else 0), C.c_int32(cout), C.c_int32(Cc), L.ptr(wc), L.ptr(coef), L.stream())
+           L.ptr(dgamma if training else None), L.ptr(dbeta if training else None), 8.0 * B * h * w * d, 1 if training else 0,
+           cout, Cc, L.ptr(wc), L.ptr(coef), L.stream())
     dx = torch.empty_like(x)
-    L.call("mivp_uphead_dx", L.ptr(D), L.ptr(wc), L.ptr(x), L.ptr(coef), L.ptr(gx), C.c_int32(B), C.c_int32(h),
-           C.c_int32(w), C.c_int32(d), C.c_int32(Cc), L.ptr(dx), L.stream())
+    L.call("mivp_uphead_dx", L.ptr(D), L.ptr(wc), L.ptr(x), L.ptr(coef), L.ptr(gx), B, h, w, d, Cc, L.ptr(dx), L.stream())
     return dx
 
 
@@ -265,8 +262,8 @@ def conv3d_wgrad_small(x, scale, shift, lrelu, dy, cout):
     ws = L.lib().mivp_conv3d_wgrad_small_ws(C.byref(d))
     part = torch.empty(ws, dtype=torch.float32, device=x.device)
     out = torch.empty(cout * 27 * cin + cout, dtype=torch.float32, device=x.device)
-    L.call("mivp_conv3d_wgrad_small", C.byref(d), L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(dy),
-           C.c_int32(dy.shape[-1]), L.ptr(part), L.ptr(out), L.stream())
+    L.call("mivp_conv3d_wgrad_small", C.byref(d), L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(dy), dy.shape[-1], L.ptr(part),
+           L.ptr(out), L.stream())
     dw = out[:cout * 27 * cin].reshape(cout, 3, 3, 3, cin).permute(0, 4, 1, 2, 3).contiguous()
     return dw, out[cout * 27 * cin:].clone()
 
@@ -292,7 +289,7 @@ def conv3d_wgrad_rows(x, dy, cout):
         raise RuntimeError("conv3d_wgrad_rows: shape not supported (needs Cout <= 8, Cin % 8 == 0, Cin < 64)")
     part = torch.empty(ws, dtype=torch.float32, device=x.device)
     gs = torch.empty((3, 80, 64), dtype=torch.float32, device=x.device)
-    L.call("mivp_conv3d_wgrad_rows", C.byref(d), L.ptr(x), L.ptr(dy), C.c_int32(8), L.ptr(part), L.ptr(gs), L.stream())
+    L.call("mivp_conv3d_wgrad_rows", C.byref(d), L.ptr(x), L.ptr(dy), 8, L.ptr(part), L.ptr(gs), L.stream())
     # gs[sd][nb*8 + co][c]  ->  [co][tap = nb*3 + sd][c]
     full = gs[:, :72].reshape(3, 9, 8, 64).permute(2, 1, 0, 3).reshape(8, 27, 64)
     return full[:cout, :, :cin], full[:cout, :, cin]
@@ -320,9 +317,8 @@ def bn_finalize(part, nblk, Cc, count, weight, bias, eps, running_mean, running_
     scale = torch.empty(Cc, dtype=torch.float32, device=dev)
     shift = torch.empty_like(scale)
     mean_rstd = torch.empty(2 * Cc, dtype=torch.float32, device=dev)
-    L.call("mivp_bn_finalize", L.ptr(part), C.c_int32(nblk), C.c_int32(Cc), C.c_double(float(count)), L.ptr(weight),
-           L.ptr(bias), C.c_float(eps), C.c_float(momentum), L.ptr(running_mean), L.ptr(running_var), L.ptr(scale),
-           L.ptr(shift), L.ptr(mean_rstd), L.stream())
+    L.call("mivp_bn_finalize", L.ptr(part), nblk, Cc, float(count), L.ptr(weight), L.ptr(bias), eps, momentum,
+           L.ptr(running_mean), L.ptr(running_var), L.ptr(scale), L.ptr(shift), L.ptr(mean_rstd), L.stream())
     return scale, shift, mean_rstd
 
 
@@ -333,7 +329,7 @@ def bn_partial_sums(x):
     n_vox = x.numel() // Cc
     nblk = _nblk(n_vox * (Cc // 8), Cc // 8)
     part = torch.empty((nblk, 2 * Cc), dtype=torch.float32, device=x.device)
-    L.call("mivp_bn_stats", L.ptr(x), C.c_int64(n_vox), C.c_int32(Cc), C.c_int32(nblk), L.ptr(part), L.stream())
+    L.call("mivp_bn_stats", L.ptr(x), n_vox, Cc, nblk, L.ptr(part), L.stream())
     return part, nblk, n_vox
 
 
@@ -354,8 +350,8 @@ def bn_eval_affine(weight, bias, running_mean, running_var, eps):
 def affine_act(x, scale, shift, lrelu=False):
     y = torch.empty_like(x)
     Cc = x.shape[-1]
-    L.call("mivp_affine_act", L.ptr(x), C.c_int64(x.numel() // Cc), C.c_int32(Cc), L.ptr(scale), L.ptr(shift),
-           C.c_int32(1 if lrelu else 0), L.ptr(y), L.stream())
+    L.call("mivp_affine_act", L.ptr(x), x.numel() // Cc, Cc, L.ptr(scale), L.ptr(shift), 1 if lrelu else 0, L.ptr(y),
+           L.stream())
     return y
 
 
@@ -365,13 +361,13 @@ def bn_backward(x, dy, scale, shift, mean_rstd, lrelu):
     n_vox = x.numel() // Cc
     nblk = _nblk(n_vox * (Cc // 8), Cc // 8)
     part = torch.empty((nblk, 2 * Cc), dtype=torch.float32, device=x.device)
-    L.call("mivp_bn_bwd_stats", L.ptr(x), L.ptr(dy), C.c_int64(n_vox), C.c_int32(Cc), L.ptr(scale), L.ptr(shift),
-           L.ptr(mean_rstd), C.c_int32(1 if lrelu else 0), C.c_int32(nblk), L.ptr(part), L.stream())
+    L.call("mivp_bn_bwd_stats", L.ptr(x), L.ptr(dy), n_vox, Cc, L.ptr(scale), L.ptr(shift), L.ptr(mean_rstd), 1 if lrelu else 0,
+           nblk, L.ptr(part), L.stream())
     sums = torch.empty(2 * Cc, dtype=torch.float32, device=x.device)
-    L.call("mivp_reduce_rows", L.ptr(part), C.c_int64(nblk), C.c_int64(2 * Cc), L.ptr(sums), L.stream())
+    L.call("mivp_reduce_rows", L.ptr(part), nblk, 2 * Cc, L.ptr(sums), L.stream())
     dx = torch.empty_like(x)
-    L.call("mivp_bn_bwd_apply", L.ptr(x), L.ptr(dy), C.c_int64(n_vox), C.c_int32(Cc), L.ptr(scale), L.ptr(shift),
-           L.ptr(mean_rstd), L.ptr(sums), C.c_int32(1 if lrelu else 0), L.ptr(dx), L.stream())
+    L.call("mivp_bn_bwd_apply", L.ptr(x), L.ptr(dy), n_vox, Cc, L.ptr(scale), L.ptr(shift), L.ptr(mean_rstd), L.ptr(sums),
+           1 if lrelu else 0, L.ptr(dx), L.stream())
     return dx, sums[Cc:], sums[:Cc]
 
 
@@ -381,14 +377,14 @@ def bn_backward_eval(x, dy, scale, shift, mean_rstd, lrelu):
     n_vox = x.numel() // Cc
     nblk = _nblk(n_vox * (Cc // 8), Cc // 8)
     part = torch.empty((nblk, 2 * Cc), dtype=torch.float32, device=x.device)
-    L.call("mivp_bn_bwd_stats", L.ptr(x), L.ptr(dy), C.c_int64(n_vox), C.c_int32(Cc), L.ptr(scale), L.ptr(shift),
-           L.ptr(mean_rstd), C.c_int32(1 if lrelu else 0), C.c_int32(nblk), L.ptr(part), L.stream())
+    L.call("mivp_bn_bwd_stats", L.ptr(x), L.ptr(dy), n_vox, Cc, L.ptr(scale), L.ptr(shift), L.ptr(mean_rstd), 1 if lrelu else 0,
+           nblk, L.ptr(part), L.stream())
     sums = torch.empty(2 * Cc, dtype=torch.float32, device=x.device)
-    L.call("mivp_reduce_rows", L.ptr(part), C.c_int64(nblk), C.c_int64(2 * Cc), L.ptr(sums), L.stream())
+    L.call("mivp_reduce_rows", L.ptr(part), nblk, 2 * Cc, L.ptr(sums), L.stream())
     zeros = torch.zeros_like(sums)
     dx = torch.empty_like(x)
-    L.call("mivp_bn_bwd_apply", L.ptr(x), L.ptr(dy), C.c_int64(n_vox), C.c_int32(Cc), L.ptr(scale), L.ptr(shift),
-           L.ptr(mean_rstd), L.ptr(zeros), C.c_int32(1 if lrelu else 0), L.ptr(dx), L.stream())
+    L.call("mivp_bn_bwd_apply", L.ptr(x), L.ptr(dy), n_vox, Cc, L.ptr(scale), L.ptr(shift), L.ptr(mean_rstd), L.ptr(zeros),
+           1 if lrelu else 0, L.ptr(dx), L.stream())
     return dx, sums[Cc:], sums[:Cc]
 
 
@@ -412,14 +408,14 @@ def patch_embed(x, w, bias, bn_w, bn_b, eps, running_mean, running_var, training
     st = L.stream()
     if training:
         part = torch.empty((d.nblk, 2 * Cc), dtype=torch.float32, device=x.device)
-        L.call("mivp_patch_embed", C.byref(d), C.c_int(0), L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(None), L.ptr(None),
-               L.ptr(part), L.ptr(None), st)
+        L.call("mivp_patch_embed", C.byref(d), 0, L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(None), L.ptr(None), L.ptr(part),
+               L.ptr(None), st)
         scale, shift, mean_rstd = bn_finalize(part, d.nblk, Cc, n_out, bn_w, bn_b, eps, running_mean, running_var, momentum)
     else:
         scale, shift, mean_rstd = bn_eval_affine(bn_w, bn_b, running_mean, running_var, eps)
     y = torch.empty((B, H // 2, W // 2, D // 2, Cc), dtype=BF16, device=x.device)
-    L.call("mivp_patch_embed", C.byref(d), C.c_int(1), L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(scale), L.ptr(shift),
-           L.ptr(None), L.ptr(y), st)
+    L.call("mivp_patch_embed", C.byref(d), 1, L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(scale), L.ptr(shift), L.ptr(None),
+           L.ptr(y), st)
     if return_stats:
         return y, (scale, shift, mean_rstd)
     return y
@@ -444,13 +440,12 @@ def patch_embed_backward(x, w, bias, dy, stats, training=True):
     st = L.stream()
     z = torch.empty((B, H // 2, W // 2, D // 2, Cc), dtype=BF16, device=x.device)
     one = torch.ones(Cc, dtype=torch.float32, device=x.device)
-    L.call("mivp_patch_embed", C.byref(d), C.c_int(1), L.ptr(x), L.ptr(wf), L.ptr(bf), L.ptr(one), L.ptr(torch.zeros_like(one)),
+    L.call("mivp_patch_embed", C.byref(d), 1, L.ptr(x), L.ptr(wf), L.ptr(bf), L.ptr(one), L.ptr(torch.zeros_like(one)),
            L.ptr(None), L.ptr(z), st)
     dz, dgamma, dbeta = (bn_backward if training else bn_backward_eval)(z, dy.contiguous(), scale, shift, mean_rstd, False)
     patches = torch.empty((n_out, cin * 8), dtype=BF16, device=x.device)
     L.call("mivp_patch_im2col", C.byref(d), L.ptr(x), L.ptr(patches), st)
     dw = gemm_tn(dz, operand_rows(Cc), patches, operand_rows(cin * 8), n_out, Cc, cin * 8)
-    from .swin_ops import _colsum_bf16
     db = _colsum_bf16(dz.view(n_out, Cc))
     return dw.view(Cc, cin, 2, 2, 2), db, dgamma, dbeta
 
@@ -519,7 +514,7 @@ def upcat_stats(x, skip, scale: Sequence[int]):
     lines = x.shape[0] * odims[0]     # nx workgroups walk one (b, oh) line: ~1024 workgroups = one resident round (4 per CU)
     nblk = lines * max(1, min(odims[1], 1024 // lines))
     part = torch.empty((nblk, 2 * ct), dtype=torch.float32, device=x.device)
-    L.call("mivp_upcat_stats", C.byref(d), L.ptr(x), L.ptr(skip), C.c_int32(nblk), L.ptr(part), L.stream())
+    L.call("mivp_upcat_stats", C.byref(d), L.ptr(x), L.ptr(skip), nblk, L.ptr(part), L.stream())
     return part, nblk, rows * odims[2]
 
 
@@ -527,8 +522,8 @@ def upcat_affine(x, skip, scale: Sequence[int], bn_scale, bn_shift, lrelu: bool)
     """act(BatchNorm-affine(cat(upsample(x), skip))) in one pass (bit-equal to upcat + affine_act)."""
     d, odims, ct = _upcat_args(x, skip, scale)
     y = torch.empty((x.shape[0],) + odims + (ct,), dtype=BF16, device=x.device)
-    L.call("mivp_upcat_affine_fwd", C.byref(d), L.ptr(x), L.ptr(skip), L.ptr(bn_scale), L.ptr(bn_shift),
-           C.c_int32(1 if lrelu else 0), L.ptr(y), L.stream())
+    L.call("mivp_upcat_affine_fwd", C.byref(d), L.ptr(x), L.ptr(skip), L.ptr(bn_scale), L.ptr(bn_shift), 1 if lrelu else 0,
+           L.ptr(y), L.stream())
     return y
 
 
@@ -545,13 +540,13 @@ def upcat_backward(dy, idims, scale, cx, cs, need_skip=True, align_corners=False
 def cast_bf16(t: torch.Tensor) -> torch.Tensor:
     t = t.detach().float().contiguous()
     out = torch.empty(t.shape, dtype=BF16, device=t.device)
-    L.call("mivp_cast_f32_bf16", L.ptr(t), C.c_int64(t.numel()), L.ptr(out), L.stream())
+    L.call("mivp_cast_f32_bf16", L.ptr(t), t.numel(), L.ptr(out), L.stream())
     return out
 
 
 def add_bf16(a, b):
     y = torch.empty_like(a)
-    L.call("mivp_add_bf16", L.ptr(a), L.ptr(b), C.c_int64(a.numel()), L.ptr(y), L.stream())
+    L.call("mivp_add_bf16", L.ptr(a), L.ptr(b), a.numel(), L.ptr(y), L.stream())
     return y
 
 
@@ -575,7 +570,6 @@ def patch_merge_backward(dy, x, ln_w, ln_b, w_t_bf16, merge_last, need_w=False, 
            L.ptr(wbet), L.ptr(w_t_bf16), L.ptr(dx), L.ptr(wg_dn), L.ptr(wg_x), L.stream())
     if not need_w:
         return dx
-    from .swin_ops import ln_wgrad
     n, dgamma, dbeta = ln_wgrad(wg_x, wg_dn, ln_w, ln_b, float(d.ln_eps), T, kC)
     dw = gemm_tn(dy, operand_rows(cout), n, operand_rows(kC), T, cout, kC)
     return dx, dw, dgamma, dbeta
@@ -593,7 +587,6 @@ def conv3d_wgrad(x: torch.Tensor, dy: torch.Tensor, cout: int, cin: Optional[int
     if ld % 8 or cin_p % 4:
         raise RuntimeError("conv3d_wgrad: dy channels must be padded to 8, x channels to 4")
     vox = B * H * W * D
-    from .swin_ops import _colsum_bf16
     db = _colsum_bf16(dy.view(vox, ld))[:cout]
     if ld <= 16 and cin_p > ld:
         # few output channels (segmentation heads): let x supply the rows and the shifted dy the columns,
@@ -632,7 +625,7 @@ def gemm_tn(a: torch.Tensor, a_desc: L.OperandDesc, b: torch.Tensor, b_desc: L.O
     d = L.GemmTnDesc(T, M, N, a_desc, b_desc, alpha, 1 if accumulate else 0, perm_cin)
     ws_bytes = L.lib().mivp_gemm_tn_ws(C.byref(d))
     ws = torch.empty(ws_bytes // 4, device=a.device, dtype=torch.float32)
-    L.call("mivp_gemm_tn", C.byref(d), L.ptr(a), L.ptr(b), L.ptr(ws), C.c_size_t(ws_bytes), L.ptr(out), L.stream())
+    L.call("mivp_gemm_tn", C.byref(d), L.ptr(a), L.ptr(b), L.ptr(ws), ws_bytes, L.ptr(out), L.stream())
     return out
 
 
@@ -646,7 +639,7 @@ def pointwise_conv(x, w, bias):
     wf = w.detach().float().reshape(cout, Cc).contiguous()
     y = torch.empty((B, H, W, D, cout), dtype=torch.float32, device=x.device)
     L.call("mivp_pointwise_fwd", L.ptr(x), L.ptr(wf), L.ptr(None if bias is None else bias.detach().float().contiguous()),
-           C.c_int64(B * H * W * D), C.c_int32(Cc), C.c_int32(cout), L.ptr(y), L.stream())
+           B * H * W * D, Cc, cout, L.ptr(y), L.stream())
     return y
 
 
@@ -659,8 +652,7 @@ def pointwise_conv_backward(x, w, dy, need_dx=True):
     dy = dy.contiguous().float()
     dx = torch.empty_like(x)
     dyb = torch.empty((n, 4), dtype=BF16, device=x.device)
-    L.call("mivp_pointwise_bwd", L.ptr(dy), L.ptr(wf), C.c_int64(n), C.c_int32(Cc), C.c_int32(cout), L.ptr(dx), L.ptr(dyb),
-           L.stream())
+    L.call("mivp_pointwise_bwd", L.ptr(dy), L.ptr(wf), n, Cc, cout, L.ptr(dx), L.ptr(dyb), L.stream())
     dw = gemm_tn(dyb, operand_rows(4), x, operand_rows(Cc), n, cout, Cc)
     db = dy.view(n, cout).sum(0)
     return (dx if need_dx else None), dw, db
@@ -691,7 +683,6 @@ def instance_norm_act_backward(x, dy, saved, lrelu=True):
 
 def global_avg_pool(x):
     """nn.AdaptiveAvgPool3d((1,1,1)) on channels-last bf16: f32 [B, C]."""
-    from .swin_ops import _colsum_bf16
     B, Cc = x.shape[0], x.shape[-1]
     n = x.numel() // (B * Cc)
     return torch.stack([_colsum_bf16(x[b].reshape(n, Cc)) for b in range(B)]) / float(n)
@@ -713,8 +704,8 @@ def pack_convt_weight(w: torch.Tensor):
 def convt_forward(x: torch.Tensor, w1: torch.Tensor, stride, cout: int) -> torch.Tensor:
     B, h, w, d, cin = x.shape
     y = torch.empty((B, h * stride[0], w * stride[1], d * stride[2], cout), dtype=BF16, device=x.device)
-    L.call("mivp_convt_fwd", C.c_int32(B), (C.c_int32 * 3)(h, w, d), (C.c_int32 * 3)(*stride), C.c_int32(cin), C.c_int32(cout),
-           L.ptr(x), L.ptr(w1), L.ptr(y), L.stream())
+    L.call("mivp_convt_fwd", B, (C.c_int32 * 3)(h, w, d), (C.c_int32 * 3)(*stride), cin, cout, L.ptr(x), L.ptr(w1), L.ptr(y),
+           L.stream())
     return y
 
 
@@ -722,8 +713,8 @@ def convt_dgrad(dy: torch.Tensor, w2: torch.Tensor, stride, cin: int) -> torch.T
     B, H, W, D, cout = dy.shape
     h, w, d = H // stride[0], W // stride[1], D // stride[2]
     dx = torch.empty((B, h, w, d, cin), dtype=BF16, device=dy.device)
-    L.call("mivp_convt_dgrad", C.c_int32(B), (C.c_int32 * 3)(h, w, d), (C.c_int32 * 3)(*stride), C.c_int32(cin), C.c_int32(cout),
-           L.ptr(dy), L.ptr(w2), L.ptr(dx), L.stream())
+    L.call("mivp_convt_dgrad", B, (C.c_int32 * 3)(h, w, d), (C.c_int32 * 3)(*stride), cin, cout, L.ptr(dy), L.ptr(w2),
+           L.ptr(dx), L.stream())
     return dx
 
 

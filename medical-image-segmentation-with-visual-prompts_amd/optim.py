@@ -118,7 +118,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._hyper_dev is None or self._hyper_dev.device != device:
             self._hyper_dev = torch.zeros(64, dtype=torch.float32, device=device)
         flat = np.ascontiguousarray(hyper.reshape(-1))
-        L.call("mivp_store_floats", L.ptr(self._hyper_dev), flat.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(flat.size), L.stream())
+        L.call("mivp_store_floats", L.ptr(self._hyper_dev), flat.ctypes.data_as(C.POINTER(C.c_float)), flat.size, L.stream())
 
     @torch.no_grad()
     def advance(self):
@@ -177,13 +177,13 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.capturable:
             if hyper is not None:
                 self._upload(hyper, entries[0][1].device)
-            L.call("mivp_adamw_multi_dev", L.ptr(plan["tensors"]), gptr, C.c_int32(len(grads)),
-                   plan["begin"].ctypes.data_as(C.POINTER(C.c_int32)), L.ptr(self._hyper_dev),
-                   C.c_int32(len(self.param_groups)), L.ptr(plan["chunks"]), L.stream())
+            L.call("mivp_adamw_multi_dev", L.ptr(plan["tensors"]), gptr, len(grads),
+                   plan["begin"].ctypes.data_as(C.POINTER(C.c_int32)), L.ptr(self._hyper_dev), len(self.param_groups),
+                   L.ptr(plan["chunks"]), L.stream())
         else:
-            L.call("mivp_adamw_multi", L.ptr(plan["tensors"]), gptr, C.c_int32(len(grads)),
+            L.call("mivp_adamw_multi", L.ptr(plan["tensors"]), gptr, len(grads),
                    plan["begin"].ctypes.data_as(C.POINTER(C.c_int32)), hyper.ctypes.data_as(C.POINTER(C.c_float)),
-                   C.c_int32(len(self.param_groups)), L.ptr(plan["chunks"]), L.stream())
+                   len(self.param_groups), L.ptr(plan["chunks"]), L.stream())
         return loss
 
 
@@ -230,5 +230,5 @@ def ema_update_(teacher_params, student_params, tau: float, plan: EmaPlan):
         plan.tensors = torch.from_numpy(rows).to(dev)
         plan.chunks = _chunk_table([t.numel() for t, _ in pairs], dev)
         plan.key = key
-    L.call("mivp_ema_multi", L.ptr(plan.tensors), L.ptr(plan.chunks), C.c_int32(plan.chunks.shape[0]), C.c_float(tau), L.stream())
+    L.call("mivp_ema_multi", L.ptr(plan.tensors), L.ptr(plan.chunks), plan.chunks.shape[0], tau, L.stream())
     Fn.invalidate_weight_caches()                              # raw in-place writes: no version counter saw them

@@ -58,16 +58,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._lib import RegionTable as _CTable
 from ._host import (LABEL_DTYPES, check_classes, check_connectivity, check_gpu, check_min_size, check_spacing, class_mask,
                     i3, label_volume, workspace)
 
 _IMAGE_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.float32: 3, torch.int16: 4}
-
-
-class _CTable(C.Structure):
-    _fields_ = [("capacity", C.c_int32), ("image_dtype", C.c_int32)] + [
-        (k, C.c_void_p) for k in ("n", "overflow", "cls", "size", "first", "bbox", "coord_sum", "vmin", "vmax", "vsum",
-                                  "vsqsum")]
 
 
 def _check_region_args(num_classes, connectivity=26, classes: Optional[Iterable[int]] = None, max_regions=4096,
@@ -225,8 +220,8 @@ def _stats_launch(v: torch.Tensor, args, image: Optional[torch.Tensor], ws: Opti
     tab = RegionTable(dims, max_regions, spacing, v.device, None if image is None else image.dtype)
     if ws is None:
         ws = workspace("region_stats", dims, v.device)
-    L.call("mivp_region_stats", L.ptr(v), C.c_int32(LABEL_DTYPES[v.dtype]), i3(dims), C.c_int32(ncls), C.c_uint32(mask),
-           C.c_int32(conn), L.ptr(image), L.ptr(tab.labels), C.byref(tab._c), L.ptr(ws), L.stream())
+    L.call("mivp_region_stats", L.ptr(v), LABEL_DTYPES[v.dtype], i3(dims), ncls, mask, conn, L.ptr(image), L.ptr(tab.labels),
+           C.byref(tab._c), L.ptr(ws), L.stream())
     return tab
 
 
@@ -252,7 +247,7 @@ class LesionReport:
         self.pred_regions, self.target_regions = pred_regions, target_regions
         self.num_classes, self.min_size, self.iou_threshold, self.max_pairs = num_classes, min_size, iou_threshold, max_pairs
         mt, mp = target_regions.max_regions, pred_regions.max_regions
-        self.pairs = torch.empty(int(L.lib().mivp_region_overlap_ws(C.c_int64(max_pairs))) // 8, dtype=torch.int64, device=dev)
+        self.pairs = torch.empty(int(L.lib().mivp_region_overlap_ws(max_pairs)) // 8, dtype=torch.int64, device=dev)
         self.counts = torch.empty((num_classes, 4), dtype=torch.int64, device=dev)
         self.overlap = torch.empty(mt, dtype=torch.int64, device=dev)
         self.touching = torch.empty(mt, dtype=torch.int64, device=dev)
@@ -432,17 +427,16 @@ def _lesion_launch(pv: torch.Tensor, tv: torch.Tensor, rargs, largs, pred_image:
     pred = _stats_launch(pv, rargs, pred_image)
     target = _stats_launch(tv, rargs, None)
     rep = LesionReport(pred, target, ncls, min_size, thr, max_pairs)
-    L.call("mivp_region_overlap", L.ptr(pred.labels), L.ptr(target.labels), i3(pv.shape), C.byref(pred._c),
-           C.byref(target._c), C.c_int64(max_pairs), L.ptr(rep.pairs), L.stream())
-    L.call("mivp_lesion_match", C.byref(pred._c), C.byref(target._c), L.ptr(rep.pairs), C.c_int64(max_pairs),
-           C.c_int32(ncls), C.c_int64(min_size), C.c_double(thr), L.ptr(rep.counts), L.ptr(rep.overlap),
-           L.ptr(rep.touching), L.ptr(rep.best_overlap), L.ptr(rep.best_pred), L.ptr(rep.detected), L.ptr(rep.matched),
-           L.stream())
+    L.call("mivp_region_overlap", L.ptr(pred.labels), L.ptr(target.labels), i3(pv.shape), C.byref(pred._c), C.byref(target._c),
+           max_pairs, L.ptr(rep.pairs), L.stream())
+    L.call("mivp_lesion_match", C.byref(pred._c), C.byref(target._c), L.ptr(rep.pairs), max_pairs, ncls, min_size, thr,
+           L.ptr(rep.counts), L.ptr(rep.overlap), L.ptr(rep.touching), L.ptr(rep.best_overlap), L.ptr(rep.best_pred),
+           L.ptr(rep.detected), L.ptr(rep.matched), L.stream())
     if pred_image is not None:
         rep.score = torch.empty(pred.max_regions, dtype=torch.float32, device=pv.device)
         rep.best_score = torch.empty(target.max_regions, dtype=torch.float32, device=pv.device)
-        L.call("mivp_lesion_best_score", C.byref(pred._c), C.byref(target._c), L.ptr(rep.pairs), C.c_int64(max_pairs),
-               C.c_int64(min_size), C.c_double(thr), L.ptr(rep.best_score), L.ptr(rep.score), L.stream())
+        L.call("mivp_lesion_best_score", C.byref(pred._c), C.byref(target._c), L.ptr(rep.pairs), max_pairs, min_size, thr,
+               L.ptr(rep.best_score), L.ptr(rep.score), L.stream())
     return rep
 
 

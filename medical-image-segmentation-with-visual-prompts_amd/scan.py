@@ -303,13 +303,13 @@ def prepare_scan(raw: torch.Tensor, geom: ScanGeometry, a_min: Optional[float] =
     if window is not None:
         slot = scanstats.resolve_window(window, r, mask)
         dev_clip = bool(clip) if slot.mode == scanstats.MODE_PERCENTILE else True
-        L.call("mivp_scan_prepare_dev", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(r.shape[0]), i3(src), i3(dst),
-               i3(axes), L.ptr(geom.device_tables("image", r.device)), C.c_int32(int(interp)), L.ptr(slot.words),
-               C.c_int32(int(dev_clip)), C.c_int32(int(flags)), L.ptr(out), L.stream())
+        L.call("mivp_scan_prepare_dev", L.ptr(r), _DTYPES[r.dtype], r.shape[0], i3(src), i3(dst), i3(axes),
+               L.ptr(geom.device_tables("image", r.device)), int(interp), L.ptr(slot.words), int(dev_clip), int(flags),
+               L.ptr(out), L.stream())
         return out
-    L.call("mivp_scan_prepare", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(r.shape[0]), i3(src), i3(dst), i3(axes),
-           L.ptr(geom.device_tables("image", r.device)), C.c_int32(int(interp)), (C.c_float * 4)(*mp),
-           C.c_int32(int(bool(clip))), C.c_int32(int(flags)), L.ptr(out), L.stream())
+    L.call("mivp_scan_prepare", L.ptr(r), _DTYPES[r.dtype], r.shape[0], i3(src), i3(dst), i3(axes),
+           L.ptr(geom.device_tables("image", r.device)), int(interp), (C.c_float * 4)(*mp), int(bool(clip)), int(flags),
+           L.ptr(out), L.stream())
     return out
 
 
@@ -330,8 +330,8 @@ def prepare_labels(seg: torch.Tensor, geom: ScanGeometry, out: Optional[torch.Te
         out = torch.empty(shape, dtype=torch.uint8, device=s.device)
     bad = torch.zeros(1, dtype=torch.int32, device=s.device)
     src, dst, axes, _, _ = geom.tables("labels")
-    L.call("mivp_scan_prepare_labels", L.ptr(s), C.c_int32(_DTYPES[s.dtype]), i3(src), i3(dst), i3(axes),
-           L.ptr(geom.device_tables("labels", s.device)), C.c_int32(int(flags)), L.ptr(out), L.ptr(bad), L.stream())
+    L.call("mivp_scan_prepare_labels", L.ptr(s), _DTYPES[s.dtype], i3(src), i3(dst), i3(axes),
+           L.ptr(geom.device_tables("labels", s.device)), int(flags), L.ptr(out), L.ptr(bad), L.stream())
     if check and int(bad.item()) != 0:
         raise ValueError("seg holds values outside 0..255 (or non-integer values): they do not fit a uint8 label map")
     return out
@@ -352,7 +352,7 @@ def restore_labels(labels: torch.Tensor, geom: ScanGeometry, out: Optional[torch
         out = torch.empty(geom.shape, dtype=torch.uint8, device=v.device)
     src, dst, axes, _, _ = geom.tables("restore_labels")
     L.call("mivp_scan_restore_labels", L.ptr(v), i3(src), i3(dst), i3(axes),
-           L.ptr(geom.device_tables("restore_labels", v.device)), C.c_int32(int(flags)), L.ptr(out), L.stream())
+           L.ptr(geom.device_tables("restore_labels", v.device)), int(flags), L.ptr(out), L.stream())
     return out
 
 
@@ -379,9 +379,8 @@ def restore_labels_from_logits(logits: torch.Tensor, geom: ScanGeometry, out: Op
     if out is None:
         out = torch.empty(geom.shape, dtype=torch.uint8, device=v.device)
     src, dst, axes, interp, _ = geom.tables("restore_logits")
-    L.call("mivp_scan_restore_argmax", L.ptr(v), C.c_int32(v.shape[0]), i3(src), i3(dst), i3(axes),
-           L.ptr(geom.device_tables("restore_logits", v.device)), C.c_int32(int(interp)), C.c_int32(int(flags)), L.ptr(out),
-           L.stream())
+    L.call("mivp_scan_restore_argmax", L.ptr(v), v.shape[0], i3(src), i3(dst), i3(axes),
+           L.ptr(geom.device_tables("restore_logits", v.device)), int(interp), int(flags), L.ptr(out), L.stream())
     return out
 
 

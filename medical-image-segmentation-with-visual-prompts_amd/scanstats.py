@@ -38,7 +38,6 @@ Nothing here reads back to the host; ``ScanHistogram.cpu()`` and ``WindowSlot.cp
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import numbers
 from typing import Dict, List, Optional, Tuple
@@ -257,9 +256,8 @@ def scan_histogram(raw: torch.Tensor, mask: Optional[torch.Tensor] = None, above
     r = raw.contiguous()
     m = None if mask is None else mask.contiguous()
     hist = ScanHistogram(channels, r.device) if out is None else out
-    L.call("mivp_scan_hist", L.ptr(r), C.c_int32(_DTYPES[r.dtype]), C.c_int32(channels), i3(shape), L.ptr(m),
-           C.c_int32(int(above is not None)), C.c_int32(above or 0), C.c_int32(_BASE[r.dtype] if base is None else int(base)),
-           C.c_int32(int(flags)), L.ptr(hist.table), L.stream())
+    L.call("mivp_scan_hist", L.ptr(r), _DTYPES[r.dtype], channels, i3(shape), L.ptr(m), int(above is not None), above or 0,
+           _BASE[r.dtype] if base is None else int(base), int(flags), L.ptr(hist.table), L.stream())
     return hist
 
 
@@ -279,9 +277,8 @@ def window_slot(hist: ScanHistogram, spec: IntensityWindow, out: Optional[Window
         raise RuntimeError("hist must live on the GPU (no CPU fallback)")
     slot = WindowSlot(hist.channels, hist.table.device) if out is None else out
     slot.mode = spec.mode
-    L.call("mivp_scan_window_plan", L.ptr(hist.table), C.c_int32(hist.channels), C.c_int32(spec.mode),
-           C.c_double(spec.q_lo), C.c_double(spec.q_hi), C.c_double(spec.b_min), C.c_double(spec.b_max),
-           C.c_int32(int(spec.clip)), L.ptr(slot.words), L.stream())
+    L.call("mivp_scan_window_plan", L.ptr(hist.table), hist.channels, spec.mode, spec.q_lo, spec.q_hi, spec.b_min, spec.b_max,
+           int(spec.clip), L.ptr(slot.words), L.stream())
     return slot
 
 

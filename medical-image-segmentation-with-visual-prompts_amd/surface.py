@@ -43,8 +43,8 @@ def _surface_launch(pred: torch.Tensor, target, num_classes: int):
     sp = torch.empty(dims, dtype=torch.uint8, device=pred.device)
     st = torch.empty(dims, dtype=torch.uint8, device=pred.device) if target is not None else None
     counts = torch.zeros((num_classes, 2), dtype=torch.int64, device=pred.device)
-    L.call("mivp_surface_map", L.ptr(pred), L.ptr(target), C.c_int32(LABEL_DTYPES[pred.dtype]), C.c_int32(num_classes),
-           i3(dims), L.ptr(sp), L.ptr(st), L.ptr(counts), L.stream())
+    L.call("mivp_surface_map", L.ptr(pred), L.ptr(target), LABEL_DTYPES[pred.dtype], num_classes, i3(dims), L.ptr(sp),
+           L.ptr(st), L.ptr(counts), L.stream())
     return sp, st, counts
 
 
@@ -58,8 +58,7 @@ def surface_map(labels: torch.Tensor, num_classes: int) -> torch.Tensor:
 
 
 def _edt_launch(seeds: torch.Tensor, cls: int, spacing, out: torch.Tensor, ws: torch.Tensor):
-    L.call("mivp_edt_sq", L.ptr(seeds), C.c_int32(cls), i3(seeds.shape), (C.c_float * 3)(*spacing), L.ptr(out),
-           L.ptr(ws), L.stream())
+    L.call("mivp_edt_sq", L.ptr(seeds), cls, i3(seeds.shape), (C.c_float * 3)(*spacing), L.ptr(out), L.ptr(ws), L.stream())
 
 
 def distance_transform_sq(seeds: torch.Tensor, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> torch.Tensor:
@@ -111,9 +110,8 @@ def _metrics_launch(pred, target, ncls, spacing, percentile, tolerance, include_
         # direction 0: pred's surface sampled in the EDT of target's; direction 1: the other way round
         for m, (seeds, sampled) in enumerate(((st, sp), (sp, st))):
             _edt_launch(seeds, c, spacing, dist, ews)
-            L.call("mivp_surface_stats", L.ptr(sampled), C.c_int32(c), L.ptr(dist), a,
-                   C.c_void_p(counts.data_ptr() + 8 * (2 * c + m)), C.c_double(q), C.c_double(tolerance), L.ptr(sws),
-                   C.c_void_p(recs.data_ptr() + 8 * _REC * (2 * c + m)), L.stream())
+            L.call("mivp_surface_stats", L.ptr(sampled), c, L.ptr(dist), a, C.c_void_p(counts.data_ptr() + 8 * (2 * c + m)), q,
+                   tolerance, L.ptr(sws), C.c_void_p(recs.data_ptr() + 8 * _REC * (2 * c + m)), L.stream())
     return counts, recs
 
 

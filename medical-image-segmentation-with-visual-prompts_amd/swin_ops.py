@@ -58,8 +58,7 @@ def pack_weight_frags(wm: torch.Tensor, paired: bool = False, k_steps: int = 0) 
     ks = max((K + 31) // 32, k_steps)                    # k_steps: the kernel's count when it exceeds ceil(K / 32)
     src = wm.contiguous()
     out = torch.empty(((R + 15) // 16, ks, 64, 8), dtype=BF16, device=wm.device)
-    L.call("mivp_pack_weight_frags", L.ptr(src), C.c_int32(R), C.c_int32(K), C.c_int32(ks), C.c_int32(1 if paired else 0),
-           L.ptr(out), L.stream())
+    L.call("mivp_pack_weight_frags", L.ptr(src), R, K, ks, 1 if paired else 0, L.ptr(out), L.stream())
     return out
 
 
@@ -99,9 +98,9 @@ def weights_from_state(sd, prefix, heads, embed_dim, n_prompt, device, need_bwd=
     if need_bwd:                                         # k_swin_qkv_bwd<CT> walks ceil(3 * 16 CT / 32) k-steps (C = 8: two)
         w.wqkv_t, w.wmlp_t, w.wproj_t = new(ct * ((3 * 16 * ct + 31) // 32) * 512), new(img), new(two * img)
     # one launch for all of them (a step that changes every parameter rebuilt these with ~25 launches per block)
-    L.call("mivp_pack_block_weights", C.c_int32(Cc), *[L.ptr(m) for m in mats], C.c_int32(1 if two == 2 else 0),
-           L.ptr(w.wqkv), L.ptr(w.wqkv_f), L.ptr(w.wproj_f), L.ptr(w.wmlp_f), L.ptr(w.wqkv_t), L.ptr(w.wmlp_t),
-           L.ptr(w.wproj_t), L.stream())
+    wq, wk, wv, wproj, wmlp = (L.ptr(m) for m in mats)
+    L.call("mivp_pack_block_weights", Cc, wq, wk, wv, wproj, wmlp, 1 if two == 2 else 0, L.ptr(w.wqkv), L.ptr(w.wqkv_f),
+           L.ptr(w.wproj_f), L.ptr(w.wmlp_f), L.ptr(w.wqkv_t), L.ptr(w.wmlp_t), L.ptr(w.wproj_t), L.stream())
     return w
 
 
@@ -271,9 +270,9 @@ def _colsum_bf16(x2d: torch.Tensor) -> torch.Tensor:
     rows, Cc = x2d.shape
     nblk = ops._nblk(rows * (Cc // 8), Cc // 8)
     part = torch.empty((nblk, 2 * Cc), dtype=torch.float32, device=x2d.device)
-    L.call("mivp_bn_stats", L.ptr(x2d), C.c_int64(rows), C.c_int32(Cc), C.c_int32(nblk), L.ptr(part), L.stream())
+    L.call("mivp_bn_stats", L.ptr(x2d), rows, Cc, nblk, L.ptr(part), L.stream())
     sums = torch.empty(2 * Cc, dtype=torch.float32, device=x2d.device)
-    L.call("mivp_reduce_rows", L.ptr(part), C.c_int64(nblk), C.c_int64(2 * Cc), L.ptr(sums), L.stream())
+    L.call("mivp_reduce_rows", L.ptr(part), nblk, 2 * Cc, L.ptr(sums), L.stream())
     return sums[:Cc]
 
 
@@ -286,11 +285,10 @@ def ln_wgrad(x: torch.Tensor, dn: torch.Tensor, gamma: torch.Tensor, beta: torch
     n = torch.empty((T, Cc), dtype=BF16, device=dev)
     nblk = ops._nblk(T * (Cc // 8), Cc // 8)
     part = torch.empty((nblk, 2 * Cc), dtype=torch.float32, device=dev)
-    L.call("mivp_ln_wgrad", L.ptr(x), L.ptr(tok_src), L.ptr(dn), C.c_int64(T), C.c_int32(Cc), C.c_int32(Nqp), C.c_int32(P),
-           C.c_int64(vol), C.c_float(eps), L.ptr(gamma), L.ptr(beta), L.ptr(stats), L.ptr(n), C.c_int32(nblk), L.ptr(part),
-           L.stream())
+    L.call("mivp_ln_wgrad", L.ptr(x), L.ptr(tok_src), L.ptr(dn), T, Cc, Nqp, P, vol, eps, L.ptr(gamma), L.ptr(beta),
+           L.ptr(stats), L.ptr(n), nblk, L.ptr(part), L.stream())
     sums = torch.empty(2 * Cc, dtype=torch.float32, device=dev)
-    L.call("mivp_reduce_rows", L.ptr(part), C.c_int64(nblk), C.c_int64(2 * Cc), L.ptr(sums), L.stream())
+    L.call("mivp_reduce_rows", L.ptr(part), nblk, 2 * Cc, L.ptr(sums), L.stream())
     return n, sums[Cc:], sums[:Cc]
 
 
@@ -376,7 +374,7 @@ def swin_block_backward(sv: SwinSaved, w: SwinBlockWeights, prompt: Optional[tor
                    L.ptr(dkp_part), L.ptr(dvp_part), L.ptr(dtok_part), L.ptr(dka_part), st)
             if need_w:
                 dka = torch.empty((heads, d.Nkp, 32), dtype=torch.float32, device=dev)
-                L.call("mivp_reduce_rows", L.ptr(dka_part), C.c_int64(BP), C.c_int64(heads * d.Nkp * 32), L.ptr(dka), st)
+                L.call("mivp_reduce_rows", L.ptr(dka_part), BP, heads * d.Nkp * 32, L.ptr(dka), st)
                 del dka_part
                 win = [int(d.win[a]) for a in range(3)]
                 tabs = [torch.empty((heads, 2 * win[a] - 1), dtype=torch.float32, device=dev) for a in range(3)]
@@ -404,7 +402,7 @@ def swin_block_backward(sv: SwinSaved, w: SwinBlockWeights, prompt: Optional[tor
         ins = (C.c_void_p * 3)(dkp_part.data_ptr(), dvp_part.data_ptr(), dtok_part.data_ptr())
         outs = (C.c_void_p * 3)(dkp.data_ptr(), dvp.data_ptr(), dtok.data_ptr())
         nrows = (C.c_int64 * 3)(rows, rows, heads * d.Npp)
-        L.call("mivp_reduce_rows_multi", C.c_int32(3), ins, nrows, outs, C.c_int64(BP), st)     # one launch for the three
+        L.call("mivp_reduce_rows_multi", 3, ins, nrows, outs, BP, st)     # one launch for the three
         pr = prompt.detach().to(torch.float32).contiguous()
         dprompt = torch.empty_like(pr)
         wg_a = wg_n = wg_ln = None
@@ -420,8 +418,8 @@ def swin_block_backward(sv: SwinSaved, w: SwinBlockWeights, prompt: Optional[tor
             ops.gemm_tn(wg_a[0], rows, wg_n, rows, d.Np, Cc, Cc, out=wg["wk"], accumulate=True)
             ops.gemm_tn(wg_a[1], rows, wg_n, rows, d.Np, Cc, Cc, out=wg["wv"], accumulate=True)
             ln_rows = torch.empty((2, Cc), dtype=torch.float32, device=dev)
-            L.call("mivp_reduce_rows", L.ptr(wg_ln[0]), C.c_int64(d.Np), C.c_int64(Cc), L.ptr(ln_rows[0]), st)
-            L.call("mivp_reduce_rows", L.ptr(wg_ln[1]), C.c_int64(d.Np), C.c_int64(Cc), L.ptr(ln_rows[1]), st)
+            L.call("mivp_reduce_rows", L.ptr(wg_ln[0]), d.Np, Cc, L.ptr(ln_rows[0]), st)
+            L.call("mivp_reduce_rows", L.ptr(wg_ln[1]), d.Np, Cc, L.ptr(ln_rows[1]), st)
             wg["ln1_b"] = wg["ln1_b"] + ln_rows[0]
             wg["ln1_w"] = wg["ln1_w"] + ln_rows[1]
     if need_w:

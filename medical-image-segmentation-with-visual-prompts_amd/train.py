@@ -92,28 +92,26 @@ class _DiceFocalFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits_cl, target, include_background, gamma):
-        import ctypes as C
         from . import _lib as L
         B, H, W, D, Cc = logits_cl.shape
         vol = H * W * D
-        ws = torch.empty(L.lib().mivp_dice_focal_ws(C.c_int32(B), C.c_int64(vol)), dtype=torch.float32, device=logits_cl.device)
+        ws = torch.empty(L.lib().mivp_dice_focal_ws(B, vol), dtype=torch.float32, device=logits_cl.device)
         loss = torch.empty(1, dtype=torch.float32, device=logits_cl.device)
-        L.call("mivp_dice_focal", L.ptr(logits_cl), L.ptr(target), C.c_int32(B), C.c_int64(vol), C.c_int32(Cc),
-               C.c_int32(1 if include_background else 0), C.c_float(gamma), L.ptr(ws), L.ptr(loss), L.ptr(None), L.stream())
+        L.call("mivp_dice_focal", L.ptr(logits_cl), L.ptr(target), B, vol, Cc, 1 if include_background else 0, gamma, L.ptr(ws),
+               L.ptr(loss), L.ptr(None), L.stream())
         ctx.save_for_backward(logits_cl, target, ws)
         ctx.meta = (B, vol, Cc, include_background, gamma)
         return loss[0]
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes as C
         from . import _lib as L
         logits_cl, target, ws = ctx.saved_tensors
         B, vol, Cc, include_background, gamma = ctx.meta
         g = g.detach().to(torch.float32).contiguous()
         dz = torch.empty_like(logits_cl)
-        L.call("mivp_dice_focal_grad", L.ptr(logits_cl), L.ptr(target), C.c_int32(B), C.c_int64(vol), C.c_int32(Cc),
-               C.c_int32(1 if include_background else 0), C.c_float(gamma), L.ptr(ws), L.ptr(g), L.ptr(dz), L.stream())
+        L.call("mivp_dice_focal_grad", L.ptr(logits_cl), L.ptr(target), B, vol, Cc, 1 if include_background else 0, gamma,
+               L.ptr(ws), L.ptr(g), L.ptr(dz), L.stream())
         return dz, None, None, None
 
 

@@ -2,7 +2,6 @@
 ``SlidingWindowPredictor(fit=...)`` and ``foreground_box`` (csrc/window_fit.hip).  ``mivp_amd.inference`` re-exports both."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import numpy as np
@@ -68,6 +67,6 @@ def foreground_box(vol_or_mask: torch.Tensor, channel: int = 0, threshold: float
     elif not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (6,) \
             or out.device != t.device or not out.is_contiguous():
         raise ValueError("out must be a contiguous int32 [6] tensor on the input's device")
-    L.call("mivp_foreground_box", L.ptr(vol), C.c_int32(cin), C.c_int32(int(channel) if vol is not None else 0),
-           C.c_float(float(threshold) if vol is not None else 0.0), L.ptr(mask), i3(dims), L.ptr(out), L.stream())
+    L.call("mivp_foreground_box", L.ptr(vol), cin, int(channel) if vol is not None else 0,
+           float(threshold) if vol is not None else 0.0, L.ptr(mask), i3(dims), L.ptr(out), L.stream())
     return out
