@@ -973,6 +973,35 @@ int mivp_window_fit_plan(const int32_t* box, const int32_t* dims, const int32_t*
                          int32_t n_flips, int32_t* table, int32_t n_entries, int32_t* origins, int32_t n_origins,
                          int32_t* meta, mivp_stream_t stream);
 
+/* Training-batch sampling from a bank of resident scans (csrc/crops.hip; mivp_amd/batches.py).  These entry
+ * points joined the current ABI without a bump: they are additive and no earlier signature changed.  One gather kernel
+ * family (k_crop): every output voxel is written exactly once, no atomics, bitwise reproducible, no host synchronisation.
+ * Whatever selects the crops is DEVICE memory (the slot), so a launch records into a graph and a replay follows whatever
+ * the slot holds then.
+ *   slot: DEVICE int32 [B][slot_stride], one record per sample: [0] volume id, [1] rotation code -- 0 none, 1 / 2 / 3 =
+ *     rot90(k = 1) over the spatial axes (0,1) / (0,2) / (1,2) --, [2..4] the crop origin in the ROTATED frame; words 5..
+ *     are the caller's (batches.py keeps the students' origins there).  slot_stride >= 5.
+ *   roi: host int32 [3] = {h, w, d}, the output extents (each 1..65535; fewer than 2^31 voxels per output tensor).
+ *   Rule for output voxel u of sample b, with n the stored extents and n_rot the rotated ones: r = origin + u - pad_before,
+ *     pad_before = (roi - min(roi, n_rot)) / 2 per axis (the symmetric pad: the larger half comes after the crop).  r
+ *     outside the rotated volume on any axis: every output is 0.  Otherwise p = r mapped back through the rotation (for
+ *     axes (a, b): p_a = r_b, p_b = n_b - 1 - r_a) and image = vol[:, p], mask = lut[lab[p]], coord[k] = p[k] - (n[k] - 1) / 2.
+ *   mivp_crop_fill: table DEVICE int64 [n_volumes][5] = (image pointer, label pointer or 0, H, W, D); images fp32
+ *     [C][H][W][D] (C in 1..16, common to the bank), labels uint8 [H][W][D].  image fp32 [B][C][h][w][d]; mask fp32
+ *     [B][1][h][w][d] or NULL (lut: DEVICE uint8 [256], required with mask; a volume without labels gives 0); coord fp32
+ *     [B][3][h][w][d] or NULL.  A sample whose volume id is outside [0, n_volumes), whose table row is empty (image pointer
+ *     0: the table may be a fixed-capacity one that the host fills in place, so that a recorded launch sees volumes added
+ *     later) or whose code is outside 0..3 is left unwritten; any origin is safe (r is range-checked per voxel).  The host validates the draws before it uploads them.
+ *   mivp_crop_tensor: the same kernel with sample b's source being row b of src fp32 [B][Cs][sdims] (Cs in 1..16): no
+ *     rotation, no table, out fp32 [B][Cs][h][w][d]; the origin is read at slot[b * slot_stride + 0..2] (pass the slot
+ *     pointer advanced to the origin words).  The student views are this call on the teacher's image, coord and mask.
+ * Codes 0 and 1 keep D in place: rows move in 16-byte pieces (4-byte aligned) with a scalar path at the edges; codes 2
+ * and 3 exchange D with H or W and move 64 x 64 tiles through LDS so that loads and stores both run along D. */
+int mivp_crop_fill(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot, int32_t slot_stride, int32_t B,
+                   const int32_t* roi, const uint8_t* lut, float* image, float* mask, float* coord, mivp_stream_t stream);
+int mivp_crop_tensor(const float* src, int32_t Cs, const int32_t* sdims, const int32_t* slot, int32_t slot_stride,
+                     int32_t B, const int32_t* roi, float* out, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,194 @@
+#!/usr/bin/env python3
+"""Training-batch sampling throughput (mivp_amd.batches), timed on device events after a warm-up, from a bank of three
+resident 512 x 512 x 96 volumes with label maps.  Cases, each with ``random_orientation`` off and on:
+
+- ``downstream``: roi 96^3, B = 4, C = 1, image + mask (what ``train_step`` takes);
+- ``students_teacher``: roi 96^3, B = 4, students 96^3 and 72^3, coordinates and student 0's mask;
+- ``yml``: the yml's roi 128 x 128 x 8, B = 14, image + mask.
+
+Per case one JSON line: ``ms`` = one ``fill`` issued from Python with the slot as it stands, ``load_ms`` = the same with a
+new draw set checked and loaded before every call, ``graph_ms`` = the replay of ``fill`` recorded once (what a recorded
+step pays), ``eager_ms`` = the same batch from eager torch ops on the same GPU (the crop sliced in the stored frame, then
+``rot90``, ``F.pad`` and ``stack``, the label map by table indexing, the coordinates from per-crop ``meshgrid``s) after it
+was checked to be bit-equal, and per launch group the compulsory bytes -- 4 B per channel and 1 B of label read for every
+voxel inside the volume, 4 B written per output value -- over the event time of that group's calls issued back to back
+from Python (``issue_TB_per_s``).  That figure is NOT a kernel rate and NOT an HBM rate: at ~10 us per call the loop can be
+bound by the host's issue, and every call re-reads the same crops and rewrites the same outputs, which fit the Infinity
+Cache.  Kernel times come from a kernel trace of one case at a time (``--only NAME:0|1`` under ``rocprofv3 --kernel-trace
+--stats``: then every k_crop launch of a ``downstream`` / ``yml`` process is the same teacher launch).  ``share_of_step``
+relates ``graph_ms`` to the step the batch feeds: the cfg1 step of DESIGN 6 for ``downstream``, the phase-1 steps of the
+README for the other two (the students / teacher step has not been measured at these shapes).
+The lines are appended to profiles/batches_bench.jsonl."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+BANK_SHAPE = (512, 512, 96)
+CASES = [("downstream", (96, 96, 96), 4, (), False, 2.41, "cfg1 step (DESIGN 6)"),
+         ("students_teacher", (96, 96, 96), 4, ((96, 96, 96), (72, 72, 72)), True, 21.7, "phase-1 eager step (README)"),
+         ("yml", (128, 128, 8), 14, (), False, 18.7, "phase-1 graphed step (README)")]
+ACTIVE = [1, 2]
+
+
+def timed(fn, calls, warmup):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / calls
+
+
+def eager_batch(images, labels, lut, d, roi, sizes, with_coord):
+    """The batch of draws ``d`` from eager torch ops: per sample the stored-frame slice, rot90 of the crop, the pad."""
+    import torch
+    import torch.nn.functional as F
+    from mivp_amd.batches import ROT_AXES, rotated_shape
+
+    def pad(v, size):
+        flat = []
+        for k in (2, 1, 0):
+            t = size[k] - v.shape[v.dim() - 3 + k]
+            flat += [t // 2, t - t // 2]
+        return F.pad(v, flat)
+
+    img, mask, coord = [], [], []
+    for b in range(d.batch):
+        v, rot = int(d.volume[b]), int(d.rot[b])
+        n = images[v].shape[1:]
+        n_rot = rotated_shape(n, rot)
+        lo = [int(a) for a in d.origin[b]]
+        ext = [min(roi[k], n_rot[k]) for k in range(3)]
+        if rot:                                                 # rotated box -> stored box: p_a = r_b, p_b = n_b - 1 - r_a
+            a, c = ROT_AXES[rot]
+            lo_s, ext_s = list(lo), list(ext)
+            lo_s[a], ext_s[a] = lo[c], ext[c]
+            lo_s[c], ext_s[c] = n[c] - lo[a] - ext[a], ext[a]
+        else:
+            lo_s, ext_s = lo, ext
+        sl = tuple(slice(lo_s[k], lo_s[k] + ext_s[k]) for k in range(3))
+        turn = (lambda t: torch.rot90(t, 1, (t.dim() - 3 + a, t.dim() - 3 + c))) if rot else (lambda t: t)
+        img.append(pad(turn(images[v][(slice(None),) + sl]), roi))
+        mask.append(pad(turn(lut[labels[v][sl].long()][None]), roi))
+        if with_coord:
+            axes = [torch.arange(lo_s[k], lo_s[k] + ext_s[k], dtype=torch.float32, device=lut.device) - (n[k] - 1) / 2.0
+                    for k in range(3)]
+            coord.append(pad(turn(torch.stack(torch.meshgrid(*axes, indexing="ij"), 0)), roi))
+    out = dict(image=torch.stack(img), mask=torch.stack(mask))
+    if with_coord:
+        out["coord"] = torch.stack(coord)
+
+    def view(t, s, size):
+        rows = []
+        for b in range(d.batch):
+            o = [int(a) for a in d.student_origin[s, b]]
+            e = [min(size[k], t.shape[2 + k]) for k in range(3)]
+            rows.append(pad(t[b][:, o[0]:o[0] + e[0], o[1]:o[1] + e[1], o[2]:o[2] + e[2]], size))
+        return torch.stack(rows)
+
+    if sizes:
+        out["image_st"] = [view(out["image"], s, size) for s, size in enumerate(sizes)]
+        out["coord_st"] = [view(out["coord"], s, size) for s, size in enumerate(sizes)]
+        out["mask_st_0"] = view(out["mask"], 0, sizes[0])
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--draw-sets", type=int, default=32)
+    ap.add_argument("--volumes", type=int, default=3)
+    ap.add_argument("--only", default=None, help="one case, as NAME:0 or NAME:1 (random_orientation off / on): for a "
+                    "kernel-trace run, where every k_crop launch of the process should be the same launch")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batches_bench.jsonl"))
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    import mivp_amd  # noqa: F401
+    from mivp_amd import batches as BT
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(1)
+    bank = BT.VolumeBank(dev, 1)
+    for _ in range(a.volumes):
+        bank.add(torch.rand((1,) + BANK_SHAPE, generator=g).to(dev),
+                 torch.randint(0, 4, BANK_SHAPE, generator=g, dtype=torch.uint8).to(dev))
+    lines = []
+    for name, roi, B, sizes, with_coord, step_ms, step_kind in CASES:
+        for oriented in (False, True):
+            if a.only is not None and a.only != f"{name}:{int(oriented)}":
+                continue
+            filler = BT.BatchFiller(bank, roi, B, student_sizes=sizes, active_labels=ACTIVE, with_coord=with_coord)
+            lut = filler.lut.float()
+            rs = np.random.RandomState(3)
+            ids = [i % len(bank) for i in range(B)]
+            sets = [BT.draw_crops(rs, bank.shapes, ids, roi, 1, oriented, sizes) for _ in range(a.draw_sets)]
+            d = sets[0]
+            got = filler.fill(d)
+            want = eager_batch(bank.images, bank.labels, lut, d, roi, sizes, with_coord)
+            torch.cuda.synchronize()
+            pairs = [(filler.image, want["image"]), (filler.mask, want["mask"])]
+            if with_coord:
+                pairs.append((filler.coord, want["coord"]))
+            if sizes:
+                pairs += list(zip(got["image_st"], want["image_st"])) + list(zip(got["coord_st"], want["coord_st"]))
+                pairs.append((got["mask_st_0"], want["mask_st_0"]))
+            assert all(torch.equal(x, y) for x, y in pairs), f"{name}: the eager composition disagrees"
+
+            slot = filler.slot
+            ms = timed(lambda: filler.fill(), a.calls, a.warmup)
+            state = {"k": 0}
+
+            def loaded():
+                state["k"] += 1
+                filler.fill(sets[state["k"] % len(sets)])
+
+            load_ms = timed(loaded, a.calls, a.warmup)
+            slot.load(d, bank, roi, sizes)
+            eager_ms = timed(lambda: eager_batch(bank.images, bank.labels, lut, d, roi, sizes, with_coord),
+                             max(5, a.calls // 10), 2)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                filler.fill()
+            graph_ms = timed(graph.replay, a.calls, a.warmup)
+            # compulsory bytes per launch group
+            vox = int(np.prod(roi))
+            inside = sum(int(np.prod([min(roi[k], BT.rotated_shape(bank.shapes[int(v)], int(r))[k]) for k in range(3)]))
+                         for v, r in zip(d.volume, d.rot))
+            n_out = 1 + 1 + (3 if with_coord else 0)
+            groups = [("teacher", 1, inside * (4 + 1) + B * vox * 4 * n_out, lambda: filler._fill_teacher(slot))]
+            if sizes:
+                sb = sum(int(np.prod([min(s[k], roi[k]) for k in range(3)])) * 4 + int(np.prod(s)) * 4 for s in sizes) * B * 4
+                sb += (int(np.prod([min(sizes[0][k], roi[k]) for k in range(3)])) + int(np.prod(sizes[0]))) * 4 * B
+                groups.append(("students", 2 * len(sizes) + 1, sb, lambda: filler._fill_students(slot)))
+            launches = []
+            for gname, n, nbytes, fn in groups:
+                gms = timed(fn, a.calls, a.warmup)
+                launches.append({"group": gname, "launches": n, "bytes": int(nbytes), "ms": round(gms, 4),
+                                 "issue_TB_per_s": round(nbytes / (gms * 1e-3) / 1e12, 3)})
+            rec = {"case": name, "roi": list(roi), "B": B, "students": [list(s) for s in sizes], "random_orientation": oriented,
+                   "codes": sorted(set(int(r) for r in d.rot)), "ms": round(ms, 4), "load_ms": round(load_ms, 4),
+                   "graph_ms": round(graph_ms, 4), "eager_ms": round(eager_ms, 4),
+                   "eager_over_fill": round(eager_ms / ms, 2), "eager_over_graph": round(eager_ms / graph_ms, 2),
+                   "groups": launches, "step_ms": step_ms, "step": step_kind, "share_of_step": round(graph_ms / step_ms, 4)}
+            print(json.dumps(rec), flush=True)
+            lines.append(json.dumps(rec))
+    if not lines:
+        raise SystemExit(f"--only {a.only}: no such case")
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
