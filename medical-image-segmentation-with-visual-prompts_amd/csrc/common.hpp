@@ -44,6 +44,13 @@ MIVP_DEV bf16x8 cat44(bf16x4 lo, bf16x4 hi) {
     o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
     return o;
 }
+// Transposing LDS read.  4 rows x 16 columns of bf16 per 16-lane group, delivered column-major: lane 4q+p of the group passes
+// the address of row q, columns 4p..4p+3; lane i receives column i of the four rows (EXEC must be full: callers keep the
+// wave converged)
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+MIVP_DEV bf16x4 tr_read(const char* p) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p);
+}
 // sum / max over the 4 lanes that share a token column (lanes r, r+16, r+32, r+48)
 MIVP_DEV float col_sum(float v) { v += __shfl_xor(v, 16); v += __shfl_xor(v, 32); return v; }
 MIVP_DEV float col_max(float v) { v = fmaxf(v, __shfl_xor(v, 16)); v = fmaxf(v, __shfl_xor(v, 32)); return v; }

@@ -450,10 +450,6 @@ extern "C" int mivp_conv3d_wgrad_small(const MivpConvDesc* d, const void* x, con
 // G and S are linear in the raw x: the BatchNorm affine in front of the conv, the conv weight gradient, dgamma
 // and dbeta all follow from (G, S) by O(27*Cout*Cin) algebra on the host.
 // ---------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) bf16x4 wr_lds_bf16x4;
-MIVP_DEV bf16x4 wr_tr_read(const char* smem, int byte_off) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((wr_lds_bf16x4*)(smem + byte_off));
-}
 // blocks of 4 rows x 16 columns (128 B); S blocks per 4-row group, column block XOR-ed with bit 3 of the row so that
 // the two 16-lane groups of a half (8 rows apart) fall into opposite halves of the 256-byte bank row
 template <int S>
@@ -512,13 +508,13 @@ __global__ __launch_bounds__(256) void k_conv3d_wgrad_rows(MivpConvDesc d, const
 #pragma unroll
                 for (int sd = 0; sd < 3; ++sd) {
                     const int rb = r0 + 4 + (sd - 1);
-                    bf[sd] = cat44(wr_tr_read(Bimg, wr_off<WR_BS>(rb, 16 * wave + 4 * pp)),
-                                   wr_tr_read(Bimg, wr_off<WR_BS>(rb + 4, 16 * wave + 4 * pp)));
+                    bf[sd] = cat44(tr_read(Bimg + wr_off<WR_BS>(rb, 16 * wave + 4 * pp)),
+                                   tr_read(Bimg + wr_off<WR_BS>(rb + 4, 16 * wave + 4 * pp)));
                 }
 #pragma unroll
                 for (int mt = 0; mt < WR_MT; ++mt) {
-                    const bf16x8 a = cat44(wr_tr_read(Aimg, wr_off<WR_AS>(r0, 16 * mt + 4 * pp)),
-                                           wr_tr_read(Aimg, wr_off<WR_AS>(r0 + 4, 16 * mt + 4 * pp)));
+                    const bf16x8 a = cat44(tr_read(Aimg + wr_off<WR_AS>(r0, 16 * mt + 4 * pp)),
+                                           tr_read(Aimg + wr_off<WR_AS>(r0 + 4, 16 * mt + 4 * pp)));
 #pragma unroll
                     for (int sd = 0; sd < 3; ++sd) acc[sd][mt] = mfma16(a, bf[sd], acc[sd][mt]);
                 }

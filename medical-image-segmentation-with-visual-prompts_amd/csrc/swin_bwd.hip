@@ -6,36 +6,7 @@
 //   dkv pass: one wave owns 16 keys,    walks all queries (S   = Q' K'^T : key on the lane)
 // so every reduction a wave needs is over the MFMA row index of its own accumulators and the
 // probabilities feed the next MFMA without leaving their lanes (common.hpp convention).
-#include "common.hpp"
-
-int mivp_attn_tile_config(const MivpSwinDesc* d, int* dks, int* nt);
-// swin_tok_wide.hip: the column-split token kernels of the wide stages
-int mivp_tok_wide_supported(const MivpSwinDesc* d);
-int mivp_tok_rows_supported(const MivpSwinDesc* d);
-long mivp_tok_natural_offset(int C);
-int mivp_tok_wide_qkv_bwd(const MivpSwinDesc* d, const void* dq, const void* dk, const void* dv, const void* x, const int32_t* tok_src,
-                          const float* ln_w, const void* wqkv_t, const void* d_t1, void* dx, void* dn_out, hipStream_t st);
-int mivp_tok_wide_proj_mlp_bwd(const MivpSwinDesc* d, const void* dy, const int32_t* tok_dst, const void* t1, const float* ln_w,
-                               const void* wmlp_t, const void* wproj_t, void* d_o, void* d_t1, hipStream_t st);
-
-namespace {
-
-struct TokInfo { long tt, bp, b; int slot, pw; bool live; };
-
-MIVP_DEV TokInfo token_info(const MivpSwinDesc& d, long t) {
-    TokInfo ti;
-    const long T = (long)d.B * d.P * d.Nqp;
-    ti.live = t < T;
-    const unsigned tu = ti.live ? (unsigned)t : 0u;          // T fits 32 bits (bwd_checks): 32-bit divisions, not 64-bit ones
-    const unsigned bpu = tu / (unsigned)d.Nqp;
-    ti.tt = tu;
-    ti.bp = bpu;
-    ti.slot = (int)(tu - bpu * (unsigned)d.Nqp);
-    ti.pw = (int)(bpu % (unsigned)d.P);
-    ti.b = bpu / (unsigned)d.P;
-    return ti;
-}
-}  // namespace
+#include "swin_common.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // proj + MLP backward:  dy -> (dO, dt1)
@@ -216,11 +187,6 @@ __global__ __launch_bounds__(256) void k_win_attn_delta(MivpSwinDesc d, const bf
 // K^T (dq), key classes.  For head_dim <= 16 (DVT == 1) the dP product uses the K=16 MFMA so the V rows
 // are only 16 wide.  The pass also produces delta[q] = sum_j dO*O (needed again by the dkv pass).
 // ---------------------------------------------------------------------------------------------
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-MIVP_DEV f32x4 mfma16k16(bf16x4 a, bf16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
-}
-
 template <int DKS, int DVT>
 struct AttnBwdGeom {
     static constexpr int DK = 32 * DKS;
@@ -1071,18 +1037,6 @@ static int bwd_checks(const MivpSwinDesc* d) {
     return MIVP_OK;
 }
 
-#define CT_SWITCH(CTV, LAUNCH)                                                              \
-    switch (CTV) {                                                                          \
-        case 1: LAUNCH(1); break;                                                           \
-        case 2: LAUNCH(2); break;                                                           \
-        case 3: LAUNCH(3); break;                                                           \
-        case 4: LAUNCH(4); break;                                                           \
-        case 6: LAUNCH(6); break;                                                           \
-        case 8: LAUNCH(8); break;                                                           \
-        case 12: LAUNCH(12); break;                                                         \
-        default: mivp_set_error("C/16 not in {1,2,3,4,6,8,12}"); return MIVP_EUNSUPPORTED; \
-    }
-
 extern "C" int mivp_swin_proj_mlp_bwd(const MivpSwinDesc* d, const void* dy, const int32_t* tok_dst, const void* t1,
                                       const float* ln_w, const float* ln_b, const void* wmlp_t, const void* wproj_t,
                                       void* d_o, void* d_t1, void* dn_out, void* dyw, void* d_pj,
@@ -1098,11 +1052,12 @@ extern "C" int mivp_swin_proj_mlp_bwd(const MivpSwinDesc* d, const void* dy, con
     if (mivp_tok_rows_supported(d) && !dn_out && !dyw && !d_pj)
         return mivp_tok_wide_proj_mlp_bwd(d, dy, tok_dst, t1, ln_w, wmlp_t, (const bf16_t*)wproj_t + mivp_tok_natural_offset(d->C),
                                           d_o, d_t1, st);
-#define L_PMB(K) hipLaunchKernelGGL((k_swin_proj_mlp_bwd<K>), dim3(grid), dim3(256), 0, st, *d, (const bf16_t*)dy, tok_dst, \
-                                     (const bf16_t*)t1, ln_w, ln_b, (const bf16_t*)wmlp_t, (const bf16_t*)wproj_t,          \
-                                     (bf16_t*)d_o, (bf16_t*)d_t1, (bf16_t*)dn_out, (bf16_t*)dyw, (bf16_t*)d_pj)
-    CT_SWITCH((d->C + 15) / 16, L_PMB)
-#undef L_PMB
+    const bool known = for_tok16_ct((d->C + 15) / 16, [&](auto ct) {
+        hipLaunchKernelGGL((k_swin_proj_mlp_bwd<decltype(ct)::value>), dim3(grid), dim3(256), 0, st, *d, (const bf16_t*)dy, tok_dst,
+                           (const bf16_t*)t1, ln_w, ln_b, (const bf16_t*)wmlp_t, (const bf16_t*)wproj_t, (bf16_t*)d_o,
+                           (bf16_t*)d_t1, (bf16_t*)dn_out, (bf16_t*)dyw, (bf16_t*)d_pj);
+    });
+    if (!known) { mivp_set_error("C/16 not in {1,2,3,4,6,8,12}"); return MIVP_EUNSUPPORTED; }
     return mivp_check_launch("swin_proj_mlp_bwd");
 }
 
@@ -1247,11 +1202,12 @@ extern "C" int mivp_swin_qkv_bwd(const MivpSwinDesc* d, const void* dq, const vo
     hipStream_t st = (hipStream_t)stream;
     if (mivp_tok_wide_supported(d))                           // C = 96 / 192 / 384: column-split form (swin_tok_wide.hip)
         return mivp_tok_wide_qkv_bwd(d, dq, dk, dv, x, tok_src, ln_w, wqkv_t, d_t1, dx, dn_out, st);
-#define L_QB(K) hipLaunchKernelGGL((k_swin_qkv_bwd<K>), dim3(grid), dim3(256), 0, st, *d, (const bf16_t*)dq, (const bf16_t*)dk, \
-                                    (const bf16_t*)dv, (const bf16_t*)x, tok_src, ln_w, ln_b, (const bf16_t*)wqkv_t,             \
-                                    (const bf16_t*)d_t1, (bf16_t*)dx, (bf16_t*)dn_out)
-    CT_SWITCH((d->C + 15) / 16, L_QB)
-#undef L_QB
+    const bool known = for_tok16_ct((d->C + 15) / 16, [&](auto ct) {
+        hipLaunchKernelGGL((k_swin_qkv_bwd<decltype(ct)::value>), dim3(grid), dim3(256), 0, st, *d, (const bf16_t*)dq,
+                           (const bf16_t*)dk, (const bf16_t*)dv, (const bf16_t*)x, tok_src, ln_w, ln_b, (const bf16_t*)wqkv_t,
+                           (const bf16_t*)d_t1, (bf16_t*)dx, (bf16_t*)dn_out);
+    });
+    if (!known) { mivp_set_error("C/16 not in {1,2,3,4,6,8,12}"); return MIVP_EUNSUPPORTED; }
     return mivp_check_launch("swin_qkv_bwd");
 }
 

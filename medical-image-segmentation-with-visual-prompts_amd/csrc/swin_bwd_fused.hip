@@ -31,18 +31,10 @@
 //   dqp   [2][8 waves][16 queries][16] f32  partial dQ^T tiles
 //   lse_s, del_s [nq] f32, ridq [nq] bytes
 // Every reduction has a fixed order: results are bit-reproducible.
-#include "common.hpp"
-
-int mivp_attn_tile_config(const MivpSwinDesc* d, int* dks, int* nt);
+#include "swin_common.hpp"
 
 namespace {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-MIVP_DEV f32x4 mfma16k16(bf16x4 a, bf16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
-}
 // f32x4 -> four bf16 as exactly two v_cvt_pk_bf16_f32.  The value feeds BOTH an LDS store and the short-typed operand of
 // the K = 16 MFMA builtin; converted element by element that second use became four single conversions plus two v_perm
 // per pack (10 + 4 VALU instructions per tile instead of 4, in a VALU-issue-bound loop).  Converting PAIRS and carrying
@@ -60,24 +52,13 @@ MIVP_DEV u32x2 pack4_pk(f32x4 v) {
 MIVP_DEV f32x4 mfma16k16(bf16x4 a, u32x2 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
 }
-// 4 rows x 16 columns of bf16 per 16-lane group, delivered column-major: lane 4q+p of the group passes the address of row
-// q, columns 4p..4p+3; lane i receives column i of the four rows (EXEC must be full: callers keep the wave converged)
-MIVP_DEV bf16x4 tr_read(const char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p);
-}
 
-// LDS-DMA staging (DMA form of the fused kernel): constant source words and one 4-byte global -> LDS transfer per lane
-// (LDS address = wave-uniform base + 4 * lane), as in the forward kernel (swin_fwd.hip)
+// LDS-DMA staging (DMA form of the fused kernel; glds4: swin_common.hpp): the constant source words
 __device__ __attribute__((aligned(16))) unsigned int g_bwd_zero[4] = {0u, 0u, 0u, 0u};
-MIVP_DEV void glds4(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
-}
 
 constexpr int FUSED_KPW = 4;                                   // key tiles per wave (8 waves: up to 512 keys)
 using KR = OperandRows<32>;
 
-MIVP_DEV int oimg_off(int row, int byte) { return row * 32 + (byte ^ (((row >> 3) & 1) << 4)); }
 MIVP_DEV int exch_off(int tile, int key, int quad) { return tile * 512 + 128 * quad + 8 * (key ^ ((quad >> 1) << 3)); }
 
 // ---- staging of the query-side images (shared by the two kernels of this file) ----
@@ -118,7 +99,7 @@ MIVP_DEV void o_store(char* Oimg, float* del_s, int e, bf16x4 gv, bf16x4 ov) {
     for (int i = 0; i < 4; ++i) part += (float)gv[i] * (float)ov[i];
     part += __shfl_xor(part, 1);
     part += __shfl_xor(part, 2);
-    *reinterpret_cast<bf16x4*>(Oimg + oimg_off(lrow, 8 * c4)) = gv;
+    *reinterpret_cast<bf16x4*>(Oimg + row32_off(lrow, 8 * c4)) = gv;
     if (c4 == 0) del_s[lrow] = -part;                          // delta = sum_j dO * O, negated: the dP accumulators start from it
 }
 // One batch: UQ pieces of Q' and UO pieces of dO / O per thread, all loads before the first LDS store.  Indices beyond the
@@ -266,7 +247,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_win_attn_bwd_fused(
             for (; gi < Nqp / 4; gi += NW) { glds4(src, Qimg + gi * 256); src += stride; }
             for (; gi < nq / 4; gi += NW) glds4(zsrc, Qimg + gi * 256);                  // phantom rows
         }
-        {   // dO image: 8 rows (32 B, halves swapped in rows 8..15 of every 16: oimg_off) per instruction
+        {   // dO image: 8 rows (32 B, halves swapped in rows 8..15 of every 16: row32_off) per instruction
             const int sl = lane & 7, rowin = lane >> 3;
             const int ld = sl ^ ((wave & 1) << 2);
             const bool fo = ld < hd2;
@@ -380,8 +361,8 @@ __global__ __launch_bounds__(64 * NW, 4) void k_win_attn_bwd_fused(
     // the row swizzles of Qimg / Oimg repeat every 16 rows)
     const char* q_rd = Qimg + KR::off(r, 8 * g);                                   // + 1024 t : S operand row of this lane
     const char* q_tr = Qimg + KR::off(4 * g + (r >> 2), 4 * (r & 3));              // + 1024 t : Q'^T block for dK^T
-    const char* o_rd = Oimg + oimg_off(r, 8 * g);                                  // +  512 t : dP operand row
-    const char* o_tr = Oimg + oimg_off(4 * g + (r >> 2), 8 * (r & 3));             // +  512 t : dO^T block for dV^T
+    const char* o_rd = Oimg + row32_off(r, 8 * g);                                  // +  512 t : dP operand row
+    const char* o_tr = Oimg + row32_off(4 * g + (r >> 2), 8 * (r & 3));             // +  512 t : dO^T block for dV^T
     char* ex_wr = exch + exch_off(wave, r, g);                                     // + 4096 i : this wave's slot, as written
     const char* ex_tr = exch + exch_off(wave, 4 * g + (r >> 2), r & 3);            // + 4096 i : ... as read back transposed
     // K^T columns of key tile i (+ 256 i classic; DMA: + 4096 i, a transposing read of the tile's rows 4g .. 4g+3)
@@ -587,8 +568,8 @@ __global__ __launch_bounds__(64 * NW, DROP ? 4 : 8) void k_win_attn_bwd_prompt(
     const uint32_t dbase = DROP ? attn_row(bph, 0, Nqp, Nkp) : 0u;
     const char* q_rd = Qimg + KR::off(r, 8 * g);
     const char* q_tr = Qimg + KR::off(4 * g + (r >> 2), 4 * (r & 3));
-    const char* o_rd = Oimg + oimg_off(r, 8 * g);
-    const char* o_tr = Oimg + oimg_off(4 * g + (r >> 2), 8 * (r & 3));
+    const char* o_rd = Oimg + row32_off(r, 8 * g);
+    const char* o_tr = Oimg + row32_off(4 * g + (r >> 2), 8 * (r & 3));
     const int t_begin = part * nqt / parts, t_end = (part + 1) * nqt / parts;
     for (int t = t_begin; t < t_end; ++t) {
         const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + 16 * t + 4 * g);

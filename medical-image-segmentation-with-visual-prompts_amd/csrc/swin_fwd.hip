@@ -1,17 +1,7 @@
 // Swin block forward: gather+LN+QKV, prompt K/V, bias augmentation, window attention,
 // proj+MLP+scatter.  Reference semantics: swin_transformer/swin_block.py:145-255,
 // multi_head_attention/window_attention.py:35-61, relative_positional_encoding.py:99-142.
-#include "common.hpp"
-
-// swin_tok_wide.hip: the column-split token kernels of the wide stages
-int mivp_tok_wide_supported(const MivpSwinDesc* d);
-int mivp_tok_rows_supported(const MivpSwinDesc* d);
-long mivp_tok_natural_offset(int C);
-int mivp_tok_wide_qkv_fwd(const MivpSwinDesc* d, const void* x, const int32_t* tok_src, const float* ln_w, const float* ln_b,
-                          const void* wqkv, void* q, void* k, void* v, hipStream_t st);
-int mivp_tok_wide_proj_mlp_fwd(const MivpSwinDesc* d, const void* o, const void* x, const int32_t* tok_src, const int32_t* tok_dst,
-                               const void* wproj, const float* bproj, const float* ln_w, const float* ln_b, const void* wmlp,
-                               const float* bmlp, void* t1_out, void* y, hipStream_t st);
+#include "swin_common.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // K1a  gather + LayerNorm + QKV
@@ -398,17 +388,8 @@ __global__ __launch_bounds__(256) void k_relbias_aug(MivpSwinDesc d, const float
 //   stage-0 launch).  A row sum outside [2^-100, 2^100) sends the tile to the tested walk.  Calls that save for backward
 //   keep the first-step maximum: their rounding pattern is the one the backward parity bars were measured with
 //   (oracle/swin_ref.py models both: ``zero_ref``).
-// LDS-DMA staging helpers of the DMA form (below): constant source words (zero | bf16 (1, 0)), one 4-byte global -> LDS
-// transfer per lane (LDS address = wave-uniform base + 4 * lane), and the transposing LDS read (wgrad.hip)
+// LDS-DMA staging of the DMA form (below; glds4 and tr_read: swin_common.hpp): constant source words (zero | bf16 (1, 0))
 __device__ __attribute__((aligned(16))) unsigned int g_attn_consts[4] = {0u, 0x00003F80u, 0u, 0u};
-MIVP_DEV void glds4(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
-}
-typedef __attribute__((address_space(3))) bf16x4 attn_lds_bf16x4;
-MIVP_DEV bf16x4 attn_tr_read(const char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((attn_lds_bf16x4*)p);
-}
 
 // waves per SIMD asked of the register allocator: the one-k-step kernels hold four workgroups per CU (34 KB of LDS each at 7^3
 // windows) when they fit 64 VGPRs
@@ -810,7 +791,7 @@ __global__ __launch_bounds__(64 * NW, (attn_fwd_occupancy<DKS, DROP, MASKED>()))
                 // V^T fragment by transposing reads of the row-major image: the 16-lane group g passes the addresses of keys
                 // 4g .. 4g+3 (lane 4q+p: row q, dv 4p ..), lane r receives dv = r of those four keys
                 const char* vblk = Vt + (32 * u + 4 * g + (r >> 2)) * 32 + 8 * (r & 3);
-                vfr[0] = cat44(attn_tr_read(vblk), attn_tr_read(vblk + 512));
+                vfr[0] = cat44(tr_read(vblk), tr_read(vblk + 512));
             } else {
 #pragma unroll
                 for (int dd = 0; dd < DVT; ++dd) {
@@ -1129,20 +1110,17 @@ extern "C" int mivp_swin_qkv_fwd(const MivpSwinDesc* d, const void* x, const int
     if (nsplit < 1) nsplit = 1;
     const dim3 grid(gx, (unsigned)nsplit);
     hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_QKV2(K, CH) hipLaunchKernelGGL((k_swin_qkv_fwd<K, CH>), grid, dim3(256), 0, st, *d, (const bf16_t*)x, tok_src, \
-                                              ln_w, ln_b, (const bf16_t*)wqkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v)
-#define LAUNCH_QKV(K) LAUNCH_QKV2(K, false)
     // contiguous chunk stores (kernel header): C = 48 with four heads of 12, all output columns in one workgroup
     const bool ch12 = d->C == 48 && d->heads == 4 && nsplit == 1 && d->Nqp % 32 == 0;
-    switch (KS) {
-        case 1: LAUNCH_QKV(1); break;
-        case 2: if (ch12) LAUNCH_QKV2(2, true); else LAUNCH_QKV(2); break;
-        case 3: LAUNCH_QKV(3); break;
-        case 4: LAUNCH_QKV(4); break;
-        case 6: LAUNCH_QKV(6); break;
-        default: mivp_set_error("swin_qkv_fwd: C/32 not in {1,2,3,4,6}"); return MIVP_EUNSUPPORTED;
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, *d, (const bf16_t*)x, tok_src, ln_w, ln_b, (const bf16_t*)wqkv,
+                           (bf16_t*)q, (bf16_t*)k, (bf16_t*)v);
+    };
+    if (ch12) launch(k_swin_qkv_fwd<2, true>);
+    else if (!for_tile_count<1, 2, 3, 4, 6>(KS, [&](auto ks) { launch(k_swin_qkv_fwd<decltype(ks)::value, false>); })) {
+        mivp_set_error("swin_qkv_fwd: C/32 not in {1,2,3,4,6}");
+        return MIVP_EUNSUPPORTED;
     }
-#undef LAUNCH_QKV
     return mivp_check_launch("swin_qkv_fwd");
 }
 
@@ -1279,19 +1257,11 @@ extern "C" int mivp_swin_proj_mlp_fwd(const MivpSwinDesc* d, const void* o, cons
     if (mivp_tok_rows_supported(d))
         return mivp_tok_wide_proj_mlp_fwd(d, o, x, tok_src, tok_dst, wproj, bproj, ln_w, ln_b,
                                           (const bf16_t*)wmlp + mivp_tok_natural_offset(d->C), bmlp, t1, y, st);
-#define LAUNCH_PM(K) hipLaunchKernelGGL((k_swin_proj_mlp_fwd<K>), dim3(grid), dim3(256), 0, st, *d, (const bf16_t*)o, \
-                                         (const bf16_t*)x, tok_src, tok_dst, (const bf16_t*)wproj, bproj, ln_w, ln_b,   \
-                                         (const bf16_t*)wmlp, bmlp, (bf16_t*)t1, (bf16_t*)y)
-    switch (CT) {
-        case 1: LAUNCH_PM(1); break;
-        case 2: LAUNCH_PM(2); break;
-        case 3: LAUNCH_PM(3); break;
-        case 4: LAUNCH_PM(4); break;
-        case 6: LAUNCH_PM(6); break;
-        case 8: LAUNCH_PM(8); break;
-        case 12: LAUNCH_PM(12); break;
-        default: mivp_set_error("swin_proj_mlp_fwd: C/16 not in {1,2,3,4,6,8,12}"); return MIVP_EUNSUPPORTED;
-    }
-#undef LAUNCH_PM
+    const bool known = for_tok16_ct(CT, [&](auto ct) {
+        hipLaunchKernelGGL((k_swin_proj_mlp_fwd<decltype(ct)::value>), dim3(grid), dim3(256), 0, st, *d, (const bf16_t*)o,
+                           (const bf16_t*)x, tok_src, tok_dst, (const bf16_t*)wproj, bproj, ln_w, ln_b, (const bf16_t*)wmlp, bmlp,
+                           (bf16_t*)t1, (bf16_t*)y);
+    });
+    if (!known) { mivp_set_error("swin_proj_mlp_fwd: C/16 not in {1,2,3,4,6,8,12}"); return MIVP_EUNSUPPORTED; }
     return mivp_check_launch("swin_proj_mlp_fwd");
 }

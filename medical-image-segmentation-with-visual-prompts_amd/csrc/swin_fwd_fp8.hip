@@ -10,7 +10,7 @@
 // conversion instructions in fp8 as in bf16 -- so the only gain is half the LDS image.  tools/fp8_attn.py measures time and
 // error next to the bf16 kernel; the numbers are in profiles/r02_fp8_attention.json.  Not used unless
 // mivp_amd.swin_ops.USE_FP8_ATTN_FWD is set.
-#include "common.hpp"
+#include "swin_common.hpp"
 
 namespace {
 
@@ -27,8 +27,7 @@ MIVP_DEV unsigned pk4_fp8(bf16x4 v) { return pk4_fp8(sat448((float)v[0]), sat448
 MIVP_DEV f32x4 mfma_fp8(u32x2 a, u32x2 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(__builtin_bit_cast(long, a), __builtin_bit_cast(long, b), c, 0, 0, 0);
 }
-// K' image: 32-byte rows (32 fp8), the two 16-byte halves swapped in rows 8..15 of every 16 (conflict-free ds_read_b64)
-MIVP_DEV int krow_off(int row, int byte) { return row * 32 + (byte ^ (((row >> 3) & 1) << 4)); }
+// K' image: 32-byte rows (32 fp8) in the half-swapped layout (row32_off, swin_common.hpp: conflict-free ds_read_b64)
 
 }  // namespace
 
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(512, 2) void k_win_attn_fwd_fp8(MivpSwinDesc d, con
             val = ld4(kab + ((uint32_t)row * A + 4 * (c4 - hd4)));
             // the padding-key bias (-30000 log2 e) saturates E4M3 at -448: still far below every real logit
         }
-        *reinterpret_cast<unsigned*>(Kimg + krow_off(row, 4 * c4)) = pk4_fp8(val);
+        *reinterpret_cast<unsigned*>(Kimg + row32_off(row, 4 * c4)) = pk4_fp8(val);
     }
     // ---- stage V^T (fp8): four consecutive keys of one 4-channel group, transposed 4x4; row hd = 1 (softmax denominator) ----
     for (int e = tid; e < (Nkp / 4) * 4; e += 64 * NW) {
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(512, 2) void k_win_attn_fwd_fp8(MivpSwinDesc d, con
             f32x4 sv[2];
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
-                const u32x2 kf = *reinterpret_cast<const u32x2*>(Kimg + krow_off(16 * (2 * u + hh) + r, 8 * g));
+                const u32x2 kf = *reinterpret_cast<const u32x2*>(Kimg + row32_off(16 * (2 * u + hh) + r, 8 * g));
                 f32x4 acc = mfma_fp8(kf, qf, negm);
                 if (MASKED && cut) {
                     const uint32_t kr = *reinterpret_cast<const uint32_t*>(ridk + 16 * (2 * u + hh) + 4 * g);

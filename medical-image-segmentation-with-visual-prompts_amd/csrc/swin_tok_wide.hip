@@ -17,7 +17,7 @@
 //   * row reductions across column groups meet in LDS in column-group order (bit-reproducible);
 //   * every global load is unconditional (common.hpp "Branch-free loads").
 // The launchers at the bottom are called by the C entries of swin_fwd.hip / swin_bwd.hip when mivp_tok_wide_supported().
-#include "common.hpp"
+#include "swin_common.hpp"
 
 namespace {
 
@@ -45,20 +45,6 @@ struct RowImg {
     static MIVP_DEV void put8(char* img, int row, int k0, bf16x8 v) { *reinterpret_cast<bf16x8*>(img + row * ROWB + 2 * k0) = v; }
 };
 
-struct RowTok { long tt, bp, b; int slot, pw; bool live; };
-MIVP_DEV RowTok row_token(const MivpSwinDesc& d, long t) {      // a dead row decodes as token 0 (valid addresses)
-    RowTok ti;
-    const long T = (long)d.B * d.P * d.Nqp;
-    ti.live = t < T;
-    const unsigned tu = ti.live ? (unsigned)t : 0u;
-    const unsigned bpu = tu / (unsigned)d.Nqp;
-    ti.tt = tu;
-    ti.bp = bpu;
-    ti.slot = (int)(tu - bpu * (unsigned)d.Nqp);
-    ti.pw = (int)(bpu % (unsigned)d.P);
-    ti.b = bpu / (unsigned)d.P;
-    return ti;
-}
 template <int TPR>
 MIVP_DEV float row_sum(float v) {                                // sum over the TPR adjacent lanes of a token row
 #pragma unroll
@@ -80,14 +66,14 @@ struct FlatRows {
     static constexpr int PPR = G::C / 8, N = G::XPT;
     static_assert(G::ROWS * PPR == 256 * N, "pieces split evenly over the threads");
     int prow[N], col[N];
-    RowTok tk[N];
+    TokInfo tk[N];
     MIVP_DEV FlatRows(const MivpSwinDesc& d, long row0, int tid) {
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             const int P = tid + 256 * i;
             prow[i] = P / PPR;
             col[i] = 8 * (P - prow[i] * PPR);
-            tk[i] = row_token(d, row0 + prow[i]);
+            tk[i] = token_info(d, row0 + prow[i]);
         }
     }
 };
@@ -162,7 +148,7 @@ __global__ __launch_bounds__(256, CT <= 3 ? 4 : (CT <= 12 ? 3 : 2)) void k_qkv_f
     const long row0 = (long)blockIdx.x * ROWS;
     {   // ---- rows: gather, LayerNorm ----
         const int row = tid / TPR, sub = tid % TPR;
-        const RowTok ti = row_token(d, row0 + row);
+        const TokInfo ti = token_info(d, row0 + row);
         const int src = sel(ti.live, tok_src[ti.pw * d.Nqp + ti.slot], -2);
         const long xoff = (ti.b * d.vol_in + max(src, 0)) * (long)C;
         bf16x8 xr[XPT];
@@ -316,7 +302,7 @@ __global__ __launch_bounds__(256, CT <= 6 ? 3 : 2) void k_qkv_fwd_ws(MivpSwinDes
     ws_load_pair<KS>(wqkv, wave, lane, a0);
     {   // ---- rows: gather, LayerNorm ----
         const int row = tid / TPR, sub = tid % TPR;
-        const RowTok ti = row_token(d, row0 + row);
+        const TokInfo ti = token_info(d, row0 + row);
         const int src = sel(ti.live, tok_src[ti.pw * d.Nqp + ti.slot], -2);
         const long xoff = (ti.b * d.vol_in + max(src, 0)) * (long)C;
         bf16x8 xr[XPT];
@@ -388,7 +374,7 @@ __global__ __launch_bounds__(256, 3) void k_proj_mlp_fwd_wide(MivpSwinDesc d, co
     const int r = lane & 15, g = lane >> 4;
     const long row0 = (long)blockIdx.x * ROWS;
     const int row = tid / TPR, sub = tid % TPR;                  // the row phases' lane map
-    const RowTok ti = row_token(d, row0 + row);
+    const TokInfo ti = token_info(d, row0 + row);
     const uint32_t proj_key = drop_seed(d.proj_seed, d.seed_epoch);      // (uniform; unused without dropout)
     constexpr bool FLAT = flat_rows<CT>();
     // C = 96: the wave's weight fragments of a GEMM are requested a phase EARLY (proj: before the rows come in, MLP: before the
@@ -582,7 +568,7 @@ __global__ __launch_bounds__(256, 3) void k_proj_mlp_bwd_wide(MivpSwinDesc d, co
     const int r = lane & 15, g = lane >> 4;
     const long row0 = (long)blockIdx.x * ROWS;
     const int row = tid / TPR, sub = tid % TPR;
-    const RowTok ti = row_token(d, row0 + row);
+    const TokInfo ti = token_info(d, row0 + row);
     const uint32_t proj_key = drop_seed(d.proj_seed, d.seed_epoch);      // (uniform; unused without dropout)
     const bool drop = d.proj_drop_thr != 0;
     {   // ---- rows in: dy (gathered), t1 + its LayerNorm statistics ----
@@ -749,7 +735,7 @@ __global__ __launch_bounds__(256, CT <= 12 ? 3 : 2) void k_qkv_bwd_wide(MivpSwin
     const int r = lane & 15, g = lane >> 4;
     const long row0 = (long)blockIdx.x * ROWS;
     const int row = tid / TPR, sub = tid % TPR;
-    const RowTok ti = row_token(d, row0 + row);
+    const TokInfo ti = token_info(d, row0 + row);
     const int src = sel(ti.live, tok_src[ti.pw * d.Nqp + ti.slot], -2);
     const long xoff = (ti.b * d.vol_in + max(src, 0)) * (long)C;
 
@@ -1019,95 +1005,81 @@ int mivp_tok_rows_supported(const MivpSwinDesc* d) {
 // element offset of the natural-order image behind the paired one (swin_ops.paired_and_natural)
 long mivp_tok_natural_offset(int C) { return (long)(C / 16) * ((C + 31) / 32) * 512; }
 
-#define ROWS_SWITCH(LAUNCH)                                                                  \
-    switch (d->C) {                                                                          \
-        case 48: LAUNCH(3); break;                                                           \
-        case 96: LAUNCH(6); break;                                                           \
-        case 192: LAUNCH(12); break;                                                         \
-        case 384: LAUNCH(24); break;                                                         \
-        default: mivp_set_error("tok_rows: C not in {48, 96, 192, 384}"); return MIVP_EUNSUPPORTED; \
-    }
-#define WIDE_SWITCH(LAUNCH)                                                                  \
-    switch (d->C) {                                                                          \
-        case 96: LAUNCH(6); break;                                                           \
-        case 192: LAUNCH(12); break;                                                         \
-        case 384: LAUNCH(24); break;                                                         \
-        default: mivp_set_error("tok_wide: C not in {96, 192, 384}"); return MIVP_EUNSUPPORTED; \
-    }
-#define WIDE_GRID(CTV) dim3((unsigned)((T + WideGeom<CTV>::ROWS - 1) / WideGeom<CTV>::ROWS))
+namespace {
+// channel counts of the row-image kernels and of the wide ones (the callable derives CT = C / 16)
+template <class F> bool for_rows_c(int C, F&& f) { return for_tile_count<48, 96, 192, 384>(C, f); }
+template <class F> bool for_wide_c(int C, F&& f) { return for_tile_count<96, 192, 384>(C, f); }
+
+// opt-in to the LDS image, one workgroup per WideGeom<CT>::ROWS of the T token rows, launch
+template <int CT, class Kern, class... Args>
+int launch_wide(Kern kern, size_t lds, long T, hipStream_t st, Args... args) {
+    MIVP_LDS_OPT_IN(kern, lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((T + WideGeom<CT>::ROWS - 1) / WideGeom<CT>::ROWS)), dim3(256), lds, st, args...);
+    return MIVP_OK;
+}
+}  // namespace
 
 int mivp_tok_wide_qkv_fwd(const MivpSwinDesc* d, const void* x, const int32_t* tok_src, const float* ln_w, const float* ln_b,
                           const void* wqkv, void* q, void* k, void* v, hipStream_t st) {
     const long T = (long)d->B * d->P * d->Nqp;
-#define L_W(CTV)                                                                                                             \
-    do {                                                                                                                     \
-        const size_t lds = lds_qkv_fwd<CTV>();                                                                               \
-        MIVP_LDS_OPT_IN(k_qkv_fwd_wide<CTV>, lds);                                                                           \
-        hipLaunchKernelGGL((k_qkv_fwd_wide<CTV>), WIDE_GRID(CTV), dim3(256), lds, st, *d, (const bf16_t*)x, tok_src, ln_w,   \
-                           ln_b, (const bf16_t*)wqkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v);                                   \
-    } while (0)
     const int hd = d->C / d->heads;
+    int rc = MIVP_OK;
     if ((d->C == 96 || d->C == 192) && hd % 4 == 0 && d->Nqp % 16 == 0 && d->Nqp >= 64) {
-#define L_WS(CTV)                                                                                                            \
-    do {                                                                                                                     \
-        const size_t lds = (size_t)64 * RowImg<WideGeom<CTV>::KP>::ROWB;                                                     \
-        hipLaunchKernelGGL((k_qkv_fwd_ws<CTV>), dim3((unsigned)((T + 63) / 64)), dim3(256), lds, st, *d, (const bf16_t*)x,   \
-                           tok_src, ln_w, ln_b, (const bf16_t*)wqkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v);                    \
-    } while (0)
-        if (d->C == 96) L_WS(6); else L_WS(12);
-#undef L_WS
+        for_tile_count<96, 192>(d->C, [&](auto c) {
+            constexpr int CT = decltype(c)::value / 16;
+            const size_t lds = (size_t)64 * RowImg<WideGeom<CT>::KP>::ROWB;
+            hipLaunchKernelGGL((k_qkv_fwd_ws<CT>), dim3((unsigned)((T + 63) / 64)), dim3(256), lds, st, *d, (const bf16_t*)x,
+                               tok_src, ln_w, ln_b, (const bf16_t*)wqkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v);
+        });
         return mivp_check_launch("swin_qkv_fwd(weight-stationary)");
     }
-    WIDE_SWITCH(L_W)
-#undef L_W
-    return mivp_check_launch("swin_qkv_fwd(wide)");
+    const bool known = for_wide_c(d->C, [&](auto c) {
+        constexpr int CT = decltype(c)::value / 16;
+        rc = launch_wide<CT>(k_qkv_fwd_wide<CT>, lds_qkv_fwd<CT>(), T, st, *d, (const bf16_t*)x, tok_src, ln_w, ln_b,
+                             (const bf16_t*)wqkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v);
+    });
+    if (!known) { mivp_set_error("tok_wide: C not in {96, 192, 384}"); return MIVP_EUNSUPPORTED; }
+    return rc ? rc : mivp_check_launch("swin_qkv_fwd(wide)");
 }
 
 int mivp_tok_wide_proj_mlp_fwd(const MivpSwinDesc* d, const void* o, const void* x, const int32_t* tok_src, const int32_t* tok_dst,
                                const void* wproj, const float* bproj, const float* ln_w, const float* ln_b, const void* wmlp,
                                const float* bmlp, void* t1_out, void* y, hipStream_t st) {
     const long T = (long)d->B * d->P * d->Nqp;
-#define L_W(CTV)                                                                                                              \
-    do {                                                                                                                      \
-        const size_t lds = lds_proj_mlp_fwd<CTV>();                                                                           \
-        MIVP_LDS_OPT_IN(k_proj_mlp_fwd_wide<CTV>, lds);                                                                       \
-        hipLaunchKernelGGL((k_proj_mlp_fwd_wide<CTV>), WIDE_GRID(CTV), dim3(256), lds, st, *d, (const bf16_t*)o,              \
-                           (const bf16_t*)x, tok_src, tok_dst, (const bf16_t*)wproj, bproj, ln_w, ln_b, (const bf16_t*)wmlp,  \
-                           bmlp, (bf16_t*)t1_out, (bf16_t*)y);                                                                \
-    } while (0)
-    ROWS_SWITCH(L_W)
-#undef L_W
-    return mivp_check_launch("swin_proj_mlp_fwd(wide)");
+    int rc = MIVP_OK;
+    const bool known = for_rows_c(d->C, [&](auto c) {
+        constexpr int CT = decltype(c)::value / 16;
+        rc = launch_wide<CT>(k_proj_mlp_fwd_wide<CT>, lds_proj_mlp_fwd<CT>(), T, st, *d, (const bf16_t*)o, (const bf16_t*)x, tok_src,
+                             tok_dst, (const bf16_t*)wproj, bproj, ln_w, ln_b, (const bf16_t*)wmlp, bmlp, (bf16_t*)t1_out,
+                             (bf16_t*)y);
+    });
+    if (!known) { mivp_set_error("tok_rows: C not in {48, 96, 192, 384}"); return MIVP_EUNSUPPORTED; }
+    return rc ? rc : mivp_check_launch("swin_proj_mlp_fwd(wide)");
 }
 
 int mivp_tok_wide_proj_mlp_bwd(const MivpSwinDesc* d, const void* dy, const int32_t* tok_dst, const void* t1, const float* ln_w,
                                const void* wmlp_t, const void* wproj_t, void* d_o, void* d_t1, hipStream_t st) {
     const long T = (long)d->B * d->P * d->Nqp;
-#define L_W(CTV)                                                                                                             \
-    do {                                                                                                                     \
-        const size_t lds = lds_proj_mlp_bwd<CTV>();                                                                          \
-        MIVP_LDS_OPT_IN(k_proj_mlp_bwd_wide<CTV>, lds);                                                                      \
-        hipLaunchKernelGGL((k_proj_mlp_bwd_wide<CTV>), WIDE_GRID(CTV), dim3(256), lds, st, *d, (const bf16_t*)dy, tok_dst,   \
-                           (const bf16_t*)t1, ln_w, (const bf16_t*)wmlp_t, (const bf16_t*)wproj_t, (bf16_t*)d_o,             \
-                           (bf16_t*)d_t1);                                                                                   \
-    } while (0)
-    ROWS_SWITCH(L_W)
-#undef L_W
-    return mivp_check_launch("swin_proj_mlp_bwd(wide)");
+    int rc = MIVP_OK;
+    const bool known = for_rows_c(d->C, [&](auto c) {
+        constexpr int CT = decltype(c)::value / 16;
+        rc = launch_wide<CT>(k_proj_mlp_bwd_wide<CT>, lds_proj_mlp_bwd<CT>(), T, st, *d, (const bf16_t*)dy, tok_dst,
+                             (const bf16_t*)t1, ln_w, (const bf16_t*)wmlp_t, (const bf16_t*)wproj_t, (bf16_t*)d_o, (bf16_t*)d_t1);
+    });
+    if (!known) { mivp_set_error("tok_rows: C not in {48, 96, 192, 384}"); return MIVP_EUNSUPPORTED; }
+    return rc ? rc : mivp_check_launch("swin_proj_mlp_bwd(wide)");
 }
 
 int mivp_tok_wide_qkv_bwd(const MivpSwinDesc* d, const void* dq, const void* dk, const void* dv, const void* x, const int32_t* tok_src,
                           const float* ln_w, const void* wqkv_t, const void* d_t1, void* dx, void* dn_out, hipStream_t st) {
     const long T = (long)d->B * d->P * d->Nqp;
-#define L_W(CTV)                                                                                                             \
-    do {                                                                                                                     \
-        const size_t lds = lds_qkv_bwd<CTV>();                                                                               \
-        MIVP_LDS_OPT_IN(k_qkv_bwd_wide<CTV>, lds);                                                                           \
-        hipLaunchKernelGGL((k_qkv_bwd_wide<CTV>), WIDE_GRID(CTV), dim3(256), lds, st, *d, (const bf16_t*)dq, (const bf16_t*)dk, \
-                           (const bf16_t*)dv, (const bf16_t*)x, tok_src, ln_w, (const bf16_t*)wqkv_t, (const bf16_t*)d_t1,   \
-                           (bf16_t*)dx, (bf16_t*)dn_out);                                                                    \
-    } while (0)
-    WIDE_SWITCH(L_W)
-#undef L_W
-    return mivp_check_launch("swin_qkv_bwd(wide)");
+    int rc = MIVP_OK;
+    const bool known = for_wide_c(d->C, [&](auto c) {
+        constexpr int CT = decltype(c)::value / 16;
+        rc = launch_wide<CT>(k_qkv_bwd_wide<CT>, lds_qkv_bwd<CT>(), T, st, *d, (const bf16_t*)dq, (const bf16_t*)dk,
+                             (const bf16_t*)dv, (const bf16_t*)x, tok_src, ln_w, (const bf16_t*)wqkv_t, (const bf16_t*)d_t1,
+                             (bf16_t*)dx, (bf16_t*)dn_out);
+    });
+    if (!known) { mivp_set_error("tok_wide: C not in {96, 192, 384}"); return MIVP_EUNSUPPORTED; }
+    return rc ? rc : mivp_check_launch("swin_qkv_bwd(wide)");
 }

@@ -26,12 +26,6 @@ namespace {
 constexpr int TN_TOK = 128;      // tokens per chunk (4 waves x 32)
 constexpr int TN_BLK = 64;       // output block edge
 
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-MIVP_DEV bf16x4 tr_read(const char* smem, int byte_off) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(smem + byte_off));
-}
-
 // LDS image of one operand chunk: blocks of 4 tokens x 16 channels (128 B, token-major inside the block);
 // block (t4, cb) lives at slot t4*4 + (cb ^ ((t4 >> 1) & 1)): the two 16-lane groups of a 32-lane half read
 // blocks two t4 apart in the same cb and the XOR puts those in opposite halves of the 256-byte bank row.
@@ -179,8 +173,8 @@ __global__ __launch_bounds__(256) void k_gemm_tn(MivpGemmTnDesc d, const bf16_t*
     const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
     auto frag = [&](const char* img, int ct) -> bf16x8 {
         const int t4 = wave * 8 + 2 * g;
-        const bf16x4 lo = tr_read(img, blk_off(t4, ct) + q * 32 + pp * 8);
-        const bf16x4 hi = tr_read(img, blk_off(t4 + 1, ct) + q * 32 + pp * 8);
+        const bf16x4 lo = tr_read(img + (blk_off(t4, ct) + q * 32 + pp * 8));
+        const bf16x4 hi = tr_read(img + (blk_off(t4 + 1, ct) + q * 32 + pp * 8));
         return cat44(lo, hi);
     };
 

@@ -104,45 +104,34 @@ def weights_from_state(sd, prefix, heads, embed_dim, n_prompt, device, need_bwd=
     return w
 
 
-def make_desc(B, C, heads, tb: BlockTables, n_prompt: int) -> L.SwinDesc:
+def _fill_desc(B, C, heads, window, P, Nq, Nqp, vol, n_prompt, has_mask) -> L.SwinDesc:
+    """The field rules of a block descriptor: prompt rows padded to 16, keys to 32, the bias augmentation to 4."""
     d = L.SwinDesc()
-    d.B, d.C, d.heads = B, C, heads
-    d.vol_in = d.vol_out = tb.dims[0] * tb.dims[1] * tb.dims[2]
-    d.P, d.Nq, d.Nqp = tb.P, tb.Nq, tb.Nqp
-    d.Np = n_prompt
-    d.Npp = round_up(n_prompt, 16) if n_prompt else 0
+    d.B, d.C, d.heads = int(B), int(C), int(heads)
+    d.vol_in = d.vol_out = int(vol)
+    d.P, d.Nq, d.Nqp = int(P), int(Nq), int(Nqp)
+    d.Np = int(n_prompt)
+    d.Npp = round_up(d.Np, 16)
     d.Nkp = round_up(d.Nqp + d.Npp, 32)
-    w = tb.window
+    w = [int(v) for v in window]
     d.aug = w[0] + w[1] + w[2] - 1
     d.augp = round_up(d.aug, 4)
-    d.has_mask = 1 if tb.has_mask else 0
+    d.has_mask = 1 if has_mask else 0
     for a in range(3):
         d.win[a] = w[a]
-    d.q_scale = float((C // heads) ** -0.5)
+    d.q_scale = float((d.C // d.heads) ** -0.5)
     d.ln_eps = 1e-6
     return d
+
+
+def make_desc(B, C, heads, tb: BlockTables, n_prompt: int) -> L.SwinDesc:
+    return _fill_desc(B, C, heads, tb.window, tb.P, tb.Nq, tb.Nqp, tb.dims[0] * tb.dims[1] * tb.dims[2], n_prompt, tb.has_mask)
 
 
 def prompt_desc(Cc: int, heads: int, window, n_prompt: int) -> L.SwinDesc:
-    """The descriptor fields the prompt-side kernels read (no volume geometry: B = P = 1)."""
-    d = L.SwinDesc()
-    d.B, d.C, d.heads = 1, int(Cc), int(heads)
-    w = [int(v) for v in window]
-    d.P = 1
-    d.Nq = w[0] * w[1] * w[2]
-    d.Nqp = round_up(d.Nq, 16)
-    d.vol_in = d.vol_out = d.Nq
-    d.Np = int(n_prompt)
-    d.Npp = round_up(n_prompt, 16)
-    d.Nkp = round_up(d.Nqp + d.Npp, 32)
-    d.aug = w[0] + w[1] + w[2] - 1
-    d.augp = round_up(d.aug, 4)
-    d.has_mask = 0
-    for a in range(3):
-        d.win[a] = w[a]
-    d.q_scale = float((Cc // heads) ** -0.5)
-    d.ln_eps = 1e-6
-    return d
+    """The descriptor fields the prompt-side kernels read (no volume geometry: one window, B = P = 1)."""
+    Nq = int(window[0]) * int(window[1]) * int(window[2])
+    return _fill_desc(1, Cc, heads, window, 1, Nq, round_up(Nq, 16), Nq, n_prompt, False)
 
 
 def prompt_aug_image(w: SwinBlockWeights, d: L.SwinDesc):

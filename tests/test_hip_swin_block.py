@@ -89,6 +89,16 @@ def test_block_forward_golden_shapes(tag):
     ((7, 7, 7), (6, 6, 24), 192, 4, 64, (3, 3, 3)),      # decoder with prompts: hd 48
     ((8, 8, 4), (16, 16, 16), 48, 4, 64, (4, 4, 2)),     # yml window
     ((8, 8, 4), (4, 4, 8), 192, 16, 0, (4, 4, 2)),       # divisible axis padded by a full window
+    # one 32-slot window per sample: the dispatch arms of the token kernels that the shapes above do not select
+    ((2, 4, 4), (2, 4, 4), 96, 8, 0, (0, 0, 0)),         # QKV in the column-split form at C = 96 (Nqp < 64: not weight-stationary)
+    ((2, 4, 4), (2, 4, 4), 192, 16, 0, (0, 0, 0)),       # ... at C = 192
+    ((2, 4, 4), (2, 4, 4), 128, 16, 0, (0, 0, 0)),       # 16-token kernels: QKV with four k-steps, proj + MLP with eight channel tiles
+    ((2, 4, 4), (2, 4, 4), 40, 10, 0, (0, 0, 0)),        # 16-token proj + MLP with three channel tiles (C = 48 takes the row images)
+    ((2, 4, 4), (2, 4, 4), 64, 16, 0, (0, 0, 0)),        # 16-token proj + MLP with four channel tiles
+    ((2, 4, 4), (2, 4, 4), 384, 32, 0, (0, 0, 0)),       # C = 384: column-split QKV and row-image proj + MLP with 24 channel tiles
+    # one 16-slot window (not a multiple of 32 slots): the 16-token kernels at the widths that otherwise take the row images
+    ((2, 2, 4), (2, 2, 4), 96, 8, 0, (0, 0, 0)),         # QKV with three k-steps, proj + MLP with six channel tiles
+    ((2, 2, 4), (2, 2, 4), 192, 16, 0, (0, 0, 0)),       # ... six k-steps, twelve channel tiles
 ])
 def test_block_forward_real_sizes(window, dims, C, heads, n_prompt, shift):
     import mivp_amd

@@ -103,6 +103,11 @@ def test_block_backward_golden_shapes(tag):
     ((7, 7, 7), (6, 6, 24), 192, 4, 0, (3, 3, 3), True),        # hd 48 without prompts: 22 key tiles, two per wave in the shifted dkv pass
     ((7, 7, 7), (6, 6, 24), 192, 4, 0, (0, 0, 0), True),        # ... three per wave (one workgroup per window and head) un-shifted
     ((8, 8, 4), (16, 16, 8), 48, 4, 64, (4, 4, 2), True),
+    ((2, 4, 4), (2, 4, 4), 128, 16, 0, (0, 0, 0), True),        # one 32-slot window: the 16-token backward kernels with eight channel tiles
+    ((2, 4, 4), (2, 4, 4), 64, 16, 0, (0, 0, 0), True),         # ... with four
+    ((2, 4, 4), (2, 4, 4), 384, 32, 0, (0, 0, 0), True),        # C = 384: the column-split / row-image backward kernels with 24 channel tiles
+    ((2, 2, 4), (2, 2, 4), 96, 8, 0, (0, 0, 0), True),          # one 16-slot window: the 16-token backward kernels with six channel tiles
+    ((2, 2, 4), (2, 2, 4), 192, 16, 0, (0, 0, 0), True),        # ... with twelve
 ])
 def test_block_backward_real_sizes(window, dims, C, heads, n_prompt, shift, need_dx):
     from oracle.unetr_ref import _block_state
