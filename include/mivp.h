@@ -1002,6 +1002,36 @@ int mivp_crop_fill(const int64_t* table, int32_t n_volumes, int32_t C, const int
 int mivp_crop_tensor(const float* src, int32_t Cs, const int32_t* sdims, const int32_t* slot, int32_t slot_stride,
                      int32_t B, const int32_t* roi, float* out, mivp_stream_t stream);
 
+/* Class-balanced crop centres for the batch filler (csrc/crops_index.hip; mivp_amd/batches.py).  Additive
+ * again: the ABI stays 18.  The centre of a crop is the rank-th voxel, in C order of the stored [H][W][D] label map, of
+ * class cls of the sample's volume (RandCropByPosNegLabeld / RandCropByLabelClassesd); the device resolves it from a
+ * per-volume index and writes the crop origin into the slot record that mivp_crop_fill reads.  Integers only, no atomics,
+ * bitwise reproducible, no host synchronisation; the pick records into a graph.
+ *   class of a voxel: c = lut[lab] (lut: DEVICE uint8 [256]); the voxel belongs to class c if c < num_classes (1..16),
+ *     otherwise to no class.  A chunk is 1024 consecutive voxels; nchunks = ceil(numel / 1024).
+ *   mivp_label_index_build: labels DEVICE uint8 [numel] (1 <= numel < 2^31; any alignment, dword loads where it is
+ *     4-byte aligned) -> index DEVICE int32 [num_classes][nchunks + 1]: row c holds the exclusive prefix sums of the
+ *     per-chunk counts of class c, the last column is the class total.  Two launches: a count (one 256-thread workgroup
+ *     per chunk, lane t reads voxels 4 t .. 4 t + 3 of the chunk, wave ballots and popcounts) and a scan (one workgroup per
+ *     class, in place, ascending).  MIVP_EINVAL for null pointers, non-positive sizes, num_classes outside 1..16 and an
+ *     nchunks other than ceil(numel / 1024).
+ *   mivp_crop_pick: table = the bank's source table of mivp_crop_fill; index_table DEVICE int64 [n_volumes][2] = (pointer
+ *     to the volume's index or 0, its nchunks); slot as for mivp_crop_fill (this call WRITES words 2..4 of a record);
+ *     pick DEVICE int32 [B][2] = (cls, rank); roi host int32 [3].  One 256-thread workgroup per sample: a binary search
+ *     of the class's prefix row for the chunk j with prefix[j] <= rank < prefix[j + 1], the chunk's labels with the
+ *     count's lane-to-voxel map, the (rank - prefix[j])-th match q by popcounts and ballots, q -> p = (q / (W D),
+ *     (q / D) % W, q % D), p -> r through the rotation (for axes (a, b): r_b = p_a, r_a = n_b - 1 - p_b, the inverse of the
+ *     rule above), and origin[k] = clamp(r[k] - roi[k] / 2, 0, max(n_rot[k] - roi[k], 0)) (MONAI's correct_crop_centers),
+ *     stored by the one lane that holds the voxel.  A sample whose volume id is outside [0, n_volumes), whose index row or
+ *     label pointer is 0, whose nchunks does not fit the volume, whose class is outside [0, num_classes), whose rank is
+ *     outside [0, total) or whose code is outside 0..3 is left unwritten.  The host validates the draws before it
+ *     uploads them. */
+int mivp_label_index_build(const uint8_t* labels, int64_t numel, const uint8_t* lut, int32_t num_classes, int32_t* index,
+                           int32_t nchunks, mivp_stream_t stream);
+int mivp_crop_pick(const int64_t* table, const int64_t* index_table, int32_t n_volumes, const uint8_t* lut,
+                   int32_t num_classes, int32_t* slot, int32_t slot_stride, const int32_t* pick, int32_t B,
+                   const int32_t* roi, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,13 @@ records into a graph, and a ``train.GraphedStep`` recorded on the filler's tenso
 
 The draw rule restates MONAI's documented ``get_random_patch`` (a uniform integer origin per axis); MONAI's own draw
 streams are not reproduced (``Compose`` reseeds every child transform), so parity is unpinned at that boundary, as for
-``augment`` and ``scan``.  The draw ORDER documented at ``draw_crops`` is this project's."""
+``augment`` and ``scan``.  The draw ORDER documented at ``draw_crops`` is this project's.
+
+Class-balanced crops (csrc/crops_index.hip): ``ClassIndex`` keeps, per volume, the prefix sums of the
+per-chunk class counts of its label map; ``draw_class_crops`` draws a class and a rank among that class's voxels
+(``RandCropByPosNegLabeld`` / ``RandCropByLabelClassesd``; MONAI's stream is not reproduced here either), and a class-mode
+``CropSlot`` has the device turn (class, rank) into the crop origin -- ``resolve``, one launch in front of the teacher's --
+so the label map is never read back and a recorded ``fill`` still follows the slot."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -26,6 +32,7 @@ from ._host import check_gpu, check_int_from, i3, plain_int
 HEAD = 5                        # int32 words per sample in front of the students' origins: volume, rot, origin[3] (mivp.h)
 ROT_AXES = {1: (0, 1), 2: (0, 2), 3: (1, 2)}    # rotation code -> the spatial axes of torch.rot90(k=1)
 MAX_CHANNELS = 16
+MAX_CLASSES = 16                # of a ClassIndex (mivp.h)
 
 
 def _size3(name: str, v) -> Tuple[int, int, int]:
@@ -220,21 +227,239 @@ class VolumeBank:
         return vid
 
 
+class ClassIndex:
+    """Where the voxels of each class are, per volume of ``bank``, for class-balanced crops.
+
+    A voxel belongs to class ``c = label_table(active_labels)[lab]`` if ``c < num_classes`` (1..16), otherwise to no
+    class; voxels count in C order of the stored ``[H, W, D]`` label map, in chunks of ``CHUNK`` voxels.  Each indexed volume
+    gets an int32 ``[num_classes][nchunks + 1]`` tensor (``prefix[vid]``): the exclusive prefix sums of the per-chunk class
+    counts, the last column the class total.  ``table`` -- int64 ``[bank.capacity][2]`` = (pointer to that tensor or 0,
+    nchunks) -- is ONE allocation made here and never replaced, like the bank's source table: a graph recorded earlier
+    serves volumes indexed later.
+
+    ``update()`` indexes every bank volume not indexed yet (two launches each) and leaves ``counts`` on the host: numpy
+    int64 ``[n_volumes][num_classes]``, what ``draw_class_crops`` and ``ClassCropDraws.check`` read.  It is outside the step:
+    it makes one blocking read per call and refuses during a graph capture."""
+
+    CHUNK = 1024
+
+    def __init__(self, bank: "VolumeBank", num_classes: int, active_labels=None):
+        if not isinstance(bank, VolumeBank):
+            raise ValueError("ClassIndex: a VolumeBank expected (a GPU bank: no CPU fallback)")
+        if not plain_int(num_classes) or not 1 <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError(f"ClassIndex: num_classes must be an integer in 1..{MAX_CLASSES}, got {num_classes!r}")
+        self.bank, self.num_classes = bank, int(num_classes)
+        self.lut = torch.from_numpy(label_table(active_labels)).to(bank.device)
+        self.table = torch.zeros((bank.capacity, 2), dtype=torch.int64, device=bank.device)      # (mivp.h)
+        self.prefix = []
+        self.counts = np.zeros((0, self.num_classes), dtype=np.int64)
+
+    def __len__(self) -> int:
+        return len(self.prefix)
+
+    def update(self) -> "ClassIndex":
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ClassIndex.update: not while a graph is being recorded (it reads the class totals back)")
+        bank, first = self.bank, len(self.prefix)
+        for vid in range(first, len(bank)):
+            if bank.labels[vid] is None:
+                raise ValueError(f"ClassIndex.update: volume {vid} of the bank has no label map")
+        new = []
+        for vid in range(first, len(bank)):
+            lab = bank.labels[vid]
+            nch = -(-lab.numel() // self.CHUNK)
+            t = torch.empty((self.num_classes, nch + 1), dtype=torch.int32, device=bank.device)
+            L.call("mivp_label_index_build", L.ptr(lab), lab.numel(), L.ptr(self.lut), self.num_classes, L.ptr(t), nch,
+                   L.stream())
+            new.append(t)
+        if new:
+            totals = torch.stack([t[:, -1] for t in new]).cpu().numpy().astype(np.int64)          # the one blocking read
+            rows = torch.tensor([[t.data_ptr(), t.shape[1] - 1] for t in new], dtype=torch.int64)
+            self.table[first:first + len(new)].copy_(rows.pin_memory(), non_blocking=True)
+            self.prefix += new
+            self.counts = np.concatenate([self.counts, totals])
+        return self
+
+
+@dataclass
+class ClassCropDraws:
+    """What one class-balanced step draws on the host, one entry per sample: the crop is centred on voxel ``rank`` (in C
+    order of the stored label map) of class ``cls`` of ``volume``.  The origin is the one value only the device knows
+    (``CropSlot.resolve``)."""
+    volume: np.ndarray              # int32 [B]: the bank's volume id
+    rot: np.ndarray                 # int32 [B]: the rotation code, as in CropDraws
+    cls: np.ndarray                 # int32 [B]: the class of the centre voxel
+    rank: np.ndarray                # int32 [B]: which voxel of that class, 0 .. counts[volume][cls] - 1
+    student_origin: np.ndarray      # int32 [S, B, 3]: each student's origin inside the teacher crop
+
+    @property
+    def batch(self) -> int:
+        return int(np.shape(self.volume)[0])
+
+    @property
+    def n_students(self) -> int:
+        return int(np.shape(self.student_origin)[0])
+
+    def pack(self) -> np.ndarray:
+        """int32 [B, 5 + 3 S]: the slot's records, the origin words 0 (the pick launch writes them)."""
+        return CropDraws(self.volume, self.rot, np.zeros((self.batch, 3), np.int32), self.student_origin).pack()
+
+    def picks(self) -> np.ndarray:
+        """int32 [B, 2] = (cls, rank): the slot's pick buffer."""
+        return np.stack([np.asarray(self.cls), np.asarray(self.rank)], axis=1).astype(np.int32)
+
+    def check(self, index, roi, student_sizes=()):
+        """Every draw against ``index`` (a ``ClassIndex``, or anything with its ``counts`` and ``num_classes``): the volume is
+        indexed, the code is in 0..3, the class exists, the rank is below the class's count in that volume and the students'
+        origins are in range.  Nothing unchecked is ever uploaded.  Raises ``ValueError`` naming the sample."""
+        counts, nc = np.asarray(index.counts), int(index.num_classes)
+        roi = _size3("roi", roi)
+        sizes = [_size3("student size", s) for s in student_sizes]
+        arrays = [np.asarray(a) for a in (self.volume, self.rot, self.cls, self.rank, self.student_origin)]
+        if any(a.dtype.kind not in "iu" for a in arrays):
+            raise ValueError("ClassCropDraws: integer arrays expected")
+        vol, rot, cls, rank, st = [a.astype(np.int64) for a in arrays]
+        B = vol.shape[0] if vol.ndim == 1 else -1
+        if B < 1 or rot.shape != (B,) or cls.shape != (B,) or rank.shape != (B,) or st.shape != (len(sizes), B, 3):
+            raise ValueError(f"ClassCropDraws: volume, rot, cls and rank [B] and student_origin [{len(sizes)}, B, 3] of one "
+                             f"batch size expected, got {vol.shape}, {rot.shape}, {cls.shape}, {rank.shape}, {st.shape}")
+
+        def refuse(bad, what):
+            if bad.any():
+                b = int(np.flatnonzero(bad)[0])
+                raise ValueError(f"ClassCropDraws: sample {b}: {what(b)}")
+
+        refuse((vol < 0) | (vol >= len(counts)),
+               lambda b: f"volume id {vol[b]} is not indexed (the index holds volumes 0..{len(counts) - 1})")
+        refuse((rot < 0) | (rot > 3), lambda b: f"rotation code {rot[b]} outside 0..3")
+        refuse((cls < 0) | (cls >= nc), lambda b: f"class {cls[b]} outside 0..{nc - 1}")
+        total = counts[vol, cls]
+        refuse((rank < 0) | (rank >= total),
+               lambda b: f"rank {rank[b]} outside [0, {total[b]}), the voxels of class {cls[b]} in volume {vol[b]}")
+        for s, size in enumerate(sizes):
+            hi = np.asarray([max(roi[k] - size[k], 0) for k in range(3)])
+            refuse(((st[s] < 0) | (st[s] > hi)).any(axis=1),
+                   lambda b: f"origin {st[s, b].tolist()} of student {s} outside [0, {hi.tolist()}] (roi {roi}, student "
+                             f"size {size})")
+        return self
+
+
+def draw_class_crops(rs: np.random.RandomState, index, volume_ids: Sequence[int], roi, num_samples: int, ratios,
+                     random_orientation: bool = False, student_sizes=()) -> ClassCropDraws:
+    """The host draws of one batch of ``len(volume_ids) * num_samples`` class-balanced crops from ONE RandomState, in this
+    order (``counts = index.counts``, ``v`` the sample's volume):
+
+    1. for each volume of ``volume_ids``, in order: one ``rs.randint(3)`` if ``random_orientation``, exactly as
+       ``draw_crops`` step 1;
+    2. then per sample: ``p = ratios * (counts[v] > 0)`` (``ValueError`` naming the volume if that sums to 0),
+       ``cls = rs.choice(num_classes, p=p / p.sum())``, then ``rank = rs.randint(0, counts[v][cls])``;
+    3. then per sample, per student and per axis: ``rs.randint(0, roi - min(s, roi) + 1)``, exactly as ``draw_crops`` step 3.
+
+    ``ratios`` holds one non-negative weight per class of the index.  ``ratios=(neg, pos)`` with ``num_classes=2`` is
+    MONAI's ``RandCropByPosNegLabeld``, longer ``ratios`` are ``RandCropByLabelClassesd``: a centre uniform among the voxels
+    of a class chosen by the ratios, never a class the volume lacks.  MONAI's own stream is NOT reproduced (as for
+    ``draw_crops``): parity is unpinned at the MONAI boundary and this order is the project's own."""
+    roi = _size3("roi", roi)
+    sizes = [_size3("student size", s) for s in student_sizes]
+    counts, nc = np.asarray(index.counts), int(index.num_classes)
+    ids = [int(v) for v in volume_ids]
+    check_int_from("num_samples", num_samples, 1)
+    if not ids or any(not 0 <= v < len(counts) for v in ids):
+        raise ValueError(f"draw_class_crops: volume_ids {ids} must be a non-empty list of indexed ids in 0..{len(counts) - 1}")
+    w = np.asarray(ratios, dtype=np.float64)
+    if w.shape != (nc,) or not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError(f"draw_class_crops: ratios must be {nc} finite non-negative weights, got {ratios!r}")
+    B = len(ids) * int(num_samples)
+    d = ClassCropDraws(np.repeat(np.asarray(ids, np.int32), int(num_samples)), np.zeros(B, np.int32), np.zeros(B, np.int32),
+                       np.zeros(B, np.int32), np.zeros((len(sizes), B, 3), np.int32))
+    if random_orientation:
+        for i in range(len(ids)):
+            d.rot[i * num_samples:(i + 1) * num_samples] = int(rs.randint(3)) + 1
+    for b in range(B):
+        v = int(d.volume[b])
+        p = w * (counts[v] > 0)
+        if not p.sum() > 0:
+            raise ValueError(f"draw_class_crops: volume {v} holds no voxel of a class with a positive ratio (counts "
+                             f"{counts[v].tolist()}, ratios {w.tolist()})")
+        d.cls[b] = rs.choice(nc, p=p / p.sum())
+        d.rank[b] = rs.randint(0, counts[v][d.cls[b]])
+    for b in range(B):
+        for s, size in enumerate(sizes):
+            for k in range(3):
+                d.student_origin[s, b, k] = rs.randint(0, roi[k] - min(size[k], roi[k]) + 1)
+    return d
+
+
 class CropSlot:
     """Fixed device memory of one batch's draws -- int32 [B][5 + 3 S] records -- whose pointer a recorded graph keeps.
     ``load`` checks the draws against the bank, then refreshes the records from a new pinned staging buffer without blocking;
-    it does nothing while a graph is being recorded, exactly as ``augment.IntensitySlot.load``."""
+    it does nothing while a graph is being recorded, exactly as ``augment.IntensitySlot.load``.
 
-    def __init__(self, B: int, n_students: int, device):
+    With ``class_index`` the slot is in class mode for life: it also owns the int32 [B][2] pick buffer (class, rank) behind
+    the records, ``load`` takes ``ClassCropDraws`` only and uploads records whose origin words are 0, and ``resolve`` issues
+    the launch that writes them."""
+
+    def __init__(self, B: int, n_students: int, device, class_index: Optional[ClassIndex] = None):
         self.B = check_int_from("B", B, 1)
         self.n_students = check_int_from("n_students", n_students, 0)
         self.words = record_words(self.n_students)
-        self.records = torch.zeros(self.B * self.words, dtype=torch.int32, device=device)
+        self.class_index = class_index
+        if class_index is None:
+            self.records = torch.zeros(self.B * self.words, dtype=torch.int32, device=device)
+            self.picks = None
+        else:
+            device = torch.device(device)
+            if not isinstance(class_index, ClassIndex) or device.type != "cuda":
+                raise ValueError("CropSlot: class_index must be a ClassIndex and the device its bank's GPU (no CPU fallback)")
+            if device.index is None:
+                device = torch.device("cuda", torch.cuda.current_device())
+            if device != class_index.bank.device or self.B > 65535:
+                raise ValueError(f"CropSlot: a class-mode slot of batch <= 65535 on {class_index.bank.device} expected, got "
+                                 f"batch {self.B} on {device}")
+            self.buffer = torch.zeros(self.B * (self.words + 2), dtype=torch.int32, device=device)     # ONE upload per load
+            self.records, self.picks = self.buffer[:self.B * self.words], self.buffer[self.B * self.words:]
         self.student_views = [self.records[HEAD + 3 * s:] for s in range(self.n_students)]   # advanced to the origin words
         self.draws = None
         self.checked = None             # (bank shapes, roi, student sizes) the loaded draws were checked against
 
+    def _load_class(self, draws, bank, roi, student_sizes):
+        index = self.class_index
+        if not isinstance(draws, ClassCropDraws):
+            raise ValueError("CropSlot.load: a class-mode slot takes ClassCropDraws only")
+        if bank is not index and bank is not index.bank:
+            raise ValueError("CropSlot.load: a class-mode slot loads against its own index (or that index's bank)")
+        if len(tuple(student_sizes)) != self.n_students:
+            raise ValueError(f"CropSlot: {len(tuple(student_sizes))} student sizes for a slot of {self.n_students} students")
+        if draws.check(index, roi, student_sizes).batch != self.B:
+            raise ValueError(f"CropSlot: draws of batch {draws.batch} do not match the slot's batch {self.B}")
+        if torch.cuda.is_current_stream_capturing():
+            return
+        words = np.concatenate([draws.pack().reshape(-1), draws.picks().reshape(-1)])
+        self.buffer.copy_(torch.from_numpy(words).pin_memory(), non_blocking=True)
+        self.draws = draws
+        self.checked = (index, _size3("roi", roi), [_size3("student size", s) for s in student_sizes])
+
+    def resolve(self, roi):
+        """Class mode: the pick launch alone, on the current stream -- it writes the crop origin of every sample into the
+        records (words 2..4) from the index.  No host read; records into a graph."""
+        index = self.class_index
+        if index is None:
+            raise ValueError("CropSlot.resolve: the slot has no class index (its draws carry their origins)")
+        if self.draws is None:
+            raise ValueError("CropSlot.resolve: the slot holds no draws (CropSlot.load)")
+        roi = _size3("roi", roi)
+        if roi != self.checked[1]:
+            raise ValueError(f"CropSlot.resolve: roi {roi}, but the slot's draws were checked against roi {self.checked[1]}")
+        L.call("mivp_crop_pick", L.ptr(index.bank.table), L.ptr(index.table), index.bank.capacity, L.ptr(index.lut),
+               index.num_classes, L.ptr(self.records), self.words, L.ptr(self.picks), self.B, i3(roi), L.stream())
+
+    def resolved_origins(self) -> np.ndarray:
+        """int32 [B, 3]: the origin words as they stand on the device.  A BLOCKING read, for tests and debugging only."""
+        return self.records.view(self.B, self.words)[:, 2:HEAD].cpu().numpy()
+
     def load(self, draws: CropDraws, bank, roi, student_sizes=()):
+        if self.class_index is not None:
+            return self._load_class(draws, bank, roi, student_sizes)
         if not isinstance(draws, CropDraws):
             raise ValueError("CropSlot.load: CropDraws expected")
         if len(tuple(student_sizes)) != self.n_students:
@@ -261,12 +486,19 @@ class BatchFiller:
 
     ``fill(draws_or_slot)`` issues one bank-mode launch for the teacher and one tensor-mode launch per student and kind on
     the current stream; no host read, no allocation.  The outputs are fixed tensors: a graph recorded on them (``fill``
-    itself, or a ``GraphedStep`` whose inputs they are) sees every later ``fill``."""
+    itself, or a ``GraphedStep`` whose inputs they are) sees every later ``fill``.
+
+    With ``class_index`` the filler's own slot is in class mode and ``fill`` takes ``ClassCropDraws`` (or a class-mode slot
+    of the same index): it issues the pick launch first (``CropSlot.resolve``), then the teacher, then the students, so a
+    recorded ``fill`` contains the pick and is fed by ``slot.load`` before each replay, as without an index."""
 
     def __init__(self, bank: VolumeBank, roi, batch: int, student_sizes=(), active_labels=None, with_coord: bool = False,
-                 with_mask: bool = True):
+                 with_mask: bool = True, class_index: Optional[ClassIndex] = None):
         if not isinstance(bank, VolumeBank):
             raise ValueError("BatchFiller: a VolumeBank expected")
+        if class_index is not None and (not isinstance(class_index, ClassIndex) or class_index.bank is not bank):
+            raise ValueError("BatchFiller: class_index must be a ClassIndex of this bank")
+        self.class_index = class_index
         self.bank, self.roi, self.B = bank, _size3("roi", roi), check_int_from("batch", batch, 1)
         self.student_sizes = [_size3("student size", s) for s in student_sizes]
         if self.B > 65535 or any(v > 65535 for v in self.roi + tuple(a for s in self.student_sizes for a in s)):
@@ -281,7 +513,7 @@ class BatchFiller:
         self.image_st = [new(Cn, s) for s in self.student_sizes]
         self.coord_st = [new(3, s) for s in self.student_sizes]
         self.mask_st_0 = new(1, self.student_sizes[0]) if (S and with_mask) else None
-        self.slot = CropSlot(self.B, S, dev)
+        self.slot = CropSlot(self.B, S, dev, class_index=class_index)
         self.xy = (self.image, self.mask)
         if S:
             self.batch = dict(image=self.image, coord=self.coord, image_st=self.image_st, coord_st=self.coord_st)
@@ -314,10 +546,11 @@ class BatchFiller:
 
     @torch.no_grad()
     def fill(self, draws_or_slot=None):
-        """``CropDraws``: checked and loaded into the filler's own slot first.  A ``CropSlot``: used as it stands (its
-        ``load`` did the checking).  ``None``: the filler's own slot as last loaded."""
+        """``CropDraws`` (``ClassCropDraws`` on a filler with a class index): checked and loaded into the filler's own slot
+        first.  A ``CropSlot``: used as it stands (its ``load`` did the checking).  ``None``: the filler's own slot as last
+        loaded."""
         slot = self.slot
-        if isinstance(draws_or_slot, CropDraws):
+        if isinstance(draws_or_slot, (CropDraws, ClassCropDraws)):
             slot.load(draws_or_slot, self.bank, self.roi, self.student_sizes)
         elif isinstance(draws_or_slot, CropSlot):
             slot = draws_or_slot
@@ -327,12 +560,20 @@ class BatchFiller:
             raise ValueError(f"BatchFiller.fill: a slot of batch {slot.B} / {slot.n_students} students on "
                              f"{slot.records.device} for a filler of batch {self.B} / {len(self.student_sizes)} students on "
                              f"{self.bank.device}")
+        if (slot.class_index is None) != (self.class_index is None):
+            raise ValueError("BatchFiller.fill: a class-mode slot needs a filler with a class index, and a filler with a "
+                             "class index a class-mode slot")
         if slot.draws is None:
             raise ValueError("BatchFiller.fill: the slot holds no draws (CropSlot.load)")
         shapes, roi, sizes = slot.checked
-        if shapes != tuple(self.bank.shapes[:len(shapes)]) or roi != self.roi or sizes != self.student_sizes:
+        if self.class_index is not None:
+            if shapes is not self.class_index or roi != self.roi or sizes != self.student_sizes:
+                raise ValueError("BatchFiller.fill: the slot's draws were checked against another index, roi or student sizes")
+        elif shapes != tuple(self.bank.shapes[:len(shapes)]) or roi != self.roi or sizes != self.student_sizes:
             raise ValueError("BatchFiller.fill: the slot's draws were checked against another bank, roi or student sizes")
         self._check_outputs()
+        if self.class_index is not None:
+            slot.resolve(self.roi)
         self._fill_teacher(slot)
         self._fill_students(slot)
         return self.batch

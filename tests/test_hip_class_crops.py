@@ -1,0 +1,419 @@
+"""GPU tests of the class-balanced crop sampling (mivp_amd.batches: ClassIndex, class-mode CropSlot / BatchFiller;
+csrc/crops_index.hip) against the plain numpy restatement in tests/class_crops_ref.py -- ``flatnonzero``, ``unravel_index``,
+``rot90`` of an index volume, the clamp.  Everything is integers or moved values, so every comparison is exact.  Nothing
+here hands the device a draw that the host checks refuse, except the three kinds of record that make a workgroup return
+(test_invalid_records_leave_the_origin_unwritten), written straight to the pick buffer."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import class_crops_ref as CR
+import crops_ref as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+# (13, 9, 21): 2457 voxels, 3 chunks, a 409-voxel tail, numel % 4 = 1; (6, 8, 5): 240 voxels, less than one chunk;
+# (70, 5, 67): 23450 voxels, 23 chunks (the search has depth); (16, 8, 8): exactly one chunk; (32, 8, 8): exactly two
+SHAPES = [(13, 9, 21), (6, 8, 5), (70, 5, 67), (16, 8, 8), (32, 8, 8)]
+ACTIVE, NCLS = [2, 5], 3        # label 5 is class 1, every other label class 0 (map_label_indices), class 2 exists nowhere
+ROIS = [(8, 8, 8), (8, 12, 4), (7, 5, 9)]
+INSIDE = (6, 4, 10)             # a voxel of volume 0 whose 8^3 crop needs no clamp under any code; (7, 4, 10) is another
+_state = {}
+
+
+def _labels():
+    """Labels 0..7 at random, then planted: volume 1: class 1's only voxel is the FIRST; volume 2: class 1's only voxel is
+    the LAST (in the tail chunk); volume 3: all class 1 (class 0 is absent); volume 0: the two INSIDE voxels are class 1
+    and class 0.  Class 2 is absent everywhere."""
+    if "labels" not in _state:
+        g = torch.Generator().manual_seed(23)
+        labs = [torch.randint(0, 8, s, generator=g, dtype=torch.uint8).numpy() for s in SHAPES]
+        for v in (1, 2):
+            labs[v][labs[v] == 5] = 4
+        labs[1].reshape(-1)[0] = 5
+        labs[2].reshape(-1)[-1] = 5
+        labs[3][:] = 5
+        labs[0][INSIDE] = 5
+        labs[0][7, 4, 10] = 3
+        _state["labels"] = labs
+    return _state["labels"]
+
+
+def _bank(channels):
+    """(VolumeBank, ClassIndex, images, device labels): arange-based images (every voxel value of the bank is unique)."""
+    from mivp_amd import batches as BT
+    key = ("bank", channels)
+    if key not in _state:
+        bank, images, labels, first = BT.VolumeBank(DEV, channels), [], [], 1
+        for s, lab in zip(SHAPES, _labels()):
+            n = channels * s[0] * s[1] * s[2]
+            images.append(torch.arange(first, first + n, dtype=torch.float32).reshape((channels,) + s).to(DEV))
+            labels.append(torch.from_numpy(lab).to(DEV))
+            first += n
+            bank.add(images[-1], labels[-1])
+        index = BT.ClassIndex(bank, NCLS, ACTIVE).update()
+        _state[key] = (bank, index, images, labels)
+    return _state[key]
+
+
+def _lut():
+    from mivp_amd import batches as BT
+    return BT.label_table(ACTIVE)
+
+
+def _grid(shape, device):
+    from mivp_amd.students_teacher import coord_grid
+    return coord_grid(shape, device)
+
+
+def _every_pick(counts_v, volume, code):
+    """ClassCropDraws that hold every (cls, rank) pair of one volume: each of its voxels exactly once."""
+    from mivp_amd import batches as BT
+    cls = np.concatenate([np.full(int(n), c, np.int32) for c, n in enumerate(counts_v)])
+    rank = np.concatenate([np.arange(int(n), dtype=np.int32) for n in counts_v])
+    B = len(cls)
+    return BT.ClassCropDraws(np.full(B, volume, np.int32), np.full(B, code, np.int32), cls, rank, np.zeros((0, B, 3), np.int32))
+
+
+def _prefill(slot, value=-7):
+    slot.records.view(slot.B, slot.words)[:, 2:5] = value
+
+
+# ------------------------------------------------------------------------------------------------ 1. the index
+def test_index_equals_the_per_chunk_counts():
+    from mivp_amd import batches as BT
+    bank, index, _, _ = _bank(1)
+    assert len(index) == 5 and index.counts.shape == (5, NCLS) and index.counts.dtype == np.int64
+    table = index.table.cpu().numpy()
+    assert table.shape == (bank.capacity, 2) and not table[5:].any()
+    for v, lab in enumerate(_labels()):
+        want = CR.chunk_prefix(lab, _lut(), NCLS)
+        got = index.prefix[v]
+        assert got.dtype == torch.int32 and tuple(got.shape) == want.shape == (NCLS, -(-lab.size // BT.ClassIndex.CHUNK) + 1)
+        assert np.array_equal(got.cpu().numpy(), want), v
+        assert index.counts[v].tolist() == want[:, -1].tolist()
+        assert table[v].tolist() == [got.data_ptr(), want.shape[1] - 1]
+    assert index.counts.tolist() == [[2457 - index.counts[0][1], index.counts[0][1], 0], [239, 1, 0], [23449, 1, 0],
+                                     [0, 1024, 0], [2048 - index.counts[4][1], index.counts[4][1], 0]]
+    assert 200 < index.counts[0][1] < 420 and 150 < index.counts[4][1] < 360        # about an eighth of the voxels
+    again = BT.ClassIndex(bank, NCLS, ACTIVE).update()          # integers: the same bits
+    assert all(torch.equal(a, b) for a, b in zip(again.prefix, index.prefix)) and np.array_equal(again.counts, index.counts)
+    before = index.table.clone()
+    assert index.update() is index and len(index) == 5 and torch.equal(index.table, before)   # nothing new: nothing done
+
+
+def test_index_with_the_identity_table_unaligned_labels_and_refusals():
+    """``active_labels=None``, 5 classes: labels 5..7 belong to no class.  A label map at an odd address (a contiguous slice
+    that starts one byte into its storage) takes the byte path and gives the same index; its picks are exact too."""
+    from mivp_amd import batches as BT
+    lab = _labels()[0]
+    store = torch.zeros(lab.size + 1, dtype=torch.uint8, device=DEV)
+    store[1:] = torch.from_numpy(lab.reshape(-1)).to(DEV)
+    odd = store[1:].view(lab.shape)
+    assert odd.is_contiguous() and odd.data_ptr() % 4 == 1
+    bank = BT.VolumeBank(DEV, 1, capacity=4)
+    image = torch.zeros((1,) + lab.shape, device=DEV)
+    bank.add(image, torch.from_numpy(lab).to(DEV))
+    bank.add(image, odd)
+    index = BT.ClassIndex(bank, 5).update()
+    lut = BT.label_table(None)
+    want = CR.chunk_prefix(lab, lut, 5)
+    assert want[:, -1].sum() == int((lab < 5).sum()) < lab.size
+    for v in (0, 1):
+        assert np.array_equal(index.prefix[v].cpu().numpy(), want)
+    draws = _every_pick(index.counts[1], 1, 3)
+    slot = BT.CropSlot(draws.batch, 0, DEV, class_index=index)
+    slot.load(draws, index, (7, 5, 9))
+    _prefill(slot)
+    slot.resolve((7, 5, 9))
+    assert np.array_equal(slot.resolved_origins(), CR.origins([lab, lab], lut, 5, draws, (7, 5, 9))[0])
+
+    bank.add(image)                                             # a volume without labels
+    with pytest.raises(ValueError, match="volume 2 .* no label map"):
+        index.update()
+    assert len(index) == 2
+    for bad in (0, 17, 2.0, True):
+        with pytest.raises(ValueError, match="num_classes"):
+            BT.ClassIndex(bank, bad)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        slot.resolve((7, 5, 9))                                 # recording the pick is fine, indexing is not
+        with pytest.raises(RuntimeError, match="recorded"):
+            index.update()
+
+
+# ------------------------------------------------------------------------------------------------ 2. the pick, exhaustively
+@pytest.mark.parametrize("volume", range(len(SHAPES)))
+def test_every_voxel_is_picked_exactly_once(volume):
+    """ONE ``resolve`` per (code, roi) whose batch holds every (cls, rank) pair of the volume.  The rois cover even and odd
+    ``roi / 2``, the clamp on both sides and a roi larger than the volume; with roi (1, 1, 1) the origin IS the rotated
+    voxel, so the origins of one launch are as many distinct voxels as the volume has."""
+    from mivp_amd import batches as BT
+    bank, index, _, _ = _bank(1)
+    numel = int(np.prod(SHAPES[volume]))
+    assert int(index.counts[volume].sum()) == numel < 65535     # every voxel has a class under this table
+    slot = BT.CropSlot(numel, 0, DEV, class_index=index)
+    for code in range(4):
+        draws = _every_pick(index.counts[volume], volume, code)
+        for roi in ROIS + [(1, 1, 1)]:
+            slot.load(draws, index, roi)
+            _prefill(slot)
+            slot.resolve(roi)
+            got = slot.resolved_origins()
+            want, _ = CR.origins(_labels(), _lut(), NCLS, draws, roi)
+            assert got.dtype == np.int32 and np.array_equal(got, want), (code, roi, int((got != want).any(axis=1).sum()))
+            if roi == (1, 1, 1):
+                n_rot = BT.rotated_shape(SHAPES[volume], code)
+                assert len(np.unique(np.ravel_multi_index(tuple(got.T), n_rot))) == numel
+
+
+# ------------------------------------------------------------------------------------------------ 3. invalid records
+def test_invalid_records_leave_the_origin_unwritten():
+    """Records that ``check`` refuses, written straight to the device with values that make the workgroup return: rank =
+    the class total, class = num_classes, and a volume of the bank that is not indexed (an empty index row)."""
+    from mivp_amd import batches as BT
+    labs = _labels()
+    bank = BT.VolumeBank(DEV, 1, capacity=4)
+    bank.add(torch.zeros((1,) + SHAPES[0], device=DEV), torch.from_numpy(labs[0]).to(DEV))
+    index = BT.ClassIndex(bank, NCLS, ACTIVE).update()
+    bank.add(torch.zeros((1,) + SHAPES[1], device=DEV), torch.from_numpy(labs[1]).to(DEV))      # in the bank, not indexed
+    total = int(index.counts[0][1])
+    roi = (8, 8, 8)
+    good = BT.ClassCropDraws(np.zeros(4, np.int32), np.array([0, 1, 2, 3], np.int32), np.array([1, 0, 1, 0], np.int32),
+                             np.array([total - 1, 5, 0, 9], np.int32), np.zeros((0, 4, 3), np.int32))
+    bad = [("rank", 0, total, "sample 0: rank"), ("cls", 1, NCLS, "sample 1: class"), ("volume", 2, 1, "sample 2: volume id")]
+    for field, b, value, match in bad:
+        d = copy.deepcopy(good)
+        getattr(d, field)[b] = value
+        with pytest.raises(ValueError, match=match):
+            d.check(index, roi)
+    slot = BT.CropSlot(4, 0, DEV, class_index=index)
+    with pytest.raises(ValueError, match="no draws"):
+        slot.resolve(roi)
+    slot.load(good, index, roi)
+    _prefill(slot)
+    slot.picks.view(4, 2)[0, 1] = total
+    slot.picks.view(4, 2)[1, 0] = NCLS
+    slot.records.view(4, slot.words)[2, 0] = 1
+    slot.resolve(roi)
+    got = slot.resolved_origins()
+    assert got[:3].tolist() == [[-7, -7, -7]] * 3               # as prefilled
+    assert got[3].tolist() == CR.origin(labs[0], _lut(), NCLS, 3, 0, 9, roi)[0]       # the launch did run
+    with pytest.raises(ValueError, match="roi"):
+        slot.resolve((8, 8, 4))
+    with pytest.raises(ValueError, match="ClassCropDraws"):
+        slot.load(BT.CropDraws(good.volume, good.rot, np.zeros((4, 3), np.int32), good.student_origin), index, roi)
+    with pytest.raises(ValueError, match="own index"):
+        slot.load(good, _bank(1)[0], roi)
+    with pytest.raises(ValueError, match="no class index"):
+        BT.CropSlot(4, 0, DEV).resolve(roi)
+
+
+# ------------------------------------------------------------------------------------------------ 4. end to end
+STUDENTS = [(8, 8, 8), (6, 6, 6)]
+
+
+def _e2e_draws(index, seed, roi=(8, 8, 8), sizes=STUDENTS):
+    """Two samples per volume drawn by ``draw_class_crops`` under random codes, then the two INSIDE voxels of volume 0 under
+    each of the four codes (their crops need no clamp)."""
+    from mivp_amd import batches as BT
+    rs = np.random.RandomState(seed)
+    d = BT.draw_class_crops(rs, index, [0, 1, 2, 3, 4], roi, 2, (1, 2, 1), True, sizes)
+    picks = [CR.rank_of(_labels()[0], _lut(), NCLS, p) for p in (INSIDE, (7, 4, 10))]
+    assert [c for c, _ in picks] == [1, 0]
+    extra = [(code, c, r) for code in range(4) for c, r in picks]
+    st = np.concatenate([d.student_origin, rs.randint(0, 3, (len(sizes), len(extra), 3)) * (np.asarray(sizes)[:, None, :] < 8)],
+                        axis=1).astype(np.int32)
+    return BT.ClassCropDraws(np.concatenate([d.volume, np.zeros(len(extra), np.int32)]),
+                             np.concatenate([d.rot, np.array([e[0] for e in extra], np.int32)]),
+                             np.concatenate([d.cls, np.array([e[1] for e in extra], np.int32)]),
+                             np.concatenate([d.rank, np.array([e[2] for e in extra], np.int32)]), st)
+
+
+def _poison(filler):
+    outs = [filler.image, filler.mask, filler.coord, filler.mask_st_0] + filler.image_st + filler.coord_st
+    for t in outs:
+        if t is not None:
+            t.fill_(float("nan"))
+
+
+def _check_batch(filler, draws, channels, roi, sizes):
+    """The filler's tensors against crops_ref given ``CropDraws`` built from the restated origins; returns those and the
+    clamp flags."""
+    from mivp_amd import batches as BT
+    _, _, images, labels = _bank(channels)
+    origin, moved = CR.origins(_labels(), _lut(), NCLS, draws, roi)
+    plain = BT.CropDraws(draws.volume, draws.rot, origin, draws.student_origin).check(SHAPES, roi, sizes)
+    want = R.teacher_batch(images, labels, plain, roi, ACTIVE, _grid)
+    torch.cuda.synchronize()
+    for name, got, ref in zip(("image", "mask", "coord"), (filler.image, filler.mask, filler.coord), want):
+        assert not torch.isnan(got).any(), f"{name}: an output voxel was not written"
+        assert torch.equal(got, ref), f"{name}: {int((got != ref).sum())} voxels differ"
+    for i, size in enumerate(sizes):
+        assert torch.equal(filler.image_st[i], R.student_view(filler.image, draws.student_origin[i], size))
+        assert torch.equal(filler.coord_st[i], R.student_view(filler.coord, draws.student_origin[i], size))
+    if sizes:
+        assert torch.equal(filler.mask_st_0, R.student_view(filler.mask, draws.student_origin[0], sizes[0]))
+    return plain, moved
+
+
+@pytest.mark.parametrize("channels", [1, 2])
+def test_class_balanced_batches_equal_the_restatement(channels):
+    from mivp_amd import batches as BT
+    bank, index, _, _ = _bank(channels)
+    roi = (8, 8, 8)
+    draws = _e2e_draws(index, 5)
+    filler = BT.BatchFiller(bank, roi, draws.batch, student_sizes=STUDENTS, active_labels=ACTIVE, class_index=index)
+    assert filler.slot.class_index is index and filler.slot.picks.numel() == 2 * draws.batch
+    _poison(filler)
+    batch = filler.fill(draws)
+    plain, moved = _check_batch(filler, draws, channels, roi, STUDENTS)
+    assert np.array_equal(filler.slot.resolved_origins(), plain.origin)
+    # where no clamp applied the crop is centred on the drawn voxel: the mask there is the drawn class
+    assert (~moved[-8:]).all() and (~moved).sum() >= 8
+    centre = filler.mask[:, 0, 4, 4, 4].cpu().numpy()
+    assert np.array_equal(centre[~moved], draws.cls[~moved].astype(np.float32))
+    assert set(draws.cls[~moved].tolist()) == {0, 1}
+    assert batch is filler.batch and sorted(batch) == ["coord", "coord_st", "image", "image_st", "mask_st_0"]
+
+    # refusals: the two modes do not mix, and a slot of another index, roi or student sizes is not used
+    plain_filler = BT.BatchFiller(bank, roi, draws.batch, student_sizes=STUDENTS, active_labels=ACTIVE)
+    with pytest.raises(ValueError, match="class-mode slot"):
+        plain_filler.fill(filler.slot)
+    with pytest.raises(ValueError, match="CropDraws expected"):
+        plain_filler.fill(draws)
+    plain_slot = BT.CropSlot(draws.batch, 2, DEV)
+    plain_slot.load(plain, bank, roi, STUDENTS)
+    with pytest.raises(ValueError, match="class-mode slot"):
+        filler.fill(plain_slot)
+    with pytest.raises(ValueError, match="ClassCropDraws"):
+        filler.fill(plain)
+    other = BT.CropSlot(draws.batch, 2, DEV, class_index=BT.ClassIndex(bank, NCLS, ACTIVE).update())
+    other.load(draws, bank, roi, STUDENTS)
+    with pytest.raises(ValueError, match="another index"):
+        filler.fill(other)
+    mine = BT.CropSlot(draws.batch, 2, DEV, class_index=index)
+    mine.load(draws, index, roi, [(8, 8, 8), (6, 6, 4)])
+    with pytest.raises(ValueError, match="another index, roi or student sizes"):
+        filler.fill(mine)
+    with pytest.raises(ValueError, match="of this bank"):
+        BT.BatchFiller(_bank(3 - channels)[0], roi, 2, class_index=index)
+    mine.load(draws, index, roi, STUDENTS)                      # and a good slot of the same index is used as it stands
+    _poison(filler)
+    filler.fill(mine)
+    _check_batch(filler, draws, channels, roi, STUDENTS)
+
+
+# ------------------------------------------------------------------------------------------------ 5. recording
+def test_recorded_fill_contains_the_pick_and_follows_the_slot():
+    """``fill`` recorded once; three replays after three loads each equal the eager result (and the restatement)."""
+    from mivp_amd import batches as BT
+    bank, index, _, _ = _bank(1)
+    roi = (8, 8, 8)
+    loads = [_e2e_draws(index, seed) for seed in (1, 2, 3)]
+    B = loads[0].batch
+    own = BT.BatchFiller(bank, roi, B, student_sizes=STUDENTS, active_labels=ACTIVE, class_index=index)
+    ref = BT.BatchFiller(bank, roi, B, student_sizes=STUDENTS, active_labels=ACTIVE, class_index=index)
+    own.fill(loads[0])
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        own.fill()
+    for draws in loads[::-1]:
+        own.slot.load(draws, index, roi, STUDENTS)
+        _poison(own)
+        graph.replay()
+        ref.fill(draws)
+        torch.cuda.synchronize()
+        for n in ("image", "coord", "mask", "mask_st_0"):
+            assert torch.equal(getattr(own, n), getattr(ref, n)), n
+        for i in range(len(STUDENTS)):
+            assert torch.equal(own.image_st[i], ref.image_st[i]) and torch.equal(own.coord_st[i], ref.coord_st[i])
+        plain, _ = _check_batch(own, draws, 1, roi, STUDENTS)
+        assert np.array_equal(own.slot.resolved_origins(), plain.origin)
+
+
+def test_a_recorded_fill_serves_volumes_indexed_later():
+    """The index table is one fixed allocation written in place: a graph recorded when one volume was indexed serves a
+    volume added to the bank and indexed afterwards."""
+    from mivp_amd import batches as BT
+    _, _, images, labels = _bank(1)
+    bank = BT.VolumeBank(DEV, 1, capacity=4)
+    bank.add(images[0], labels[0])
+    index = BT.ClassIndex(bank, NCLS, ACTIVE).update()
+    table = index.table.data_ptr()
+    roi = (8, 12, 4)
+    filler = BT.BatchFiller(bank, roi, 3, active_labels=ACTIVE, with_coord=True, class_index=index)
+    none = np.zeros((0, 3, 3), np.int32)
+    first = BT.ClassCropDraws(np.zeros(3, np.int32), np.array([0, 2, 3], np.int32), np.array([0, 1, 0], np.int32),
+                              np.array([100, 7, 2000], np.int32), none)
+    filler.fill(first)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        filler.fill()
+    later = BT.ClassCropDraws(np.array([1, 0, 1], np.int32), np.array([1, 3, 2], np.int32), np.array([0, 1, 1], np.int32),
+                              np.array([23448, 11, 0], np.int32), none)
+    with pytest.raises(ValueError, match="sample 0: volume id 1 is not indexed"):
+        filler.slot.load(later, index, roi)
+    bank.add(images[2], labels[2])
+    with pytest.raises(ValueError, match="not indexed"):
+        filler.slot.load(later, index, roi)                     # in the bank, but the index has not seen it
+    assert index.update().table.data_ptr() == table and len(index) == 2
+    labs = [_labels()[0], _labels()[2]]
+    for draws in (later, first):
+        filler.slot.load(draws, index, roi)
+        for t in (filler.image, filler.mask, filler.coord):
+            t.fill_(float("nan"))
+        graph.replay()
+        origin, _ = CR.origins(labs, _lut(), NCLS, draws, roi)
+        plain = BT.CropDraws(draws.volume, draws.rot, origin, none)
+        want = R.teacher_batch([images[0], images[2]], [labels[0], labels[2]], plain, roi, ACTIVE, _grid)
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip((filler.image, filler.mask, filler.coord), want))
+        assert np.array_equal(filler.slot.resolved_origins(), origin)
+
+
+def test_class_fill_feeds_a_recorded_train_step():
+    """As tests/test_hip_batches.py::test_fill_feeds_a_recorded_train_step, the crops placed by class: a
+    ``graphed_train_step`` recorded on the filler's tensors, a class-mode ``fill`` before each of two replays, against two
+    eager ``train_step`` calls on clones of the same crops -- loss and parameter bits."""
+    from mivp_amd import batches as BT, train
+    from mivp_amd.swin_unetr import SwinUnetR
+    conf, size, batch = train.make_conf("tiny")
+    assert conf.training_mode == "downstream"
+    ncls = conf.output_channels_downstream
+    g = torch.Generator().manual_seed(3)
+    bank = BT.VolumeBank(DEV, conf.input_channels)
+    for s in [(size + 5, size + 2, size + 9), (size, size + 7, size + 1)]:
+        bank.add(torch.rand((conf.input_channels,) + s, generator=g).to(DEV),
+                 torch.randint(0, 4, s, generator=g, dtype=torch.uint8).to(DEV))
+    roi = (size, size, size)
+    active = list(range(ncls))
+    index = BT.ClassIndex(bank, ncls, active).update()
+    filler = BT.BatchFiller(bank, roi, batch, active_labels=active, class_index=index)
+    rs = np.random.RandomState(5)
+    draws = [BT.draw_class_crops(rs, index, [i % 2] * batch, roi, 1, [1.0] * ncls, random_orientation=True) for i in range(4)]
+    torch.manual_seed(5)
+    ref = SwinUnetR(conf).to(DEV).train()
+    own = copy.deepcopy(ref)
+    o_ref = train.build_optimizer(ref, conf)
+    o_own = train.build_optimizer(own, conf, capturable=True)
+    x, y = filler.xy
+    filler.fill(draws[0])                                       # the two warm-up steps of the recording run on these crops
+    x0, y0 = x.clone(), y.clone()
+    step = train.graphed_train_step(own, o_own, conf, x, y, warmup=2)
+    for _ in range(2):
+        train.train_step(ref, o_ref, conf, x0, y0)
+    for d in draws[1:3]:
+        filler.fill(d)
+        l_own = float(step())
+        l_ref = float(train.train_step(ref, o_ref, conf, x.clone(), y.clone()))
+        assert l_own == l_ref
+    torch.cuda.synchronize()
+    assert not torch.equal(x, x0) and y.max() <= ncls - 1
+    assert [k for k, v in ref.state_dict().items() if not torch.equal(v, own.state_dict()[k])] == []

@@ -18,7 +18,22 @@ Cache.  Kernel times come from a kernel trace of one case at a time (``--only NA
 --stats``: then every k_crop launch of a ``downstream`` / ``yml`` process is the same teacher launch).  ``share_of_step``
 relates ``graph_ms`` to the step the batch feeds: the cfg1 step of DESIGN 6 for ``downstream``, the phase-1 steps of the
 README for the other two (the students / teacher step has not been measured at these shapes).
-The lines are appended to profiles/batches_bench.jsonl."""
+The lines are appended to profiles/batches_bench.jsonl.
+
+``--class-balanced`` measures the class-balanced sampling of DESIGN 4.27 instead (``ClassIndex``, class-mode ``fill``), the
+whole measurement ``--runs`` times (2) in one process, every figure as the list of the runs plus their spread
+((max - min) / min), appended to profiles/class_crops_bench.jsonl:
+
+- ``index``: the build of the index of ONE 512 x 512 x 96 label map (3 classes; 1 % and 3 % of the voxels in the two
+  foreground classes): ``launches_ms`` = the count and scan launches alone, issued back to back (the 25 MB label map stays
+  in the Infinity Cache between calls), ``update_ms`` = ``ClassIndex.update()`` of a new index of that one volume, with its
+  allocation, its blocking read of the totals and its table write;
+- ``fill``: for the ``downstream`` and ``yml`` rows, ``fill`` recorded once and replayed, without an index (``plain_ms``,
+  uniform origins) and with one (``class_ms``: pick, then the same teacher launch), the pick recorded alone
+  (``pick_ms``), and ``pick_share_of_step`` = (class_ms - plain_ms) / the step the batch feeds;
+- ``eager_ms``: the same centres from eager torch on the same GPU, per sample
+  ``(lut[lab] == c).flatten().nonzero()[rank]`` (checked to give the voxels the device picked).
+Random orientation is on in every class-balanced row."""
 import argparse
 import json
 import os
@@ -102,6 +117,104 @@ def eager_batch(images, labels, lut, d, roi, sizes, with_coord):
     return out
 
 
+def spread(v):
+    return round((max(v) - min(v)) / min(v), 4) if min(v) > 0 else None
+
+
+def class_balanced(a):
+    """``--class-balanced``: see the module docstring."""
+    import numpy as np
+    import torch
+    import mivp_amd  # noqa: F401
+    from mivp_amd import _lib as L, batches as BT
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(1)
+    active, ncls, ratios = [0, 1, 2], 3, (1.0, 1.0, 1.0)
+    bank = BT.VolumeBank(dev, 1)
+    for _ in range(a.volumes):
+        u = torch.rand(BANK_SHAPE, generator=g)
+        bank.add(torch.rand((1,) + BANK_SHAPE, generator=g).to(dev), ((u < 0.04).to(torch.uint8) + (u < 0.01).to(torch.uint8)).to(dev))
+    index = BT.ClassIndex(bank, ncls, active).update()
+    numel = int(np.prod(BANK_SHAPE))
+    assert index.counts.sum(axis=1).tolist() == [numel] * a.volumes
+    one = BT.VolumeBank(dev, 1, capacity=1)
+    one.add(bank.images[0], bank.labels[0])
+    scratch = torch.empty_like(index.prefix[0])
+    recs = {"index": {"shape": list(BANK_SHAPE), "num_classes": ncls, "chunks": scratch.shape[1] - 1,
+                      "counts": index.counts[0].tolist(), "launches_ms": [], "update_ms": []}}
+    rows = [c for c in CASES if c[0] in ("downstream", "yml")]
+    for name, roi, B, _, _, step_ms, step_kind in rows:
+        recs[name] = {"case": name, "roi": list(roi), "B": B, "random_orientation": True, "plain_ms": [], "class_ms": [],
+                      "pick_ms": [], "eager_ms": [], "step_ms": step_ms, "step": step_kind}
+    for run in range(a.runs):
+        r = recs["index"]
+        r["launches_ms"].append(round(timed(lambda: L.call("mivp_label_index_build", L.ptr(bank.labels[0]), numel,
+                                                           L.ptr(index.lut), ncls, L.ptr(scratch), scratch.shape[1] - 1,
+                                                           L.stream()), a.calls, a.warmup), 4))
+        assert torch.equal(scratch, index.prefix[0])
+        r["update_ms"].append(round(timed(lambda: BT.ClassIndex(one, ncls, active).update(), max(5, a.calls // 10), 2), 4))
+        for name, roi, B, _, _, step_ms, _ in rows:
+            r = recs[name]
+            rs = np.random.RandomState(3 + run)
+            ids = [i % len(bank) for i in range(B)]
+            plain = BT.BatchFiller(bank, roi, B, active_labels=active)
+            balanced = BT.BatchFiller(bank, roi, B, active_labels=active, class_index=index)
+            plain.fill(BT.draw_crops(rs, bank.shapes, ids, roi, 1, True))
+            d = BT.draw_class_crops(rs, index, ids, roi, 1, ratios, True)
+            balanced.fill(d)
+            lut = index.lut
+
+            def eager_centres():
+                return [(lut[bank.labels[int(v)].long()] == int(c)).flatten().nonzero()[int(k)]
+                        for v, c, k in zip(d.volume, d.cls, d.rank)]
+
+            # the device's origins are those of the eager centres, and an unclamped crop has its class at the centre
+            q = torch.stack(eager_centres()).reshape(-1).cpu().numpy()
+            r_c = rotated(d.rot, np.stack(np.unravel_index(q, BANK_SHAPE), axis=1), BT.ROT_AXES)
+            n_rot = np.asarray([BT.rotated_shape(BANK_SHAPE, int(code)) for code in d.rot])
+            free = r_c - np.asarray(roi) // 2
+            want = np.minimum(np.maximum(free, 0), np.maximum(n_rot - np.asarray(roi), 0))
+            assert np.array_equal(balanced.slot.resolved_origins(), want), f"{name}: the eager centres disagree"
+            centre = balanced.mask[:, 0, roi[0] // 2, roi[1] // 2, roi[2] // 2].cpu().numpy()
+            same = (want == free).all(axis=1)
+            assert np.array_equal(centre[same], d.cls[same].astype(np.float32)), f"{name}: a crop is not on its class"
+            torch.cuda.synchronize()
+            graphs = []
+            for fn in (plain.fill, balanced.fill, lambda: balanced.slot.resolve(roi)):
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    fn()
+                graphs.append(graph)
+            for key, graph in zip(("plain_ms", "class_ms", "pick_ms"), graphs):
+                r[key].append(round(timed(graph.replay, a.calls, a.warmup), 4))
+            r["eager_ms"].append(round(timed(eager_centres, max(5, a.calls // 10), 2), 4))
+    lines = []
+    for key, r in recs.items():
+        for k in [k for k, v in r.items() if k.endswith("_ms") and isinstance(v, list)]:
+            r[k.replace("_ms", "_spread")] = spread(r[k])
+        if key != "index":
+            r["pick_share_of_step"] = [round((c - p) / r["step_ms"], 5) for c, p in zip(r["class_ms"], r["plain_ms"])]
+            r["eager_over_pick"] = [round(e / k, 1) for e, k in zip(r["eager_ms"], r["pick_ms"])]
+        else:
+            r["case"] = "index"
+        print(json.dumps(r), flush=True)
+        lines.append(json.dumps(r))
+    os.makedirs(os.path.dirname(a.class_out), exist_ok=True)
+    with open(a.class_out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def rotated(codes, p, rot_axes):
+    """Stored voxels ``p`` [B, 3] in the frames rotated by ``codes``: for axes (a, b), r_b = p_a and r_a = n_b - 1 - p_b."""
+    import numpy as np
+    out = np.array(p, dtype=np.int64)
+    for b, code in enumerate(codes):
+        if int(code):
+            x, y = rot_axes[int(code)]
+            out[b, y], out[b, x] = p[b][x], BANK_SHAPE[y] - 1 - p[b][y]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
@@ -111,7 +224,12 @@ def main():
     ap.add_argument("--only", default=None, help="one case, as NAME:0 or NAME:1 (random_orientation off / on): for a "
                     "kernel-trace run, where every k_crop launch of the process should be the same launch")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batches_bench.jsonl"))
+    ap.add_argument("--class-balanced", action="store_true", help="measure the class-balanced sampling (DESIGN 4.27)")
+    ap.add_argument("--runs", type=int, default=2, help="--class-balanced: how often the whole measurement is made")
+    ap.add_argument("--class-out", default=os.path.join(ROOT, "profiles", "class_crops_bench.jsonl"))
     a = ap.parse_args()
+    if a.class_balanced:
+        return class_balanced(a)
     import numpy as np
     import torch
     import mivp_amd  # noqa: F401
