@@ -1032,6 +1032,45 @@ int mivp_crop_pick(const int64_t* table, const int64_t* index_table, int32_t n_v
                    int32_t num_classes, int32_t* slot, int32_t slot_stride, const int32_t* pick, int32_t B,
                    const int32_t* roi, mivp_stream_t stream);
 
+/* Random flip, rotation and zoom for the batch filler (csrc/crops_affine.hip; mivp_amd/batches.py).  Additive
+ * again: the ABI stays 18.  The teacher launch of mivp_crop_fill with an affine map per sample and interpolation: every
+ * output voxel is written exactly once, no atomics, bitwise reproducible, no host synchronisation; the map is DEVICE
+ * memory like the slot, so the launch records into a graph and a replay follows what both hold then.
+ *   affine: DEVICE fp32 [B][12]: A row-major (9 words: output offset -> source offset), then the sub-voxel shift s (3).
+ *   Rule for output voxel u of sample b; origin, rot, n, n_rot and pad_before exactly as for mivp_crop_fill above; all
+ *   arithmetic is fp32, per axis k:
+ *       q = u - (roi - 1) / 2
+ *       r_k = fma(A_k2, q_2, fma(A_k1, q_1, A_k0 * q_0)) + ((roi_k - 1) / 2 + (origin_k - pad_before_k) + s_k)
+ *     image: trilinear.  i = floor(r), w = r - i; of the eight corners i + e, one outside [0, n_rot) on any axis reads 0,
+ *       the others read vol[:, p(corner)] with p the corner mapped back through the quarter turn as above; interpolated
+ *       along D first, then W, then H, each step a + w * (b - a).
+ *     mask: j = floor(r + 0.5); lut[lab[p(j)]] if j is inside [0, n_rot) on every axis, else 0 (0 without a label map).
+ *     coord: under the mask's inside test the continuous r mapped back through the quarter turn (for axes (a, b):
+ *       p_a = r_b, p_b = (n_b - 1) - r_a), coord[k] = p[k] - (n[k] - 1) / 2; otherwise 0.
+ *     a non-finite r_k gives 0 in every output (float comparisons before any conversion to an integer).
+ *   With A = diag(+-1) and s = 0 every r is an exact integer and every w is 0: the outputs equal mivp_crop_fill's (at the
+ *   mirrored voxel) bit for bit.  With dyadic A and s and small integer voxel values every step is exact in fp32.
+ *   mivp_crop_fill_affine: every other argument and every refusal as for mivp_crop_fill (an empty table row, a volume id
+ *     outside [0, n_volumes) or a code outside 0..3 leaves the sample unwritten; MIVP_EINVAL for null required pointers
+ *     and bad sizes).  One 256-thread workgroup per 8 x 8 x 16 output brick of one sample, each lane four voxels along d
+ *     (16-byte stores), the eight corners of every voxel read from global memory, each range-checked (the direct path).
+ *   mivp_crop_fill_affine_debug: the same launch with the staged path switched on by stage != 0.  A workgroup then bounds
+ *     the source positions of its brick by a box (the eight brick corners through the map, one voxel of slack, clipped to
+ *     the volume plus a one-voxel rim of zeros); if the box has at least two planes on every axis and e0 * e1 * (e2 | 1)
+ *     <= 12288 cells it is staged into LDS once per channel, by rows along the stored D axis, and the corners come from
+ *     LDS; otherwise (strong minification, a non-finite map) the workgroup takes the direct path.  Both paths give the
+ *     same bits.  The staged path measured slower on typical draws, which is why the product entry does not
+ *     take it.  paths (DEVICE int32 [B][bricks], bricks = ceil(h / 8) * ceil(w / 8) * ceil(d / 16), brick index
+ *     ((bh * nbw) + bw) * nbd + bd; may be NULL) receives 1 where a workgroup took the staged path and 0 where the direct
+ *     one.  For the tests and tools/bench_batches.py. */
+int mivp_crop_fill_affine(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot, int32_t slot_stride,
+                          const float* affine, int32_t B, const int32_t* roi, const uint8_t* lut, float* image, float* mask,
+                          float* coord, mivp_stream_t stream);
+int mivp_crop_fill_affine_debug(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot,
+                                int32_t slot_stride, const float* affine, int32_t B, const int32_t* roi, const uint8_t* lut,
+                                float* image, float* mask, float* coord, int32_t stage, int32_t* paths,
+                                mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,12 @@ Class-balanced crops (csrc/crops_index.hip): ``ClassIndex`` keep
 per-chunk class counts of its label map; ``draw_class_crops`` draws a class and a rank among that class's voxels
 (``RandCropByPosNegLabeld`` / ``RandCropByLabelClassesd``; MONAI's stream is not reproduced here either), and a class-mode
 ``CropSlot`` has the device turn (class, rank) into the crop origin -- ``resolve``, one launch in front of the teacher's --
-so the label map is never read back and a recorded ``fill`` still follows the slot."""
+so the label map is never read back and a recorded ``fill`` still follows the slot.
+
+Random flip, rotation and zoom (csrc/crops_affine.hip): ``draw_spatial`` draws one affine map per sample
+(``SpatialDraws``), a ``SpatialSlot`` holds the maps on the device beside the ``CropSlot``, and a filler built with
+``spatial=True`` issues the interpolating teacher launch in place of the plain one -- trilinear for the image, nearest for
+the labels, analytic coordinates; the pick and the students' launches are the same as without it."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -390,6 +395,124 @@ def draw_class_crops(rs: np.random.RandomState, index, volume_ids: Sequence[int]
     return d
 
 
+AFFINE_WORDS = 12               # fp32 words per sample of a spatial map: A row-major, then the sub-voxel shift (mivp.h)
+SPATIAL_BRICK = (8, 8, 16)      # the output brick of one workgroup of mivp_crop_fill_affine (mivp.h)
+SPATIAL_BOX_CELLS = 12288       # its staged path's box budget: e0 * e1 * (e2 | 1) cells (mivp.h)
+
+
+@dataclass
+class SpatialDraws:
+    """The affine maps one step draws on the host: per sample the matrix ``A`` that takes an offset from the centre of the
+    output crop to an offset in the (rotated) source volume, and a sub-voxel shift ``s`` of the crop centre."""
+    affine: np.ndarray              # float32 [B, 12]: A row-major (9 words), then the sub-voxel shift s (3 words)
+
+    @property
+    def batch(self) -> int:
+        return int(np.shape(self.affine)[0])
+
+    @classmethod
+    def identity(cls, B: int) -> "SpatialDraws":
+        a = np.zeros((check_int_from("B", B, 1), AFFINE_WORDS), dtype=np.float32)
+        a[:, [0, 4, 8]] = 1.0
+        return cls(a)
+
+    def check(self, B: int) -> "SpatialDraws":
+        """float32 ``[B, 12]``, every word finite, ``|A_ij| <= 16`` and ``|s_k| <= 1``: what the kernel's box arithmetic
+        and the documented error bounds assume.  Raises ``ValueError`` naming the sample."""
+        a = self.affine
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.shape != (int(B), AFFINE_WORDS):
+            got = f"{a.dtype} {a.shape}" if isinstance(a, np.ndarray) else repr(type(a))
+            raise ValueError(f"SpatialDraws: affine must be a float32 [{int(B)}, {AFFINE_WORDS}] array (every sample of "
+                             f"the batch), got {got}")
+        for b in range(a.shape[0]):
+            if not np.isfinite(a[b]).all():
+                raise ValueError(f"SpatialDraws: sample {b}: a non-finite word in {a[b].tolist()}")
+            if (np.abs(a[b, :9]) > 16).any():
+                raise ValueError(f"SpatialDraws: sample {b}: an entry of A outside [-16, 16]: {a[b, :9].tolist()}")
+            if (np.abs(a[b, 9:]) > 1).any():
+                raise ValueError(f"SpatialDraws: sample {b}: a shift outside [-1, 1]: {a[b, 9:].tolist()}")
+        return self
+
+
+def _triple(name: str, v) -> Tuple[float, float, float]:
+    v = tuple(float(x) for x in (v if np.ndim(v) else (v, v, v)))
+    if len(v) != 3 or not np.isfinite(v).all():
+        raise ValueError(f"draw_spatial: {name} must be three finite numbers, got {v!r}")
+    return v
+
+
+def affine_matrix(flips, angles, zoom) -> np.ndarray:
+    """float64 ``A = F . R2 . R1 . R0 . diag(1 / zoom)``: output offset -> source offset.  ``F = diag(-1 where flipped)``;
+    ``R_k`` turns by ``angles[k]`` radians about axis k of the ``[H, W, D]`` frame (R0 = [[1, 0, 0], [0, c, -s], [0, s, c]],
+    R1 = [[c, 0, s], [0, 1, 0], [-s, 0, c]], R2 = [[c, -s, 0], [s, c, 0], [0, 0, 1]]); zoom > 1 enlarges the content."""
+    c, s = np.cos(np.asarray(angles, np.float64)), np.sin(np.asarray(angles, np.float64))
+    R0 = np.array([[1, 0, 0], [0, c[0], -s[0]], [0, s[0], c[0]]], np.float64)
+    R1 = np.array([[c[1], 0, s[1]], [0, 1, 0], [-s[1], 0, c[1]]], np.float64)
+    R2 = np.array([[c[2], -s[2], 0], [s[2], c[2], 0], [0, 0, 1]], np.float64)
+    F = np.diag([-1.0 if f else 1.0 for f in flips])
+    return F @ R2 @ R1 @ R0 @ np.diag(1.0 / np.asarray(zoom, np.float64))
+
+
+def draw_spatial(rs: np.random.RandomState, B: int, p_flip=(0., 0., 0.), p_affine: float = 0., rotate_range=(0., 0., 0.),
+                 scale_range=(1., 1.), isotropic: bool = True, shift: bool = False) -> SpatialDraws:
+    """The spatial draws of one batch of ``B`` samples from ONE RandomState.  Per sample, in this order:
+
+    1. three flip draws: axis k of the rotated ``[H, W, D]`` frame is mirrored if ``rs.random_sample() < p_flip[k]``;
+    2. one apply draw: ``rs.random_sample() < p_affine``;
+    3. if it applies: three angles ``rs.uniform(-rotate_range[k], rotate_range[k])`` in radians about axes 0, 1, 2, then
+       ONE zoom ``rs.uniform(*scale_range)`` if ``isotropic``, else three;
+    4. if ``shift``: three ``rs.uniform(-0.5, 0.5)``, the sub-voxel shift of the crop centre.
+
+    A branch that does not apply consumes NO draws: a sample whose apply draw fails costs four draws (seven with
+    ``shift``), and ``p_flip = 0`` / ``p_affine = 0`` still make their four comparisons' draws.  The matrix is
+    ``affine_matrix`` composed in float64 and rounded to fp32 once.  MONAI's ``RandFlipd`` / ``RandAffined`` streams are
+    NOT reproduced (``Compose`` reseeds every child, and MONAI resamples through a stored grid): parity is unpinned at the
+    MONAI boundary, as for ``draw_crops``, and this order is the project's own."""
+    B = check_int_from("B", B, 1)
+    p_flip, rot = _triple("p_flip", p_flip), _triple("rotate_range", rotate_range)
+    lo, hi = (float(v) for v in scale_range)
+    if not (0 <= min(p_flip) and max(p_flip) <= 1 and 0 <= float(p_affine) <= 1):
+        raise ValueError(f"draw_spatial: probabilities must be in [0, 1], got p_flip {p_flip}, p_affine {p_affine}")
+    if not (np.isfinite([lo, hi]).all() and 0 < lo <= hi):
+        raise ValueError(f"draw_spatial: scale_range must be 0 < low <= high, got {scale_range!r}")
+    out = np.zeros((B, AFFINE_WORDS), dtype=np.float32)
+    for b in range(B):
+        flips = [rs.random_sample() < p_flip[k] for k in range(3)]
+        angles, zoom = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
+        if rs.random_sample() < float(p_affine):
+            angles = [rs.uniform(-rot[k], rot[k]) for k in range(3)]
+            zoom = [rs.uniform(lo, hi)] * 3 if isotropic else [rs.uniform(lo, hi) for _ in range(3)]
+        out[b, :9] = affine_matrix(flips, angles, zoom).reshape(-1)
+        if shift:
+            out[b, 9:] = [rs.uniform(-0.5, 0.5) for _ in range(3)]
+    return SpatialDraws(out).check(B)
+
+
+class SpatialSlot:
+    """Fixed device memory of one batch's spatial maps -- ONE fp32 [B * 12] allocation made here, the identity at first --
+    whose pointer a recorded graph keeps.  ``load`` checks the draws, then refreshes the words from a new pinned staging
+    buffer without blocking; it does nothing while a graph is being recorded, exactly as ``CropSlot.load``."""
+
+    def __init__(self, B: int, device):
+        self.B = check_int_from("B", B, 1)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("SpatialSlot: a GPU device expected (no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.words = torch.from_numpy(SpatialDraws.identity(self.B).affine.reshape(-1)).to(device)
+        self.draws = SpatialDraws.identity(self.B)
+
+    def load(self, draws: SpatialDraws):
+        if not isinstance(draws, SpatialDraws):
+            raise ValueError("SpatialSlot.load: SpatialDraws expected")
+        draws.check(self.B)
+        if torch.cuda.is_current_stream_capturing():
+            return
+        self.words.copy_(torch.from_numpy(np.ascontiguousarray(draws.affine).reshape(-1)).pin_memory(), non_blocking=True)
+        self.draws = draws
+
+
 class CropSlot:
     """Fixed device memory of one batch's draws -- int32 [B][5 + 3 S] records -- whose pointer a recorded graph keeps.
     ``load`` checks the draws against the bank, then refreshes the records from a new pinned staging buffer without blocking;
@@ -490,10 +613,16 @@ class BatchFiller:
 
     With ``class_index`` the filler's own slot is in class mode and ``fill`` takes ``ClassCropDraws`` (or a class-mode slot
     of the same index): it issues the pick launch first (``CropSlot.resolve``), then the teacher, then the students, so a
-    recorded ``fill`` contains the pick and is fed by ``slot.load`` before each replay, as without an index."""
+    recorded ``fill`` contains the pick and is fed by ``slot.load`` before each replay, as without an index.
+
+    With ``spatial=True`` the filler owns ``spatial_slot`` (the identity at first) and the teacher launch is the
+    interpolating ``mivp_crop_fill_affine``: flips, rotation and zoom about the centre of the crop, which
+    therefore stays centred on a picked voxel.  The pick runs first as before and the students are crops of the augmented
+    teacher tensors, so image, coordinates and mask agree across the views.  ``spatial=False`` issues exactly the
+    launches described above."""
 
     def __init__(self, bank: VolumeBank, roi, batch: int, student_sizes=(), active_labels=None, with_coord: bool = False,
-                 with_mask: bool = True, class_index: Optional[ClassIndex] = None):
+                 with_mask: bool = True, class_index: Optional[ClassIndex] = None, spatial: bool = False):
         if not isinstance(bank, VolumeBank):
             raise ValueError("BatchFiller: a VolumeBank expected")
         if class_index is not None and (not isinstance(class_index, ClassIndex) or class_index.bank is not bank):
@@ -514,6 +643,7 @@ class BatchFiller:
         self.coord_st = [new(3, s) for s in self.student_sizes]
         self.mask_st_0 = new(1, self.student_sizes[0]) if (S and with_mask) else None
         self.slot = CropSlot(self.B, S, dev, class_index=class_index)
+        self.spatial_slot = SpatialSlot(self.B, dev) if spatial else None
         self.xy = (self.image, self.mask)
         if S:
             self.batch = dict(image=self.image, coord=self.coord, image_st=self.image_st, coord_st=self.coord_st)
@@ -545,11 +675,26 @@ class BatchFiller:
                                  f"got {got}")
 
     @torch.no_grad()
-    def fill(self, draws_or_slot=None):
+    def fill(self, draws_or_slot=None, spatial=None):
         """``CropDraws`` (``ClassCropDraws`` on a filler with a class index): checked and loaded into the filler's own slot
         first.  A ``CropSlot``: used as it stands (its ``load`` did the checking).  ``None``: the filler's own slot as last
-        loaded."""
+        loaded.  ``spatial`` (a filler built with ``spatial=True`` only): ``SpatialDraws``, checked and loaded into
+        ``spatial_slot`` first; a ``SpatialSlot``, used as it stands; ``None``: ``spatial_slot`` as last loaded.  Every
+        refusal comes before the first launch and before either slot is loaded."""
         slot = self.slot
+        sp_slot = self.spatial_slot
+        if spatial is not None:
+            if sp_slot is None:
+                raise ValueError("BatchFiller.fill: spatial= needs a filler built with spatial=True")
+            if isinstance(spatial, SpatialDraws):
+                spatial.check(self.B)
+            elif isinstance(spatial, SpatialSlot):
+                sp_slot = spatial
+                if sp_slot.B != self.B or sp_slot.words.device != self.bank.device:
+                    raise ValueError(f"BatchFiller.fill: a spatial slot of batch {sp_slot.B} on {sp_slot.words.device} for a "
+                                     f"filler of batch {self.B} on {self.bank.device}")
+            else:
+                raise ValueError("BatchFiller.fill: spatial= takes SpatialDraws, a SpatialSlot, or nothing")
         if isinstance(draws_or_slot, (CropDraws, ClassCropDraws)):
             slot.load(draws_or_slot, self.bank, self.roi, self.student_sizes)
         elif isinstance(draws_or_slot, CropSlot):
@@ -572,14 +717,21 @@ class BatchFiller:
         elif shapes != tuple(self.bank.shapes[:len(shapes)]) or roi != self.roi or sizes != self.student_sizes:
             raise ValueError("BatchFiller.fill: the slot's draws were checked against another bank, roi or student sizes")
         self._check_outputs()
+        if isinstance(spatial, SpatialDraws):
+            sp_slot.load(spatial)
         if self.class_index is not None:
             slot.resolve(self.roi)
-        self._fill_teacher(slot)
+        self._fill_teacher(slot, sp_slot)
         self._fill_students(slot)
         return self.batch
 
-    def _fill_teacher(self, slot: CropSlot):
+    def _fill_teacher(self, slot: CropSlot, spatial_slot: Optional[SpatialSlot] = None):
         bank = self.bank
+        if spatial_slot is not None:
+            L.call("mivp_crop_fill_affine", L.ptr(bank.table), bank.capacity, bank.channels, L.ptr(slot.records), slot.words,
+                   L.ptr(spatial_slot.words), self.B, i3(self.roi), L.ptr(self.lut), L.ptr(self.image), L.ptr(self.mask),
+                   L.ptr(self.coord), L.stream())
+            return
         L.call("mivp_crop_fill", L.ptr(bank.table), bank.capacity, bank.channels, L.ptr(slot.records), slot.words, self.B,
                i3(self.roi), L.ptr(self.lut), L.ptr(self.image), L.ptr(self.mask), L.ptr(self.coord), L.stream())
 

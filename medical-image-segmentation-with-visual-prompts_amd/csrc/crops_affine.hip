@@ -1,0 +1,386 @@
+// Random flip, rotation and zoom for the batch filler (mivp_amd/batches.py): the teacher launch of crops.hip
+// with an affine map per sample and interpolation -- MONAI's RandFlipd / RandAffined (rotate, scale) as ONE gather.  The
+// rule (mivp.h) for output voxel u, all fp32:
+//
+//   q = u - (roi - 1) / 2        r_k = fma(A_k2, q_2, fma(A_k1, q_1, A_k0 * q_0)) + t_k
+//   t_k = (roi_k - 1) / 2 + (origin_k - pad_before_k) + s_k                         (position in the ROTATED volume)
+//   image: trilinear over the eight corners floor(r) + e (zero outside the rotated volume), D, then W, then H
+//   mask : lut[lab] at floor(r + 0.5), coord: r mapped back through the quarter turn, both 0 outside the volume
+//
+// One workgroup owns an 8 x 8 x 16 output brick of one sample; thread = (u_h, u_w, a group of four voxels along d), so a
+// lane stores 16 bytes per tensor.  Every workgroup bounds its brick's source positions by an integer box -- the eight brick
+// corners through the map, one voxel of slack for the rounding of r inside the brick, clipped to the volume plus a
+// one-voxel rim that holds zeros -- and then takes one of two paths of the same template.  MEASURED: on
+// typical draws the staged path took 2.0-2.2x the time of the direct one, so mivp_crop_fill_affine sends every workgroup down
+// the direct path; the staged one is kept behind mivp_crop_fill_affine_debug(stage = 1), where the tests prove it equal.
+//   staged   (stage = 1 only) the box fits BOXV cells: it is read once per channel by rows along the STORED D axis (32 lanes per row,
+//            coalesced; under codes 2 and 3 that is another axis of the box, the LDS write is the strided side) and the
+//            eight corners of every voxel come from LDS.  The rim makes the zero rule free: no per-corner range test.  The
+//            label map is staged through the lut as bytes in the same pass.  Rows have an odd pitch.
+//   direct   the corners are read from global memory, each range-checked and mapped through the quarter turn (strong
+//            minification, a non-finite map, a brick wholly outside the volume -- which then loads nothing; with
+//            stage = 0, every workgroup).
+// No atomics, no per-lane arrays in scratch (everything below is unrolled over constant indices), no host synchronisation.
+// No out-of-range address can be formed from device memory: the volume id and the code are checked per workgroup, r per
+// voxel with float comparisons BEFORE it becomes an integer, and every LDS index is clamped into the box.
+#include "common.hpp"
+
+namespace {
+constexpr int TPB = 256;
+constexpr int BH = 8, BW = 8, BD = 16;     // the output brick; BD / 4 lanes along d
+constexpr int BOXV = 12288;                // cells of the staged box: 48 KiB of image + 12 KiB of labels
+constexpr int MAXC = 16;
+
+typedef f32x4 f32x4u __attribute__((aligned(4)));
+
+struct AffArgs {
+    const int64_t* table;
+    int n_volumes, C, B;
+    const int32_t* slot;
+    int slot_stride;
+    const float* affine;
+    int h, w, d;
+    int nbw, nbd;            // bricks along w and d
+    const uint8_t* lut;
+    float* image;
+    float* mask;
+    float* coord;
+    int stage;               // 0: every workgroup reads global memory; 1: a workgroup stages its box where it fits
+    int32_t* paths;
+};
+
+struct Src {
+    const float* img;
+    const uint8_t* lab;
+    int n0, n1, n2;          // stored extents H, W, D
+    int m0, m1, m2;          // rotated extents
+    int code;
+    float A[9];
+    float t[3];              // (roi - 1) / 2 + (origin - pad_before) + s
+    float c[3];              // (roi - 1) / 2
+};
+
+struct Box {
+    int lo0, lo1, lo2;       // first cell, rotated frame (-1: the rim)
+    int e0, e1, e2;          // extents
+    int pitch;               // e2 | 1
+};
+
+MIVP_DEV int pad_before(int roi, int m) { return (roi - min(roi, m)) >> 1; }
+MIVP_DEV bool inside(int r, int m) { return (unsigned)r < (unsigned)m; }
+MIVP_DEV int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+MIVP_DEV float src_pos(const Src& s, int k, float q0, float q1, float q2) {
+    return __builtin_fmaf(s.A[3 * k + 2], q2, __builtin_fmaf(s.A[3 * k + 1], q1, s.A[3 * k] * q0)) + s.t[k];
+}
+
+// r (rotated frame, in range) -> the offset of p in the stored volume
+MIVP_DEV long stored_offset(const Src& s, int r0, int r1, int r2) {
+    int p0, p1, p2;
+    switch (s.code) {
+        case 1: p0 = r1; p1 = s.n1 - 1 - r0; p2 = r2; break;
+        case 2: p0 = r2; p1 = r1; p2 = s.n2 - 1 - r0; break;
+        case 3: p0 = r0; p1 = r2; p2 = s.n2 - 1 - r1; break;
+        default: p0 = r0; p1 = r1; p2 = r2; break;
+    }
+    return ((long)p0 * s.n1 + p1) * s.n2 + p2;
+}
+
+// the trilinear taps of one voxel: false (and harmless integers) where every corner is outside, NaN included
+struct Tap {
+    int i0, i1, i2;
+    float w0, w1, w2;
+    bool ok;
+};
+MIVP_DEV Tap make_tap(const Src& s, float r0, float r1, float r2) {
+    Tap t;
+    t.ok = r0 >= -1.f && r0 < (float)s.m0 && r1 >= -1.f && r1 < (float)s.m1 && r2 >= -1.f && r2 < (float)s.m2;
+    const float a0 = t.ok ? r0 : 0.f, a1 = t.ok ? r1 : 0.f, a2 = t.ok ? r2 : 0.f;
+    const float f0 = floorf(a0), f1 = floorf(a1), f2 = floorf(a2);
+    t.i0 = (int)f0; t.i1 = (int)f1; t.i2 = (int)f2;
+    t.w0 = a0 - f0; t.w1 = a1 - f1; t.w2 = a2 - f2;
+    return t;
+}
+
+// the nearest voxel: false where it is outside
+struct Near {
+    int j0, j1, j2;
+    bool ok;
+};
+MIVP_DEV Near make_near(const Src& s, float r0, float r1, float r2) {
+    const float h0 = r0 + 0.5f, h1 = r1 + 0.5f, h2 = r2 + 0.5f;
+    Near n;
+    n.ok = h0 >= 0.f && h0 < (float)s.m0 && h1 >= 0.f && h1 < (float)s.m1 && h2 >= 0.f && h2 < (float)s.m2;
+    n.j0 = n.ok ? (int)floorf(h0) : 0;
+    n.j1 = n.ok ? (int)floorf(h1) : 0;
+    n.j2 = n.ok ? (int)floorf(h2) : 0;
+    return n;
+}
+
+// v[4 e0 + 2 e1 + e2]: along D, then W, then H
+MIVP_DEV float lerp3(const float (&v)[8], const Tap& t) {
+    const float c00 = v[0] + t.w2 * (v[1] - v[0]), c01 = v[2] + t.w2 * (v[3] - v[2]);
+    const float c10 = v[4] + t.w2 * (v[5] - v[4]), c11 = v[6] + t.w2 * (v[7] - v[6]);
+    const float c0 = c00 + t.w1 * (c01 - c00), c1 = c10 + t.w1 * (c11 - c10);
+    return c0 + t.w0 * (c1 - c0);
+}
+
+template <bool STAGED>
+MIVP_DEV float sample_image(const Src& s, const Box& bx, const float* box, const float* img, const Tap& t) {
+    float v[8];
+    if (STAGED) {
+        const int b0 = clampi(t.i0 - bx.lo0, 0, bx.e0 - 2), b1 = clampi(t.i1 - bx.lo1, 0, bx.e1 - 2);
+        const int b2 = clampi(t.i2 - bx.lo2, 0, bx.e2 - 2);
+        const int s1 = bx.pitch, s0 = bx.e1 * bx.pitch;
+        const float* p = box + b0 * s0 + b1 * s1 + b2;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = p[(e >> 2) * s0 + ((e >> 1) & 1) * s1 + (e & 1)];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int c0 = t.i0 + (e >> 2), c1 = t.i1 + ((e >> 1) & 1), c2 = t.i2 + (e & 1);
+            const bool ok = t.ok && inside(c0, s.m0) && inside(c1, s.m1) && inside(c2, s.m2);
+            v[e] = ok ? img[stored_offset(s, c0, c1, c2)] : 0.f;
+        }
+    }
+    const float out = lerp3(v, t);
+    return t.ok ? out : 0.f;
+}
+
+template <bool STAGED>
+MIVP_DEV float sample_mask(const Src& s, const Box& bx, const uint8_t* lbox, const uint8_t* s_lut, const Near& n) {
+    if (!s.lab) return 0.f;
+    if (STAGED) {
+        const int b0 = clampi(n.j0 - bx.lo0, 0, bx.e0 - 1), b1 = clampi(n.j1 - bx.lo1, 0, bx.e1 - 1);
+        const int b2 = clampi(n.j2 - bx.lo2, 0, bx.e2 - 1);
+        const float v = (float)lbox[(b0 * bx.e1 + b1) * bx.pitch + b2];
+        return n.ok ? v : 0.f;
+    }
+    return n.ok ? (float)s_lut[s.lab[stored_offset(s, n.j0, n.j1, n.j2)]] : 0.f;
+}
+
+// One channel of the box (and, with `labels`, the label map through the lut): rows along the stored D axis.
+MIVP_DEV void stage(const Src& s, const Box& bx, const float* img, float* box, bool labels, uint8_t* lbox,
+                    const uint8_t* s_lut) {
+    const int hi0 = bx.lo0 + bx.e0 - 1, hi1 = bx.lo1 + bx.e1 - 1;
+    int plo0 = bx.lo0, plo1 = bx.lo1, plo2 = bx.lo2, E0 = bx.e0, E1 = bx.e1, E2 = bx.e2;       // the box in the stored frame
+    switch (s.code) {
+        case 1: plo0 = bx.lo1; E0 = bx.e1; plo1 = s.n1 - 1 - hi0; E1 = bx.e0; break;
+        case 2: plo0 = bx.lo2; E0 = bx.e2; plo2 = s.n2 - 1 - hi0; E2 = bx.e0; break;
+        case 3: plo1 = bx.lo2; E1 = bx.e2; plo2 = s.n2 - 1 - hi1; E2 = bx.e1; break;
+        default: break;
+    }
+    const int nrows = E0 * E1;
+    for (int row = (int)threadIdx.x >> 5; row < nrows; row += TPB >> 5) {
+        const int ra = row / E1;
+        const int p0 = plo0 + ra, p1 = plo1 + (row - ra * E1);
+        const bool row_ok = inside(p0, s.n0) && inside(p1, s.n1);
+        const long base = ((long)p0 * s.n1 + p1) * s.n2;
+        for (int x = (int)threadIdx.x & 31; x < E2; x += 32) {
+            const int p2 = plo2 + x;
+            const bool ok = row_ok && inside(p2, s.n2);
+            int r0 = p0, r1 = p1, r2 = p2;
+            switch (s.code) {
+                case 1: r0 = s.n1 - 1 - p1; r1 = p0; break;
+                case 2: r0 = s.n2 - 1 - p2; r2 = p0; break;
+                case 3: r1 = s.n2 - 1 - p2; r2 = p1; break;
+                default: break;
+            }
+            const int cell = ((r0 - bx.lo0) * bx.e1 + (r1 - bx.lo1)) * bx.pitch + (r2 - bx.lo2);
+            box[cell] = ok ? img[base + p2] : 0.f;
+            if (labels) lbox[cell] = ok ? s_lut[s.lab[base + p2]] : (uint8_t)0;
+        }
+    }
+}
+
+template <bool STAGED>
+MIVP_DEV void fill_brick(const AffArgs& a, const Src& s, const Box& bx, int b, int u0h, int u0w, int u0d, float* box,
+                         uint8_t* lbox, const uint8_t* s_lut) {
+    const int tid = threadIdx.x;
+    const int uh = u0h + (tid >> 5), uw = u0w + ((tid >> 2) & 7), ud = u0d + 4 * (tid & 3);
+    const bool active = uh < a.h && uw < a.w && ud < a.d;        // (an idle lane still stages and meets the barriers)
+    const int nv = active ? min(4, a.d - ud) : 0;
+    const long ovol = (long)a.h * a.w * a.d;
+    const long orow = ((long)uh * a.w + uw) * a.d + ud;
+    const float q0 = (float)uh - s.c[0], q1 = (float)uw - s.c[1];
+    float r0[4], r1[4], r2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float q2 = (float)(ud + j) - s.c[2];
+        r0[j] = src_pos(s, 0, q0, q1, q2);
+        r1[j] = src_pos(s, 1, q0, q1, q2);
+        r2[j] = src_pos(s, 2, q0, q1, q2);
+    }
+    if (a.coord && active) {
+        const float h0 = 0.5f * (float)(s.n0 - 1), h1 = 0.5f * (float)(s.n1 - 1), h2 = 0.5f * (float)(s.n2 - 1);
+        f32x4 k0, k1, k2;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const Near n = make_near(s, r0[j], r1[j], r2[j]);
+            float p0 = r0[j], p1 = r1[j], p2 = r2[j];
+            switch (s.code) {
+                case 1: p0 = r1[j]; p1 = (float)(s.n1 - 1) - r0[j]; break;
+                case 2: p0 = r2[j]; p2 = (float)(s.n2 - 1) - r0[j]; break;
+                case 3: p1 = r2[j]; p2 = (float)(s.n2 - 1) - r1[j]; break;
+                default: break;
+            }
+            k0[j] = n.ok ? p0 - h0 : 0.f;
+            k1[j] = n.ok ? p1 - h1 : 0.f;
+            k2[j] = n.ok ? p2 - h2 : 0.f;
+        }
+        float* oc = a.coord + (long)b * 3 * ovol + orow;
+        if (nv == 4) {
+            *reinterpret_cast<f32x4u*>(oc) = k0;
+            *reinterpret_cast<f32x4u*>(oc + ovol) = k1;
+            *reinterpret_cast<f32x4u*>(oc + 2 * ovol) = k2;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (j < nv) { oc[j] = k0[j]; oc[ovol + j] = k1[j]; oc[2 * ovol + j] = k2[j]; }
+        }
+    }
+    const long cs = (long)s.n0 * s.n1 * s.n2;
+    for (int c = 0; c < a.C; ++c) {
+        const bool labels = c == 0 && a.mask && s.lab;
+        if (STAGED) {
+            if (c) __syncthreads();                              // the box's readers of the last channel are done
+            stage(s, bx, s.img + c * cs, box, labels, lbox, s_lut);
+            __syncthreads();
+        }
+        if (!active) continue;
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = sample_image<STAGED>(s, bx, box, s.img + c * cs, make_tap(s, r0[j], r1[j], r2[j]));
+        float* oi = a.image + ((long)b * a.C + c) * ovol + orow;
+        if (nv == 4) *reinterpret_cast<f32x4u*>(oi) = v;
+        else {
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (j < nv) oi[j] = v[j];
+        }
+        if (c == 0 && a.mask) {
+            f32x4 m;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) m[j] = sample_mask<STAGED>(s, bx, lbox, s_lut, make_near(s, r0[j], r1[j], r2[j]));
+            float* om = a.mask + (long)b * ovol + orow;
+            if (nv == 4) *reinterpret_cast<f32x4u*>(om) = m;
+            else {
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    if (j < nv) om[j] = m[j];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(TPB) void k_crop_affine(AffArgs a) {
+    extern __shared__ float box[];                               // BOXV floats, then BOXV label bytes -- or nothing (stage == 0)
+    uint8_t* lbox = reinterpret_cast<uint8_t*>(box + BOXV);
+    __shared__ uint8_t s_lut[256];
+    const int b = blockIdx.y;
+    if (a.lut) {
+        s_lut[threadIdx.x] = a.lut[threadIdx.x];
+        __syncthreads();
+    }
+    const int32_t* rec = a.slot + (long)b * a.slot_stride;
+    Src s;
+    const int vol = rec[0];
+    s.code = rec[1];
+    if ((unsigned)vol >= (unsigned)a.n_volumes || (unsigned)s.code > 3u) return;          // never follow a wild row
+    const int64_t* row = a.table + (long)vol * 5;
+    s.img = reinterpret_cast<const float*>(row[0]);
+    if (!s.img) return;                                          // an empty row of a fixed-capacity table
+    s.lab = reinterpret_cast<const uint8_t*>(row[1]);
+    s.n0 = (int)row[2]; s.n1 = (int)row[3]; s.n2 = (int)row[4];
+    s.m0 = s.code == 2 ? s.n2 : (s.code == 1 ? s.n1 : s.n0);
+    s.m1 = s.code == 3 ? s.n2 : (s.code == 1 ? s.n0 : s.n1);
+    s.m2 = s.code == 2 ? s.n0 : (s.code == 3 ? s.n1 : s.n2);
+    const float* aff = a.affine + (long)b * 12;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s.A[i] = aff[i];
+    const int roi[3] = {a.h, a.w, a.d};
+    const int m[3] = {s.m0, s.m1, s.m2};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        s.c[k] = 0.5f * (float)(roi[k] - 1);
+        s.t[k] = (s.c[k] + (float)(rec[2 + k] - pad_before(roi[k], m[k]))) + aff[9 + k];
+    }
+    // the brick and the box of its source positions
+    int unit = blockIdx.x;
+    const int bh = unit / (a.nbw * a.nbd);
+    unit -= bh * (a.nbw * a.nbd);
+    const int bw = unit / a.nbd, bd = unit - bw * a.nbd;
+    const int u0h = bh * BH, u0w = bw * BW, u0d = bd * BD;
+    const int u1h = min(u0h + BH, a.h) - 1, u1w = min(u0w + BW, a.w) - 1, u1d = min(u0d + BD, a.d) - 1;
+    float mn[3], mx[3];
+    bool finite = true;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float q0 = (float)((e & 4) ? u1h : u0h) - s.c[0], q1 = (float)((e & 2) ? u1w : u0w) - s.c[1];
+        const float q2 = (float)((e & 1) ? u1d : u0d) - s.c[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float r = src_pos(s, k, q0, q1, q2);
+            finite = finite && fabsf(r) < 1e9f;                  // false for NaN and infinity
+            mn[k] = e ? fminf(mn[k], r) : r;
+            mx[k] = e ? fmaxf(mx[k], r) : r;
+        }
+    }
+    Box bx = {};
+    bool staged = finite && a.stage;
+    if (staged) {
+        // r is affine in u up to its rounding (far below one voxel): the brick's floor(r) lie in [floor(mn) - 1,
+        // floor(mx) + 1] and their upper corners one above; clipped to the volume and its rim of zeros at -1 and m
+        const int lo0 = max((int)floorf(mn[0]) - 1, -1), hi0 = min((int)floorf(mx[0]) + 2, s.m0);
+        const int lo1 = max((int)floorf(mn[1]) - 1, -1), hi1 = min((int)floorf(mx[1]) + 2, s.m1);
+        const int lo2 = max((int)floorf(mn[2]) - 1, -1), hi2 = min((int)floorf(mx[2]) + 2, s.m2);
+        bx.lo0 = lo0; bx.lo1 = lo1; bx.lo2 = lo2;
+        bx.e0 = hi0 - lo0 + 1; bx.e1 = hi1 - lo1 + 1; bx.e2 = hi2 - lo2 + 1;
+        bx.pitch = bx.e2 | 1;
+        staged = bx.e0 >= 2 && bx.e1 >= 2 && bx.e2 >= 2 && (long)bx.e0 * bx.e1 * bx.pitch <= (long)BOXV;
+    }
+    if (a.paths && threadIdx.x == 0) a.paths[(long)b * gridDim.x + blockIdx.x] = staged ? 1 : 0;
+    if (staged) fill_brick<true>(a, s, bx, b, u0h, u0w, u0d, box, lbox, s_lut);
+    else fill_brick<false>(a, s, bx, b, u0h, u0w, u0d, box, lbox, s_lut);
+}
+
+int launch(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot, int32_t slot_stride, const float* affine,
+           int32_t B, const int32_t* roi, const uint8_t* lut, float* image, float* mask, float* coord, int stage,
+           int32_t* paths, mivp_stream_t stream) {
+    MIVP_REQUIRE(table && slot && affine && image && roi);
+    MIVP_REQUIRE(((uintptr_t)table & 7) == 0 && ((uintptr_t)slot & 3) == 0 && ((uintptr_t)affine & 3) == 0);
+    MIVP_REQUIRE(((uintptr_t)image & 3) == 0 && ((uintptr_t)mask & 3) == 0 && ((uintptr_t)coord & 3) == 0 &&
+                 ((uintptr_t)paths & 3) == 0);
+    MIVP_REQUIRE(n_volumes >= 1 && C >= 1 && C <= MAXC && B >= 1 && B <= 65535 && slot_stride >= 5);
+    for (int k = 0; k < 3; ++k) MIVP_REQUIRE(roi[k] >= 1 && roi[k] <= 65535);
+    MIVP_REQUIRE((long)roi[0] * roi[1] * roi[2] * (C > 3 ? C : 3) < (1L << 31));
+    MIVP_REQUIRE(!mask || lut);
+    AffArgs a{};
+    a.table = table; a.n_volumes = n_volumes; a.C = C; a.B = B;
+    a.slot = slot; a.slot_stride = slot_stride; a.affine = affine;
+    a.h = roi[0]; a.w = roi[1]; a.d = roi[2];
+    a.nbw = (a.w + BW - 1) / BW; a.nbd = (a.d + BD - 1) / BD;
+    a.lut = mask ? lut : nullptr;
+    a.image = image; a.mask = mask; a.coord = coord;
+    a.stage = stage; a.paths = paths;
+    const long units = (long)((a.h + BH - 1) / BH) * a.nbw * a.nbd;
+    if (units >= (1L << 31)) { mivp_set_error("crop_fill_affine: too many work units"); return MIVP_EINVAL; }
+    // the box is dynamic LDS: a launch that stages nothing asks for none, and its occupancy is the registers'
+    const size_t lds = stage ? (size_t)BOXV * (sizeof(float) + 1) : 0;
+    hipLaunchKernelGGL(k_crop_affine, dim3((unsigned)units, (unsigned)B), dim3(TPB), lds, (hipStream_t)stream, a);
+    return mivp_check_launch("crop_fill_affine");
+}
+}  // namespace
+
+extern "C" int mivp_crop_fill_affine(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot,
+                                     int32_t slot_stride, const float* affine, int32_t B, const int32_t* roi,
+                                     const uint8_t* lut, float* image, float* mask, float* coord, mivp_stream_t stream) {
+    return launch(table, n_volumes, C, slot, slot_stride, affine, B, roi, lut, image, mask, coord, 0, nullptr, stream);
+}
+
+extern "C" int mivp_crop_fill_affine_debug(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot,
+                                           int32_t slot_stride, const float* affine, int32_t B, const int32_t* roi,
+                                           const uint8_t* lut, float* image, float* mask, float* coord,
+                                           int32_t stage, int32_t* paths, mivp_stream_t stream) {
+    return launch(table, n_volumes, C, slot, slot_stride, affine, B, roi, lut, image, mask, coord, stage != 0, paths, stream);
+}

@@ -33,7 +33,22 @@ whole measurement ``--runs`` times (2) in one process, every figure as the list 
   (``pick_ms``), and ``pick_share_of_step`` = (class_ms - plain_ms) / the step the batch feeds;
 - ``eager_ms``: the same centres from eager torch on the same GPU, per sample
   ``(lut[lab] == c).flatten().nonzero()[rank]`` (checked to give the voxels the device picked).
-Random orientation is on in every class-balanced row."""
+Random orientation is on in every class-balanced row.
+
+``--spatial`` measures the random flip / rotation / zoom of DESIGN 4.28 (``BatchFiller(spatial=True)``), again ``--runs``
+whole measurements with their spread, appended to profiles/spatial_crops_bench.jsonl.  For the ``downstream`` and
+``students_teacher`` rows (random orientation off), every ``fill`` recorded once and replayed:
+
+- ``plain_ms``: the filler without the option (the parent's path); ``identity_ms``: ``spatial=True`` with the identity;
+  ``typical_ms``: flips with p = 0.5, +-0.26 rad about every axis, anisotropic zoom 0.8-1.25, sub-voxel shift;
+  ``minified_ms``: zoom 0.2 (A = 5 I), whose boxes exceed the staged path's budget;
+- ``teacher_direct_ms`` / ``teacher_staged_ms``: the teacher launch alone on the typical draws, every corner read from
+  global memory (what ``fill`` issues) and with the LDS staging switched on through the debug entry (``staged_fraction``
+  of its workgroups then staged) -- the comparison that decided the default;
+- ``eager_ms``: image and mask of the same typical draws from eager torch on the same GPU, per sample ``affine_grid`` +
+  ``grid_sample`` (bilinear, and nearest on the label map through the table), checked against the filler's image;
+- ``share_of_step`` = (typical_ms - plain_ms) / the step the batch feeds.
+The crops are re-read from the Infinity Cache on every replay: none of these is an HBM rate."""
 import argparse
 import json
 import os
@@ -204,6 +219,110 @@ def class_balanced(a):
         f.write("\n".join(lines) + "\n")
 
 
+def spatial(a):
+    """``--spatial``: see the module docstring."""
+    import numpy as np
+    import torch
+    import torch.nn.functional as F
+    import mivp_amd  # noqa: F401
+    from mivp_amd import _lib as L, batches as BT
+    from mivp_amd._host import i3
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(1)
+    bank = BT.VolumeBank(dev, 1)
+    for _ in range(a.volumes):
+        bank.add(torch.rand((1,) + BANK_SHAPE, generator=g).to(dev),
+                 torch.randint(0, 4, BANK_SHAPE, generator=g, dtype=torch.uint8).to(dev))
+    rows = [c for c in CASES if c[0] in ("downstream", "students_teacher")]
+    keys = ("plain_ms", "identity_ms", "typical_ms", "minified_ms", "teacher_staged_ms", "teacher_direct_ms", "eager_ms")
+    recs = {}
+    for name, roi, B, sizes, with_coord, step_ms, step_kind in rows:
+        recs[name] = {"case": name, "roi": list(roi), "B": B, "students": [list(x) for x in sizes], "brick": list(BT.SPATIAL_BRICK),
+                      "box_cells": BT.SPATIAL_BOX_CELLS, **{k: [] for k in keys}, "staged_fraction": [],
+                      "minified_staged_fraction": [], "step_ms": step_ms, "step": step_kind}
+    typical = dict(p_flip=(0.5, 0.5, 0.5), p_affine=1.0, rotate_range=(0.26, 0.26, 0.26), scale_range=(0.8, 1.25),
+                   isotropic=False, shift=True)
+    for run in range(a.runs):
+        for name, roi, B, sizes, with_coord, step_ms, _ in rows:
+            r = recs[name]
+            rs = np.random.RandomState(3 + run)
+            ids = [i % len(bank) for i in range(B)]
+            d = BT.draw_crops(rs, bank.shapes, ids, roi, 1, False, sizes)
+            sp = BT.draw_spatial(rs, B, **typical)
+            small = BT.draw_spatial(rs, B, p_affine=1.0, scale_range=(0.2, 0.2))
+            plain = BT.BatchFiller(bank, roi, B, student_sizes=sizes, active_labels=ACTIVE, with_coord=with_coord)
+            own = BT.BatchFiller(bank, roi, B, student_sizes=sizes, active_labels=ACTIVE, with_coord=with_coord, spatial=True)
+            plain.fill(d)
+            own.fill(d)
+            torch.cuda.synchronize()
+            assert torch.equal(plain.image, own.image) and torch.equal(plain.mask, own.mask), f"{name}: the identity differs"
+            lut = own.lut.float()
+            half = (np.asarray(roi) - 1) / 2.0
+
+            def eager():
+                img, mask = [], []
+                for b in range(B):
+                    vol = bank.images[int(d.volume[b])][None]
+                    m = np.asarray(vol.shape[2:], np.float64)
+                    A = sp.affine[b, :9].astype(np.float64).reshape(3, 3)
+                    t = half + d.origin[b] + sp.affine[b, 9:]
+                    th = np.zeros((3, 4))
+                    th[:, :3] = (2.0 / (m - 1))[:, None] * A * half[None, :]
+                    th[:, 3] = 2.0 * t / (m - 1) - 1.0
+                    th = th[::-1, [2, 1, 0, 3]].copy()              # grid_sample counts x, y, z from the LAST axis
+                    grid = F.affine_grid(torch.from_numpy(th).float().to(dev)[None], (1, 1) + tuple(roi), align_corners=True)
+                    img.append(F.grid_sample(vol, grid, mode="bilinear", padding_mode="zeros", align_corners=True)[0])
+                    lab = lut[bank.labels[int(d.volume[b])].long()][None, None]
+                    mask.append(F.grid_sample(lab, grid, mode="nearest", padding_mode="zeros", align_corners=True)[0])
+                return torch.stack(img), torch.stack(mask)
+
+            own.fill(d, spatial=sp)
+            e_img, _ = eager()
+            torch.cuda.synchronize()
+            # affine_grid works in normalised fp32 coordinates of a 512-voxel axis: the positions agree to ~1e-4 voxel
+            assert float((e_img - own.image).abs().max()) < 5e-3, f"{name}: the eager composition disagrees"
+
+            def teacher(stage, paths=None):
+                L.call("mivp_crop_fill_affine_debug", L.ptr(bank.table), bank.capacity, bank.channels, L.ptr(own.slot.records),
+                       own.slot.words, L.ptr(own.spatial_slot.words), B, i3(roi), L.ptr(own.lut), L.ptr(own.image),
+                       L.ptr(own.mask), L.ptr(own.coord), stage, L.ptr(paths), L.stream())
+
+            bricks = int(np.prod([-(-roi[k] // BT.SPATIAL_BRICK[k]) for k in range(3)]))
+            paths = torch.zeros((B, bricks), dtype=torch.int32, device=dev)
+            teacher(1, paths)
+            r["staged_fraction"].append(round(float(paths.float().mean()), 4))
+
+            def record(fn):
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    fn()
+                return graph
+
+            r["plain_ms"].append(round(timed(record(plain.fill).replay, a.calls, a.warmup), 4))
+            graph = record(own.fill)                                # one recording, fed by the spatial slot
+            for key, draws in (("identity_ms", BT.SpatialDraws.identity(B)), ("typical_ms", sp), ("minified_ms", small)):
+                own.spatial_slot.load(draws)
+                r[key].append(round(timed(graph.replay, a.calls, a.warmup), 4))
+            teacher(1, paths)
+            r["minified_staged_fraction"].append(round(float(paths.float().mean()), 4))
+            own.spatial_slot.load(sp)
+            r["teacher_staged_ms"].append(round(timed(record(lambda: teacher(1)).replay, a.calls, a.warmup), 4))
+            r["teacher_direct_ms"].append(round(timed(record(lambda: teacher(0)).replay, a.calls, a.warmup), 4))
+            r["eager_ms"].append(round(timed(eager, max(5, a.calls // 10), 2), 4))
+    lines = []
+    for r in recs.values():
+        for k in keys:
+            r[k.replace("_ms", "_spread")] = spread(r[k])
+        r["share_of_step"] = [round((t - p) / r["step_ms"], 5) for t, p in zip(r["typical_ms"], r["plain_ms"])]
+        r["eager_over_typical"] = [round(e / t, 1) for e, t in zip(r["eager_ms"], r["typical_ms"])]
+        print(json.dumps(r), flush=True)
+        lines.append(json.dumps(r))
+    os.makedirs(os.path.dirname(a.spatial_out), exist_ok=True)
+    with open(a.spatial_out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def rotated(codes, p, rot_axes):
     """Stored voxels ``p`` [B, 3] in the frames rotated by ``codes``: for axes (a, b), r_b = p_a and r_a = n_b - 1 - p_b."""
     import numpy as np
@@ -225,11 +344,15 @@ def main():
                     "kernel-trace run, where every k_crop launch of the process should be the same launch")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batches_bench.jsonl"))
     ap.add_argument("--class-balanced", action="store_true", help="measure the class-balanced sampling (DESIGN 4.27)")
-    ap.add_argument("--runs", type=int, default=2, help="--class-balanced: how often the whole measurement is made")
+    ap.add_argument("--runs", type=int, default=2, help="--class-balanced, --spatial: how often the whole measurement is made")
     ap.add_argument("--class-out", default=os.path.join(ROOT, "profiles", "class_crops_bench.jsonl"))
+    ap.add_argument("--spatial", action="store_true", help="measure the random flip / rotation / zoom (DESIGN 4.28)")
+    ap.add_argument("--spatial-out", default=os.path.join(ROOT, "profiles", "spatial_crops_bench.jsonl"))
     a = ap.parse_args()
     if a.class_balanced:
         return class_balanced(a)
+    if a.spatial:
+        return spatial(a)
     import numpy as np
     import torch
     import mivp_amd  # noqa: F401
