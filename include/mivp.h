@@ -973,6 +973,8 @@ int mivp_window_fit_plan(const int32_t* box, const int32_t* dims, const int32_t*
                          int32_t n_flips, int32_t* table, int32_t n_entries, int32_t* origins, int32_t n_origins,
                          int32_t* meta, mivp_stream_t stream);
 
+/* The three sources of the batch filler named below (csrc/crops.hip, crops_index.hip, crops_affine.hip) share
+ * csrc/crops_common.hpp: the slot record and table row decode, the quarter turn, the pad rule and the host checks. */
 /* Training-batch sampling from a bank of resident scans (csrc/crops.hip; mivp_amd/batches.py).  These entry
  * points joined the current ABI without a bump: they are additive and no earlier signature changed.  One gather kernel
  * family (k_crop): every output voxel is written exactly once, no atomics, bitwise reproducible, no host synchronisation.

@@ -47,6 +47,61 @@ def _size3(name: str, v) -> Tuple[int, int, int]:
     return tuple(check_int_from(name, a, 1) for a in v)
 
 
+def _gpu_device(who: str, device) -> torch.device:
+    """``device`` as a GPU device with its index filled in; ``ValueError`` in ``who``'s name for anything else."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"{who}: a GPU device expected (no CPU fallback)")
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _refuse(who: str, bad: np.ndarray, what):
+    """``ValueError`` naming the first sample at which ``bad`` [B] holds; ``what(b)`` says what is wrong with it."""
+    if bad.any():
+        b = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"{who}: sample {b}: {what(b)}")
+
+
+def _check_rot_and_students(who: str, rot, st, roi, sizes):
+    """What ``CropDraws.check`` and ``ClassCropDraws.check`` share: the rotation codes [B] and the students' origins
+    [S, B, 3] against ``roi`` and the student ``sizes``."""
+    _refuse(who, (rot < 0) | (rot > 3), lambda b: f"rotation code {int(rot[b])} outside 0..3")
+    for s, size in enumerate(sizes):
+        for k in range(3):
+            hi = max(roi[k] - size[k], 0)
+            _refuse(who, (st[s, :, k] < 0) | (st[s, :, k] > hi),
+                    lambda b: f"origin {st[s, b].tolist()} of student {s} outside [0, {hi}] on axis {k} (roi {roi}, student "
+                              f"size {size})")
+
+
+def _draw_start(who: str, n_bank: int, ids_kind: str, volume_ids, roi, num_samples, student_sizes):
+    """The prologue of ``draw_crops`` and ``draw_class_crops``: (roi, student sizes, ids, B, volume [B], rot [B] = 0,
+    student_origin [S, B, 3] = 0) after the checks they share; no draw is made here."""
+    roi = _size3("roi", roi)
+    sizes = [_size3("student size", s) for s in student_sizes]
+    ids = [int(v) for v in volume_ids]
+    check_int_from("num_samples", num_samples, 1)
+    if not ids or any(not 0 <= v < n_bank for v in ids):
+        raise ValueError(f"{who}: volume_ids {ids} must be a non-empty list of {ids_kind} in 0..{n_bank - 1}")
+    B = len(ids) * int(num_samples)
+    return (roi, sizes, ids, B, np.repeat(np.asarray(ids, np.int32), int(num_samples)), np.zeros(B, np.int32),
+            np.zeros((len(sizes), B, 3), np.int32))
+
+
+def _draw_orientation(rs, rot, n_ids: int, num_samples: int):
+    """Step 1 of both draw orders: one ``rs.randint(3)`` per volume, held by all its samples."""
+    for i in range(n_ids):
+        rot[i * num_samples:(i + 1) * num_samples] = int(rs.randint(3)) + 1
+
+
+def _draw_student_origins(rs, st, roi, sizes):
+    """Step 3 of both draw orders: per sample, per student and per axis one ``rs.randint(0, roi - min(s, roi) + 1)``."""
+    for b in range(st.shape[1]):
+        for s, size in enumerate(sizes):
+            for k in range(3):
+                st[s, b, k] = rs.randint(0, roi[k] - min(size[k], roi[k]) + 1)
+
+
 def rotated_shape(shape, rot: int) -> Tuple[int, int, int]:
     """The extents of a stored ``[H, W, D]`` volume after rotation code ``rot``."""
     n = list(shape)
@@ -106,23 +161,16 @@ class CropDraws:
         if B < 1 or rot.shape != (B,) or org.shape != (B, 3) or st.shape != (len(sizes), B, 3):
             raise ValueError(f"CropDraws: volume [B], rot [B], origin [B, 3] and student_origin [{len(sizes)}, B, 3] of one "
                              f"batch size expected, got {vol.shape}, {rot.shape}, {org.shape}, {st.shape}")
+        _refuse("CropDraws", (vol < 0) | (vol >= len(shapes)),
+                lambda b: f"volume id {int(vol[b])} outside the bank's 0..{len(shapes) - 1}")
+        _check_rot_and_students("CropDraws", rot, st, roi, sizes)
         for b in range(B):
-            if not 0 <= int(vol[b]) < len(shapes):
-                raise ValueError(f"CropDraws: sample {b}: volume id {int(vol[b])} outside the bank's 0..{len(shapes) - 1}")
-            if not 0 <= int(rot[b]) <= 3:
-                raise ValueError(f"CropDraws: sample {b}: rotation code {int(rot[b])} outside 0..3")
             n_rot = rotated_shape(shapes[int(vol[b])], int(rot[b]))
             for k in range(3):
                 hi = max(n_rot[k] - roi[k], 0)
                 if not 0 <= int(org[b, k]) <= hi:
                     raise ValueError(f"CropDraws: sample {b}: origin {org[b].tolist()} outside [0, {hi}] on axis {k} (rotated "
                                      f"volume {n_rot}, roi {roi})")
-            for s, size in enumerate(sizes):
-                for k in range(3):
-                    hi = max(roi[k] - size[k], 0)
-                    if not 0 <= int(st[s, b, k]) <= hi:
-                        raise ValueError(f"CropDraws: sample {b}: origin {st[s, b].tolist()} of student {s} outside [0, {hi}] "
-                                         f"on axis {k} (roi {roi}, student size {size})")
         return self
 
 
@@ -138,27 +186,17 @@ def draw_crops(rs: np.random.RandomState, bank_shapes, volume_ids: Sequence[int]
     Sample ``i * num_samples + j`` is crop ``j`` of ``volume_ids[i]``.  The uniform origin restates MONAI's documented
     ``get_random_patch``; MONAI's own stream is NOT reproduced (``Compose`` reseeds every child), so parity is unpinned at the
     MONAI boundary and this order is the project's own."""
-    roi = _size3("roi", roi)
-    sizes = [_size3("student size", s) for s in student_sizes]
     shapes = list(bank_shapes)
-    ids = [int(v) for v in volume_ids]
-    check_int_from("num_samples", num_samples, 1)
-    if not ids or any(not 0 <= v < len(shapes) for v in ids):
-        raise ValueError(f"draw_crops: volume_ids {ids} must be a non-empty list of ids in 0..{len(shapes) - 1}")
-    B = len(ids) * int(num_samples)
-    d = CropDraws(np.repeat(np.asarray(ids, np.int32), int(num_samples)), np.zeros(B, np.int32), np.zeros((B, 3), np.int32),
-                  np.zeros((len(sizes), B, 3), np.int32))
+    roi, sizes, ids, B, volume, rot, st = _draw_start("draw_crops", len(shapes), "ids", volume_ids, roi, num_samples,
+                                                      student_sizes)
+    d = CropDraws(volume, rot, np.zeros((B, 3), np.int32), st)
     if random_orientation:
-        for i in range(len(ids)):
-            d.rot[i * num_samples:(i + 1) * num_samples] = int(rs.randint(3)) + 1
+        _draw_orientation(rs, d.rot, len(ids), num_samples)
     for b in range(B):
         n_rot = rotated_shape(shapes[int(d.volume[b])], int(d.rot[b]))
         for k in range(3):
             d.origin[b, k] = rs.randint(0, n_rot[k] - min(roi[k], n_rot[k]) + 1)
-    for b in range(B):
-        for s, size in enumerate(sizes):
-            for k in range(3):
-                d.student_origin[s, b, k] = rs.randint(0, roi[k] - min(size[k], roi[k]) + 1)
+    _draw_student_origins(rs, d.student_origin, roi, sizes)
     return d
 
 
@@ -185,11 +223,7 @@ class VolumeBank:
     recorded in a graph therefore keeps a valid table pointer for the bank's lifetime and sees volumes added later."""
 
     def __init__(self, device, channels: int = 1, capacity: int = 256):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("VolumeBank: a GPU device expected (no CPU fallback)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _gpu_device("VolumeBank", device)
         self.channels = check_int_from("channels", channels, 1)
         if self.channels > MAX_CHANNELS:
             raise ValueError(f"VolumeBank: channels must be in 1..{MAX_CHANNELS}, got {channels}")
@@ -329,23 +363,14 @@ class ClassCropDraws:
             raise ValueError(f"ClassCropDraws: volume, rot, cls and rank [B] and student_origin [{len(sizes)}, B, 3] of one "
                              f"batch size expected, got {vol.shape}, {rot.shape}, {cls.shape}, {rank.shape}, {st.shape}")
 
-        def refuse(bad, what):
-            if bad.any():
-                b = int(np.flatnonzero(bad)[0])
-                raise ValueError(f"ClassCropDraws: sample {b}: {what(b)}")
-
-        refuse((vol < 0) | (vol >= len(counts)),
-               lambda b: f"volume id {vol[b]} is not indexed (the index holds volumes 0..{len(counts) - 1})")
-        refuse((rot < 0) | (rot > 3), lambda b: f"rotation code {rot[b]} outside 0..3")
-        refuse((cls < 0) | (cls >= nc), lambda b: f"class {cls[b]} outside 0..{nc - 1}")
+        who = "ClassCropDraws"
+        _refuse(who, (vol < 0) | (vol >= len(counts)),
+                lambda b: f"volume id {vol[b]} is not indexed (the index holds volumes 0..{len(counts) - 1})")
+        _check_rot_and_students(who, rot, st, roi, sizes)
+        _refuse(who, (cls < 0) | (cls >= nc), lambda b: f"class {cls[b]} outside 0..{nc - 1}")
         total = counts[vol, cls]
-        refuse((rank < 0) | (rank >= total),
-               lambda b: f"rank {rank[b]} outside [0, {total[b]}), the voxels of class {cls[b]} in volume {vol[b]}")
-        for s, size in enumerate(sizes):
-            hi = np.asarray([max(roi[k] - size[k], 0) for k in range(3)])
-            refuse(((st[s] < 0) | (st[s] > hi)).any(axis=1),
-                   lambda b: f"origin {st[s, b].tolist()} of student {s} outside [0, {hi.tolist()}] (roi {roi}, student "
-                             f"size {size})")
+        _refuse(who, (rank < 0) | (rank >= total),
+                lambda b: f"rank {rank[b]} outside [0, {total[b]}), the voxels of class {cls[b]} in volume {vol[b]}")
         return self
 
 
@@ -364,22 +389,15 @@ def draw_class_crops(rs: np.random.RandomState, index, volume_ids: Sequence[int]
     MONAI's ``RandCropByPosNegLabeld``, longer ``ratios`` are ``RandCropByLabelClassesd``: a centre uniform among the voxels
     of a class chosen by the ratios, never a class the volume lacks.  MONAI's own stream is NOT reproduced (as for
     ``draw_crops``): parity is unpinned at the MONAI boundary and this order is the project's own."""
-    roi = _size3("roi", roi)
-    sizes = [_size3("student size", s) for s in student_sizes]
     counts, nc = np.asarray(index.counts), int(index.num_classes)
-    ids = [int(v) for v in volume_ids]
-    check_int_from("num_samples", num_samples, 1)
-    if not ids or any(not 0 <= v < len(counts) for v in ids):
-        raise ValueError(f"draw_class_crops: volume_ids {ids} must be a non-empty list of indexed ids in 0..{len(counts) - 1}")
+    roi, sizes, ids, B, volume, rot, st = _draw_start("draw_class_crops", len(counts), "indexed ids", volume_ids, roi,
+                                                      num_samples, student_sizes)
     w = np.asarray(ratios, dtype=np.float64)
     if w.shape != (nc,) or not np.isfinite(w).all() or (w < 0).any():
         raise ValueError(f"draw_class_crops: ratios must be {nc} finite non-negative weights, got {ratios!r}")
-    B = len(ids) * int(num_samples)
-    d = ClassCropDraws(np.repeat(np.asarray(ids, np.int32), int(num_samples)), np.zeros(B, np.int32), np.zeros(B, np.int32),
-                       np.zeros(B, np.int32), np.zeros((len(sizes), B, 3), np.int32))
+    d = ClassCropDraws(volume, rot, np.zeros(B, np.int32), np.zeros(B, np.int32), st)
     if random_orientation:
-        for i in range(len(ids)):
-            d.rot[i * num_samples:(i + 1) * num_samples] = int(rs.randint(3)) + 1
+        _draw_orientation(rs, d.rot, len(ids), num_samples)
     for b in range(B):
         v = int(d.volume[b])
         p = w * (counts[v] > 0)
@@ -388,10 +406,7 @@ def draw_class_crops(rs: np.random.RandomState, index, volume_ids: Sequence[int]
                              f"{counts[v].tolist()}, ratios {w.tolist()})")
         d.cls[b] = rs.choice(nc, p=p / p.sum())
         d.rank[b] = rs.randint(0, counts[v][d.cls[b]])
-    for b in range(B):
-        for s, size in enumerate(sizes):
-            for k in range(3):
-                d.student_origin[s, b, k] = rs.randint(0, roi[k] - min(size[k], roi[k]) + 1)
+    _draw_student_origins(rs, d.student_origin, roi, sizes)
     return d
 
 
@@ -495,12 +510,7 @@ class SpatialSlot:
 
     def __init__(self, B: int, device):
         self.B = check_int_from("B", B, 1)
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("SpatialSlot: a GPU device expected (no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.words = torch.from_numpy(SpatialDraws.identity(self.B).affine.reshape(-1)).to(device)
+        self.words = torch.from_numpy(SpatialDraws.identity(self.B).affine.reshape(-1)).to(_gpu_device("SpatialSlot", device))
         self.draws = SpatialDraws.identity(self.B)
 
     def load(self, draws: SpatialDraws):
@@ -528,14 +538,12 @@ class CropSlot:
         self.words = record_words(self.n_students)
         self.class_index = class_index
         if class_index is None:
-            self.records = torch.zeros(self.B * self.words, dtype=torch.int32, device=device)
+            self.buffer = self.records = torch.zeros(self.B * self.words, dtype=torch.int32, device=device)
             self.picks = None
         else:
-            device = torch.device(device)
-            if not isinstance(class_index, ClassIndex) or device.type != "cuda":
+            if not isinstance(class_index, ClassIndex) or torch.device(device).type != "cuda":
                 raise ValueError("CropSlot: class_index must be a ClassIndex and the device its bank's GPU (no CPU fallback)")
-            if device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
+            device = _gpu_device("CropSlot", device)
             if device != class_index.bank.device or self.B > 65535:
                 raise ValueError(f"CropSlot: a class-mode slot of batch <= 65535 on {class_index.bank.device} expected, got "
                                  f"batch {self.B} on {device}")
@@ -543,24 +551,7 @@ class CropSlot:
             self.records, self.picks = self.buffer[:self.B * self.words], self.buffer[self.B * self.words:]
         self.student_views = [self.records[HEAD + 3 * s:] for s in range(self.n_students)]   # advanced to the origin words
         self.draws = None
-        self.checked = None             # (bank shapes, roi, student sizes) the loaded draws were checked against
-
-    def _load_class(self, draws, bank, roi, student_sizes):
-        index = self.class_index
-        if not isinstance(draws, ClassCropDraws):
-            raise ValueError("CropSlot.load: a class-mode slot takes ClassCropDraws only")
-        if bank is not index and bank is not index.bank:
-            raise ValueError("CropSlot.load: a class-mode slot loads against its own index (or that index's bank)")
-        if len(tuple(student_sizes)) != self.n_students:
-            raise ValueError(f"CropSlot: {len(tuple(student_sizes))} student sizes for a slot of {self.n_students} students")
-        if draws.check(index, roi, student_sizes).batch != self.B:
-            raise ValueError(f"CropSlot: draws of batch {draws.batch} do not match the slot's batch {self.B}")
-        if torch.cuda.is_current_stream_capturing():
-            return
-        words = np.concatenate([draws.pack().reshape(-1), draws.picks().reshape(-1)])
-        self.buffer.copy_(torch.from_numpy(words).pin_memory(), non_blocking=True)
-        self.draws = draws
-        self.checked = (index, _size3("roi", roi), [_size3("student size", s) for s in student_sizes])
+        self.checked = None             # (bank shapes or the class index, roi, student sizes) the draws were checked against
 
     def resolve(self, roi):
         """Class mode: the pick launch alone, on the current stream -- it writes the crop origin of every sample into the
@@ -581,20 +572,25 @@ class CropSlot:
         return self.records.view(self.B, self.words)[:, 2:HEAD].cpu().numpy()
 
     def load(self, draws: CropDraws, bank, roi, student_sizes=()):
-        if self.class_index is not None:
-            return self._load_class(draws, bank, roi, student_sizes)
-        if not isinstance(draws, CropDraws):
-            raise ValueError("CropSlot.load: CropDraws expected")
+        index = self.class_index
+        if index is None:
+            if not isinstance(draws, CropDraws):
+                raise ValueError("CropSlot.load: CropDraws expected")
+        elif not isinstance(draws, ClassCropDraws):
+            raise ValueError("CropSlot.load: a class-mode slot takes ClassCropDraws only")
+        elif bank is not index and bank is not index.bank:
+            raise ValueError("CropSlot.load: a class-mode slot loads against its own index (or that index's bank)")
         if len(tuple(student_sizes)) != self.n_students:
             raise ValueError(f"CropSlot: {len(tuple(student_sizes))} student sizes for a slot of {self.n_students} students")
-        if draws.check(bank, roi, student_sizes).batch != self.B:
+        if draws.check(bank if index is None else index, roi, student_sizes).batch != self.B:
             raise ValueError(f"CropSlot: draws of batch {draws.batch} do not match the slot's batch {self.B}")
         if torch.cuda.is_current_stream_capturing():
             return
-        self.records.copy_(torch.from_numpy(draws.pack().reshape(-1)).pin_memory(), non_blocking=True)
+        words = [draws.pack().reshape(-1)] + ([] if index is None else [draws.picks().reshape(-1)])      # ONE upload
+        self.buffer.copy_(torch.from_numpy(np.concatenate(words)).pin_memory(), non_blocking=True)
         self.draws = draws
-        shapes = bank.shapes if hasattr(bank, "shapes") else bank
-        self.checked = (tuple(tuple(s) for s in shapes), _size3("roi", roi), [_size3("student size", s) for s in student_sizes])
+        held = index if index is not None else tuple(tuple(s) for s in (bank.shapes if hasattr(bank, "shapes") else bank))
+        self.checked = (held, _size3("roi", roi), [_size3("student size", s) for s in student_sizes])
 
 
 class BatchFiller:
@@ -726,14 +722,15 @@ class BatchFiller:
         return self.batch
 
     def _fill_teacher(self, slot: CropSlot, spatial_slot: Optional[SpatialSlot] = None):
-        bank = self.bank
-        if spatial_slot is not None:
-            L.call("mivp_crop_fill_affine", L.ptr(bank.table), bank.capacity, bank.channels, L.ptr(slot.records), slot.words,
-                   L.ptr(spatial_slot.words), self.B, i3(self.roi), L.ptr(self.lut), L.ptr(self.image), L.ptr(self.mask),
-                   L.ptr(self.coord), L.stream())
-            return
-        L.call("mivp_crop_fill", L.ptr(bank.table), bank.capacity, bank.channels, L.ptr(slot.records), slot.words, self.B,
-               i3(self.roi), L.ptr(self.lut), L.ptr(self.image), L.ptr(self.mask), L.ptr(self.coord), L.stream())
+        bank, roi, st = self.bank, i3(self.roi), L.stream()         # every argument is formed once, for either entry
+        table, records, lut = L.ptr(bank.table), L.ptr(slot.records), L.ptr(self.lut)
+        image, mask, coord = L.ptr(self.image), L.ptr(self.mask), L.ptr(self.coord)
+        if spatial_slot is None:
+            L.call("mivp_crop_fill", table, bank.capacity, bank.channels, records, slot.words, self.B, roi, lut, image, mask,
+                   coord, st)
+        else:
+            L.call("mivp_crop_fill_affine", table, bank.capacity, bank.channels, records, slot.words,
+                   L.ptr(spatial_slot.words), self.B, roi, lut, image, mask, coord, st)
 
     def _fill_students(self, slot: CropSlot):
         st, Cn = L.stream(), self.bank.channels

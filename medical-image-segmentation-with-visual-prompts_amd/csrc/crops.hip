@@ -20,15 +20,12 @@
 //         ([64][65]: the transposed read is conflict-free) and is written along the output's d, as k_mv_permute does.  The
 //         coordinates are arithmetic and skip the LDS.
 // No division in the voxel loops; the per-workgroup ones are 32-bit and uniform.  No out-of-range address can be formed from
-// the slot: the volume id and the code are checked per workgroup, r per voxel.
-#include "common.hpp"
+// the slot: the volume id and the code are checked per workgroup, r per voxel.  The record and row decode, the quarter turn
+// and the pad rule are crops_common.hpp's, shared with crops_index.hip and crops_affine.hip.
+#include "crops_common.hpp"
 
 namespace {
-constexpr int TPB = 256;
 constexpr int TILE = 64;
-constexpr int MAXC = 16;
-
-typedef f32x4 f32x4u __attribute__((aligned(4)));      // four voxels of a row: crops start at any multiple of 4 bytes
 
 struct CropArgs {
     const int64_t* table;    // bank mode: [n_volumes][5]; NULL in tensor mode
@@ -47,28 +44,9 @@ struct CropArgs {
 };
 
 // what a workgroup knows about its sample
-struct Sample {
-    const float* img;
-    const uint8_t* lab;
-    int n0, n1, n2;          // stored extents H, W, D
-    int m0, m1, m2;          // rotated extents
+struct Sample : BankVol {
     int s0, s1, s2;          // origin - pad_before: r = s + u
-    int code;
 };
-
-MIVP_DEV int pad_before(int roi, int m) { return (roi - min(roi, m)) >> 1; }
-
-// r (rotated frame, in range) -> p (stored frame); torch.rot90(v, 1, (a, b)): out[i_a, i_b] = in[i_b, n_b - 1 - i_a]
-MIVP_DEV void unrotate(const Sample& s, int r0, int r1, int r2, int& p0, int& p1, int& p2) {
-    switch (s.code) {
-        case 1: p0 = r1; p1 = s.n1 - 1 - r0; p2 = r2; break;
-        case 2: p0 = r2; p1 = r1; p2 = s.n2 - 1 - r0; break;
-        case 3: p0 = r0; p1 = r2; p2 = s.n2 - 1 - r1; break;
-        default: p0 = r0; p1 = r1; p2 = r2; break;
-    }
-}
-
-MIVP_DEV bool inside(int r, int m) { return (unsigned)r < (unsigned)m; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // rows: D in place.  Thread = (row u_w of the chunk, lane along d).
@@ -82,8 +60,8 @@ MIVP_DEV void crop_rows(const CropArgs& a, const Sample& s, int b, const uint8_t
     if (uw >= a.w) return;
     const int r0 = s.s0 + uh, r1 = s.s1 + uw;
     const bool row_ok = inside(r0, s.m0) & inside(r1, s.m1);
-    int p0 = 0, p1 = 0, pz;
-    if (row_ok) unrotate(s, r0, r1, 0, p0, p1, pz);
+    int p0 = 0, p1 = 0;
+    if (row_ok) { const Vox<int> p = to_stored(s, r0, r1, 0); p0 = p.p0; p1 = p.p1; }
     const long cs = (long)s.n0 * s.n1 * s.n2;                            // source channel stride
     const long srow = ((long)p0 * s.n1 + p1) * s.n2;
     const long ovol = (long)a.h * a.w * a.d;
@@ -193,8 +171,8 @@ MIVP_DEV void crop_tiles(const CropArgs& a, const Sample& s, int b, const uint8_
             const bool ok = f_ok && inside(re, me) && inside(r2, s.m2);
             float k0 = 0.f, k1 = 0.f, k2 = 0.f;
             if (ok) {
-                int p0, p1, p2;
-                unrotate(s, c2 ? re : rf, c2 ? rf : re, r2, p0, p1, p2);
+                const Vox<int> p = to_stored(s, c2 ? re : rf, c2 ? rf : re, r2);
+                const int p0 = p.p0, p1 = p.p1, p2 = p.p2;
                 k0 = (float)p0 - 0.5f * (float)(s.n0 - 1);
                 k1 = (float)p1 - 0.5f * (float)(s.n1 - 1);
                 k2 = (float)p2 - 0.5f * (float)(s.n2 - 1);
@@ -211,21 +189,11 @@ __global__ __launch_bounds__(TPB) void k_crop(CropArgs a) {
     __shared__ float tile[TILE][TILE + 1];
     __shared__ uint8_t s_lut[256];
     const int b = blockIdx.y;
-    if (a.lut) {
-        s_lut[threadIdx.x] = a.lut[threadIdx.x];
-        __syncthreads();
-    }
+    if (a.lut) load_lut(s_lut, a.lut);
     const int32_t* rec = a.slot + (long)b * a.slot_stride;
     Sample s;
     if (a.table) {
-        const int vol = rec[0];
-        s.code = rec[1];
-        if ((unsigned)vol >= (unsigned)a.n_volumes || (unsigned)s.code > 3u) return;      // never follow a wild row
-        const int64_t* row = a.table + (long)vol * 5;
-        s.img = reinterpret_cast<const float*>(row[0]);
-        if (!s.img) return;                                              // an empty row of a fixed-capacity table
-        s.lab = reinterpret_cast<const uint8_t*>(row[1]);
-        s.n0 = (int)row[2]; s.n1 = (int)row[3]; s.n2 = (int)row[4];
+        if (!bank_volume(s, a.table, a.n_volumes, rec)) return;
         rec += 2;
     } else {
         s.code = 0;
@@ -233,21 +201,12 @@ __global__ __launch_bounds__(TPB) void k_crop(CropArgs a) {
         s.img = a.src + (long)b * a.C * s.n0 * s.n1 * s.n2;
         s.lab = nullptr;
     }
-    s.m0 = s.code == 2 ? s.n2 : (s.code == 1 ? s.n1 : s.n0);
-    s.m1 = s.code == 3 ? s.n2 : (s.code == 1 ? s.n0 : s.n1);
-    s.m2 = s.code == 2 ? s.n0 : (s.code == 3 ? s.n1 : s.n2);
+    rotate_extents(s);
     s.s0 = rec[0] - pad_before(a.h, s.m0);
     s.s1 = rec[1] - pad_before(a.w, s.m1);
     s.s2 = rec[2] - pad_before(a.d, s.m2);
     if (s.code >= 2) crop_tiles(a, s, b, s_lut, tile);
     else crop_rows(a, s, b, s_lut);
-}
-
-bool roi_ok(const int32_t* roi) {
-    if (!roi) return false;
-    for (int k = 0; k < 3; ++k)
-        if (roi[k] < 1 || roi[k] > 65535) return false;
-    return (long)roi[0] * roi[1] * roi[2] < (1L << 31);
 }
 
 int launch(CropArgs& a, bool tiles, mivp_stream_t stream, const char* what) {
@@ -273,11 +232,8 @@ int launch(CropArgs& a, bool tiles, mivp_stream_t stream, const char* what) {
 extern "C" int mivp_crop_fill(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot, int32_t slot_stride,
                               int32_t B, const int32_t* roi, const uint8_t* lut, float* image, float* mask, float* coord,
                               mivp_stream_t stream) {
-    MIVP_REQUIRE(table && slot && image && ((uintptr_t)table & 7) == 0 && ((uintptr_t)slot & 3) == 0);
-    MIVP_REQUIRE(((uintptr_t)image & 3) == 0 && ((uintptr_t)mask & 3) == 0 && ((uintptr_t)coord & 3) == 0);
-    MIVP_REQUIRE(n_volumes >= 1 && C >= 1 && C <= MAXC && B >= 1 && B <= 65535 && slot_stride >= 5);
-    MIVP_REQUIRE(roi_ok(roi) && (long)roi[0] * roi[1] * roi[2] * (C > 3 ? C : 3) < (1L << 31));
-    MIVP_REQUIRE(!mask || lut);
+    const int rc = check_fill_args(table, n_volumes, C, slot, slot_stride, B, roi, lut, image, mask, coord);
+    if (rc) return rc;
     CropArgs a{};
     a.table = table; a.n_volumes = n_volumes; a.C = C; a.B = B;
     a.slot = slot; a.slot_stride = slot_stride;

@@ -22,16 +22,13 @@
 //            stage = 0, every workgroup).
 // No atomics, no per-lane arrays in scratch (everything below is unrolled over constant indices), no host synchronisation.
 // No out-of-range address can be formed from device memory: the volume id and the code are checked per workgroup, r per
-// voxel with float comparisons BEFORE it becomes an integer, and every LDS index is clamped into the box.
-#include "common.hpp"
+// voxel with float comparisons BEFORE it becomes an integer, and every LDS index is clamped into the box.  The record and row
+// decode, the quarter turn and the pad rule are crops_common.hpp's; `stage` writes out its box permutation (a box, not a point).
+#include "crops_common.hpp"
 
 namespace {
-constexpr int TPB = 256;
 constexpr int BH = 8, BW = 8, BD = 16;     // the output brick; BD / 4 lanes along d
 constexpr int BOXV = 12288;                // cells of the staged box: 48 KiB of image + 12 KiB of labels
-constexpr int MAXC = 16;
-
-typedef f32x4 f32x4u __attribute__((aligned(4)));
 
 struct AffArgs {
     const int64_t* table;
@@ -49,12 +46,7 @@ struct AffArgs {
     int32_t* paths;
 };
 
-struct Src {
-    const float* img;
-    const uint8_t* lab;
-    int n0, n1, n2;          // stored extents H, W, D
-    int m0, m1, m2;          // rotated extents
-    int code;
+struct Src : BankVol {
     float A[9];
     float t[3];              // (roi - 1) / 2 + (origin - pad_before) + s
     float c[3];              // (roi - 1) / 2
@@ -66,24 +58,10 @@ struct Box {
     int pitch;               // e2 | 1
 };
 
-MIVP_DEV int pad_before(int roi, int m) { return (roi - min(roi, m)) >> 1; }
-MIVP_DEV bool inside(int r, int m) { return (unsigned)r < (unsigned)m; }
 MIVP_DEV int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 MIVP_DEV float src_pos(const Src& s, int k, float q0, float q1, float q2) {
     return __builtin_fmaf(s.A[3 * k + 2], q2, __builtin_fmaf(s.A[3 * k + 1], q1, s.A[3 * k] * q0)) + s.t[k];
-}
-
-// r (rotated frame, in range) -> the offset of p in the stored volume
-MIVP_DEV long stored_offset(const Src& s, int r0, int r1, int r2) {
-    int p0, p1, p2;
-    switch (s.code) {
-        case 1: p0 = r1; p1 = s.n1 - 1 - r0; p2 = r2; break;
-        case 2: p0 = r2; p1 = r1; p2 = s.n2 - 1 - r0; break;
-        case 3: p0 = r0; p1 = r2; p2 = s.n2 - 1 - r1; break;
-        default: p0 = r0; p1 = r1; p2 = r2; break;
-    }
-    return ((long)p0 * s.n1 + p1) * s.n2 + p2;
 }
 
 // the trilinear taps of one voxel: false (and harmless integers) where every corner is outside, NaN included
@@ -179,13 +157,8 @@ MIVP_DEV void stage(const Src& s, const Box& bx, const float* img, float* box, b
         for (int x = (int)threadIdx.x & 31; x < E2; x += 32) {
             const int p2 = plo2 + x;
             const bool ok = row_ok && inside(p2, s.n2);
-            int r0 = p0, r1 = p1, r2 = p2;
-            switch (s.code) {
-                case 1: r0 = s.n1 - 1 - p1; r1 = p0; break;
-                case 2: r0 = s.n2 - 1 - p2; r2 = p0; break;
-                case 3: r1 = s.n2 - 1 - p2; r2 = p1; break;
-                default: break;
-            }
+            int r0, r1, r2;
+            to_rotated(s, p0, p1, p2, r0, r1, r2);
             const int cell = ((r0 - bx.lo0) * bx.e1 + (r1 - bx.lo1)) * bx.pitch + (r2 - bx.lo2);
             box[cell] = ok ? img[base + p2] : 0.f;
             if (labels) lbox[cell] = ok ? s_lut[s.lab[base + p2]] : (uint8_t)0;
@@ -217,13 +190,8 @@ MIVP_DEV void fill_brick(const AffArgs& a, const Src& s, const Box& bx, int b, i
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const Near n = make_near(s, r0[j], r1[j], r2[j]);
-            float p0 = r0[j], p1 = r1[j], p2 = r2[j];
-            switch (s.code) {
-                case 1: p0 = r1[j]; p1 = (float)(s.n1 - 1) - r0[j]; break;
-                case 2: p0 = r2[j]; p2 = (float)(s.n2 - 1) - r0[j]; break;
-                case 3: p1 = r2[j]; p2 = (float)(s.n2 - 1) - r1[j]; break;
-                default: break;
-            }
+            const Vox<float> p = to_stored(s, r0[j], r1[j], r2[j]);
+            const float p0 = p.p0, p1 = p.p1, p2 = p.p2;
             k0[j] = n.ok ? p0 - h0 : 0.f;
             k1[j] = n.ok ? p1 - h1 : 0.f;
             k2[j] = n.ok ? p2 - h2 : 0.f;
@@ -278,23 +246,13 @@ __global__ __launch_bounds__(TPB) void k_crop_affine(AffArgs a) {
     uint8_t* lbox = reinterpret_cast<uint8_t*>(box + BOXV);
     __shared__ uint8_t s_lut[256];
     const int b = blockIdx.y;
-    if (a.lut) {
-        s_lut[threadIdx.x] = a.lut[threadIdx.x];
-        __syncthreads();
-    }
+    if (a.lut) load_lut(s_lut, a.lut);
     const int32_t* rec = a.slot + (long)b * a.slot_stride;
     Src s;
-    const int vol = rec[0];
-    s.code = rec[1];
-    if ((unsigned)vol >= (unsigned)a.n_volumes || (unsigned)s.code > 3u) return;          // never follow a wild row
-    const int64_t* row = a.table + (long)vol * 5;
-    s.img = reinterpret_cast<const float*>(row[0]);
-    if (!s.img) return;                                          // an empty row of a fixed-capacity table
-    s.lab = reinterpret_cast<const uint8_t*>(row[1]);
-    s.n0 = (int)row[2]; s.n1 = (int)row[3]; s.n2 = (int)row[4];
-    s.m0 = s.code == 2 ? s.n2 : (s.code == 1 ? s.n1 : s.n0);
-    s.m1 = s.code == 3 ? s.n2 : (s.code == 1 ? s.n0 : s.n1);
-    s.m2 = s.code == 2 ? s.n0 : (s.code == 3 ? s.n1 : s.n2);
+    if (!bank_volume(s, a.table, a.n_volumes, rec)) return;
+    s.m0 = s.code == 2 ? s.n2 : (s.code == 1 ? s.n1 : s.n0);      // rotate_extents, written out: through the shared function
+    s.m1 = s.code == 3 ? s.n2 : (s.code == 1 ? s.n0 : s.n1);      // this kernel's registers are numbered differently
+    s.m2 = s.code == 2 ? s.n0 : (s.code == 3 ? s.n1 : s.n2);      // (profiles/README.md)
     const float* aff = a.affine + (long)b * 12;
 #pragma unroll
     for (int i = 0; i < 9; ++i) s.A[i] = aff[i];
@@ -347,14 +305,9 @@ __global__ __launch_bounds__(TPB) void k_crop_affine(AffArgs a) {
 int launch(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot, int32_t slot_stride, const float* affine,
            int32_t B, const int32_t* roi, const uint8_t* lut, float* image, float* mask, float* coord, int stage,
            int32_t* paths, mivp_stream_t stream) {
-    MIVP_REQUIRE(table && slot && affine && image && roi);
-    MIVP_REQUIRE(((uintptr_t)table & 7) == 0 && ((uintptr_t)slot & 3) == 0 && ((uintptr_t)affine & 3) == 0);
-    MIVP_REQUIRE(((uintptr_t)image & 3) == 0 && ((uintptr_t)mask & 3) == 0 && ((uintptr_t)coord & 3) == 0 &&
-                 ((uintptr_t)paths & 3) == 0);
-    MIVP_REQUIRE(n_volumes >= 1 && C >= 1 && C <= MAXC && B >= 1 && B <= 65535 && slot_stride >= 5);
-    for (int k = 0; k < 3; ++k) MIVP_REQUIRE(roi[k] >= 1 && roi[k] <= 65535);
-    MIVP_REQUIRE((long)roi[0] * roi[1] * roi[2] * (C > 3 ? C : 3) < (1L << 31));
-    MIVP_REQUIRE(!mask || lut);
+    const int rc = check_fill_args(table, n_volumes, C, slot, slot_stride, B, roi, lut, image, mask, coord);
+    if (rc) return rc;
+    MIVP_REQUIRE(affine && ((uintptr_t)affine & 3) == 0 && ((uintptr_t)paths & 3) == 0);
     AffArgs a{};
     a.table = table; a.n_volumes = n_volumes; a.C = C; a.B = B;
     a.slot = slot; a.slot_stride = slot_stride; a.affine = affine;

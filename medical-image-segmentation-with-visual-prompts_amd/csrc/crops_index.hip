@@ -14,11 +14,11 @@
 // that is not dword-aligned go byte by byte.  Integers only: counts are wave ballots and popcounts, added in a fixed order.
 // The pick writes the crop origin -- correct_crop_centers: clamp(r - roi / 2, 0, max(n_rot - roi, 0)) -- into words 2..4 of
 // the sample's slot record with a plain store from the one lane that holds the voxel; k_crop (crops.hip) reads it from
-// there.  Anything invalid in the record or the pick makes the workgroup return without writing.
-#include "common.hpp"
+// there.  Anything invalid in the record or the pick makes the workgroup return without writing.  k_crop_pick keeps its own
+// decode and turn (see there); the small definitions and the host checks are crops_common.hpp's.
+#include "crops_common.hpp"
 
 namespace {
-constexpr int TPB = 256;
 constexpr int CHUNK = 1024;              // = 4 * TPB (batches.ClassIndex.CHUNK)
 constexpr int MAXCLS = 16;
 constexpr uint32_t NONE4 = 0xFFFFFFFFu;  // four voxels of no class
@@ -61,8 +61,7 @@ __global__ __launch_bounds__(TPB) void k_label_count(const uint8_t* __restrict__
     __shared__ uint8_t s_lut[256];
     __shared__ int s_w[TPB / 64][MAXCLS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    s_lut[tid] = lut[tid];
-    __syncthreads();
+    load_lut(s_lut, lut);
     const uint32_t j = blockIdx.x;
     const uint32_t cls4 = lane_classes(lab, n, j * (uint32_t)CHUNK + 4u * tid, ((uintptr_t)lab & 3) == 0, s_lut, nc);
     for (int c = 0; c < nc; ++c) {
@@ -150,8 +149,7 @@ __global__ __launch_bounds__(TPB) void k_crop_pick(PickArgs a) {
     }
     const int target = rank - pre[lo];                                   // the target-th match of chunk lo
 
-    s_lut[tid] = a.lut[tid];
-    __syncthreads();
+    load_lut(s_lut, a.lut);
     const uint32_t q0 = (uint32_t)lo * (uint32_t)CHUNK + 4u * tid;
     const uint32_t m = match_mask(lane_classes(lab, n, q0, ((uintptr_t)lab & 3) == 0, s_lut, a.nc), (uint32_t)cls);
     const int cnt = __popc(m);                                           // 0..4: three bits
@@ -177,7 +175,9 @@ __global__ __launch_bounds__(TPB) void k_crop_pick(PickArgs a) {
     const int p0 = (int)(q / plane);
     const uint32_t rem = q - (uint32_t)p0 * plane;
     const int p1 = (int)(rem / (uint32_t)n2), p2 = (int)(rem - (uint32_t)p1 * (uint32_t)n2);
-    // p (stored frame) -> r (rotated frame): for axes (a, b), r_b = p_a and r_a = n_b - 1 - p_b
+    // p (stored frame) -> r (rotated frame) with the rotated extents, in one switch: to_rotated and rotate_extents of
+    // crops_common.hpp written out, like the decode above with its own read order (the index row first) -- through the
+    // shared functions this kernel's assembly changes (profiles/README.md)
     int r0 = p0, r1 = p1, r2 = p2, m0 = n0, m1 = n1, m2 = n2;
     switch (code) {
         case 1: r0 = n1 - 1 - p1; r1 = p0; m0 = n1; m1 = n0; break;
@@ -207,11 +207,10 @@ extern "C" int mivp_label_index_build(const uint8_t* labels, int64_t numel, cons
 extern "C" int mivp_crop_pick(const int64_t* table, const int64_t* index_table, int32_t n_volumes, const uint8_t* lut,
                               int32_t num_classes, int32_t* slot, int32_t slot_stride, const int32_t* pick, int32_t B,
                               const int32_t* roi, mivp_stream_t stream) {
-    MIVP_REQUIRE(table && index_table && lut && slot && pick && roi);
-    MIVP_REQUIRE(((uintptr_t)table & 7) == 0 && ((uintptr_t)index_table & 7) == 0 && ((uintptr_t)slot & 3) == 0 &&
-                 ((uintptr_t)pick & 3) == 0);
-    MIVP_REQUIRE(n_volumes >= 1 && num_classes >= 1 && num_classes <= MAXCLS && B >= 1 && B <= 65535 && slot_stride >= 5);
-    for (int k = 0; k < 3; ++k) MIVP_REQUIRE(roi[k] >= 1 && roi[k] <= 65535);
+    const int rc = check_bank_args(table, n_volumes, slot, slot_stride, B, roi);
+    if (rc) return rc;
+    MIVP_REQUIRE(index_table && lut && pick && ((uintptr_t)index_table & 7) == 0 && ((uintptr_t)pick & 3) == 0);
+    MIVP_REQUIRE(num_classes >= 1 && num_classes <= MAXCLS);
     PickArgs a{};
     a.table = table; a.itable = index_table; a.n_volumes = n_volumes; a.nc = num_classes; a.B = B;
     a.lut = lut; a.slot = slot; a.slot_stride = slot_stride; a.pick = pick;

@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+import class_crops_ref as CR
 import crops_ref as R
+from batch_outputs import grid as _grid, poison as _poison
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -36,11 +38,6 @@ def _bank(channels):
     return _banks[channels]
 
 
-def _grid(shape, device):
-    from mivp_amd.students_teacher import coord_grid
-    return coord_grid(shape, device)
-
-
 def _draws(volume, rot, roi, where, student_sizes=(), student_where="lo"):
     """Draws at the extremes: ``where`` = 'lo' (origin 0), 'hi' (the maximum) or 'odd' (an odd origin where there is room:
     a 16-byte store then starts at a misaligned source address)."""
@@ -59,15 +56,6 @@ def _draws(volume, rot, roi, where, student_sizes=(), student_where="lo"):
                 hi = max(roi[k] - size[k], 0)
                 st[s, b, k] = {"lo": 0, "hi": hi, "mix": (hi, 0, hi // 2)[(b + k + s) % 3]}[student_where]
     return BT.CropDraws(np.asarray(volume, np.int32), np.asarray(rot, np.int32), origin, st)
-
-
-def _poison(filler):
-    """NaN in every output: a voxel the kernels do not write stays visible."""
-    outs = [filler.image, filler.mask, filler.coord, filler.mask_st_0] + filler.image_st + filler.coord_st
-    outs = [t for t in outs if t is not None]
-    for t in outs:
-        t.fill_(float("nan"))
-    return outs
 
 
 def _check_teacher(filler, draws, channels, roi):
@@ -435,3 +423,60 @@ def test_bad_draws_and_bad_outputs_are_refused_before_any_launch():
         with pytest.raises(RuntimeError, match="recorded"):
             bank.add(late)
     assert len(bank) == 3
+
+
+# ------------------------------------------------------------------------------------------------ 8. device refusals
+@pytest.mark.parametrize("entry", ["mivp_crop_fill", "mivp_crop_fill_affine", "mivp_crop_pick"])
+def test_an_empty_row_and_a_wild_code_leave_the_sample_unwritten(entry):
+    """The two fills decode the slot record and the table row through csrc/crops_common.hpp, the pick with its own code.  Called
+    raw on records the host checks refuse: a bank of capacity 2 that holds one (6, 8, 5) volume, roi (4, 4, 4), B = 3 -- a
+    valid record, one with volume id 1 (the empty row) and one with code 7.  Sample 0 equals the restatement, samples 1 and
+    2 stay as prefilled (NaN; -7 in the origin words for the pick).  Documented returns of the kernels, not faults."""
+    from mivp_amd import _lib as L, batches as BT
+    from mivp_amd._host import i3
+    shape, roi, ncls = SHAPES[2], (4, 4, 4), 3
+    g = torch.Generator().manual_seed(41)
+    image = torch.arange(1, 1 + int(np.prod(shape)), dtype=torch.float32).reshape((1,) + shape).to(DEV)
+    lab = torch.randint(0, 8, shape, generator=g, dtype=torch.uint8)
+    labels = lab.to(DEV)
+    bank = BT.VolumeBank(DEV, 1, capacity=2)
+    bank.add(image, labels)
+    records = torch.tensor([[0, 1, 1, 2, 1], [1, 0, 0, 0, 0], [0, 7, 0, 0, 0]], dtype=torch.int32)
+    if entry == "mivp_crop_pick":
+        index = BT.ClassIndex(bank, ncls, ACTIVE).update()
+        records[:, 2:] = -7
+        slot = records.to(DEV)
+        picks = torch.tensor([[1, 0], [0, 0], [0, 0]], dtype=torch.int32, device=DEV)
+        assert int(index.counts[0][1]) >= 1
+        L.call("mivp_crop_pick", L.ptr(bank.table), L.ptr(index.table), bank.capacity, L.ptr(index.lut), ncls, L.ptr(slot), 5,
+               L.ptr(picks), 3, i3(roi), L.stream())
+        got = slot.cpu().numpy()
+        assert got[0, 2:].tolist() == CR.origin(lab.numpy(), BT.label_table(ACTIVE), ncls, 1, 1, 0, roi)[0]
+        assert got[1:].tolist() == [[1, 0, -7, -7, -7], [0, 7, -7, -7, -7]]
+        return
+    slot = records.to(DEV)
+    lut = torch.from_numpy(BT.label_table(ACTIVE)).to(DEV)
+    outs = [torch.full((3, c) + roi, float("nan"), device=DEV) for c in (1, 1, 3)]
+    table, rec, r3, st = L.ptr(bank.table), L.ptr(slot), i3(roi), L.stream()
+
+    def plain_fill(image, mask, coord):
+        L.call("mivp_crop_fill", table, bank.capacity, 1, rec, 5, 3, r3, L.ptr(lut), L.ptr(image), L.ptr(mask), L.ptr(coord), st)
+
+    if entry == "mivp_crop_fill":
+        plain_fill(*outs)
+    else:
+        maps = torch.from_numpy(BT.SpatialDraws.identity(3).affine.reshape(-1)).to(DEV)
+        L.call("mivp_crop_fill_affine", table, bank.capacity, 1, rec, 5, L.ptr(maps), 3, r3, L.ptr(lut), L.ptr(outs[0]),
+               L.ptr(outs[1]), L.ptr(outs[2]), st)
+    draws = BT.CropDraws(np.zeros(1, np.int32), np.ones(1, np.int32), np.asarray([[1, 2, 1]], np.int32),
+                         np.zeros((0, 1, 3), np.int32)).check([shape], roi)
+    want = R.teacher_batch([image], [labels], draws, roi, ACTIVE, _grid)
+    torch.cuda.synchronize()
+    for name, t, ref in zip(("image", "mask", "coord"), outs, want):
+        assert torch.equal(t[:1], ref), f"{name}: sample 0 differs from the restatement"
+        assert torch.isnan(t[1:]).all(), f"{name}: a refused sample was written"
+    if entry == "mivp_crop_fill_affine":                        # the identity map: the plain fill's bits
+        plain = [torch.full_like(t, float("nan")) for t in outs]
+        plain_fill(*plain)
+        torch.cuda.synchronize()
+        assert all(torch.equal(a[:1], b[:1]) and torch.isnan(b[1:]).all() for a, b in zip(outs, plain))

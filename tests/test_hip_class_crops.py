@@ -11,6 +11,7 @@ import torch
 
 import class_crops_ref as CR
 import crops_ref as R
+from batch_outputs import grid as _grid, poison as _poison
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -62,11 +63,6 @@ def _bank(channels):
 def _lut():
     from mivp_amd import batches as BT
     return BT.label_table(ACTIVE)
-
-
-def _grid(shape, device):
-    from mivp_amd.students_teacher import coord_grid
-    return coord_grid(shape, device)
 
 
 def _every_pick(counts_v, volume, code):
@@ -232,13 +228,6 @@ def _e2e_draws(index, seed, roi=(8, 8, 8), sizes=STUDENTS):
                              np.concatenate([d.rot, np.array([e[0] for e in extra], np.int32)]),
                              np.concatenate([d.cls, np.array([e[1] for e in extra], np.int32)]),
                              np.concatenate([d.rank, np.array([e[2] for e in extra], np.int32)]), st)
-
-
-def _poison(filler):
-    outs = [filler.image, filler.mask, filler.coord, filler.mask_st_0] + filler.image_st + filler.coord_st
-    for t in outs:
-        if t is not None:
-            t.fill_(float("nan"))
 
 
 def _check_batch(filler, draws, channels, roi, sizes):

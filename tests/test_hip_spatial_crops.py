@@ -12,6 +12,7 @@ import torch
 import class_crops_ref as CR
 import crops_ref as R
 import spatial_crops_ref as SR
+from batch_outputs import outs as _outs, poison as _poison
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -69,15 +70,6 @@ def _spatial(mats, shifts=None):
         if shifts is not None:
             a[b, 9:] = shifts[b]
     return BT.SpatialDraws(a).check(len(mats))
-
-
-def _outs(f):
-    return [t for t in [f.image, f.mask, f.coord, f.mask_st_0] + f.image_st + f.coord_st if t is not None]
-
-
-def _poison(f):
-    for t in _outs(f):
-        t.fill_(float("nan"))
 
 
 def _teacher(f):
