@@ -1073,6 +1073,40 @@ int mivp_crop_fill_affine_debug(const int64_t* table, int32_t n_volumes, int32_t
                                 float* image, float* mask, float* coord, int32_t stage, int32_t* paths,
                                 mivp_stream_t stream);
 
+/* Elastic (non-rigid) deformation for the batch filler (csrc/crops_affine.hip; mivp_amd/batches.py).
+ * Additive again: the ABI stays 18.  The affine teacher launch with one more term in the source position: a smooth
+ * displacement evaluated on the fly from a small control lattice per sample.  No displacement volume is stored; every
+ * output voxel is written exactly once, no atomics, bitwise reproducible, no host synchronisation; flags and lattice
+ * are DEVICE memory like the slot and the map, so the launch records into a graph and a replay follows all of them.
+ *   nodes: HOST int32 [3] = (n0, n1, n2), 4 <= n_k <= 8, the same for the whole batch.
+ *   lattice: DEVICE fp32 [B][3][n0][n1][n2]: P[c][j0][j1][j2], component c of the displacement of node j, in output voxels.
+ *   flags: DEVICE int32 [B]: 0 = the sample is not deformed, anything else = it is.
+ *   Rule for output voxel u of a sample whose flag is not 0, all arithmetic fp32, per axis k:
+ *       x_k = (u_k + 0.5) * ((n_k - 3) / roi_k)               (in (0, n_k - 3))
+ *       i_k = min(floor(x_k), n_k - 4),  f_k = x_k - i_k
+ *       the uniform cubic B-spline basis  B0 = (1 - f)^3 / 6,        B1 = (3 f^3 - 6 f^2 + 4) / 6,
+ *                                         B2 = (-3 f^3 + 3 f^2 + 3 f + 1) / 6,  B3 = f^3 / 6
+ *       d_c(u) = sum over a, b, e in 0..3 of B_a(f_0) B_b(f_1) B_e(f_2) * P[c][i_0 + a][i_1 + b][i_2 + e]
+ *       r = A (q + d(u)) + t
+ *     with q, A and t exactly as for mivp_crop_fill_affine: the offset first, then the affine map (MONAI's order).  The sum
+ *     q_k + d_k is formed first and goes through the same fma chain, so a displacement of exactly 0.0f gives that launch's
+ *     r bit for bit.  The order of the sum: w_ab = B_a(f_0) * B_b(f_1); per lattice column i_2 + e the 16 taps accumulate
+ *     by fma over a, then b, from w_00 * P; then d_c = fma over e = 1..3 onto B_0(f_2) * column 0.
+ *     Everything after r is mivp_crop_fill_affine's: the trilinear image with zeros outside, the mask through the lut at
+ *     floor(r + 0.5), coord = r mapped back through the quarter turn.  A non-finite or huge displacement gives a
+ *     non-finite or far r, which fails the float comparisons in front of every conversion to an integer: zeros.
+ *   A sample whose flag is 0 never reads the lattice (which may then hold anything): its workgroups run the arithmetic of
+ *     mivp_crop_fill_affine and give its bits.  The branch is uniform per workgroup.
+ *   mivp_crop_fill_elastic: every other argument and every refusal as for mivp_crop_fill_affine; MIVP_EINVAL also for a
+ *     null flags, lattice or nodes and for a node count outside 4..8.  The same bricks and lanes; a deformed sample's
+ *     workgroups stage its lattice (at most 6 KiB) in LDS and read every corner from global memory (the direct path: the
+ *     staged path's box is bounded through an affine map, which does not hold under a deformation).  A lane's four voxels
+ *     share (u_0, u_1), so the 16-tap sums are formed once per lattice column its voxels touch. */
+int mivp_crop_fill_elastic(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot, int32_t slot_stride,
+                           const float* affine, int32_t B, const int32_t* roi, const uint8_t* lut, float* image, float* mask,
+                           float* coord, const int32_t* flags, const float* lattice, const int32_t* nodes,
+                           mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,12 @@ so the label map is never read back and a recorded ``fill`` still follows the sl
 Random flip, rotation and zoom (csrc/crops_affine.hip): ``draw_spatial`` draws one affine map per sample
 (``SpatialDraws``), a ``SpatialSlot`` holds the maps on the device beside the ``CropSlot``, and a filler built with
 ``spatial=True`` issues the interpolating teacher launch in place of the plain one -- trilinear for the image, nearest for
-the labels, analytic coordinates; the pick and the students' launches are the same as without it."""
+the labels, analytic coordinates; the pick and the students' launches are the same as without it.
+
+Elastic deformation (the second kernel of csrc/crops_affine.hip): ``draw_elastic`` draws, per sample, a coin
+and a small control lattice of displacements (``ElasticDraws``), an ``ElasticSlot`` holds them on the device beside the
+other two slots, and a filler built with ``spatial=True, elastic=nodes`` issues ``mivp_crop_fill_elastic`` for the teacher:
+the cubic B-spline of the lattice is added to the output offset in front of the affine map, evaluated on the fly."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -523,6 +528,118 @@ class SpatialSlot:
         self.draws = draws
 
 
+ELASTIC_NODES = (4, 8)          # the node count of a control lattice, per axis: at least one knot interval, at most 6 KiB (mivp.h)
+
+
+def _nodes3(who: str, nodes) -> Tuple[int, int, int]:
+    v = tuple(nodes) if not plain_int(nodes) else (nodes, nodes, nodes)
+    lo, hi = ELASTIC_NODES
+    if len(v) != 3 or any(not plain_int(a) or not lo <= int(a) <= hi for a in v):
+        raise ValueError(f"{who}: nodes must be three integers in {lo}..{hi}, got {nodes!r}")
+    return tuple(int(a) for a in v)
+
+
+@dataclass
+class ElasticDraws:
+    """The elastic deformation one step draws on the host: per sample a flag and a control lattice ``P[c, j0, j1, j2]``, the
+    displacement (component ``c``, in output voxels) of node ``j``; the cubic B-spline of the lattice is the displacement
+    field (the rule is written out in include/mivp.h).  A sample whose flag is 0 is not deformed and its lattice is not read."""
+    flags: np.ndarray               # int32 [B]: 1 = the sample is deformed
+    lattice: np.ndarray             # float32 [B, 3, n0, n1, n2]
+
+    @property
+    def batch(self) -> int:
+        return int(np.shape(self.flags)[0])
+
+    @classmethod
+    def identity(cls, B: int, nodes) -> "ElasticDraws":
+        B, nodes = check_int_from("B", B, 1), _nodes3("ElasticDraws.identity", nodes)
+        return cls(np.zeros(B, np.int32), np.zeros((B, 3) + nodes, np.float32))
+
+    def check(self, B: int, nodes) -> "ElasticDraws":
+        """int32 ``[B]`` flags, each 0 or 1, and a float32 ``[B, 3, n0, n1, n2]`` lattice of finite values.  Raises
+        ``ValueError`` naming the sample."""
+        nodes = _nodes3("ElasticDraws", nodes)
+        f, p = self.flags, self.lattice
+        if not isinstance(f, np.ndarray) or f.dtype != np.int32 or f.shape != (int(B),):
+            got = f"{f.dtype} {f.shape}" if isinstance(f, np.ndarray) else repr(type(f))
+            raise ValueError(f"ElasticDraws: flags must be an int32 [{int(B)}] array (every sample of the batch), got {got}")
+        want = (int(B), 3) + nodes
+        if not isinstance(p, np.ndarray) or p.dtype != np.float32 or p.shape != want:
+            got = f"{p.dtype} {p.shape}" if isinstance(p, np.ndarray) else repr(type(p))
+            raise ValueError(f"ElasticDraws: lattice must be a float32 {list(want)} array, got {got}")
+        _refuse("ElasticDraws", (f != 0) & (f != 1), lambda b: f"flag {int(f[b])} is neither 0 nor 1")
+        _refuse("ElasticDraws", ~np.isfinite(p).reshape(int(B), -1).all(axis=1), lambda b: "a non-finite displacement")
+        return self
+
+
+def draw_elastic(rs: np.random.RandomState, B: int, roi, nodes=(7, 7, 7), p_elastic: float = 0., magnitude_range=(0., 0.),
+                 locked_borders: int = 2) -> ElasticDraws:
+    """The elastic draws of one batch of ``B`` samples from ONE RandomState.  Per sample, in this order:
+
+    1. one coin: the sample is deformed if ``rs.random_sample() < p_elastic``;
+    2. if it is: one magnitude ``m = rs.uniform(lo, hi)`` in output voxels (``magnitude_range = (lo, hi)``);
+    3. then every node component ``rs.uniform(-m, m)``, in C order of ``[3, n0, n1, n2]`` (the component slowest);
+    4. then the outer ``locked_borders`` node layers on every axis are set to zero (no draw), so the rim of the crop does
+       not move (TorchIO's ``locked_borders``).
+
+    A sample that is not deformed consumes its coin only and keeps a zero lattice.  The draws are float64 and the lattice
+    is rounded to fp32 once.  Refused: a probability outside [0, 1]; a range that is not ``0 <= lo <= hi``; ``hi >= 0.5 *
+    roi_k / (n_k - 3)`` on any axis -- beyond half a node spacing the map can fold; ``locked_borders`` that leave no free
+    node (``2 * locked_borders >= n_k``).  TorchIO's and MONAI's own streams are NOT reproduced (neither is installed; MONAI
+    smooths full-resolution noise instead): parity is unpinned at that boundary and this order is the project's own
+    (DESIGN.md 8)."""
+    B, roi, nodes = check_int_from("B", B, 1), _size3("roi", roi), _nodes3("draw_elastic", nodes)
+    if not isinstance(p_elastic, (int, float, np.floating)) or not 0 <= float(p_elastic) <= 1:
+        raise ValueError(f"draw_elastic: p_elastic must be in [0, 1], got {p_elastic!r}")
+    lo, hi = (float(v) for v in magnitude_range)
+    if not (np.isfinite([lo, hi]).all() and 0 <= lo <= hi):
+        raise ValueError(f"draw_elastic: magnitude_range must be 0 <= low <= high, got {magnitude_range!r}")
+    for k in range(3):
+        if hi >= 0.5 * roi[k] / (nodes[k] - 3):
+            raise ValueError(f"draw_elastic: magnitude {hi} on axis {k} is not below half the node spacing "
+                             f"{0.5 * roi[k] / (nodes[k] - 3):.4g} voxels (roi {roi}, nodes {nodes}): the map could fold")
+    if not plain_int(locked_borders) or int(locked_borders) < 0 or any(2 * int(locked_borders) >= n for n in nodes):
+        raise ValueError(f"draw_elastic: locked_borders {locked_borders!r} must be an integer >= 0 that leaves a free node "
+                         f"on every axis of {nodes}")
+    lb = int(locked_borders)
+    d = ElasticDraws.identity(B, nodes)
+    for b in range(B):
+        if rs.random_sample() < float(p_elastic):
+            m = rs.uniform(lo, hi)
+            P = rs.uniform(-m, m, size=(3,) + nodes)
+            if lb:
+                free = np.zeros(nodes, bool)
+                free[lb:nodes[0] - lb, lb:nodes[1] - lb, lb:nodes[2] - lb] = True
+                P = np.where(free[None], P, 0.0)
+            d.flags[b], d.lattice[b] = 1, P
+    return d.check(B, nodes)
+
+
+class ElasticSlot:
+    """Fixed device memory of one batch's elastic draws -- ONE allocation made here, int32 flags [B] in front of the fp32
+    lattice [B * 3 * n0 * n1 * n2], the identity (no sample deformed) at first -- whose pointers a recorded graph keeps.
+    ``load`` checks the draws, then refreshes both from a new pinned staging buffer in one copy without blocking; it does
+    nothing while a graph is being recorded, exactly as ``SpatialSlot.load``."""
+
+    def __init__(self, B: int, nodes, device):
+        self.B, self.nodes = check_int_from("B", B, 1), _nodes3("ElasticSlot", nodes)
+        words = self.B * 3 * int(np.prod(self.nodes))
+        self.buffer = torch.zeros(self.B + words, dtype=torch.float32, device=_gpu_device("ElasticSlot", device))
+        self.flags, self.lattice = self.buffer[:self.B].view(torch.int32), self.buffer[self.B:]
+        self.draws = ElasticDraws.identity(self.B, self.nodes)
+
+    def load(self, draws: ElasticDraws):
+        if not isinstance(draws, ElasticDraws):
+            raise ValueError("ElasticSlot.load: ElasticDraws expected")
+        draws.check(self.B, self.nodes)
+        if torch.cuda.is_current_stream_capturing():
+            return
+        words = np.concatenate([np.ascontiguousarray(draws.flags).view(np.float32), draws.lattice.reshape(-1)])   # ONE upload
+        self.buffer.copy_(torch.from_numpy(words).pin_memory(), non_blocking=True)
+        self.draws = draws
+
+
 class CropSlot:
     """Fixed device memory of one batch's draws -- int32 [B][5 + 3 S] records -- whose pointer a recorded graph keeps.
     ``load`` checks the draws against the bank, then refreshes the records from a new pinned staging buffer without blocking;
@@ -615,14 +732,22 @@ class BatchFiller:
     interpolating ``mivp_crop_fill_affine``: flips, rotation and zoom about the centre of the crop, which
     therefore stays centred on a picked voxel.  The pick runs first as before and the students are crops of the augmented
     teacher tensors, so image, coordinates and mask agree across the views.  ``spatial=False`` issues exactly the
-    launches described above."""
+    launches described above.
+
+    With ``spatial=True, elastic=nodes`` (three node counts in 4..8) the filler also owns ``elastic_slot`` (no sample
+    deformed at first) and the teacher launch is ``mivp_crop_fill_elastic``: the B-spline displacement of
+    each flagged sample's control lattice is added in front of the affine map; a sample whose flag is 0 gets the bits of
+    the ``spatial=True`` filler.  Pick and students as before.  Without ``elastic`` nothing changes."""
 
     def __init__(self, bank: VolumeBank, roi, batch: int, student_sizes=(), active_labels=None, with_coord: bool = False,
-                 with_mask: bool = True, class_index: Optional[ClassIndex] = None, spatial: bool = False):
+                 with_mask: bool = True, class_index: Optional[ClassIndex] = None, spatial: bool = False, elastic=None):
         if not isinstance(bank, VolumeBank):
             raise ValueError("BatchFiller: a VolumeBank expected")
         if class_index is not None and (not isinstance(class_index, ClassIndex) or class_index.bank is not bank):
             raise ValueError("BatchFiller: class_index must be a ClassIndex of this bank")
+        if elastic is not None and not spatial:
+            raise ValueError("BatchFiller: elastic= needs spatial=True (the displacement is added in front of the affine map)")
+        nodes = None if elastic is None else _nodes3("BatchFiller", elastic)
         self.class_index = class_index
         self.bank, self.roi, self.B = bank, _size3("roi", roi), check_int_from("batch", batch, 1)
         self.student_sizes = [_size3("student size", s) for s in student_sizes]
@@ -640,6 +765,7 @@ class BatchFiller:
         self.mask_st_0 = new(1, self.student_sizes[0]) if (S and with_mask) else None
         self.slot = CropSlot(self.B, S, dev, class_index=class_index)
         self.spatial_slot = SpatialSlot(self.B, dev) if spatial else None
+        self.elastic_slot = ElasticSlot(self.B, nodes, dev) if nodes is not None else None
         self.xy = (self.image, self.mask)
         if S:
             self.batch = dict(image=self.image, coord=self.coord, image_st=self.image_st, coord_st=self.coord_st)
@@ -671,14 +797,29 @@ class BatchFiller:
                                  f"got {got}")
 
     @torch.no_grad()
-    def fill(self, draws_or_slot=None, spatial=None):
+    def fill(self, draws_or_slot=None, spatial=None, elastic=None):
         """``CropDraws`` (``ClassCropDraws`` on a filler with a class index): checked and loaded into the filler's own slot
         first.  A ``CropSlot``: used as it stands (its ``load`` did the checking).  ``None``: the filler's own slot as last
         loaded.  ``spatial`` (a filler built with ``spatial=True`` only): ``SpatialDraws``, checked and loaded into
-        ``spatial_slot`` first; a ``SpatialSlot``, used as it stands; ``None``: ``spatial_slot`` as last loaded.  Every
-        refusal comes before the first launch and before either slot is loaded."""
+        ``spatial_slot`` first; a ``SpatialSlot``, used as it stands; ``None``: ``spatial_slot`` as last loaded.
+        ``elastic`` (a filler built with ``elastic=nodes`` only) follows the same rules with ``ElasticDraws``, an
+        ``ElasticSlot`` and ``elastic_slot``.  Every refusal comes before the first launch and before any slot is loaded."""
         slot = self.slot
         sp_slot = self.spatial_slot
+        el_slot = self.elastic_slot
+        if elastic is not None:
+            if el_slot is None:
+                raise ValueError("BatchFiller.fill: elastic= needs a filler built with elastic=nodes")
+            if isinstance(elastic, ElasticDraws):
+                elastic.check(self.B, el_slot.nodes)
+            elif isinstance(elastic, ElasticSlot):
+                if elastic.B != self.B or elastic.nodes != el_slot.nodes or elastic.buffer.device != self.bank.device:
+                    raise ValueError(f"BatchFiller.fill: an elastic slot of batch {elastic.B} and nodes {elastic.nodes} on "
+                                     f"{elastic.buffer.device} for a filler of batch {self.B} and nodes {el_slot.nodes} on "
+                                     f"{self.bank.device}")
+                el_slot = elastic
+            else:
+                raise ValueError("BatchFiller.fill: elastic= takes ElasticDraws, an ElasticSlot, or nothing")
         if spatial is not None:
             if sp_slot is None:
                 raise ValueError("BatchFiller.fill: spatial= needs a filler built with spatial=True")
@@ -715,22 +856,29 @@ class BatchFiller:
         self._check_outputs()
         if isinstance(spatial, SpatialDraws):
             sp_slot.load(spatial)
+        if isinstance(elastic, ElasticDraws):
+            el_slot.load(elastic)
         if self.class_index is not None:
             slot.resolve(self.roi)
-        self._fill_teacher(slot, sp_slot)
+        self._fill_teacher(slot, sp_slot, el_slot)
         self._fill_students(slot)
         return self.batch
 
-    def _fill_teacher(self, slot: CropSlot, spatial_slot: Optional[SpatialSlot] = None):
+    def _fill_teacher(self, slot: CropSlot, spatial_slot: Optional[SpatialSlot] = None,
+                      elastic_slot: Optional[ElasticSlot] = None):
         bank, roi, st = self.bank, i3(self.roi), L.stream()         # every argument is formed once, for either entry
         table, records, lut = L.ptr(bank.table), L.ptr(slot.records), L.ptr(self.lut)
         image, mask, coord = L.ptr(self.image), L.ptr(self.mask), L.ptr(self.coord)
         if spatial_slot is None:
             L.call("mivp_crop_fill", table, bank.capacity, bank.channels, records, slot.words, self.B, roi, lut, image, mask,
                    coord, st)
-        else:
+        elif elastic_slot is None:
             L.call("mivp_crop_fill_affine", table, bank.capacity, bank.channels, records, slot.words,
                    L.ptr(spatial_slot.words), self.B, roi, lut, image, mask, coord, st)
+        else:
+            L.call("mivp_crop_fill_elastic", table, bank.capacity, bank.channels, records, slot.words,
+                   L.ptr(spatial_slot.words), self.B, roi, lut, image, mask, coord, L.ptr(elastic_slot.flags),
+                   L.ptr(elastic_slot.lattice), i3(elastic_slot.nodes), st)
 
     def _fill_students(self, slot: CropSlot):
         st, Cn = L.stream(), self.bank.channels

@@ -24,6 +24,17 @@
 // No out-of-range address can be formed from device memory: the volume id and the code are checked per workgroup, r per
 // voxel with float comparisons BEFORE it becomes an integer, and every LDS index is clamped into the box.  The record and row
 // decode, the quarter turn and the pad rule are crops_common.hpp's; `stage` writes out its box permutation (a box, not a point).
+//
+// Elastic deformation (mivp_crop_fill_elastic): a second kernel of the same template, r = A (q + d(u)) + t
+// with d the cubic B-spline of a per-sample control lattice P[3][n0][n1][n2] (4..8 nodes per axis, output-voxel units;
+// the rule is in mivp.h).  A sample's workgroups read its int32 flag first: 0 takes fill_brick<false, false>, the affine
+// launch's direct path and its bits, and never touches the lattice; otherwise the lattice (at most 6 KiB) is staged in
+// LDS and fill_brick<false, true> adds d to q in front of the unchanged fma chain -- d = +0 gives the affine r bit for
+// bit.  The basis is separable and a lane's four voxels share (u_h, u_w): the 16 taps over axes 0 and 1 are summed once
+// per lattice d-column (`lat_column`), four columns are live, and a voxel that steps into the next knot interval shifts
+// them by one and sums one new column.  Only the direct path: the staged box is bounded through an affine map, and that
+// bound does not hold under a deformation.  Every LDS index is clamped (an idle lane's too); a non-finite or huge d makes
+// r fail make_tap's and make_near's float comparisons, which give zeros.
 #include "crops_common.hpp"
 
 namespace {
@@ -103,6 +114,43 @@ MIVP_DEV float lerp3(const float (&v)[8], const Tap& t) {
     return c0 + t.w0 * (c1 - c0);
 }
 
+// A sample's control lattice as its workgroups see it: uniform values, the nodes in LDS.
+struct Lat {
+    const float* P;          // LDS [3][n0][n1][n2], output-voxel units
+    int n0, n1, n2;          // 4..8 (checked on the host)
+    float sc0, sc1, sc2;     // (n_k - 3) / roi_k
+};
+// The knot interval and the four cubic B-spline weights of output index u on one axis: x = (u + 0.5) * sc,
+// i = min(floor(x), n - 4), f = x - i.  An idle lane's u lies past the roi: its i is clamped like any other.
+struct Knot {
+    int i;
+    float b[4];
+};
+MIVP_DEV Knot make_knot(int u, float sc, int n) {
+    const float x = ((float)u + 0.5f) * sc;
+    Knot k;
+    k.i = clampi((int)floorf(x), 0, n - 4);
+    const float f = x - (float)k.i, g = 1.f - f, f2 = f * f, sixth = 1.f / 6.f;
+    k.b[0] = g * g * g * sixth;
+    k.b[1] = __builtin_fmaf(f2, __builtin_fmaf(3.f, f, -6.f), 4.f) * sixth;
+    k.b[2] = __builtin_fmaf(f, __builtin_fmaf(f, __builtin_fmaf(-3.f, f, 3.f), 3.f), 1.f) * sixth;
+    k.b[3] = f2 * f * sixth;
+    return k;
+}
+// One lattice d-column: the 16 taps over axes 0 and 1, w[4 a + b] = B_a(f_0) B_b(f_1), summed in the order a, then b, for
+// the three components.  p -> P[0][i_0][i_1][column].
+MIVP_DEV void lat_column(const Lat& lt, const float* p, const float (&w)[16], float& c0, float& c1, float& c2) {
+    const int s1 = lt.n2, s0 = lt.n1 * lt.n2, cs = lt.n0 * s0;
+    c0 = w[0] * p[0]; c1 = w[0] * p[cs]; c2 = w[0] * p[2 * cs];
+#pragma unroll
+    for (int t = 1; t < 16; ++t) {
+        const float* n = p + (t >> 2) * s0 + (t & 3) * s1;
+        c0 = __builtin_fmaf(w[t], n[0], c0);
+        c1 = __builtin_fmaf(w[t], n[cs], c1);
+        c2 = __builtin_fmaf(w[t], n[2 * cs], c2);
+    }
+}
+
 template <bool STAGED>
 MIVP_DEV float sample_image(const Src& s, const Box& bx, const float* box, const float* img, const Tap& t) {
     float v[8];
@@ -166,9 +214,9 @@ MIVP_DEV void stage(const Src& s, const Box& bx, const float* img, float* box, b
     }
 }
 
-template <bool STAGED>
+template <bool STAGED, bool ELASTIC>
 MIVP_DEV void fill_brick(const AffArgs& a, const Src& s, const Box& bx, int b, int u0h, int u0w, int u0d, float* box,
-                         uint8_t* lbox, const uint8_t* s_lut) {
+                         uint8_t* lbox, const uint8_t* s_lut, const Lat& lt) {
     const int tid = threadIdx.x;
     const int uh = u0h + (tid >> 5), uw = u0w + ((tid >> 2) & 7), ud = u0d + 4 * (tid & 3);
     const bool active = uh < a.h && uw < a.w && ud < a.d;        // (an idle lane still stages and meets the barriers)
@@ -177,12 +225,48 @@ MIVP_DEV void fill_brick(const AffArgs& a, const Src& s, const Box& bx, int b, i
     const long orow = ((long)uh * a.w + uw) * a.d + ud;
     const float q0 = (float)uh - s.c[0], q1 = (float)uw - s.c[1];
     float r0[4], r1[4], r2[4];
+    if (ELASTIC) {
+        const Knot k0 = make_knot(uh, lt.sc0, lt.n0), k1 = make_knot(uw, lt.sc1, lt.n1);
+        float w[16];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float q2 = (float)(ud + j) - s.c[2];
-        r0[j] = src_pos(s, 0, q0, q1, q2);
-        r1[j] = src_pos(s, 1, q0, q1, q2);
-        r2[j] = src_pos(s, 2, q0, q1, q2);
+        for (int t = 0; t < 16; ++t) w[t] = k0.b[t >> 2] * k1.b[t & 3];
+        const float* row = lt.P + (k0.i * lt.n1 + k1.i) * lt.n2;
+        float S0[4], S1[4], S2[4];                               // columns cb .. cb + 3 of the three components
+        int cb = -1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const Knot k2 = make_knot(ud + j, lt.sc2, lt.n2);
+            if (k2.i != cb) {
+                if (j && k2.i == cb + 1) {
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) { S0[e] = S0[e + 1]; S1[e] = S1[e + 1]; S2[e] = S2[e + 1]; }
+                    lat_column(lt, row + k2.i + 3, w, S0[3], S1[3], S2[3]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) lat_column(lt, row + k2.i + e, w, S0[e], S1[e], S2[e]);
+                }
+                cb = k2.i;
+            }
+            float d0 = k2.b[0] * S0[0], d1 = k2.b[0] * S1[0], d2 = k2.b[0] * S2[0];
+#pragma unroll
+            for (int e = 1; e < 4; ++e) {
+                d0 = __builtin_fmaf(k2.b[e], S0[e], d0);
+                d1 = __builtin_fmaf(k2.b[e], S1[e], d1);
+                d2 = __builtin_fmaf(k2.b[e], S2[e], d2);
+            }
+            const float p0 = q0 + d0, p1 = q1 + d1, p2 = ((float)(ud + j) - s.c[2]) + d2;     // q + d first: d = 0 keeps r
+            r0[j] = src_pos(s, 0, p0, p1, p2);
+            r1[j] = src_pos(s, 1, p0, p1, p2);
+            r2[j] = src_pos(s, 2, p0, p1, p2);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float q2 = (float)(ud + j) - s.c[2];
+            r0[j] = src_pos(s, 0, q0, q1, q2);
+            r1[j] = src_pos(s, 1, q0, q1, q2);
+            r2[j] = src_pos(s, 2, q0, q1, q2);
+        }
     }
     if (a.coord && active) {
         const float h0 = 0.5f * (float)(s.n0 - 1), h1 = 0.5f * (float)(s.n1 - 1), h2 = 0.5f * (float)(s.n2 - 1);
@@ -241,8 +325,18 @@ MIVP_DEV void fill_brick(const AffArgs& a, const Src& s, const Box& bx, int b, i
     }
 }
 
-__global__ __launch_bounds__(TPB) void k_crop_affine(AffArgs a) {
-    extern __shared__ float box[];                               // BOXV floats, then BOXV label bytes -- or nothing (stage == 0)
+struct ElArgs {
+    const int32_t* flags;    // DEVICE int32 [B]
+    const float* lattice;    // DEVICE fp32 [B][3][n0][n1][n2]
+    int n0, n1, n2;
+};
+constexpr int MAXN = 8;      // nodes per axis: 4 .. MAXN
+
+// The body of both kernels: k_crop_affine is crop_body<false>; k_crop_elastic, crop_body<true>, never stages a box and
+// branches per sample on its flag.  box: BOXV floats, then BOXV label bytes -- or nothing (stage == 0, ELASTIC); s_lat: room
+// for one sample's lattice (ELASTIC).
+template <bool ELASTIC>
+MIVP_DEV void crop_body(const AffArgs& a, const ElArgs& el, float* box, float* s_lat) {
     uint8_t* lbox = reinterpret_cast<uint8_t*>(box + BOXV);
     __shared__ uint8_t s_lut[256];
     const int b = blockIdx.y;
@@ -285,7 +379,7 @@ __global__ __launch_bounds__(TPB) void k_crop_affine(AffArgs a) {
         }
     }
     Box bx = {};
-    bool staged = finite && a.stage;
+    bool staged = !ELASTIC && finite && a.stage;
     if (staged) {
         // r is affine in u up to its rounding (far below one voxel): the brick's floor(r) lie in [floor(mn) - 1,
         // floor(mx) + 1] and their upper corners one above; clipped to the volume and its rim of zeros at -1 and m
@@ -298,26 +392,58 @@ __global__ __launch_bounds__(TPB) void k_crop_affine(AffArgs a) {
         staged = bx.e0 >= 2 && bx.e1 >= 2 && bx.e2 >= 2 && (long)bx.e0 * bx.e1 * bx.pitch <= (long)BOXV;
     }
     if (a.paths && threadIdx.x == 0) a.paths[(long)b * gridDim.x + blockIdx.x] = staged ? 1 : 0;
-    if (staged) fill_brick<true>(a, s, bx, b, u0h, u0w, u0d, box, lbox, s_lut);
-    else fill_brick<false>(a, s, bx, b, u0h, u0w, u0d, box, lbox, s_lut);
+    Lat lt = {};
+    if (ELASTIC && el.flags[b] != 0) {                           // workgroup-uniform; flag 0 never reads the lattice
+        const int words = 3 * el.n0 * el.n1 * el.n2;
+        const float* P = el.lattice + (long)b * words;
+        for (int i = threadIdx.x; i < words; i += TPB) s_lat[i] = P[i];
+        __syncthreads();
+        lt.P = s_lat; lt.n0 = el.n0; lt.n1 = el.n1; lt.n2 = el.n2;
+        lt.sc0 = (float)(el.n0 - 3) / (float)a.h; lt.sc1 = (float)(el.n1 - 3) / (float)a.w;
+        lt.sc2 = (float)(el.n2 - 3) / (float)a.d;
+        fill_brick<false, true>(a, s, bx, b, u0h, u0w, u0d, box, lbox, s_lut, lt);
+    } else if (staged) fill_brick<true, false>(a, s, bx, b, u0h, u0w, u0d, box, lbox, s_lut, lt);
+    else fill_brick<false, false>(a, s, bx, b, u0h, u0w, u0d, box, lbox, s_lut, lt);
 }
 
-int launch(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot, int32_t slot_stride, const float* affine,
-           int32_t B, const int32_t* roi, const uint8_t* lut, float* image, float* mask, float* coord, int stage,
-           int32_t* paths, mivp_stream_t stream) {
+__global__ __launch_bounds__(TPB) void k_crop_affine(AffArgs a) {
+    extern __shared__ float box[];
+    crop_body<false>(a, ElArgs{}, box, nullptr);
+}
+
+__global__ __launch_bounds__(TPB) void k_crop_elastic(AffArgs a, ElArgs el) {      // a.stage = 0: the direct path only
+    __shared__ float s_lat[3 * MAXN * MAXN * MAXN];
+    crop_body<true>(a, el, nullptr, s_lat);
+}
+
+// the checks and the kernel arguments both launches share; `units`: the bricks of one sample
+int make_args(AffArgs& a, long& units, const char* who, const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot,
+              int32_t slot_stride, const float* affine, int32_t B, const int32_t* roi, const uint8_t* lut, float* image,
+              float* mask, float* coord) {
     const int rc = check_fill_args(table, n_volumes, C, slot, slot_stride, B, roi, lut, image, mask, coord);
     if (rc) return rc;
-    MIVP_REQUIRE(affine && ((uintptr_t)affine & 3) == 0 && ((uintptr_t)paths & 3) == 0);
-    AffArgs a{};
+    MIVP_REQUIRE(affine && ((uintptr_t)affine & 3) == 0);
     a.table = table; a.n_volumes = n_volumes; a.C = C; a.B = B;
     a.slot = slot; a.slot_stride = slot_stride; a.affine = affine;
     a.h = roi[0]; a.w = roi[1]; a.d = roi[2];
     a.nbw = (a.w + BW - 1) / BW; a.nbd = (a.d + BD - 1) / BD;
     a.lut = mask ? lut : nullptr;
     a.image = image; a.mask = mask; a.coord = coord;
+    units = (long)((a.h + BH - 1) / BH) * a.nbw * a.nbd;
+    if (units >= (1L << 31)) { mivp_set_error(who); return MIVP_EINVAL; }
+    return MIVP_OK;
+}
+
+int launch(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot, int32_t slot_stride, const float* affine,
+           int32_t B, const int32_t* roi, const uint8_t* lut, float* image, float* mask, float* coord, int stage,
+           int32_t* paths, mivp_stream_t stream) {
+    AffArgs a{};
+    long units;
+    const int rc = make_args(a, units, "crop_fill_affine: too many work units", table, n_volumes, C, slot, slot_stride, affine,
+                             B, roi, lut, image, mask, coord);
+    if (rc) return rc;
+    MIVP_REQUIRE(((uintptr_t)paths & 3) == 0);
     a.stage = stage; a.paths = paths;
-    const long units = (long)((a.h + BH - 1) / BH) * a.nbw * a.nbd;
-    if (units >= (1L << 31)) { mivp_set_error("crop_fill_affine: too many work units"); return MIVP_EINVAL; }
     // the box is dynamic LDS: a launch that stages nothing asks for none, and its occupancy is the registers'
     const size_t lds = stage ? (size_t)BOXV * (sizeof(float) + 1) : 0;
     hipLaunchKernelGGL(k_crop_affine, dim3((unsigned)units, (unsigned)B), dim3(TPB), lds, (hipStream_t)stream, a);
@@ -336,4 +462,20 @@ extern "C" int mivp_crop_fill_affine_debug(const int64_t* table, int32_t n_volum
                                            const uint8_t* lut, float* image, float* mask, float* coord,
                                            int32_t stage, int32_t* paths, mivp_stream_t stream) {
     return launch(table, n_volumes, C, slot, slot_stride, affine, B, roi, lut, image, mask, coord, stage != 0, paths, stream);
+}
+
+extern "C" int mivp_crop_fill_elastic(const int64_t* table, int32_t n_volumes, int32_t C, const int32_t* slot,
+                                      int32_t slot_stride, const float* affine, int32_t B, const int32_t* roi,
+                                      const uint8_t* lut, float* image, float* mask, float* coord, const int32_t* flags,
+                                      const float* lattice, const int32_t* nodes, mivp_stream_t stream) {
+    AffArgs a{};
+    long units;
+    const int rc = make_args(a, units, "crop_fill_elastic: too many work units", table, n_volumes, C, slot, slot_stride, affine,
+                             B, roi, lut, image, mask, coord);
+    if (rc) return rc;
+    MIVP_REQUIRE(flags && lattice && nodes && ((uintptr_t)flags & 3) == 0 && ((uintptr_t)lattice & 3) == 0);
+    MIVP_REQUIRE(nodes[0] >= 4 && nodes[0] <= MAXN && nodes[1] >= 4 && nodes[1] <= MAXN && nodes[2] >= 4 && nodes[2] <= MAXN);
+    ElArgs el{flags, lattice, nodes[0], nodes[1], nodes[2]};
+    hipLaunchKernelGGL(k_crop_elastic, dim3((unsigned)units, (unsigned)B), dim3(TPB), 0, (hipStream_t)stream, a, el);
+    return mivp_check_launch("crop_fill_elastic");
 }

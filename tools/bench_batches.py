@@ -48,7 +48,20 @@ whole measurements with their spread, appended to profiles/spatial_crops_bench.j
 - ``eager_ms``: image and mask of the same typical draws from eager torch on the same GPU, per sample ``affine_grid`` +
   ``grid_sample`` (bilinear, and nearest on the label map through the table), checked against the filler's image;
 - ``share_of_step`` = (typical_ms - plain_ms) / the step the batch feeds.
-The crops are re-read from the Infinity Cache on every replay: none of these is an HBM rate."""
+The crops are re-read from the Infinity Cache on every replay: none of these is an HBM rate.
+
+``--elastic`` measures the elastic deformation of DESIGN 4.29 (``BatchFiller(spatial=True, elastic=(7, 7, 7))``) on the
+``downstream`` row (roi 96^3, B = 4), ``--runs`` whole measurements with their spread, appended to
+profiles/elastic_crops_bench.jsonl.  Every ``fill`` is recorded once and replayed, on the typical spatial draws above:
+
+- ``spatial_ms``: the ``spatial=True`` filler, the yardstick of the same run (``mivp_crop_fill_affine``);
+- ``flags0_ms``: the elastic filler with no sample deformed (checked to give the spatial filler's bits): what the
+  ``1 - p_elastic`` share of the samples costs; ``flags0_over_spatial`` is their ratio;
+- ``flags1_ms``: every sample deformed, node displacements uniform in +-2 voxels, no locked border;
+  ``share_of_step`` = (flags1_ms - spatial_ms) / the step the batch feeds, ``flags1_share_of_step`` = flags1_ms / that step;
+- ``eager_ms``: a deformation of the same kind from eager torch on the same GPU, per sample: the lattice upsampled to a
+  displacement volume (``F.interpolate``, trilinear -- not the B-spline: a cost comparison, its values are not compared),
+  added to the output grid, the affine map applied, ``grid_sample`` (bilinear, and nearest on the label map)."""
 import argparse
 import json
 import os
@@ -323,6 +336,95 @@ def spatial(a):
         f.write("\n".join(lines) + "\n")
 
 
+def elastic(a):
+    """``--elastic``: see the module docstring."""
+    import numpy as np
+    import torch
+    import torch.nn.functional as F
+    import mivp_amd  # noqa: F401
+    from mivp_amd import batches as BT
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(1)
+    bank = BT.VolumeBank(dev, 1)
+    for _ in range(a.volumes):
+        bank.add(torch.rand((1,) + BANK_SHAPE, generator=g).to(dev),
+                 torch.randint(0, 4, BANK_SHAPE, generator=g, dtype=torch.uint8).to(dev))
+    name, roi, B, sizes, with_coord, step_ms, step_kind = CASES[0]
+    nodes = (7, 7, 7)
+    keys = ("spatial_ms", "flags0_ms", "flags1_ms", "eager_ms")
+    r = {"case": name, "roi": list(roi), "B": B, "nodes": list(nodes), "magnitude": 2.0, **{k: [] for k in keys},
+         "step_ms": step_ms, "step": step_kind}
+    typical = dict(p_flip=(0.5, 0.5, 0.5), p_affine=1.0, rotate_range=(0.26, 0.26, 0.26), scale_range=(0.8, 1.25),
+                   isotropic=False, shift=True)
+    for run in range(a.runs):
+        rs = np.random.RandomState(3 + run)
+        ids = [i % len(bank) for i in range(B)]
+        d = BT.draw_crops(rs, bank.shapes, ids, roi, 1, False, sizes)
+        sp = BT.draw_spatial(rs, B, **typical)
+        ed = BT.draw_elastic(rs, B, roi, nodes=nodes, p_elastic=1.0, magnitude_range=(2.0, 2.0), locked_borders=0)
+        ref = BT.BatchFiller(bank, roi, B, active_labels=ACTIVE, with_coord=with_coord, spatial=True)
+        own = BT.BatchFiller(bank, roi, B, active_labels=ACTIVE, with_coord=with_coord, spatial=True, elastic=nodes)
+        ref.fill(d, spatial=sp)
+        own.fill(d, spatial=sp)
+        torch.cuda.synchronize()
+        assert torch.equal(ref.image, own.image) and torch.equal(ref.mask, own.mask), "flags 0: not the spatial filler's bits"
+        own.fill(elastic=ed)
+        torch.cuda.synchronize()
+        moved = float((own.image != ref.image).float().mean())
+        assert moved > 0.5 and bool(torch.isfinite(own.image).all()), f"flags 1: only {moved:.3f} of the voxels changed"
+        lut = own.lut.float()
+        half = (np.asarray(roi) - 1) / 2.0
+        lat = torch.from_numpy(ed.lattice).to(dev)
+        to_norm = torch.tensor([2.0 / (roi[k] - 1) for k in (2, 1, 0)], dtype=torch.float32, device=dev)
+        eye = torch.eye(3, 4, device=dev)[None]
+
+        def eager():
+            img, mask = [], []
+            for b in range(B):
+                vol = bank.images[int(d.volume[b])][None]
+                m = np.asarray(vol.shape[2:], np.float64)
+                A = sp.affine[b, :9].astype(np.float64).reshape(3, 3)
+                t = half + d.origin[b] + sp.affine[b, 9:]
+                th = np.zeros((3, 4))
+                th[:, :3] = (2.0 / (m - 1))[:, None] * A * half[None, :]
+                th[:, 3] = 2.0 * t / (m - 1) - 1.0
+                th = torch.from_numpy(th[::-1, [2, 1, 0, 3]].copy()).float().to(dev)    # x, y, z count from the LAST axis
+                disp = F.interpolate(lat[b][None], size=roi, mode="trilinear", align_corners=False)     # voxels, [1, 3, h, w, d]
+                base = F.affine_grid(eye, (1, 1) + tuple(roi), align_corners=True)                      # the output grid
+                base = base + disp[0].permute(1, 2, 3, 0).flip(-1)[None] * to_norm
+                grid = base @ th[:, :3].T + th[:, 3]
+                img.append(F.grid_sample(vol, grid, mode="bilinear", padding_mode="zeros", align_corners=True)[0])
+                lab = lut[bank.labels[int(d.volume[b])].long()][None, None]
+                mask.append(F.grid_sample(lab, grid, mode="nearest", padding_mode="zeros", align_corners=True)[0])
+            return torch.stack(img), torch.stack(mask)
+
+        def record(fn):
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                fn()
+            return graph
+
+        g_ref, g_own = record(ref.fill), record(own.fill)           # one recording each; the elastic one is fed by its slot
+        for _ in range(2):                                          # the yardstick and flags 0 alternate
+            r["spatial_ms"].append(round(timed(g_ref.replay, a.calls, a.warmup), 4))
+            own.elastic_slot.load(BT.ElasticDraws.identity(B, nodes))
+            r["flags0_ms"].append(round(timed(g_own.replay, a.calls, a.warmup), 4))
+            own.elastic_slot.load(ed)
+            r["flags1_ms"].append(round(timed(g_own.replay, a.calls, a.warmup), 4))
+        r["eager_ms"].append(round(timed(eager, max(5, a.calls // 10), 2), 4))
+    for k in keys:
+        r[k.replace("_ms", "_spread")] = spread(r[k])
+    r["flags0_over_spatial"] = [round(z / s, 4) for z, s in zip(r["flags0_ms"], r["spatial_ms"])]
+    r["share_of_step"] = [round((e - s) / r["step_ms"], 5) for e, s in zip(r["flags1_ms"], r["spatial_ms"])]
+    r["flags1_share_of_step"] = [round(e / r["step_ms"], 5) for e in r["flags1_ms"]]
+    r["eager_over_flags1"] = [round(e / min(r["flags1_ms"]), 1) for e in r["eager_ms"]]
+    print(json.dumps(r), flush=True)
+    os.makedirs(os.path.dirname(a.elastic_out), exist_ok=True)
+    with open(a.elastic_out, "a") as f:
+        f.write(json.dumps(r) + "\n")
+
+
 def rotated(codes, p, rot_axes):
     """Stored voxels ``p`` [B, 3] in the frames rotated by ``codes``: for axes (a, b), r_b = p_a and r_a = n_b - 1 - p_b."""
     import numpy as np
@@ -344,11 +446,16 @@ def main():
                     "kernel-trace run, where every k_crop launch of the process should be the same launch")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batches_bench.jsonl"))
     ap.add_argument("--class-balanced", action="store_true", help="measure the class-balanced sampling (DESIGN 4.27)")
-    ap.add_argument("--runs", type=int, default=2, help="--class-balanced, --spatial: how often the whole measurement is made")
+    ap.add_argument("--runs", type=int, default=2,
+                    help="--class-balanced, --spatial, --elastic: how often the whole measurement is made")
     ap.add_argument("--class-out", default=os.path.join(ROOT, "profiles", "class_crops_bench.jsonl"))
     ap.add_argument("--spatial", action="store_true", help="measure the random flip / rotation / zoom (DESIGN 4.28)")
     ap.add_argument("--spatial-out", default=os.path.join(ROOT, "profiles", "spatial_crops_bench.jsonl"))
+    ap.add_argument("--elastic", action="store_true", help="measure the elastic deformation (DESIGN 4.29)")
+    ap.add_argument("--elastic-out", default=os.path.join(ROOT, "profiles", "elastic_crops_bench.jsonl"))
     a = ap.parse_args()
+    if a.elastic:
+        return elastic(a)
     if a.class_balanced:
         return class_balanced(a)
     if a.spatial:
