@@ -973,8 +973,8 @@ int mivp_window_fit_plan(const int32_t* box, const int32_t* dims, const int32_t*
                          int32_t n_flips, int32_t* table, int32_t n_entries, int32_t* origins, int32_t n_origins,
                          int32_t* meta, mivp_stream_t stream);
 
-/* The three sources of the batch filler named below (csrc/crops.hip, crops_index.hip, crops_affine.hip) share
- * csrc/crops_common.hpp: the slot record and table row decode, the quarter turn, the pad rule and the host checks. */
+/* The four sources of the batch filler named below (csrc/crops.hip, crops_index.hip, crops_affine.hip, crops_corrupt.hip)
+ * share csrc/crops_common.hpp: the slot record and table row decode, the quarter turn, the pad rule and the host checks. */
 /* Training-batch sampling from a bank of resident scans (csrc/crops.hip; mivp_amd/batches.py).  These entry
  * points joined the current ABI without a bump: they are additive and no earlier signature changed.  One gather kernel
  * family (k_crop): every output voxel is written exactly once, no atomics, bitwise reproducible, no host synchronisation.
@@ -1106,6 +1106,55 @@ int mivp_crop_fill_elastic(const int64_t* table, int32_t n_volumes, int32_t C, c
                            const float* affine, int32_t B, const int32_t* roi, const uint8_t* lut, float* image, float* mask,
                            float* coord, const int32_t* flags, const float* lattice, const int32_t* nodes,
                            mivp_stream_t stream);
+
+/* The students' own corruption for the batch filler (csrc/crops_corrupt.hip; mivp_amd/batches.py): the
+ * reference's students_rand_ts (datasets/transforms.py:244-297) -- nothing, RandCoarseDropoutd with dropout_holes True or
+ * False, RandCoarseShuffled -- in place on a student's image tensor, after the student crop.  Additive again: the ABI stays
+ * 18.  No atomics, no host synchronisation, bitwise reproducible; the records are DEVICE memory like the slot, so both
+ * launches record into a graph and a replay follows what the records hold then.  MONAI's own streams are not reproduced.
+ *   x: DEVICE fp32 [B][C][dims] (C in 1..16; dims host int32 [3], each 1..65535, C * voxels < 2^31), corrupted IN PLACE.
+ *   records: DEVICE int32 [B][MIVP_CORRUPT_RECORD_WORDS], one per sample: [0] mode, [1] the number of holes n (0..8),
+ *     [2] the noise key (32 bits), then 8 holes of 7 words: origin[3], size[3], the hole's shuffle key (32 bits).  Holes
+ *     n.. are not read.  A hole is the box origin <= u < origin + size, size >= 1, inside dims on every axis.
+ *   Rule for sample b by its mode:
+ *     0: the sample is not written at all (its workgroups return).
+ *     1 (dropout): every voxel inside the union of the holes, in every channel, is replaced by noise.
+ *     2 (keep): every voxel OUTSIDE the union of the holes, in every channel, is replaced by noise.
+ *       noise at element i = ((c * h + u0) * w + u1) * d + u2 of the sample (its linear index over [C][dims]):
+ *         lo, hi = the minimum and maximum of the sample over all channels BEFORE the corruption (fminf / fmaxf: values are
+ *           expected finite), each with +0.0f added so that a zero extreme is +0 whatever the order of the reduction;
+ *         t = i + key; t ^= t >> 16; t = (t & 0xFFFFFF) * 0xB5AD4F; t ^= t >> 13;
+ *         hash = (t & 0xFFFFFF) * 0x6C62B9 + (t >> 8) + rotl(key, 13)      (all mod 2^32: the dropout hash of common.hpp,
+ *           full-rate 24-bit multiplies only);
+ *         u = (hash >> 8) * 2^-24 in [0, 1);  value = lo + (hi - lo) * u, fp32, the difference, the product and the sum
+ *           each rounded to nearest, never contracted.  lo == hi gives exactly lo.  (The value lies in [lo, hi) before
+ *           the last rounding, which can reach hi when u is within a few ulp of 1.)
+ *     3 (shuffle): for each hole in list order, and for each channel alone: with n = the hole's voxel count (<= 4096),
+ *       voxel j = (u0 * size1 + u1) * size2 + u2 of the hole (C order of its own extents) receives the value voxel P(j)
+ *       held before this hole was applied; later holes see what earlier ones wrote.  Every channel uses the same P
+ *       (MONAI permutes across channels; at one channel the two coincide).
+ *       P: bits = max(2, the next even number >= ceil(log2 n)), half = bits / 2, mask = 2^half - 1; v = j; repeat
+ *         { l = v >> half, r = v & mask; four rounds r' = l ^ ((hash(r + 64 * round, key) >> 16) & mask), l' = r, with the
+ *         hash above and key = the hole's; v = (l << half) | r } until v < n; P(j) = v.  A Feistel network is a bijection
+ *         of the 2^bits values, and walking it until it returns below n makes P a bijection of {0 .. n-1}.
+ *   mivp_crop_corrupt_range: range DEVICE fp32 [B][MIVP_CORRUPT_PARTIALS][2], scratch: workgroup p of a sample in mode 1
+ *     or 2 writes the (min, max) of its share of the sample; other samples' rows are left alone.  16-byte loads at 4-byte
+ *     alignment with a scalar tail for a voxel count that is no multiple of 4.
+ *   mivp_crop_corrupt: reads range (written by the call above on the same stream) and the records and applies the rule.
+ *     Modes 1 and 2 only store: 16 bytes where four voxels along d are all replaced, single voxels elsewhere and in the
+ *     d % 4 tail.  Mode 3 stages each hole in LDS (16 KB at the bound) in one workgroup per (sample, channel).
+ *   Both: MIVP_EINVAL, before any launch, for a null or misaligned pointer and for sizes outside the ranges above.  The
+ *     records are device memory the host entry cannot see: a sample whose mode is above 3, whose hole count is above 8,
+ *     one of whose holes is empty or reaches outside dims, or (mode 3) holds more than 4096 voxels, is left unwritten by
+ *     the kernel.  The host validates the draws before it uploads them (batches.CorruptionDraws.check). */
+#define MIVP_CORRUPT_MAX_HOLES 8
+#define MIVP_CORRUPT_RECORD_WORDS 59
+#define MIVP_CORRUPT_SHUFFLE_VOXELS 4096
+#define MIVP_CORRUPT_PARTIALS 64
+int mivp_crop_corrupt_range(const float* x, int32_t C, const int32_t* dims, const int32_t* records, int32_t B,
+                            float* range, mivp_stream_t stream);
+int mivp_crop_corrupt(float* x, int32_t C, const int32_t* dims, const int32_t* records, int32_t B, const float* range,
+                      mivp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,12 @@ the labels, analytic coordinates; the pick and the students' launches are the sa
 Elastic deformation (the second kernel of csrc/crops_affine.hip): ``draw_elastic`` draws, per sample, a coin
 and a small control lattice of displacements (``ElasticDraws``), an ``ElasticSlot`` holds them on the device beside the
 other two slots, and a filler built with ``spatial=True, elastic=nodes`` issues ``mivp_crop_fill_elastic`` for the teacher:
-the cubic B-spline of the lattice is added to the output offset in front of the affine map, evaluated on the fly."""
+the cubic B-spline of the lattice is added to the output offset in front of the affine map, evaluated on the fly.
+
+The students' own corruption (csrc/crops_corrupt.hip): ``draw_student_corruption`` draws, per student and
+sample, one of none / coarse dropout / coarse keep / coarse shuffle with its holes and keys (``CorruptionDraws``, the
+reference's ``students_rand_ts``), a ``CorruptionSlot`` holds the records on the device, and a filler built with
+``corruption=True`` corrupts ``image_st[i]`` in place after the student crops, two launches per student."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -640,6 +645,187 @@ class ElasticSlot:
         self.draws = draws
 
 
+MAX_HOLES = 8                   # holes per (student, sample) of a corruption record (mivp.h)
+MAX_SHUFFLE_VOXELS = 4096       # of one shuffle hole: what the kernel stages in LDS (mivp.h)
+HOLE_WORDS = 7                  # int32 words of one hole: origin[3], size[3], key
+CORRUPT_WORDS = 3 + MAX_HOLES * HOLE_WORDS      # of one record: mode, hole count, noise key, then the holes (mivp.h)
+CORRUPT_PARTIALS = 64           # (min, max) pairs per sample of the range scratch (mivp.h)
+CORRUPT_MODES = ("none", "dropout", "keep", "shuffle")
+
+
+@dataclass
+class CorruptionDraws:
+    """The students' own corruption one step draws on the host, one entry per (student, sample): a mode
+    -- 0 none, 1 dropout (noise inside the holes), 2 keep (noise outside their union), 3 shuffle (voxels permuted inside
+    each hole, in list order) --, up to ``MAX_HOLES`` boxes inside the student's extents, and the 32-bit keys of the
+    counter-based noise and of each hole's permutation (the rule is written out in include/mivp.h).  Holes ``n_holes..``
+    are not read."""
+    mode: np.ndarray                # int32 [S, B]
+    n_holes: np.ndarray             # int32 [S, B]: 0 .. MAX_HOLES
+    key: np.ndarray                 # uint32 [S, B]: the noise key (modes 1 and 2)
+    origin: np.ndarray              # int32 [S, B, MAX_HOLES, 3]
+    size: np.ndarray                # int32 [S, B, MAX_HOLES, 3]
+    hole_key: np.ndarray            # uint32 [S, B, MAX_HOLES]: each hole's permutation key (mode 3)
+
+    @property
+    def n_students(self) -> int:
+        return int(np.shape(self.mode)[0])
+
+    @property
+    def batch(self) -> int:
+        return int(np.shape(self.mode)[1])
+
+    @classmethod
+    def identity(cls, B: int, n_students: int) -> "CorruptionDraws":
+        S, B = check_int_from("n_students", n_students, 1), check_int_from("B", B, 1)
+        return cls(np.zeros((S, B), np.int32), np.zeros((S, B), np.int32), np.zeros((S, B), np.uint32),
+                   np.zeros((S, B, MAX_HOLES, 3), np.int32), np.zeros((S, B, MAX_HOLES, 3), np.int32),
+                   np.zeros((S, B, MAX_HOLES), np.uint32))
+
+    def pack(self) -> np.ndarray:
+        """int32 [S, B, CORRUPT_WORDS]: the slot's records."""
+        S, B = self.n_students, self.batch
+        w = np.zeros((S, B, CORRUPT_WORDS), dtype=np.int32)
+        w[..., 0], w[..., 1], w[..., 2] = self.mode, self.n_holes, np.asarray(self.key, np.uint32).view(np.int32)
+        holes = w[..., 3:].reshape(S, B, MAX_HOLES, HOLE_WORDS)
+        holes[..., 0:3], holes[..., 3:6] = self.origin, self.size
+        holes[..., 6] = np.asarray(self.hole_key, np.uint32).view(np.int32)
+        return w
+
+    @classmethod
+    def unpack(cls, words: np.ndarray, n_students: int) -> "CorruptionDraws":
+        w = np.ascontiguousarray(words, dtype=np.int32).reshape(int(n_students), -1, CORRUPT_WORDS)
+        holes = w[..., 3:].reshape(w.shape[0], w.shape[1], MAX_HOLES, HOLE_WORDS)
+        return cls(w[..., 0].copy(), w[..., 1].copy(), w[..., 2].copy().view(np.uint32), holes[..., 0:3].copy(),
+                   holes[..., 3:6].copy(), holes[..., 6].copy().view(np.uint32))
+
+    def check(self, B: int, student_sizes) -> "CorruptionDraws":
+        """Every field against the batch and the students' extents: shapes and dtypes, a mode in 0..3, at most
+        ``MAX_HOLES`` holes, every hole read non-empty and inside its student, a shuffle hole of at most
+        ``MAX_SHUFFLE_VOXELS`` voxels.  A hole outside the tensor would send the kernel to memory that is not the student's,
+        so nothing unchecked is ever uploaded.  Raises ``ValueError`` naming the field, the student and the sample."""
+        sizes = [_size3("student size", s) for s in student_sizes]
+        S, B = len(sizes), int(B)
+        want = (("mode", np.int32, (S, B)), ("n_holes", np.int32, (S, B)), ("key", np.uint32, (S, B)),
+                ("origin", np.int32, (S, B, MAX_HOLES, 3)), ("size", np.int32, (S, B, MAX_HOLES, 3)),
+                ("hole_key", np.uint32, (S, B, MAX_HOLES)))
+        for name, dtype, shape in want:
+            a = getattr(self, name)
+            if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != shape:
+                got = f"{a.dtype} {a.shape}" if isinstance(a, np.ndarray) else repr(type(a))
+                raise ValueError(f"CorruptionDraws: {name} must be a {np.dtype(dtype).name} {list(shape)} array (every "
+                                 f"student and sample of the batch), got {got}")
+        for s, ext in enumerate(sizes):
+            who = f"CorruptionDraws: student {s}"
+            mode, n = self.mode[s], self.n_holes[s]
+            _refuse(who, (mode < 0) | (mode > 3), lambda b: f"mode {int(mode[b])} outside 0..3")
+            _refuse(who, (n < 0) | (n > MAX_HOLES), lambda b: f"n_holes {int(n[b])} outside 0..{MAX_HOLES}")
+            for b in range(B):
+                for k in range(int(n[b])):
+                    o, e = self.origin[s, b, k].astype(np.int64), self.size[s, b, k].astype(np.int64)
+                    if (e < 1).any() or (o < 0).any() or (o + e > np.asarray(ext)).any():
+                        raise ValueError(f"{who}: sample {b}: hole {k} with origin {o.tolist()} and size {e.tolist()} is "
+                                         f"empty or outside the student's extents {ext}")
+                    if int(mode[b]) == 3 and int(e.prod()) > MAX_SHUFFLE_VOXELS:
+                        raise ValueError(f"{who}: sample {b}: shuffle hole {k} of size {e.tolist()} holds {int(e.prod())} "
+                                         f"voxels, more than {MAX_SHUFFLE_VOXELS}")
+        return self
+
+
+def _hole_params(name: str, p) -> Tuple[int, int, Tuple[int, int, int], Tuple[int, int, int]]:
+    """(holes, max_holes, spatial_size, max_spatial_size) of one ``draw_student_corruption`` dict; ``max_holes`` and
+    ``max_spatial_size`` default to ``holes`` and ``spatial_size`` (MONAI's None)."""
+    p = dict(p)
+    unknown = set(p) - {"holes", "max_holes", "spatial_size", "max_spatial_size"}
+    if unknown or "holes" not in p or "spatial_size" not in p:
+        raise ValueError(f"draw_student_corruption: {name} takes holes, spatial_size and optionally max_holes, "
+                         f"max_spatial_size, got {sorted(p)}")
+    lo = check_int_from(f"{name}['holes']", p["holes"], 0)
+    hi = lo if p.get("max_holes") is None else check_int_from(f"{name}['max_holes']", p["max_holes"], 0)
+    small = _size3(f"{name}['spatial_size']", p["spatial_size"])
+    large = small if p.get("max_spatial_size") is None else _size3(f"{name}['max_spatial_size']", p["max_spatial_size"])
+    if not lo <= hi <= MAX_HOLES or any(a > b for a, b in zip(small, large)):
+        raise ValueError(f"draw_student_corruption: {name} needs holes <= max_holes <= {MAX_HOLES} and spatial_size <= "
+                         f"max_spatial_size, got {p}")
+    return lo, hi, small, large
+
+
+def draw_student_corruption(rs: np.random.RandomState, B: int, student_sizes, weights=(0.7, 0.1, 0.1, 0.1),
+                            dropout=dict(holes=1, max_holes=3, spatial_size=4, max_spatial_size=16),
+                            keep=dict(holes=5, max_holes=5, spatial_size=32, max_spatial_size=48),
+                            shuffle=dict(holes=1, max_holes=3, spatial_size=4, max_spatial_size=16)) -> CorruptionDraws:
+    """The corruption draws of one batch of ``B`` samples for the students of ``student_sizes`` from ONE RandomState: the
+    reference's ``students_rand_ts`` (transforms.py:244-297), whose defaults these are.  Per sample, and within it per
+    student, in this order:
+
+    1. the mode: ``rs.choice(4, p=weights / sum(weights))`` -- none, dropout, keep, shuffle;
+    2. mode 0 consumes nothing more.  Otherwise, with the dict of that mode: the number of holes
+       ``rs.randint(holes, max_holes + 1)``;
+    3. then per hole: three extents ``min(rs.randint(spatial_size[k], max_spatial_size[k] + 1), student extent k)``, then
+       three origins ``rs.randint(0, student extent k - extent k + 1)``, then, in mode 3 only, the hole's key
+       ``rs.randint(0, 2**32, dtype=np.uint32)``;
+    4. then, in modes 1 and 2 only, the noise key ``rs.randint(0, 2**32, dtype=np.uint32)``.
+
+    The hole rule restates MONAI's documented ``RandCoarseTransform`` (a uniform count, uniform extents clipped to the
+    image, a uniform origin); MONAI's own streams are NOT reproduced (``Compose`` / ``OneOf`` reseed every child, and its
+    noise is ``R.uniform`` per voxel): parity is unpinned at the MONAI boundary and this order is the project's own
+    (DESIGN.md 8).  A shuffle hole above ``MAX_SHUFFLE_VOXELS`` voxels is refused by the final ``check``."""
+    B = check_int_from("B", B, 1)
+    sizes = [_size3("student size", s) for s in student_sizes]
+    if not sizes:
+        raise ValueError("draw_student_corruption: at least one student size expected")
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != (4,) or not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+        raise ValueError(f"draw_student_corruption: weights must be 4 finite non-negative numbers with a positive sum "
+                         f"(none, dropout, keep, shuffle), got {weights!r}")
+    params = {1: _hole_params("dropout", dropout), 2: _hole_params("keep", keep), 3: _hole_params("shuffle", shuffle)}
+    d = CorruptionDraws.identity(B, len(sizes))
+    for b in range(B):
+        for s, ext in enumerate(sizes):
+            mode = int(rs.choice(4, p=w / w.sum()))
+            d.mode[s, b] = mode
+            if mode == 0:
+                continue
+            lo, hi, small, large = params[mode]
+            n = int(rs.randint(lo, hi + 1))
+            d.n_holes[s, b] = n
+            for k in range(n):
+                e = [min(int(rs.randint(small[a], large[a] + 1)), ext[a]) for a in range(3)]
+                d.size[s, b, k] = e
+                d.origin[s, b, k] = [rs.randint(0, ext[a] - e[a] + 1) for a in range(3)]
+                if mode == 3:
+                    d.hole_key[s, b, k] = rs.randint(0, 2 ** 32, dtype=np.uint32)
+            if mode != 3:
+                d.key[s, b] = rs.randint(0, 2 ** 32, dtype=np.uint32)
+    return d.check(B, sizes)
+
+
+class CorruptionSlot:
+    """Fixed device memory of one batch's corruption draws -- ONE int32 [S * B * CORRUPT_WORDS] allocation made here, every
+    record mode 0 at first -- whose pointer a recorded graph keeps; ``records[s]`` is student s's [B * CORRUPT_WORDS] view.
+    ``load`` checks the draws against the slot's student sizes, then refreshes the records from a new pinned staging buffer
+    without blocking; it does nothing while a graph is being recorded, exactly as ``ElasticSlot.load``."""
+
+    def __init__(self, B: int, student_sizes, device):
+        self.B = check_int_from("B", B, 1)
+        self.student_sizes = [_size3("student size", s) for s in student_sizes]
+        if not self.student_sizes:
+            raise ValueError("CorruptionSlot: at least one student size expected")
+        S = len(self.student_sizes)
+        self.buffer = torch.zeros(S * self.B * CORRUPT_WORDS, dtype=torch.int32, device=_gpu_device("CorruptionSlot", device))
+        self.records = list(self.buffer.view(S, self.B * CORRUPT_WORDS))
+        self.draws = CorruptionDraws.identity(self.B, S)
+
+    def load(self, draws: CorruptionDraws):
+        if not isinstance(draws, CorruptionDraws):
+            raise ValueError("CorruptionSlot.load: CorruptionDraws expected")
+        draws.check(self.B, self.student_sizes)
+        if torch.cuda.is_current_stream_capturing():
+            return
+        self.buffer.copy_(torch.from_numpy(draws.pack().reshape(-1)).pin_memory(), non_blocking=True)
+        self.draws = draws
+
+
 class CropSlot:
     """Fixed device memory of one batch's draws -- int32 [B][5 + 3 S] records -- whose pointer a recorded graph keeps.
     ``load`` checks the draws against the bank, then refreshes the records from a new pinned staging buffer without blocking;
@@ -737,16 +923,26 @@ class BatchFiller:
     With ``spatial=True, elastic=nodes`` (three node counts in 4..8) the filler also owns ``elastic_slot`` (no sample
     deformed at first) and the teacher launch is ``mivp_crop_fill_elastic``: the B-spline displacement of
     each flagged sample's control lattice is added in front of the affine map; a sample whose flag is 0 gets the bits of
-    the ``spatial=True`` filler.  Pick and students as before.  Without ``elastic`` nothing changes."""
+    the ``spatial=True`` filler.  Pick and students as before.  Without ``elastic`` nothing changes.
+
+    With ``corruption=True`` (students only) the filler owns ``corruption_slot`` (every record mode 0 at first) and, after
+    the student crops, issues two launches per student on ``image_st[i]`` alone: the range of each sample
+    that needs one, then the corruption in place.  ``coord_st``, ``mask_st_0`` and the teacher's tensors are never touched;
+    a sample in mode 0 is not written, so an all-zero slot gives the bits of the filler built without the option.  The
+    reference would have corrupted the roi-sized copy BEFORE the student crop; acting on the cropped student is a stated
+    deviation (the noise range and the shuffle are defined on the tensor the student sees)."""
 
     def __init__(self, bank: VolumeBank, roi, batch: int, student_sizes=(), active_labels=None, with_coord: bool = False,
-                 with_mask: bool = True, class_index: Optional[ClassIndex] = None, spatial: bool = False, elastic=None):
+                 with_mask: bool = True, class_index: Optional[ClassIndex] = None, spatial: bool = False, elastic=None,
+                 corruption: bool = False):
         if not isinstance(bank, VolumeBank):
             raise ValueError("BatchFiller: a VolumeBank expected")
         if class_index is not None and (not isinstance(class_index, ClassIndex) or class_index.bank is not bank):
             raise ValueError("BatchFiller: class_index must be a ClassIndex of this bank")
         if elastic is not None and not spatial:
             raise ValueError("BatchFiller: elastic= needs spatial=True (the displacement is added in front of the affine map)")
+        if corruption and not len(tuple(student_sizes)):
+            raise ValueError("BatchFiller: corruption=True needs student_sizes (it acts on the students' image tensors)")
         nodes = None if elastic is None else _nodes3("BatchFiller", elastic)
         self.class_index = class_index
         self.bank, self.roi, self.B = bank, _size3("roi", roi), check_int_from("batch", batch, 1)
@@ -766,6 +962,10 @@ class BatchFiller:
         self.slot = CropSlot(self.B, S, dev, class_index=class_index)
         self.spatial_slot = SpatialSlot(self.B, dev) if spatial else None
         self.elastic_slot = ElasticSlot(self.B, nodes, dev) if nodes is not None else None
+        self.corruption_slot = CorruptionSlot(self.B, self.student_sizes, dev) if corruption else None
+        # the range launch's scratch: fp32 [S][B][CORRUPT_PARTIALS][2] (mivp.h)
+        self.corruption_range = torch.zeros((S, self.B * CORRUPT_PARTIALS * 2), dtype=torch.float32, device=dev) \
+            if corruption else None
         self.xy = (self.image, self.mask)
         if S:
             self.batch = dict(image=self.image, coord=self.coord, image_st=self.image_st, coord_st=self.coord_st)
@@ -797,16 +997,33 @@ class BatchFiller:
                                  f"got {got}")
 
     @torch.no_grad()
-    def fill(self, draws_or_slot=None, spatial=None, elastic=None):
+    def fill(self, draws_or_slot=None, spatial=None, elastic=None, corruption=None):
         """``CropDraws`` (``ClassCropDraws`` on a filler with a class index): checked and loaded into the filler's own slot
         first.  A ``CropSlot``: used as it stands (its ``load`` did the checking).  ``None``: the filler's own slot as last
         loaded.  ``spatial`` (a filler built with ``spatial=True`` only): ``SpatialDraws``, checked and loaded into
         ``spatial_slot`` first; a ``SpatialSlot``, used as it stands; ``None``: ``spatial_slot`` as last loaded.
         ``elastic`` (a filler built with ``elastic=nodes`` only) follows the same rules with ``ElasticDraws``, an
-        ``ElasticSlot`` and ``elastic_slot``.  Every refusal comes before the first launch and before any slot is loaded."""
+        ``ElasticSlot`` and ``elastic_slot``, and ``corruption`` (a filler built with ``corruption=True`` only) with
+        ``CorruptionDraws``, a ``CorruptionSlot`` and ``corruption_slot``.  Every refusal comes before the first launch and
+        before any slot is loaded."""
         slot = self.slot
         sp_slot = self.spatial_slot
         el_slot = self.elastic_slot
+        co_slot = self.corruption_slot
+        if corruption is not None:
+            if co_slot is None:
+                raise ValueError("BatchFiller.fill: corruption= needs a filler built with corruption=True")
+            if isinstance(corruption, CorruptionDraws):
+                corruption.check(self.B, self.student_sizes)
+            elif isinstance(corruption, CorruptionSlot):
+                if corruption.B != self.B or corruption.student_sizes != self.student_sizes \
+                        or corruption.buffer.device != self.bank.device:
+                    raise ValueError(f"BatchFiller.fill: a corruption slot of batch {corruption.B} and student sizes "
+                                     f"{corruption.student_sizes} on {corruption.buffer.device} for a filler of batch "
+                                     f"{self.B} and student sizes {self.student_sizes} on {self.bank.device}")
+                co_slot = corruption
+            else:
+                raise ValueError("BatchFiller.fill: corruption= takes CorruptionDraws, a CorruptionSlot, or nothing")
         if elastic is not None:
             if el_slot is None:
                 raise ValueError("BatchFiller.fill: elastic= needs a filler built with elastic=nodes")
@@ -858,10 +1075,14 @@ class BatchFiller:
             sp_slot.load(spatial)
         if isinstance(elastic, ElasticDraws):
             el_slot.load(elastic)
+        if isinstance(corruption, CorruptionDraws):
+            co_slot.load(corruption)
         if self.class_index is not None:
             slot.resolve(self.roi)
         self._fill_teacher(slot, sp_slot, el_slot)
         self._fill_students(slot)
+        if co_slot is not None:
+            self._corrupt_students(co_slot)
         return self.batch
 
     def _fill_teacher(self, slot: CropSlot, spatial_slot: Optional[SpatialSlot] = None,
@@ -891,3 +1112,10 @@ class BatchFiller:
         if self.mask_st_0 is not None:
             L.call("mivp_crop_tensor", L.ptr(self.mask), 1, i3(self.roi), L.ptr(slot.student_views[0]), slot.words, self.B,
                    i3(self.student_sizes[0]), L.ptr(self.mask_st_0), st)
+
+    def _corrupt_students(self, slot: CorruptionSlot):
+        st, Cn = L.stream(), self.bank.channels
+        for i, size in enumerate(self.student_sizes):
+            x, rec, rng = L.ptr(self.image_st[i]), L.ptr(slot.records[i]), L.ptr(self.corruption_range[i])
+            L.call("mivp_crop_corrupt_range", x, Cn, i3(size), rec, self.B, rng, st)
+            L.call("mivp_crop_corrupt", x, Cn, i3(size), rec, self.B, rng, st)

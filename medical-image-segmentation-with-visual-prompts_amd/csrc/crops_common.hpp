@@ -1,4 +1,5 @@
-// What the batch filler's sources crops.hip, crops_index.hip and crops_affine.hip share, written once:
+// What the batch filler's sources crops.hip, crops_index.hip, crops_affine.hip and crops_corrupt.hip (which takes the block
+// size, the row vector type and the extent checks) share, written once:
 // how a workgroup decodes its sample's slot record and table row, the quarter turn between the rotated and the stored
 // frame in both directions, the symmetric pad, the label table's way into LDS, and the host checks of the arguments the
 // bank-mode entries have in common (the rule itself is written out in mivp.h).  Device helpers are inlined into the

@@ -61,7 +61,23 @@ profiles/elastic_crops_bench.jsonl.  Every ``fill`` is recorded once and replaye
   ``share_of_step`` = (flags1_ms - spatial_ms) / the step the batch feeds, ``flags1_share_of_step`` = flags1_ms / that step;
 - ``eager_ms``: a deformation of the same kind from eager torch on the same GPU, per sample: the lattice upsampled to a
   displacement volume (``F.interpolate``, trilinear -- not the B-spline: a cost comparison, its values are not compared),
-  added to the output grid, the affine map applied, ``grid_sample`` (bilinear, and nearest on the label map)."""
+  added to the output grid, the affine map applied, ``grid_sample`` (bilinear, and nearest on the label map).
+
+``--corrupt`` measures the students' corruption of DESIGN 4.30 (``BatchFiller(..., corruption=True)``) on the recorded
+students / teacher ``fill`` of two rows -- roi 96^3, B = 4, students 96^3 and 72^3; roi 128 x 128 x 8, B = 14, students
+128 x 128 x 8 and 72 x 72 x 8 -- ``--runs`` whole measurements with their spread, appended to
+profiles/corrupt_crops_bench.jsonl.  One recording per filler; the corrupting one is fed by its slot:
+
+- ``plain_ms``: the filler without the option, the parent's path and the yardstick of the same run; it alternates with
+- ``mode0_ms``: every record at mode 0 (checked to give the plain filler's bits): the two launches per student alone;
+  ``mode0_over_plain`` is their ratio;
+- ``dropout_ms`` / ``keep_ms`` / ``shuffle_ms``: every (student, sample) in mode 1 / 2 / 3 with the reference's hole
+  parameters (``draw_student_corruption``'s defaults); ``mix_ms``: its default weights (0.7, 0.1, 0.1, 0.1), the mean
+  over ``--draw-sets`` draw sets, each loaded and then replayed;
+- ``eager_*_ms``: a corruption of the same kind from eager torch ops on the same GPU, per (student, sample): ``amin`` /
+  ``amax``, ``torch.rand`` noise into the hole slices (dropout) or through a mask (keep), ``randperm`` indexing per hole
+  (shuffle) -- a cost comparison with torch's own generators, its values are not compared;
+- ``*_share_of_step``: (that time - plain_ms) over the step the batch feeds."""
 import argparse
 import json
 import os
@@ -425,6 +441,111 @@ def elastic(a):
         f.write(json.dumps(r) + "\n")
 
 
+CORRUPT_ROWS = [("students_teacher", (96, 96, 96), 4, ((96, 96, 96), (72, 72, 72)), 21.7, "phase-1 eager step (README)"),
+                ("yml", (128, 128, 8), 14, ((128, 128, 8), (72, 72, 8)), 18.7, "phase-1 graphed step (README)")]
+
+
+def corrupt(a):
+    """``--corrupt``: see the module docstring."""
+    import numpy as np
+    import torch
+    import mivp_amd  # noqa: F401
+    from mivp_amd import batches as BT
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(1)
+    bank = BT.VolumeBank(dev, 1)
+    for _ in range(a.volumes):
+        bank.add(torch.rand((1,) + BANK_SHAPE, generator=g).to(dev),
+                 torch.randint(0, 4, BANK_SHAPE, generator=g, dtype=torch.uint8).to(dev))
+    pure = {"dropout": (0, 1, 0, 0), "keep": (0, 0, 1, 0), "shuffle": (0, 0, 0, 1)}
+    keys = ["plain_ms", "mode0_ms"] + [f"{k}_ms" for k in pure] + ["mix_ms"] + [f"eager_{k}_ms" for k in list(pure) + ["mix"]]
+    lines = []
+    for name, roi, B, sizes, step_ms, step_kind in CORRUPT_ROWS:
+        r = {"case": name, "roi": list(roi), "B": B, "students": [list(x) for x in sizes], **{k: [] for k in keys},
+             "step_ms": step_ms, "step": step_kind}
+        for run in range(a.runs):
+            rs = np.random.RandomState(3 + run)
+            ids = [i % len(bank) for i in range(B)]
+            d = BT.draw_crops(rs, bank.shapes, ids, roi, 1, False, sizes)
+            plain = BT.BatchFiller(bank, roi, B, student_sizes=sizes, active_labels=ACTIVE)
+            own = BT.BatchFiller(bank, roi, B, student_sizes=sizes, active_labels=ACTIVE, corruption=True)
+            plain.fill(d)
+            own.fill(d)
+            torch.cuda.synchronize()
+            same = lambda: all(torch.equal(x, y) for x, y in zip(plain.image_st + plain.coord_st, own.image_st + own.coord_st))
+            assert same(), f"{name}: mode 0 does not give the plain filler's bits"
+            draws = {k: BT.draw_student_corruption(rs, B, sizes, weights=w) for k, w in pure.items()}
+            mixes = [BT.draw_student_corruption(rs, B, sizes) for _ in range(a.draw_sets)]
+            for k, cd in draws.items():
+                own.fill(corruption=cd)
+                torch.cuda.synchronize()
+                changed = [float((x != y).float().mean()) for x, y in zip(plain.image_st, own.image_st)]
+                assert min(changed) > 0 and bool(torch.isfinite(torch.stack([t.sum() for t in own.image_st])).all()), (k, changed)
+                r.setdefault(f"{k}_changed", []).append([round(c, 4) for c in changed])
+
+            def eager(cd):
+                out = [t.clone() for t in plain.image_st]
+                for s, x in enumerate(out):
+                    for b in range(B):
+                        mode, n = int(cd.mode[s, b]), int(cd.n_holes[s, b])
+                        if mode == 0:
+                            continue
+                        boxes = [tuple(slice(int(o), int(o + e)) for o, e in zip(cd.origin[s, b, k], cd.size[s, b, k]))
+                                 for k in range(n)]
+                        if mode == 3:
+                            for sl in boxes:
+                                hole = x[b][(slice(None),) + sl]
+                                flat = hole.reshape(hole.shape[0], -1)
+                                x[b][(slice(None),) + sl] = flat[:, torch.randperm(flat.shape[1], device=dev)].reshape(hole.shape)
+                            continue
+                        lo, hi = x[b].amin(), x[b].amax()
+                        if mode == 1:
+                            for sl in boxes:
+                                hole = x[b][(slice(None),) + sl]
+                                x[b][(slice(None),) + sl] = lo + (hi - lo) * torch.rand(hole.shape, device=dev)
+                        else:
+                            inside = torch.zeros(x.shape[2:], dtype=torch.bool, device=dev)
+                            for sl in boxes:
+                                inside[sl] = True
+                            x[b] = torch.where(inside, x[b], lo + (hi - lo) * torch.rand(x[b].shape, device=dev))
+                return out
+
+            def record(fn):
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    fn()
+                return graph
+
+            g_plain, g_own = record(plain.fill), record(own.fill)
+            for _ in range(2):                                      # the yardstick and mode 0 alternate
+                r["plain_ms"].append(round(timed(g_plain.replay, a.calls, a.warmup), 4))
+                own.corruption_slot.load(BT.CorruptionDraws.identity(B, len(sizes)))
+                r["mode0_ms"].append(round(timed(g_own.replay, a.calls, a.warmup), 4))
+            assert same(), f"{name}: the recorded mode 0 does not give the plain filler's bits"
+            for k, cd in draws.items():
+                own.corruption_slot.load(cd)
+                r[f"{k}_ms"].append(round(timed(g_own.replay, a.calls, a.warmup), 4))
+            per_set = []
+            for cd in mixes:                                        # loaded outside the timed replays
+                own.corruption_slot.load(cd)
+                per_set.append(timed(g_own.replay, max(20, a.calls // 8), a.warmup))
+            r["mix_ms"].append(round(sum(per_set) / len(per_set), 4))
+            for k, cd in list(draws.items()) + [("mix", mixes[0])]:
+                r[f"eager_{k}_ms"].append(round(timed(lambda: eager(cd), max(5, a.calls // 20), 2), 4))
+        for k in keys:
+            r[k.replace("_ms", "_spread")] = spread(r[k])
+        base = min(r["plain_ms"])
+        r["mode0_over_plain"] = [round(z / p, 4) for z, p in zip(r["mode0_ms"], r["plain_ms"])]
+        for k in ("mode0", "dropout", "keep", "shuffle", "mix"):
+            r[f"{k}_share_of_step"] = [round((t - base) / step_ms, 5) for t in r[f"{k}_ms"]]
+        print(json.dumps(r), flush=True)
+        lines.append(json.dumps(r))
+    os.makedirs(os.path.dirname(a.corrupt_out), exist_ok=True)
+    with open(a.corrupt_out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def rotated(codes, p, rot_axes):
     """Stored voxels ``p`` [B, 3] in the frames rotated by ``codes``: for axes (a, b), r_b = p_a and r_a = n_b - 1 - p_b."""
     import numpy as np
@@ -447,13 +568,17 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batches_bench.jsonl"))
     ap.add_argument("--class-balanced", action="store_true", help="measure the class-balanced sampling (DESIGN 4.27)")
     ap.add_argument("--runs", type=int, default=2,
-                    help="--class-balanced, --spatial, --elastic: how often the whole measurement is made")
+                    help="--class-balanced, --spatial, --elastic, --corrupt: how often the whole measurement is made")
     ap.add_argument("--class-out", default=os.path.join(ROOT, "profiles", "class_crops_bench.jsonl"))
     ap.add_argument("--spatial", action="store_true", help="measure the random flip / rotation / zoom (DESIGN 4.28)")
     ap.add_argument("--spatial-out", default=os.path.join(ROOT, "profiles", "spatial_crops_bench.jsonl"))
     ap.add_argument("--elastic", action="store_true", help="measure the elastic deformation (DESIGN 4.29)")
     ap.add_argument("--elastic-out", default=os.path.join(ROOT, "profiles", "elastic_crops_bench.jsonl"))
+    ap.add_argument("--corrupt", action="store_true", help="measure the students' corruption (DESIGN 4.30)")
+    ap.add_argument("--corrupt-out", default=os.path.join(ROOT, "profiles", "corrupt_crops_bench.jsonl"))
     a = ap.parse_args()
+    if a.corrupt:
+        return corrupt(a)
     if a.elastic:
         return elastic(a)
     if a.class_balanced:
