@@ -912,6 +912,30 @@ int mivp_intensity_stats(const float* x, int32_t B, int32_t C, const int32_t* di
 int mivp_intensity_apply(const float* x, int32_t B, int32_t C, const int32_t* dims, const int32_t* slot,
                          const void* workspace, size_t workspace_bytes, float* out, mivp_stream_t stream);
 
+/* Neighbourhood augmentation of a resident batch: Gaussian noise, Gaussian blur, low-resolution simulation
+ * (csrc/filters.hip; mivp_amd/augment.py).  These entry points joined ABI 18 without a bump: they are additive
+ * and no earlier signature changed.  x, dims, B as for mivp_intensity_apply.  slot: DEVICE int32
+ * [B][MIVP_FILTER_RECORD_WORDS], one record per sample (fp32 values as their bits): [0] flags (bit 0 noise, 1 smooth,
+ * 2 low-res), [1] noise key, [2] noise mean, [3] noise std, [4..6] radius of axis H, W, D (0..8; 0: the axis is not
+ * filtered), [7..9] the low-resolution grid (1..dims per axis), [10..60] taps [3][17], tap k = -r..r of axis a at
+ * 10 + 17 a + 8 + k (non-negative), [61..63] unused.  Per sample, in this order:
+ *   noise:   v = x + (mean + std * g), g = sqrt(-2 ln u1) cos(2 pi u2), u1 = ((h1 >> 8) + 1) 2^-24, u2 = (h2 >> 8) 2^-24,
+ *            h1 / h2 the counter hashes of 2 idx / 2 idx + 1 under the key, idx the element's index inside the sample.
+ *   smooth:  separable, D then W then H, out[i] = sum_k tap[k] in[i + k] with zeros outside the volume, summed from -r
+ *            upwards, every product and sum rounded to fp32 on its own.
+ *   low-res: torch's nearest down-sampling to the low grid and trilinear (align_corners = False) up-sampling back, per
+ *            output voxel from the eight corners; the low-resolution volume is never stored.
+ *   mivp_filter_ws(B, C, dims): bytes of the workspace (two batch-sized temporaries); 0 for a shape outside the contract.
+ *   mivp_filter_apply: three launches (D and W pass with the noise, H pass, low-res), always, whatever the records hold.  out
+ *     may be x.  A sample without flags -- or with a flag word, radius or low grid outside the ranges above -- is copied bit
+ *     for bit (in place: not written).  Results are bitwise reproducible.
+ * No host synchronisation and no host-side parameter other than the shape: the launches record into a graph and a replay
+ * uses whatever the slot holds then. */
+#define MIVP_FILTER_RECORD_WORDS 64
+size_t mivp_filter_ws(int32_t B, int32_t C, const int32_t* dims);
+int mivp_filter_apply(const float* x, int32_t B, int32_t C, const int32_t* dims, const int32_t* slot, void* workspace,
+                      size_t workspace_bytes, float* out, mivp_stream_t stream);
+
 /* Skipping all-background windows in whole-volume prediction (csrc/window_skip.hip; SlidingWindowPredictor(skip=...),
  * DESIGN 4.24).  These entry points joined the current ABI without a bump: they are additive and no earlier signature
  * changed.  dims / pad / pdims / roi as for mivp_window_gather (host int32 [3]).

@@ -44,7 +44,8 @@ def __getattr__(name):
     if name in ("scan_histogram", "window_slot", "IntensityWindow", "ScanHistogram", "WindowSlot", "ScanReport"):
         from . import scanstats
         return getattr(scanstats, name)
-    if name in ("IntensityDraws", "IntensitySlot", "draw_intensity", "augment_intensity"):
+    if name in ("IntensityDraws", "IntensitySlot", "draw_intensity", "augment_intensity", "FilterDraws", "FilterSlot",
+                "draw_filters", "augment_filters"):
         from . import augment
         return getattr(augment, name)
     raise AttributeError(name)

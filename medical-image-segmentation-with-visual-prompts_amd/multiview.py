@@ -325,13 +325,14 @@ def multiview_step(model, opt, sched, conf, x: torch.Tensor, draws: ViewDraws, s
                    augment=None):
     """One eager phase-1 step (multi_view.py:115-176): load the draws, forward / backward, ``opt.step()``, ``sched.step()``.
     Returns the loss vector [rec, rot, con, mut, total] on the device.  ``augment``: ``augment.IntensityDraws`` (or an
-    ``IntensitySlot`` with draws loaded): the random intensity chain runs on ``x`` before the views are built."""
+    ``IntensitySlot`` with draws loaded): the random intensity chain runs on ``x`` before the views are built; or
+    ``augment.FilterDraws`` / a ``FilterSlot`` (noise, blur, low resolution); or a list of these, applied in order."""
     check_shapes(tuple(x.shape[2:]), conf.masking_shape, bool(conf.use_mutual_learning))
     slot = slot if slot is not None else make_slot(conf, x)
     slot.load(draws)
     if augment is not None:
-        from .augment import as_slot, augment_intensity
-        x = augment_intensity(x, as_slot(augment, x))
+        from .augment import apply_slots, as_slots
+        x = apply_slots(x, as_slots(augment, x))
     vec = multiview_forward_backward(model, opt, conf, x, slot)
     opt.step()
     if sched is not None:
@@ -346,25 +347,27 @@ def graphed_multiview_step(model, opt, sched, conf, x: torch.Tensor, draws, warm
     vector [rec, rot, con, mut, total] of the last replay (read it after the replay); ``views`` holds the recorded view
     buffers.  ``augment``: ``augment.IntensityDraws`` used for every step, a callable returning the next step's, or an
     ``IntensitySlot`` the caller reloads; ``refresh`` loads the draws into the slot (``step.augment_slot``) and the two
-    intensity launches are recorded in front of the view builder (``x`` itself is left as it is)."""
+    intensity launches are recorded in front of the view builder (``x`` itself is left as it is).  The same three forms of
+    ``augment.FilterDraws`` / ``FilterSlot``, and a list mixing both kinds (applied in order; ``step.augment_slot`` is then
+    the list of slots), are taken as well."""
     from .train import GraphedStep
     check_shapes(tuple(x.shape[2:]), conf.masking_shape, bool(conf.use_mutual_learning))
     slot = make_slot(conf, x)
     views = {}
     aug = None
     if augment is not None:
-        from . import augment as A
-        aug = augment if isinstance(augment, A.IntensitySlot) else A.IntensitySlot(x.shape[0], x.device)
+        from .augment import AugmentChain
+        aug = AugmentChain(augment, x)
 
     def refresh():
         slot.load(draws() if callable(draws) else draws)
-        if aug is not None and aug is not augment:
-            aug.load(augment() if callable(augment) else augment)
+        if aug is not None:
+            aug.refresh()
 
     def forward_backward():
-        xa = x if aug is None else A.augment_intensity(x, aug)
+        xa = x if aug is None else aug.apply(x)
         return multiview_forward_backward(model, opt, conf, xa, slot, keep_views=views)
 
     step = GraphedStep(forward_backward, opt, sched, refresh, warmup)
-    step.slot, step.views, step.augment_slot = slot, views, aug
+    step.slot, step.views, step.augment_slot = slot, views, None if aug is None else aug.augment_slot
     return step

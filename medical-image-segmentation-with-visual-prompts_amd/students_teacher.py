@@ -82,12 +82,12 @@ def students_teacher_forward_backward(model: MomentumModel, optimizer, loss_prt:
     """students_teacher.py:150-205 up to (not including) the optimizer step: EMA teacher update, students + teacher forward,
     prototype loss (+ Dice on student 0 in the supervised modes with real labels), backward.  ``augment``: an
     ``augment.IntensitySlot`` with draws loaded: the random intensity chain runs on the teacher view (the reference augments
-    ``image``, not the ``image_st_i`` copies)."""
+    ``image``, not the ``image_st_i`` copies); or a ``FilterSlot``, or a list of slots of either kind, applied in order."""
     model.update_teacher()
     x_teacher = batch["image"]
     if augment is not None:
-        from .augment import augment_intensity
-        x_teacher = augment_intensity(x_teacher, augment)
+        from .augment import apply_slots
+        x_teacher = apply_slots(x_teacher, augment if isinstance(augment, (list, tuple)) else [augment])
     out_sts, out_tch = model(batch["image_st"], x_teacher)
     total = torch.zeros((), dtype=torch.float32, device=batch["image"].device)
     if getattr(conf, "use_prototype_assignment", True):
@@ -105,10 +105,11 @@ def students_teacher_step(model: MomentumModel, optimizer, scheduler, loss_prt: 
                           batch: dict, jitters=None, augment=None) -> torch.Tensor:
     """One iteration of students_teacher.py:150-207: EMA teacher update, students + teacher forward, prototype loss
     (+ Dice on student 0 in the supervised modes with real labels), backward, optimizer and per-step scheduler.
-    ``augment``: ``augment.IntensityDraws`` (or an ``IntensitySlot`` with draws loaded) for the teacher view."""
+    ``augment``: ``augment.IntensityDraws`` (or an ``IntensitySlot`` with draws loaded) for the teacher view; the filter
+    draws / slot (``augment.FilterDraws``, ``FilterSlot``) and a list of either kind, applied in order, as well."""
     if augment is not None:
-        from .augment import as_slot
-        augment = as_slot(augment, batch["image"])
+        from .augment import as_slots
+        augment = as_slots(augment, batch["image"])
     total = students_teacher_forward_backward(model, optimizer, loss_prt, conf, batch, jitters, augment)
     optimizer.step()
     if scheduler is not None:
@@ -125,7 +126,8 @@ def graphed_students_teacher_step(model: MomentumModel, optimizer, scheduler, lo
     fixed input tensors.  ``loss_prt`` must have been built with ``static_jitter=True``.  ``augment``:
     ``augment.IntensityDraws`` used for every step, a callable returning the next step's, or an ``IntensitySlot`` the caller
     reloads: the intensity chain on the teacher view, its slot (``step.augment_slot``) refreshed before every replay and its
-    two launches recorded in the graph (``batch["image"]`` itself is left as it is)."""
+    two launches recorded in the graph (``batch["image"]`` itself is left as it is).  The filter draws / slot and a list of
+    either kind are taken in the same three forms (``step.augment_slot`` is then the list of slots)."""
     from . import train
     if not loss_prt.static_jitter:
         raise ValueError("graph mode needs ClusteredPrototypeLoss(static_jitter=True)")
@@ -133,19 +135,20 @@ def graphed_students_teacher_step(model: MomentumModel, optimizer, scheduler, lo
     state = {"j": None}
     aug = None
     if augment is not None:
-        from .augment import IntensitySlot
-        aug = augment if isinstance(augment, IntensitySlot) else IntensitySlot(batch["image"].shape[0], batch["image"].device)
+        from .augment import AugmentChain
+        aug = AugmentChain(augment, batch["image"])
 
     def refresh():
         state["j"] = jitters() if jitters is not None else loss_prt.draw_jitters(n_st)
         if loss_prt._slots:                                    # (the first eager warm-up step creates and loads the slots itself)
             loss_prt.load_jitters(state["j"])
-        if aug is not None and aug is not augment:
-            aug.load(augment() if callable(augment) else augment)
+        if aug is not None:
+            aug.refresh()
 
     def forward_backward():
-        return students_teacher_forward_backward(model, optimizer, loss_prt, conf, batch, jitters=state["j"], augment=aug)
+        return students_teacher_forward_backward(model, optimizer, loss_prt, conf, batch, jitters=state["j"],
+                                                 augment=None if aug is None else aug.slots)
 
     step = train.GraphedStep(forward_backward, optimizer, scheduler, refresh, warmup)
-    step.augment_slot = aug
+    step.augment_slot = None if aug is None else aug.augment_slot
     return step
