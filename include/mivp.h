@@ -584,12 +584,36 @@ int mivp_adamw_multi(const void* tensors, const void* const* grads, int32_t n_te
  * bias corrections of its own step.  Bit-equal to mivp_adamw_multi for equal values. */
 int mivp_adamw_multi_dev(const void* tensors, const void* const* grads, int32_t n_tensors, const int32_t* chunk_begin,
                          const float* groups_dev, int32_t n_groups, const void* chunks, mivp_stream_t stream);
+/* Global gradient-norm clipping and non-finite step skipping for the AdamW step (mivp_amd/optim.py FusedAdamW(max_grad_norm,
+ * skip_nonfinite)): three launches, nothing read back.  These entry points joined ABI 18 without a bump: they
+ * are additive and no earlier signature changed.
+ * 1. Sum of squares: tensors, grads, n_tensors, chunk_begin and chunks as for mivp_adamw_multi (only n of a tensor record is
+ *    read); partials: device f32 [chunk_begin[n_tensors]], partials[c] = sum of g*g over chunk c in a fixed order (at most 12
+ *    f32 additions on any path), every slot written once per call by a plain store; elements at or beyond n are not read. */
+int mivp_grad_sumsq_multi(const void* tensors, const void* const* grads, int32_t n_tensors, const int32_t* chunk_begin,
+                          const void* chunks, float* partials, mivp_stream_t stream);
+/* 2. The plan, one workgroup: sumsq = the partials added in index order in f64, norm = sqrt(sumsq), coef = min(1, max_norm /
+ *    (norm + 1e-6)) in f64 (torch.nn.utils.clip_grad_norm_; a NaN norm gives a NaN coef), exactly 1 for max_norm = +infinity
+ *    (no clipping); max_norm > 0.  record: device, mivp_sizeof_opt(3) = 56 bytes, zeroed once by the caller:
+ *    {f64 sumsq, f32 norm, f32 coef, u32 nonfinite = !isfinite(sumsq), u32 apply = !(skip_nonfinite && nonfinite),
+ *     i64 steps, i64 clipped (apply && coef < 1), i64 skipped (!apply), f32 max_norm_seen (finite norms only), f32 pad};
+ *    the last four run on from call to call.  One lane writes the record. */
+int mivp_grad_clip_plan(const float* partials, int32_t n_partials, double max_norm, int32_t skip_nonfinite, void* record,
+                        mivp_stream_t stream);
+/* 3. mivp_adamw_multi / mivp_adamw_multi_dev under the record: nothing is touched when apply is 0; otherwise the gradient
+ *    used is g * coef rounded to f32 once, so the step is bit-equal to the plain entry on gradients multiplied by coef
+ *    beforehand (and to the plain entry itself for coef == 1). */
+int mivp_adamw_multi_clip(const void* tensors, const void* const* grads, int32_t n_tensors, const int32_t* chunk_begin,
+                          const float* groups, int32_t n_groups, const void* chunks, const void* record, mivp_stream_t stream);
+int mivp_adamw_multi_clip_dev(const void* tensors, const void* const* grads, int32_t n_tensors, const int32_t* chunk_begin,
+                              const float* groups_dev, int32_t n_groups, const void* chunks, const void* record,
+                              mivp_stream_t stream);
 /* n <= 64 floats from a HOST array into device memory as the arguments of a one-wave kernel (stream-ordered; refreshes the
  * scalars a recorded graph reads: the optimizer's groups_dev) */
 int mivp_store_floats(float* dst, const float* host_values, int32_t n, mivp_stream_t stream);
 /* EMA teacher update (momentum_model.py:27-36): tensors = device array of {float* teacher, const float* student, int64 n} */
 int mivp_ema_multi(const void* tensors, const void* chunks, int32_t n_chunks, float tau, mivp_stream_t stream);
-int mivp_sizeof_opt(int which);   /* 0: AdamW tensor record, 1: group record, 2: EMA record */
+int mivp_sizeof_opt(int which);   /* 0: AdamW tensor record, 1: group record, 2: EMA record, 3: gradient-norm record */
 /* sizeof of the descriptor structs as the LIBRARY was compiled (bindings compare them with their own layout):
  * 0 MivpSwinDesc, 1 MivpMergeDesc, 2 MivpConvDesc, 3 MivpEmbedDesc, 4 MivpUpcatDesc, 5 MivpOperandDesc, 6 MivpGemmTnDesc */
 int mivp_sizeof_desc(int which);

@@ -146,6 +146,21 @@ struct AdamGrads { const float* g[ADAM_GRADS_PER_LAUNCH]; };    // gradient poin
 
 constexpr int OPT_CHUNK = 1024;
 
+// What one step's gradient-norm plan decided (k_grad_clip_plan writes it, one lane, ordinary stores;
+// k_adamw_multi_clip and the host's views read it): 56 bytes, mivp_sizeof_opt(3).
+struct ClipRecord {
+    double sumsq;               //  0  sum of g*g over every gradient element of this step
+    float norm;                 //  8  (float)sqrt(sumsq)
+    float coef;                 // 12  min(1, max_norm / (norm + 1e-6)), exactly 1 for an infinite max_norm
+    unsigned nonfinite;         // 16  !isfinite(sumsq)
+    unsigned apply;             // 20  0: the update of this step is skipped (skipping on and a non-finite norm)
+    long long steps;            // 24  running: plans made,
+    long long clipped;          // 32           applied steps with coef < 1,
+    long long skipped;          // 40           steps with apply == 0
+    float max_norm_seen;        // 48           largest finite norm
+    float pad;
+};
+
 // DEV: the per-group hyper-parameters come from device memory (``groups_dev``: [8] AdamGroup) instead of the kernel
 // arguments, so that a launch recorded in a HIP graph sees the learning rate and bias corrections of the step it is
 // REPLAYED in (train.GraphedStep refreshes the buffer before every replay).
@@ -177,6 +192,39 @@ __global__ __launch_bounds__(256) void k_adamw_multi(const AdamTensor* __restric
     }
 }
 
+// k_adamw_multi under the plan of k_grad_clip_plan (a sibling, so that the plain kernel stays the code it was): no
+// workgroup touches p, m or v when rec->apply is 0; the gradient used is g * rec->coef rounded to f32 ONCE (the empty asm
+// keeps the product out of a contraction with the subtract that follows) and every line after it is the plain kernel's, so
+// a clipped step has the bits of the plain kernel on gradients multiplied by coef beforehand, and coef == 1 those of the
+// plain kernel on the same gradients.
+template <bool DEV>
+__global__ __launch_bounds__(256) void k_adamw_multi_clip(const AdamTensor* __restrict__ tensors, AdamGrads grads, int grad_base,
+                                                          AdamGroups groups, const AdamGroup* __restrict__ groups_dev,
+                                                          const int2* __restrict__ chunks, const ClipRecord* __restrict__ rec) {
+    if (rec->apply == 0u) return;
+    const float coef = rec->coef;
+    const int2 ck = chunks[blockIdx.x];
+    const AdamTensor t = tensors[ck.x];
+    const float* __restrict__ tg = grads.g[ck.x - grad_base];
+    const AdamGroup h = DEV ? groups_dev[t.group] : groups.g[t.group];
+    const long base = (long)ck.y * OPT_CHUNK;
+    const float step_size = h.lr / h.bc1;
+#pragma unroll
+    for (int u = 0; u < OPT_CHUNK / 256; ++u) {
+        const long i = base + threadIdx.x + 256 * u;
+        if (i >= t.n) break;
+        float g = __fmul_rn(tg[i], coef);
+        asm volatile("" : "+v"(g));
+        float p = t.p[i], m = t.m[i], v = t.v[i];
+        p = p * (1.f - h.lr * h.weight_decay);
+        m = m + (g - m) * (1.f - h.beta1);
+        v = v * h.beta2 + (g * g) * (1.f - h.beta2);
+        const float denom = sqrtf(v) / h.bc2_sqrt + h.eps;
+        p = p - step_size * (m / denom);
+        t.p[i] = p; t.m[i] = m; t.v[i] = v;
+    }
+}
+
 struct EmaTensor { float* teacher; const float* student; long n; };
 
 __global__ __launch_bounds__(256) void k_ema_multi(const EmaTensor* __restrict__ tensors, const int2* __restrict__ chunks, float tau) {
@@ -192,11 +240,91 @@ __global__ __launch_bounds__(256) void k_ema_multi(const EmaTensor* __restrict__
     }
 }
 
+// Sum of squares of every gradient, one workgroup per chunk of the AdamW chunk table, partials[chunk] written once per step
+// with a plain store (no atomics, nothing carried between steps).  The order is fixed: a thread adds its four products
+// in element order (3 additions), the wave adds across lanes by a butterfly (6), lane 0 of wave 0 adds the four wave sums
+// in wave order (3): SUMSQ_ADDS = 12 f32 additions on the longest path (tests/clip_ref.py holds the same number).  A
+// contracted multiply-add only removes a rounding.  Elements at or beyond n are not read.
+constexpr int SUMSQ_ADDS = 3 + 6 + 3;
+
+__global__ __launch_bounds__(256) void k_grad_sumsq_multi(const AdamTensor* __restrict__ tensors, AdamGrads grads, int grad_base,
+                                                          const int2* __restrict__ chunks, float* __restrict__ partials) {
+    __shared__ float wave_sum[4];
+    const int2 ck = chunks[blockIdx.x];
+    const long n = tensors[ck.x].n;
+    const float* __restrict__ tg = grads.g[ck.x - grad_base];
+    const long base = (long)ck.y * OPT_CHUNK;
+    float s = 0.f;
+#pragma unroll
+    for (int u = 0; u < OPT_CHUNK / 256; ++u) {
+        const long i = base + threadIdx.x + 256 * u;
+        const float g = i < n ? tg[i] : 0.f;
+        s = u == 0 ? g * g : s + g * g;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+}
+
+// The plan of one step, one workgroup: the partials are staged through LDS by all 256 threads (the next tile's loads are in
+// flight while the current one is added) and added by ONE lane in index order in f64; the same lane forms norm and coef in
+// f64 (torch.nn.utils.clip_grad_norm_'s formula), updates the running values and writes the record.
+constexpr int PLAN_TILE = 4096;
+
+__global__ __launch_bounds__(256) void k_grad_clip_plan(const float* __restrict__ partials, int n, double max_norm, int skip_nonfinite,
+                                                        ClipRecord* __restrict__ rec) {
+    __shared__ float tile[PLAN_TILE];
+    float r[PLAN_TILE / 256];
+    double sumsq = 0.0;
+#pragma unroll
+    for (int k = 0; k < PLAN_TILE / 256; ++k) {
+        const int i = (int)threadIdx.x + 256 * k;
+        r[k] = i < n ? partials[i] : 0.f;
+    }
+    for (int t0 = 0; t0 < n; t0 += PLAN_TILE) {
+#pragma unroll
+        for (int k = 0; k < PLAN_TILE / 256; ++k) tile[threadIdx.x + 256 * k] = r[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < PLAN_TILE / 256; ++k) {
+            const long i = (long)t0 + PLAN_TILE + threadIdx.x + 256 * k;
+            r[k] = i < n ? partials[i] : 0.f;
+        }
+        if (threadIdx.x == 0) {
+            const int cnt = n - t0 < PLAN_TILE ? n - t0 : PLAN_TILE;
+            for (int j = 0; j < cnt; ++j) sumsq += (double)tile[j];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const bool finite = isfinite(sumsq);
+    const double norm = sqrt(sumsq);
+    double coef = 1.0;
+    if (!isinf(max_norm)) {
+        const double c = max_norm / (norm + 1e-6);
+        coef = c < 1.0 ? c : (c != c ? c : 1.0);                  // clamp(max = 1) that keeps a NaN, as torch's does
+    }
+    const unsigned apply = (skip_nonfinite && !finite) ? 0u : 1u;
+    const float normf = (float)norm, coeff = (float)coef;
+    const float seen = rec->max_norm_seen;
+    rec->sumsq = sumsq;
+    rec->norm = normf;
+    rec->coef = coeff;
+    rec->nonfinite = finite ? 0u : 1u;
+    rec->apply = apply;
+    rec->steps += 1;
+    rec->clipped += (apply && coeff < 1.f) ? 1 : 0;
+    rec->skipped += apply ? 0 : 1;
+    rec->max_norm_seen = (finite && normf > seen) ? normf : seen;
+}
+
 }  // namespace
 
 static int adamw_launch(const void* tensors, const void* const* grads, int32_t n_tensors, const int32_t* chunk_begin,
                         const float* groups_host, const float* groups_dev, int32_t n_groups, const void* chunks,
-                        mivp_stream_t stream) {
+                        mivp_stream_t stream, const void* record = nullptr) {
     AdamGroups gs;
     for (int i = 0; i < 8; ++i) {
         const float* src = groups_host ? groups_host + 8 * (i < n_groups ? i : 0) : nullptr;
@@ -209,7 +337,15 @@ static int adamw_launch(const void* tensors, const void* const* grads, int32_t n
         for (int i = 0; i < ADAM_GRADS_PER_LAUNCH; ++i) gp.g[i] = (const float*)grads[base + (i < cnt ? i : 0)];
         const int c0 = chunk_begin[base], c1 = chunk_begin[base + cnt];
         if (c1 <= c0) continue;
-        if (groups_dev)
+        const dim3 grid((unsigned)(c1 - c0));
+        const hipStream_t st = (hipStream_t)stream;
+        if (record && groups_dev)
+            hipLaunchKernelGGL(k_adamw_multi_clip<true>, grid, dim3(256), 0, st, (const AdamTensor*)tensors, gp, base, gs,
+                               (const AdamGroup*)groups_dev, (const int2*)chunks + c0, (const ClipRecord*)record);
+        else if (record)
+            hipLaunchKernelGGL(k_adamw_multi_clip<false>, grid, dim3(256), 0, st, (const AdamTensor*)tensors, gp, base, gs,
+                               (const AdamGroup*)nullptr, (const int2*)chunks + c0, (const ClipRecord*)record);
+        else if (groups_dev)
             hipLaunchKernelGGL(k_adamw_multi<true>, dim3((unsigned)(c1 - c0)), dim3(256), 0, (hipStream_t)stream,
                                (const AdamTensor*)tensors, gp, base, gs, (const AdamGroup*)groups_dev, (const int2*)chunks + c0);
         else
@@ -229,6 +365,45 @@ extern "C" int mivp_adamw_multi_dev(const void* tensors, const void* const* grad
                                     const float* groups_dev, int32_t n_groups, const void* chunks, mivp_stream_t stream) {
     MIVP_REQUIRE(tensors && grads && groups_dev && chunks && chunk_begin && n_tensors > 0 && n_groups >= 1 && n_groups <= 8);
     return adamw_launch(tensors, grads, n_tensors, chunk_begin, nullptr, groups_dev, n_groups, chunks, stream);
+}
+
+extern "C" int mivp_grad_sumsq_multi(const void* tensors, const void* const* grads, int32_t n_tensors, const int32_t* chunk_begin,
+                                     const void* chunks, float* partials, mivp_stream_t stream) {
+    MIVP_REQUIRE(tensors && grads && chunks && chunk_begin && partials && n_tensors > 0);
+    for (int base = 0; base < n_tensors; base += ADAM_GRADS_PER_LAUNCH) {
+        const int cnt = n_tensors - base < ADAM_GRADS_PER_LAUNCH ? n_tensors - base : ADAM_GRADS_PER_LAUNCH;
+        AdamGrads gp;
+        for (int i = 0; i < ADAM_GRADS_PER_LAUNCH; ++i) gp.g[i] = (const float*)grads[base + (i < cnt ? i : 0)];
+        const int c0 = chunk_begin[base], c1 = chunk_begin[base + cnt];
+        MIVP_REQUIRE(c0 >= 0 && c1 >= c0);
+        if (c1 == c0) continue;
+        hipLaunchKernelGGL(k_grad_sumsq_multi, dim3((unsigned)(c1 - c0)), dim3(256), 0, (hipStream_t)stream,
+                           (const AdamTensor*)tensors, gp, base, (const int2*)chunks + c0, partials + c0);
+    }
+    return mivp_check_launch("grad_sumsq_multi");
+}
+
+extern "C" int mivp_grad_clip_plan(const float* partials, int32_t n_partials, double max_norm, int32_t skip_nonfinite, void* record,
+                                   mivp_stream_t stream) {
+    MIVP_REQUIRE(partials && record && n_partials > 0);
+    MIVP_REQUIRE(max_norm > 0.0);                                // a NaN fails this too; +infinity: no clipping
+    hipLaunchKernelGGL(k_grad_clip_plan, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (int)n_partials, max_norm,
+                       (int)(skip_nonfinite != 0), (ClipRecord*)record);
+    return mivp_check_launch("grad_clip_plan");
+}
+
+extern "C" int mivp_adamw_multi_clip(const void* tensors, const void* const* grads, int32_t n_tensors, const int32_t* chunk_begin,
+                                     const float* groups, int32_t n_groups, const void* chunks, const void* record,
+                                     mivp_stream_t stream) {
+    MIVP_REQUIRE(tensors && grads && groups && chunks && chunk_begin && record && n_tensors > 0 && n_groups >= 1 && n_groups <= 8);
+    return adamw_launch(tensors, grads, n_tensors, chunk_begin, groups, nullptr, n_groups, chunks, stream, record);
+}
+
+extern "C" int mivp_adamw_multi_clip_dev(const void* tensors, const void* const* grads, int32_t n_tensors,
+                                         const int32_t* chunk_begin, const float* groups_dev, int32_t n_groups, const void* chunks,
+                                         const void* record, mivp_stream_t stream) {
+    MIVP_REQUIRE(tensors && grads && groups_dev && chunks && chunk_begin && record && n_tensors > 0 && n_groups >= 1 && n_groups <= 8);
+    return adamw_launch(tensors, grads, n_tensors, chunk_begin, nullptr, groups_dev, n_groups, chunks, stream, record);
 }
 
 // up to 64 floats from the HOST into device memory as kernel arguments of a one-wave launch: stream-ordered, no pinned
@@ -255,4 +430,4 @@ extern "C" int mivp_ema_multi(const void* tensors, const void* chunks, int32_t n
     return mivp_check_launch("ema_multi");
 }
 
-extern "C" int mivp_sizeof_opt(int which) { return which == 0 ? (int)sizeof(AdamTensor) : which == 1 ? (int)sizeof(AdamGroup) : which == 2 ? (int)sizeof(EmaTensor) : -1; }
+extern "C" int mivp_sizeof_opt(int which) { return which == 0 ? (int)sizeof(AdamTensor) : which == 1 ? (int)sizeof(AdamGroup) : which == 2 ? (int)sizeof(EmaTensor) : which == 3 ? (int)sizeof(ClipRecord) : -1; }

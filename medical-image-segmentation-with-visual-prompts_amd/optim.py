@@ -2,7 +2,8 @@
 
 * ``FusedAdamW``            -- ``torch.optim.AdamW`` semantics (decoupled weight decay, bias correction, per-group lr / weight
   decay: students_teacher.py:27-68, segmentation.py:25-39) with ONE kernel launch per step for all parameter tensors
-  (csrc/proto.hip ``k_adamw_multi``).  It is a ``torch.optim.Optimizer``: ``param_groups`` / ``state_dict`` have AdamW's
+  (csrc/proto.hip ``k_adamw_multi``), or three with global gradient-norm clipping / non-finite step skipping
+  (``max_grad_norm``, ``skip_nonfinite``: DESIGN 4.32).  It is a ``torch.optim.Optimizer``: ``param_groups`` / ``state_dict`` have AdamW's
   layout (``step``, ``exp_avg``, ``exp_avg_sq`` per parameter), so LR schedulers and the reference's checkpoint dicts
   (``optimizer_state_dict``) interoperate with ``torch.optim.AdamW``.
 * ``WarmupCosineSchedule``  -- modules/utils.py:67-89 (a ``LambdaLR``).
@@ -39,9 +40,29 @@ class FusedAdamW(torch.optim.Optimizer):
     """``capturable=True``: the launch reads lr / weight decay / bias corrections from a device buffer that ``step()``
     refreshes with one tiny stream-ordered launch (``mivp_store_floats``) -- the form ``train.GraphedStep`` records.  While
     the stream is being captured ``step()`` only records the update launch; every replay is preceded by ``advance()``,
-    which does the host side of a step (step counts, this step's hyper-parameters into the device buffer)."""
+    which does the host side of a step (step counts, this step's hyper-parameters into the device buffer).
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False):
+    ``max_grad_norm`` (a positive finite float) clips the global L2 norm of all gradients of the step as
+    ``torch.nn.utils.clip_grad_norm_`` does -- coef = min(1, max_grad_norm / (norm + 1e-6)) -- without rewriting a
+    gradient: one launch sums the squares per 1024-element chunk, one workgroup adds the chunk sums in f64 and writes a
+    small device record, and the update launch multiplies each gradient by the record's coef as it reads it.
+    ``skip_nonfinite=True`` makes the update launch leave every p / exp_avg / exp_avg_sq untouched when the norm is not
+    finite (a NaN or an infinity anywhere in the gradients, or a chunk whose sum of squares overflows f32).  Both are
+    attributes of the optimizer, not keys of ``param_groups``: ``state_dict()`` keeps ``torch.optim.AdamW``'s layout.  With
+    both at their defaults ``step()`` issues exactly the one launch it always did.
+
+    * Nothing is read back.  ``grad_norm`` and ``clip_coef`` are 0-dim device views of the record, valid after ``step()`` or
+      a replay; ``clip_stats()`` does the one explicit ``.cpu()``.
+    * A skipped step still consumes a step number on the host (the host cannot know a step was skipped without a read), so
+      the bias corrections of the next step are those of t + 1.
+    * With ``max_grad_norm`` set and ``skip_nonfinite=False`` a non-finite norm gives a NaN (or zero) coef and the update
+      poisons the parameters, as ``clip_grad_norm_(error_if_nonfinite=False)`` followed by a step does: use
+      ``skip_nonfinite=True`` with it.
+    * ``max_grad_norm`` and ``skip_nonfinite`` are kernel arguments, so a recorded graph holds the values of its recording:
+      changing them needs a new recording, and assigning either after a step was recorded raises."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False,
+                 max_grad_norm=None, skip_nonfinite=False):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         if len(self.param_groups) > 8:
@@ -51,6 +72,62 @@ class FusedAdamW(torch.optim.Optimizer):
         self.capturable = bool(capturable)
         self._hyper_dev = None
         self._graph_params = None  # the parameters that had gradients when a graph was recorded (they step on every replay)
+        self._clip_rec = None     # the device record of the gradient-norm plan (7 int64 = mivp_sizeof_opt(3) bytes), made once
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        if value is not None:
+            if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value <= 0:
+                raise ValueError(f"FusedAdamW: max_grad_norm must be a positive finite number or None, got {value!r}")
+            value = float(value)
+        self._refuse_after_recording("max_grad_norm")
+        self._max_grad_norm = value
+        self._plan = None         # the partials buffer belongs to the plan
+
+    @property
+    def skip_nonfinite(self):
+        return self._skip_nonfinite
+
+    @skip_nonfinite.setter
+    def skip_nonfinite(self, value):
+        if not isinstance(value, bool):
+            raise ValueError(f"FusedAdamW: skip_nonfinite must be a bool, got {value!r}")
+        self._refuse_after_recording("skip_nonfinite")
+        self._skip_nonfinite = value
+        self._plan = None
+
+    def _refuse_after_recording(self, name):
+        if self._graph_params is not None:
+            raise RuntimeError(f"FusedAdamW: {name} is a kernel argument of the recorded step; build a new optimizer and record "
+                               "again to change it")
+
+    def _record(self):
+        if self._clip_rec is None:
+            raise RuntimeError("FusedAdamW: the gradient norm exists after the first step() with max_grad_norm or skip_nonfinite")
+        return self._clip_rec
+
+    @property
+    def grad_norm(self):
+        """Global L2 norm of the last step's gradients before clipping: a 0-dim f32 device view, no host read."""
+        return self._record().view(torch.float32)[2]
+
+    @property
+    def clip_coef(self):
+        """The factor the last step's gradients were multiplied by: a 0-dim f32 device view, no host read."""
+        return self._record().view(torch.float32)[3]
+
+    def clip_stats(self):
+        """One explicit device-to-host copy of the record: steps seen, steps clipped (applied with coef < 1), steps skipped,
+        the last norm and the largest finite norm seen."""
+        raw = self._record().cpu().numpy()
+        f = raw.view(np.float32)
+        return dict(steps=int(raw[3]), clipped=int(raw[4]), skipped=int(raw[5]), last_norm=float(f[2]), max_norm_seen=float(f[12]))
 
     def state_dict(self):
         for group in self.param_groups:
@@ -77,6 +154,13 @@ class FusedAdamW(torch.optim.Optimizer):
             "key": tuple((id(p), p.data_ptr(), st["exp_avg"].data_ptr()) for _, p, st in entries),
             "tensors": torch.from_numpy(rows).to(dev), "chunks": chunks, "begin": begin,
         }
+        if self._max_grad_norm is not None or self._skip_nonfinite:
+            # one f32 per chunk, each written once per step; the record outlives a rebuilt plan (its counters run on)
+            if int(L.lib().mivp_sizeof_opt(3)) != 56:
+                raise RuntimeError("ClipRecord layout mismatch")
+            self._plan["partials"] = torch.empty(chunks.shape[0], dtype=torch.float32, device=dev)
+            if self._clip_rec is None or self._clip_rec.device != dev:
+                self._clip_rec = torch.zeros(7, dtype=torch.int64, device=dev)
 
     def _hyper(self, stepping):
         """Advance the step counts of ``stepping`` (ids of the parameters that step now) and return this step's
@@ -174,9 +258,23 @@ class FusedAdamW(torch.optim.Optimizer):
         # the gradient tensors are new every backward (zero_grad(set_to_none=True)): their pointers go to the kernel as
         # arguments (a host array here) -- an upload per step would be a synchronous pageable copy that stalls the launch queue
         gptr = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-        if self.capturable:
-            if hyper is not None:
-                self._upload(hyper, entries[0][1].device)
+        if self.capturable and hyper is not None:
+            self._upload(hyper, entries[0][1].device)
+        if "partials" in plan:
+            begin = plan["begin"].ctypes.data_as(C.POINTER(C.c_int32))
+            L.call("mivp_grad_sumsq_multi", L.ptr(plan["tensors"]), gptr, len(grads), begin, L.ptr(plan["chunks"]),
+                   L.ptr(plan["partials"]), L.stream())
+            L.call("mivp_grad_clip_plan", L.ptr(plan["partials"]), plan["partials"].numel(),
+                   math.inf if self._max_grad_norm is None else self._max_grad_norm, int(self._skip_nonfinite),
+                   L.ptr(self._clip_rec), L.stream())
+            if self.capturable:
+                L.call("mivp_adamw_multi_clip_dev", L.ptr(plan["tensors"]), gptr, len(grads), begin, L.ptr(self._hyper_dev),
+                       len(self.param_groups), L.ptr(plan["chunks"]), L.ptr(self._clip_rec), L.stream())
+            else:
+                L.call("mivp_adamw_multi_clip", L.ptr(plan["tensors"]), gptr, len(grads), begin,
+                       hyper.ctypes.data_as(C.POINTER(C.c_float)), len(self.param_groups), L.ptr(plan["chunks"]),
+                       L.ptr(self._clip_rec), L.stream())
+        elif self.capturable:
             L.call("mivp_adamw_multi_dev", L.ptr(plan["tensors"]), gptr, len(grads),
                    plan["begin"].ctypes.data_as(C.POINTER(C.c_int32)), L.ptr(self._hyper_dev), len(self.param_groups),
                    L.ptr(plan["chunks"]), L.stream())

@@ -143,11 +143,16 @@ def dice_focal_loss(logits: torch.Tensor, target: torch.Tensor, include_backgrou
     return dice + focal
 
 
-def build_optimizer(model, conf: Namespace, capturable: bool = False):
+def build_optimizer(model, conf: Namespace, capturable: bool = False, max_grad_norm=None, skip_nonfinite: bool = False):
     """AdamW over the reference's parameter partition for the mode: ``named_parameters_downstream()`` for
     ``downstream`` (segmentation.py:25-39); decoder(+encoder) and prompt-token groups with their own lr /
-    weight decay for the ``*_all`` / ``*_decoder`` modes (students_teacher.py:25-68)."""
+    weight decay for the ``*_all`` / ``*_decoder`` modes (students_teacher.py:25-68).  ``max_grad_norm`` (default:
+    ``conf.max_grad_norm`` where the configuration has one; the reference's yml has none) and ``skip_nonfinite`` go to
+    ``FusedAdamW``: global gradient-norm clipping and non-finite step skipping inside the optimizer's own launches."""
     from .optim import FusedAdamW
+    if max_grad_norm is None:
+        max_grad_norm = getattr(conf, "max_grad_norm", None)
+    clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     core = model.module if hasattr(model, "module") else model
     core = core.net_student if hasattr(core, "net_student") else core      # MomentumModel: the student trains
     mode = conf.training_mode
@@ -159,10 +164,11 @@ def build_optimizer(model, conf: Namespace, capturable: bool = False):
         if conf.use_encoder_prompting:
             groups.append({"params": [p for _, p in core.named_parameters_prompt_tokens_encoder()],
                            "lr": float(conf.lr_prompt_tokens), "weight_decay": float(conf.weight_decay_prompt_tokens)})
-        return FusedAdamW(groups, lr=lr, weight_decay=wd, capturable=capturable)
+        return FusedAdamW(groups, lr=lr, weight_decay=wd, capturable=capturable, **clip)
     if mode == "downstream":
         params = [p for _, p in core.named_parameters_downstream()]
-        return FusedAdamW(params, lr=float(conf.lr_downstream), weight_decay=float(conf.weight_decay_downstream), capturable=capturable)
+        return FusedAdamW(params, lr=float(conf.lr_downstream), weight_decay=float(conf.weight_decay_downstream), capturable=capturable,
+                          **clip)
     lr, wd = float(conf.lr_students_teacher), float(conf.weight_decay_students_teacher)
     groups = []
     if mode in ("self_supervised_learning_all", "supervised_learning_all"):
@@ -178,7 +184,7 @@ def build_optimizer(model, conf: Namespace, capturable: bool = False):
     if conf.use_decoder_prompting:
         groups.append({"params": [p for _, p in core.named_parameters_prompt_tokens_decoder()],
                        "lr": float(conf.lr_prompt_tokens), "weight_decay": float(conf.weight_decay_prompt_tokens)})
-    return FusedAdamW(groups, lr=lr, weight_decay=wd, capturable=capturable)
+    return FusedAdamW(groups, lr=lr, weight_decay=wd, capturable=capturable, **clip)
 
 
 def build_scheduler(opt, conf: Namespace):
