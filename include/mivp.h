@@ -445,6 +445,36 @@ int mivp_dice_focal_grad(const float* logits, const float* target, int32_t B, in
                          int32_t include_background, float gamma, float* workspace, const float* gscale, float* dlogits,
                          mivp_stream_t stream);
 
+/* Tversky region term + weighted (focal) softmax cross-entropy with an ignore label (csrc/segloss.hip; mivp_amd/losses.py
+ * SegLossSpec / seg_loss / SegLoss).  These entry points joined ABI 18 without a bump: they are additive and
+ * no earlier signature changed.  Operands as for mivp_dice_focal: logits f32 [B, vol, C] channels-last (2 <= C <= 8),
+ * target f32 [B, vol] class indices.  A voxel is VALID when its label is an integer in [0, C) and, with has_ignore != 0,
+ * differs from ignore_index (compared as a float: exact for |ignore_index| < 2^24; has_ignore == 0: ignore_index is not
+ * read).  An invalid voxel (ignored, non-integer, out of range, NaN) adds to no sum, gets an exactly zero gradient and
+ * never selects a class weight.  With p = softmax_c(z), t = one-hot(label), sums over the valid voxels of a sample (of the
+ * whole batch when batch != 0) and s = 1e-5:
+ *   TI_c   = (2 I_c + s) / (2 I_c + 2 alpha (P_c - I_c) + 2 beta (T_c - I_c) + s),  I = sum p t, P = sum p, T = sum t
+ *   region = mean over (b, c >= c0) [over c >= c0 when batch] of (1 - TI_c),        c0 = include_background ? 0 : 1
+ *   voxel  = - sum_v w[y_v] (1 - p_y)^focal_gamma log p_y / sum_v w[y_v]   over the valid voxels of the whole batch, exactly 0
+ *            (and a zero gradient) when sum_v w[y_v] == 0
+ *   loss[0] = lambda_region region + lambda_voxel voxel
+ * alpha, beta >= 0; focal_gamma == 0 or >= 1; lambda_region, lambda_voxel >= 0, not both 0; class_weights: DEVICE pointer
+ * to C floats >= 0, NULL = all ones (the values are not read back to be checked).
+ * workspace: mivp_seg_loss_ws(B, vol) floats = partial rows [B][bpb][26], the samples' rows [B][26], the batch-wide row [26]
+ * (row: (I, P, T) x 8 classes, voxel numerator, voxel weight sum).  dlogits may be NULL: the value pass alone;
+ * mivp_seg_loss_grad then runs the gradient pass on the SAME workspace with the SAME options, scaled by gscale[0] (device
+ * pointer, NULL = 1); it writes every element of dlogits once.  No atomics: equal calls give equal bits. */
+size_t mivp_seg_loss_ws(int32_t B, int64_t vol);
+int mivp_seg_loss(const float* logits, const float* target, int32_t B, int64_t vol, int32_t C,
+                  int32_t include_background, int32_t batch, float alpha, float beta, float focal_gamma,
+                  const float* class_weights, int32_t ignore_index, int32_t has_ignore, float lambda_region,
+                  float lambda_voxel, float* workspace, float* loss, float* dlogits, mivp_stream_t stream);
+int mivp_seg_loss_grad(const float* logits, const float* target, int32_t B, int64_t vol, int32_t C,
+                       int32_t include_background, int32_t batch, float alpha, float beta, float focal_gamma,
+                       const float* class_weights, int32_t ignore_index, int32_t has_ignore, float lambda_region,
+                       float lambda_voxel, float* workspace, const float* gscale, float* dlogits,
+                       mivp_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* downstream head on the LOW-resolution decoder output                      */
 /* (swin_unetr.py:351-355 nn.Upsample x2 trilinear, then :229-237 BatchNorm3d */

@@ -69,6 +69,20 @@ def check_finite(name: str, v) -> float:
     return float(v)
 
 
+def check_at_least(name: str, v, lo: float) -> float:
+    """A ``check_finite`` number >= ``lo``."""
+    if check_finite(name, v) < lo:
+        raise ValueError(f"{name} must be >= {lo:g}, got {v!r}")
+    return float(v)
+
+
+def check_flag(name: str, v) -> bool:
+    """A bool (numpy bools included), nothing that merely converts to one."""
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"{name} must be a bool, got {v!r}")
+    return bool(v)
+
+
 def check_int_from(name: str, v, lo: int) -> int:
     """A ``plain_int`` in ``lo .. 2^31 - 1``."""
     if not plain_int(v) or int(v) < lo or int(v) >= 2 ** 31:

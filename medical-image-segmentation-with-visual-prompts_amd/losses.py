@@ -9,6 +9,8 @@
 * ``dice_loss``               -- MONAI ``DiceLoss(include_background, to_onehot_y=True, softmax=True)`` as documented
   (students_teacher.py:96-100); the Dice-focal kernels without the focal term; MONAI is absent from the image: parity
   unpinned, restated in oracle/loss_ref.py::dice_loss.
+* ``SegLossSpec`` / ``seg_loss`` / ``SegLoss`` -- Tversky region term + weighted (focal) softmax cross-entropy with an
+  ignore label (csrc/segloss.hip): not in the reference; ``train.step_loss`` uses it when ``conf.seg_loss`` is set.
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from ._host import ImmutableValue, check_at_least, check_flag, plain_int
 
 
 def reduced_size(dims: Sequence[int], reduction_factor: float) -> List[int]:
@@ -274,3 +277,197 @@ def dice_loss(logits: torch.Tensor, target: torch.Tensor, include_background: bo
         base = base.float().contiguous()                    # (the HIP model's logits already are channels-last f32 storage)
     tgt = target.to(torch.float32).contiguous()
     return _DiceFocalFn.apply(base, tgt, include_background, -1.0)
+
+
+# ---------------------------------------------------------------------------------------------
+# Tversky region term + weighted (focal) softmax cross-entropy with an ignore label (csrc/segloss.hip)
+# ---------------------------------------------------------------------------------------------
+SEG_LOSS_MAX_CLASSES = 8
+SEG_LOSS_SMOOTH = 1e-5
+
+
+class SegLossSpec(ImmutableValue):
+    """Options of ``seg_loss`` (an immutable value; the formulas are in the docstring of ``seg_loss``).
+
+    ``alpha``, ``beta`` >= 0: the Tversky weights of false positives / false negatives (0.5, 0.5: the project's Dice);
+    ``batch``: region sums over the whole batch instead of per sample; ``include_background``: class 0 in the region term;
+    ``focal_gamma``: 0 (plain cross-entropy) or >= 1 (an exponent in (0, 1) has an unbounded gradient at p -> 1);
+    ``class_weights``: one weight >= 0 per class, or None (all ones); ``ignore_index``: the label of voxels that take no part,
+    or None; ``lambda_region``, ``lambda_voxel`` >= 0, not both 0."""
+
+    __slots__ = ("alpha", "beta", "batch", "include_background", "focal_gamma", "class_weights", "ignore_index",
+                 "lambda_region", "lambda_voxel")
+
+    def __init__(self, alpha: float = 0.5, beta: float = 0.5, batch: bool = False, include_background: bool = True,
+                 focal_gamma: float = 0.0, class_weights: Optional[Sequence[float]] = None,
+                 ignore_index: Optional[int] = None, lambda_region: float = 1.0, lambda_voxel: float = 1.0):
+        f32_max = float(np.finfo(np.float32).max)
+        for name, v in (("alpha", alpha), ("beta", beta), ("lambda_region", lambda_region), ("lambda_voxel", lambda_voxel)):
+            if check_at_least(name, v, 0.0) > f32_max:
+                raise ValueError(f"{name} must be finite in fp32, got {v!r}")
+        gamma = check_at_least("focal_gamma", focal_gamma, 0.0)
+        if 0.0 < gamma < 1.0 or gamma > f32_max:
+            raise ValueError(f"focal_gamma must be 0 or >= 1 (its gradient is unbounded at p -> 1 in between), got {focal_gamma!r}")
+        if float(lambda_region) == 0.0 and float(lambda_voxel) == 0.0:
+            raise ValueError("lambda_region and lambda_voxel must not both be 0")
+        if class_weights is not None:
+            if isinstance(class_weights, torch.Tensor):
+                class_weights = class_weights.detach().cpu().tolist()
+            class_weights = tuple(class_weights)
+            if not 2 <= len(class_weights) <= SEG_LOSS_MAX_CLASSES:
+                raise ValueError(f"class_weights must hold 2..{SEG_LOSS_MAX_CLASSES} weights, got {len(class_weights)}")
+            class_weights = tuple(check_at_least(f"class_weights[{i}]", w, 0.0) for i, w in enumerate(class_weights))
+        if ignore_index is not None:
+            # the kernel compares the f32 label with float(ignore_index): exact up to 2^24
+            if not plain_int(ignore_index) or abs(int(ignore_index)) > 2 ** 24:
+                raise ValueError(f"ignore_index must be None or an int with |ignore_index| <= 2^24, got {ignore_index!r}")
+            ignore_index = int(ignore_index)
+        self._set(alpha=float(alpha), beta=float(beta), batch=check_flag("batch", batch),
+                  include_background=check_flag("include_background", include_background), focal_gamma=gamma,
+                  class_weights=class_weights, ignore_index=ignore_index, lambda_region=float(lambda_region),
+                  lambda_voxel=float(lambda_voxel))
+
+
+def _seg_loss_torch(z: torch.Tensor, y: torch.Tensor, spec: SegLossSpec, w: Optional[torch.Tensor]) -> torch.Tensor:
+    """The formulas of ``seg_loss`` in plain torch ops, differentiable by autograd: z [B, vol, C], y [B, vol] labels."""
+    B, _, Cc = z.shape
+    y = y.to(z.dtype if z.dtype in (torch.float32, torch.float64) else torch.float32)
+    valid = (y >= 0) & (y < Cc) & (y == y.floor())
+    if spec.ignore_index is not None:
+        valid = valid & (y != spec.ignore_index)
+    idx = torch.where(valid, y, torch.zeros_like(y)).long()
+    m = valid.to(z.dtype).unsqueeze(-1)
+    hot = F.one_hot(idx, Cc).to(z.dtype)
+    logp = F.log_softmax(z, dim=-1)
+    p = logp.exp()
+    t, pm = hot * m, p * m
+    dims = (0, 1) if spec.batch else (1,)
+    c0 = 0 if spec.include_background else 1
+    inter, psum, tsum = (pm * t).sum(dims)[..., c0:], pm.sum(dims)[..., c0:], t.sum(dims)[..., c0:]
+    s = SEG_LOSS_SMOOTH
+    tversky = (2.0 * inter + s) / (2.0 * inter + 2.0 * spec.alpha * (psum - inter) + 2.0 * spec.beta * (tsum - inter) + s)
+    loss = spec.lambda_region * (1.0 - tversky).mean()
+    if spec.lambda_voxel > 0.0:
+        wt = torch.ones(Cc, dtype=z.dtype, device=z.device) if w is None else w.to(z.dtype)
+        wy = wt[idx] * m[..., 0]
+        f = -(logp * hot).sum(-1)
+        if spec.focal_gamma > 0.0:
+            f = f * (p * (1.0 - hot)).sum(-1) ** spec.focal_gamma             # 1 - p_y as the sum of the other classes
+        wsum = wy.sum()
+        loss = loss + spec.lambda_voxel * ((wy * f).sum() / torch.where(wsum > 0, wsum, torch.ones_like(wsum)))
+    return loss
+
+
+class _SegLossFn(torch.autograd.Function):
+    """Like ``train._DiceFocalFn``: the value from one streaming pass + a one-workgroup reduction; the gradient from a second
+    streaming pass when backward asks for it, already multiplied by the incoming gradient (csrc/segloss.hip)."""
+
+    @staticmethod
+    def forward(ctx, logits_cl, target, weights, spec):
+        B, H, W, D, Cc = logits_cl.shape
+        vol = H * W * D
+        ws = torch.empty(L.lib().mivp_seg_loss_ws(B, vol), dtype=torch.float32, device=logits_cl.device)
+        loss = torch.empty(1, dtype=torch.float32, device=logits_cl.device)
+        ig = spec.ignore_index
+        L.call("mivp_seg_loss", L.ptr(logits_cl), L.ptr(target), B, vol, Cc, 1 if spec.include_background else 0,
+               1 if spec.batch else 0, spec.alpha, spec.beta, spec.focal_gamma, L.ptr(weights), 0 if ig is None else ig,
+               0 if ig is None else 1, spec.lambda_region, spec.lambda_voxel, L.ptr(ws), L.ptr(loss), L.ptr(None), L.stream())
+        ctx.save_for_backward(logits_cl, target, ws)
+        ctx.weights, ctx.spec = weights, spec
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits_cl, target, ws = ctx.saved_tensors
+        spec, ig = ctx.spec, ctx.spec.ignore_index
+        B, H, W, D, Cc = logits_cl.shape
+        g = g.detach().to(torch.float32).contiguous()
+        dz = torch.empty_like(logits_cl)
+        L.call("mivp_seg_loss_grad", L.ptr(logits_cl), L.ptr(target), B, H * W * D, Cc, 1 if spec.include_background else 0,
+               1 if spec.batch else 0, spec.alpha, spec.beta, spec.focal_gamma, L.ptr(ctx.weights), 0 if ig is None else ig,
+               0 if ig is None else 1, spec.lambda_region, spec.lambda_voxel, L.ptr(ws), L.ptr(g), L.ptr(dz), L.stream())
+        return dz, None, None, None
+
+
+_seg_weight_cache = {}
+
+
+def _seg_weights(spec: SegLossSpec, class_weights, n_classes: int, device) -> Optional[torch.Tensor]:
+    """The weight table on ``device`` (f32 [C]) or None; ``class_weights`` (a tensor) takes precedence over the spec's tuple,
+    whose device copy is made once per (weights, device) -- outside a recording."""
+    if class_weights is None:
+        if spec.class_weights is None:
+            return None
+        key = (spec.class_weights, str(device))
+        if key not in _seg_weight_cache:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("seg_loss: first use of these class_weights inside a recording; run one eager step first "
+                                   "or pass the device tensor (losses.SegLoss owns one)")
+            _seg_weight_cache[key] = torch.tensor(spec.class_weights, dtype=torch.float32, device=device)
+        class_weights = _seg_weight_cache[key]
+    if not isinstance(class_weights, torch.Tensor) or class_weights.dim() != 1 or class_weights.shape[0] != n_classes:
+        raise ValueError(f"class_weights must hold one weight per class ({n_classes}), got "
+                         f"{tuple(class_weights.shape) if isinstance(class_weights, torch.Tensor) else class_weights!r}")
+    if class_weights.device != device:
+        raise ValueError(f"class_weights must be on the logits' device {device}, got {class_weights.device}")
+    return class_weights
+
+
+def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
+             class_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Tversky region term + weighted (focal) softmax cross-entropy with an ignore label.  logits [B, C, H, W, D], target
+    [B, 1, H, W, D] (or [B, H, W, D]) class indices of any dtype; ``class_weights``: a [C] tensor on the logits' device that
+    replaces ``spec.class_weights``.
+
+    A voxel is valid when its label is an integer in [0, C) other than ``spec.ignore_index``; an invalid voxel adds to no
+    sum and gets an exactly zero gradient.  With p = softmax_c(z), t = one-hot(label), sums over the valid voxels of a sample
+    (of the batch when ``spec.batch``) and s = 1e-5::
+
+        TI_c   = (2 I_c + s) / (2 I_c + 2 alpha (P_c - I_c) + 2 beta (T_c - I_c) + s),  I = sum p t, P = sum p, T = sum t
+        region = mean over (b, c >= c0) [over c >= c0 when batch] of 1 - TI_c
+        voxel  = - sum_v w[y_v] (1 - p_y)^focal_gamma log p_y / sum_v w[y_v]     (valid voxels of the batch; 0 when the sum is 0)
+        loss   = lambda_region region + lambda_voxel voxel
+
+    alpha = beta = 0.5 is ``dice_loss``'s Dice, in general MONAI's ``TverskyLoss(smooth_nr = smooth_dr = s / 2)``; focal_gamma
+    = 0 is ``F.cross_entropy(weight=, ignore_index=, reduction="mean")``.
+
+    Channels-last f32 CUDA logits (the view the HIP model returns) with C <= 8 take the fused kernels: two streaming passes,
+    nothing read back, recordable.  Any other layout, dtype or device takes the same formulas as plain torch ops."""
+    if not isinstance(spec, SegLossSpec):
+        raise TypeError(f"spec must be a SegLossSpec, got {type(spec).__name__}")
+    if logits.dim() != 5:
+        raise ValueError(f"logits must be [B, C, H, W, D], got {tuple(logits.shape)}")
+    B, Cc = logits.shape[0], logits.shape[1]
+    if Cc < 2:
+        raise ValueError(f"logits must have at least 2 classes, got {Cc}")
+    if target.numel() != logits.numel() // Cc or target.shape[0] != B:
+        raise ValueError(f"target must be [B, 1, H, W, D] for logits {tuple(logits.shape)}, got {tuple(target.shape)}")
+    w = _seg_weights(spec, class_weights, Cc, logits.device)
+    base = logits.permute(0, 2, 3, 4, 1)
+    if logits.is_cuda and logits.dtype == torch.float32 and base.is_contiguous() and Cc <= SEG_LOSS_MAX_CLASSES:
+        tgt = target.detach().to(torch.float32).contiguous()
+        if w is not None and (w.dtype != torch.float32 or not w.is_contiguous()):
+            w = w.detach().float().contiguous()
+        return _SegLossFn.apply(base, tgt, None if w is None else w.detach(), spec)
+    return _seg_loss_torch(base.reshape(B, -1, Cc), target.detach().reshape(B, -1), spec, None if w is None else w.detach())
+
+
+class SegLoss(torch.nn.Module):
+    """``seg_loss`` as a module that owns the class-weight table as a buffer (it follows ``.to(device)``, so a recorded step
+    reads a fixed device tensor).  ``train.step_loss`` uses ``conf.seg_loss`` when the configuration has one."""
+
+    def __init__(self, spec: Optional[SegLossSpec] = None, **options):
+        super().__init__()
+        if spec is None:
+            spec = SegLossSpec(**options)
+        elif options or not isinstance(spec, SegLossSpec):
+            raise TypeError("SegLoss takes a SegLossSpec or the options of one, not both")
+        self.spec = spec
+        self.register_buffer("class_weights", None if spec.class_weights is None
+                             else torch.tensor(spec.class_weights, dtype=torch.float32))
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return seg_loss(logits, target, self.spec, self.class_weights)
+
+    def extra_repr(self) -> str:
+        return repr(self.spec)

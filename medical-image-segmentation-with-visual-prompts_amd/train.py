@@ -203,8 +203,12 @@ def step_loss(out: dict, conf: Namespace, y) -> torch.Tensor:
     104-106).  ``supervised_*``: the trainer's segmentation term, ``DiceLoss`` on out['seg_pred'] (students_teacher.py:96-100,
     190-197) -- the ``sup_all`` throughput workload; the full supervised step with its prototype term is
     ``students_teacher.students_teacher_step``.  The ``self_supervised_*`` modes have no single-network objective: their
-    step is the students/teacher step."""
+    step is the students/teacher step.  A configuration with an attribute ``seg_loss`` (a ``losses.SegLoss`` on the model's
+    device) replaces the objective of the ``downstream`` and ``supervised_*`` modes by it, on the same output."""
     mode = conf.training_mode
+    seg = getattr(conf, "seg_loss", None)
+    if seg is not None and mode in ("downstream", "supervised_learning_all", "supervised_learning_decoder"):
+        return seg(out["downstream" if mode == "downstream" else "seg_pred"], y)
     if mode == "downstream":
         return dice_focal_loss(out["downstream"], y, conf.include_background, 4.0)
     if mode in ("supervised_learning_all", "supervised_learning_decoder"):

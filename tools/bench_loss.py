@@ -1,0 +1,131 @@
+"""Time the recorded loss + gradient of mivp_seg_loss (csrc/segloss.hip) against the Dice-focal kernels and eager torch.
+
+    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10]
+
+Shapes: 96^3 at B = 4 (the `downstream` step's) and 128 x 128 x 8 at B = 14, both C = 2.  Settings of the new entry:
+  (a) Dice-equivalent options (alpha = beta = 0.5), lambda_voxel = 0
+  (b) Dice + weighted cross-entropy, an ignore label on 20 % of the voxels
+  (c) Tversky (0.3, 0.7) + focal cross-entropy with gamma = 2, same weights and ignore label
+Baselines in the same job: mivp_dice_focal on the same operands with gamma = 4 and with the Dice term alone (gamma < 0), and
+the plain-torch composition of (b) (losses.seg_loss on a contiguous channels-first tensor) with autograd, eager.
+
+Each kernel variant is one call (value + gradient) recorded in a HIP graph; a run is `replays` replays between two device
+events after `warmup` replays; the figure is the median over `runs` runs with the spread (min .. max).  One JSON line per
+variant, then one summary line.  No time is a pass criterion."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mivp_amd  # noqa: E402,F401
+from mivp_amd import _lib as L  # noqa: E402
+from mivp_amd import losses  # noqa: E402
+
+DEV = "cuda"
+STEP_MS = 2.41                                                    # the `downstream` step the shares refer to
+SHAPES = (("96^3 B4", 4, (96, 96, 96)), ("128x128x8 B14", 14, (128, 128, 8)))
+WEIGHTS = (0.5, 2.0)
+IGNORE = 255
+
+
+def timed(fn, runs, replays, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(runs):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(replays):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b) / replays)
+    return dict(ms=statistics.median(ms), lo=min(ms), hi=max(ms))
+
+
+def recorded(call):
+    """One call in a HIP graph; returns the replay function."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        call()                                                    # eager once: module load, allocations
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        call()
+    return g.replay
+
+
+def seg_variant(z, y, w, dz, loss, alpha, beta, gamma, weighted, ignore, lam_r, lam_v):
+    B, vol, Cc = z.shape
+    ws = torch.empty(int(L.lib().mivp_seg_loss_ws(B, vol)), dtype=torch.float32, device=DEV)
+    wp = w if weighted else None
+
+    def call():
+        L.call("mivp_seg_loss", L.ptr(z), L.ptr(y), B, vol, Cc, 1, 0, alpha, beta, gamma, L.ptr(wp), IGNORE, 1 if ignore else 0,
+               lam_r, lam_v, L.ptr(ws), L.ptr(loss), L.ptr(dz), L.stream())
+    return call
+
+
+def dice_focal_variant(z, y, dz, loss, gamma):
+    B, vol, Cc = z.shape
+    ws = torch.empty(int(L.lib().mivp_dice_focal_ws(B, vol)), dtype=torch.float32, device=DEV)
+
+    def call():
+        L.call("mivp_dice_focal", L.ptr(z), L.ptr(y), B, vol, Cc, 1, gamma, L.ptr(ws), L.ptr(loss), L.ptr(dz), L.stream())
+    return call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--replays", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    args = ap.parse_args()
+    assert args.runs >= 3
+    summary = {}
+    for name, B, dims in SHAPES:
+        vol, Cc = dims[0] * dims[1] * dims[2], 2
+        g = torch.Generator().manual_seed(1)
+        z = (2.0 * torch.randn((B, vol, Cc), generator=g)).to(DEV)
+        y = torch.randint(0, Cc, (B, vol), generator=g).float()
+        y_ig = y.clone()
+        y_ig[torch.rand((B, vol), generator=g) < 0.2] = float(IGNORE)
+        y, y_ig = y.to(DEV), y_ig.to(DEV)
+        w = torch.tensor(WEIGHTS, dtype=torch.float32, device=DEV)
+        dz, loss = torch.empty_like(z), torch.empty(1, dtype=torch.float32, device=DEV)
+        variants = [
+            ("dice_focal gamma 4 (baseline)", dice_focal_variant(z, y, dz, loss, 4.0)),
+            ("dice alone (baseline)", dice_focal_variant(z, y, dz, loss, -1.0)),
+            ("seg (a) dice-equivalent", seg_variant(z, y, w, dz, loss, 0.5, 0.5, 0.0, False, False, 1.0, 0.0)),
+            ("seg (b) dice + weighted CE, 20% ignored", seg_variant(z, y_ig, w, dz, loss, 0.5, 0.5, 0.0, True, True, 1.0, 1.0)),
+            ("seg (c) tversky + focal CE gamma 2", seg_variant(z, y_ig, w, dz, loss, 0.3, 0.7, 2.0, True, True, 1.0, 1.0)),
+        ]
+        for label, call in variants:
+            r = timed(recorded(call), args.runs, args.replays, args.warmup)
+            r.update(shape=name, variant=label, share_of_step=r["ms"] / STEP_MS, gb_s=3 * z.numel() * 4 / r["ms"] / 1e6)
+            summary[f"{name} | {label}"] = round(r["ms"], 4)
+            print(json.dumps(r), flush=True)
+        # eager torch composition of (b), autograd
+        spec = losses.SegLossSpec(class_weights=WEIGHTS, ignore_index=IGNORE)
+        plain = z.view(B, *dims, Cc).permute(0, 4, 1, 2, 3).contiguous().requires_grad_(True)
+        target = y_ig.view(B, 1, *dims)
+
+        def eager():
+            plain.grad = None
+            losses.seg_loss(plain, target, spec, w).backward()
+        r = timed(eager, args.runs, max(3, args.replays // 10), 3)
+        r.update(shape=name, variant="torch composition of (b), eager", share_of_step=r["ms"] / STEP_MS)
+        summary[f"{name} | torch (b) eager"] = round(r["ms"], 4)
+        print(json.dumps(r), flush=True)
+    print(json.dumps({"bench_loss_ms": summary}))
+
+
+if __name__ == "__main__":
+    main()
