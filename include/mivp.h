@@ -475,6 +475,42 @@ int mivp_seg_loss_grad(const float* logits, const float* target, int32_t B, int6
                        float lambda_voxel, float* workspace, const float* gscale, float* dlogits,
                        mivp_stream_t stream);
 
+/* The same region term + TOP-K (hard-voxel) cross-entropy (csrc/segtopk.hip; SegLossSpec(top_k=...)).  These
+ * entry points joined ABI 18 without a bump: they are additive and no earlier signature changed.  Arguments, validity rule
+ * and region term as for mivp_seg_loss, plus top_k in (0, 1] (lambda_voxel > 0 is required).  Over the valid voxels of the
+ * whole batch:
+ *   u_v   = w[y_v] (1 - p_y)^focal_gamma (-log p_y) >= 0,  N = their number,  k = max(1, floor(top_k N)) (in double)
+ *   tau   = the k-th largest u_v as the statistics pass computed it in f32, n_gt = #{u > tau}, n_eq = #{u == tau}
+ *   voxel = (sum_{u > tau} u + (k - n_gt) tau) / k                  (the mean of the k largest; 0 when N == 0)
+ *   d voxel = (1 / k) sum_v s_v d u_v,  s_v = 1 where u_v > tau, rho = (k - n_gt) / n_eq where u_v == tau, 0 elsewhere:
+ *   tied voxels share the remaining weight equally, whatever their place in memory.
+ * The select is an exact three-level radix select (11 + 10 + 10 bits) over one 32-bit key per voxel: the bit pattern of
+ * u_v clamped to >= +0 (monotone as an unsigned integer), 0xFFFFFFFF at an invalid voxel.  The statistics pass stores the
+ * keys; every later pass, the gradient pass included, reads them back.  Only integer atomics; float sums in a fixed order:
+ * equal calls give equal bits.  No host read, every launch unconditional (k and tau are device data), the call zeroes its
+ * own histograms: recordable, and a recording holds for any later content.
+ * workspace: mivp_seg_topk_ws(B, vol) 4-byte words, 16-byte aligned.  With R = mivp_seg_loss_ws(B, vol) rounded up to a
+ * multiple of 4:
+ *   [0, mivp_seg_loss_ws)                 the rows of mivp_seg_loss (the two voxel columns stay 0)
+ *   [R, R + MIVP_SEG_TOPK_RECORD_WORDS)   the record: [0] N, [1] k, [2] tau (the key: f32 bits), [3] n_gt, [4] n_eq (uint32),
+ *                                         [5] rho, [6] voxel (f32 bits); the other words are internal
+ *   then the three histograms (2048, 1024, 1024 uint32) and 1024 f32 partial sums
+ *   [R + MIVP_SEG_TOPK_KEYS_OFFSET, + B vol)   the keys (uint32), voxel order of the target
+ * B vol < 2^31.  dlogits may be NULL; mivp_seg_topk_grad then runs the gradient pass on the SAME workspace with the SAME
+ * options, scaled by gscale[0] (device pointer, NULL = 1), and writes every element of dlogits once. */
+#define MIVP_SEG_TOPK_RECORD_WORDS 16
+#define MIVP_SEG_TOPK_KEYS_OFFSET 5136
+size_t mivp_seg_topk_ws(int32_t B, int64_t vol);
+int mivp_seg_topk(const float* logits, const float* target, int32_t B, int64_t vol, int32_t C,
+                  int32_t include_background, int32_t batch, float alpha, float beta, float focal_gamma,
+                  const float* class_weights, int32_t ignore_index, int32_t has_ignore, float lambda_region,
+                  float lambda_voxel, double top_k, float* workspace, float* loss, float* dlogits, mivp_stream_t stream);
+int mivp_seg_topk_grad(const float* logits, const float* target, int32_t B, int64_t vol, int32_t C,
+                       int32_t include_background, int32_t batch, float alpha, float beta, float focal_gamma,
+                       const float* class_weights, int32_t ignore_index, int32_t has_ignore, float lambda_region,
+                       float lambda_voxel, double top_k, float* workspace, const float* gscale, float* dlogits,
+                       mivp_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* downstream head on the LOW-resolution decoder output                      */
 /* (swin_unetr.py:351-355 nn.Upsample x2 trilinear, then :229-237 BatchNorm3d */

@@ -11,6 +11,8 @@
   unpinned, restated in oracle/loss_ref.py::dice_loss.
 * ``SegLossSpec`` / ``seg_loss`` / ``SegLoss`` -- Tversky region term + weighted (focal) softmax cross-entropy with an
   ignore label (csrc/segloss.hip): not in the reference; ``train.step_loss`` uses it when ``conf.seg_loss`` is set.
+  ``SegLossSpec(top_k=...)`` averages the cross-entropy over the hardest k % of the batch's voxels only (nnU-Net's
+  ``DC_and_topk_loss``; csrc/segtopk.hip).
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from ._host import ImmutableValue, check_at_least, check_flag, plain_int
+from ._host import ImmutableValue, check_at_least, check_finite, check_flag, plain_int
 
 
 def reduced_size(dims: Sequence[int], reduction_factor: float) -> List[int]:
@@ -293,14 +295,16 @@ class SegLossSpec(ImmutableValue):
     ``batch``: region sums over the whole batch instead of per sample; ``include_background``: class 0 in the region term;
     ``focal_gamma``: 0 (plain cross-entropy) or >= 1 (an exponent in (0, 1) has an unbounded gradient at p -> 1);
     ``class_weights``: one weight >= 0 per class, or None (all ones); ``ignore_index``: the label of voxels that take no part,
-    or None; ``lambda_region``, ``lambda_voxel`` >= 0, not both 0."""
+    or None; ``lambda_region``, ``lambda_voxel`` >= 0, not both 0; ``top_k``: None, or the fraction in (0, 1] of the batch's
+    valid voxels -- the hardest ones -- that the cross-entropy is averaged over (needs ``lambda_voxel`` > 0)."""
 
     __slots__ = ("alpha", "beta", "batch", "include_background", "focal_gamma", "class_weights", "ignore_index",
-                 "lambda_region", "lambda_voxel")
+                 "lambda_region", "lambda_voxel", "top_k")
 
     def __init__(self, alpha: float = 0.5, beta: float = 0.5, batch: bool = False, include_background: bool = True,
                  focal_gamma: float = 0.0, class_weights: Optional[Sequence[float]] = None,
-                 ignore_index: Optional[int] = None, lambda_region: float = 1.0, lambda_voxel: float = 1.0):
+                 ignore_index: Optional[int] = None, lambda_region: float = 1.0, lambda_voxel: float = 1.0,
+                 top_k: Optional[float] = None):
         f32_max = float(np.finfo(np.float32).max)
         for name, v in (("alpha", alpha), ("beta", beta), ("lambda_region", lambda_region), ("lambda_voxel", lambda_voxel)):
             if check_at_least(name, v, 0.0) > f32_max:
@@ -322,14 +326,21 @@ class SegLossSpec(ImmutableValue):
             if not plain_int(ignore_index) or abs(int(ignore_index)) > 2 ** 24:
                 raise ValueError(f"ignore_index must be None or an int with |ignore_index| <= 2^24, got {ignore_index!r}")
             ignore_index = int(ignore_index)
+        if top_k is not None:
+            top_k = check_finite("top_k", top_k)
+            if not 0.0 < top_k <= 1.0:
+                raise ValueError(f"top_k must be None or a fraction in (0, 1], got {top_k!r}")
+            if float(lambda_voxel) == 0.0:
+                raise ValueError("top_k selects the voxels of the cross-entropy term: it needs lambda_voxel > 0")
         self._set(alpha=float(alpha), beta=float(beta), batch=check_flag("batch", batch),
                   include_background=check_flag("include_background", include_background), focal_gamma=gamma,
                   class_weights=class_weights, ignore_index=ignore_index, lambda_region=float(lambda_region),
-                  lambda_voxel=float(lambda_voxel))
+                  lambda_voxel=float(lambda_voxel), top_k=top_k)
 
 
-def _seg_loss_torch(z: torch.Tensor, y: torch.Tensor, spec: SegLossSpec, w: Optional[torch.Tensor]) -> torch.Tensor:
-    """The formulas of ``seg_loss`` in plain torch ops, differentiable by autograd: z [B, vol, C], y [B, vol] labels."""
+def _seg_loss_torch(z: torch.Tensor, y: torch.Tensor, spec: SegLossSpec, w: Optional[torch.Tensor], record=None) -> torch.Tensor:
+    """The formulas of ``seg_loss`` in plain torch ops, differentiable by autograd: z [B, vol, C], y [B, vol] labels.
+    ``record``: a list that receives (N, k, tau, n_gt, n_eq) of a top-k call."""
     B, _, Cc = z.shape
     y = y.to(z.dtype if z.dtype in (torch.float32, torch.float64) else torch.float32)
     valid = (y >= 0) & (y < Cc) & (y == y.floor())
@@ -353,9 +364,29 @@ def _seg_loss_torch(z: torch.Tensor, y: torch.Tensor, spec: SegLossSpec, w: Opti
         f = -(logp * hot).sum(-1)
         if spec.focal_gamma > 0.0:
             f = f * (p * (1.0 - hot)).sum(-1) ** spec.focal_gamma             # 1 - p_y as the sum of the other classes
+        if spec.top_k is not None:
+            return loss + spec.lambda_voxel * _top_k_mean((wt[idx] * f)[valid], spec.top_k, record)
         wsum = wy.sum()
         loss = loss + spec.lambda_voxel * ((wy * f).sum() / torch.where(wsum > 0, wsum, torch.ones_like(wsum)))
     return loss
+
+
+def _top_k_mean(u: torch.Tensor, top_k: float, record=None) -> torch.Tensor:
+    """Mean of the k = max(1, floor(top_k N)) largest of the N values u (1-D); values equal to the k-th largest tau share
+    the weight the larger ones leave, rho = (k - n_gt) / n_eq each: the value of ``torch.topk(u, k)[0].mean()`` with a
+    gradient that does not depend on the order of equal values.  N == 0 gives 0."""
+    n = u.numel()
+    k = max(1, math.floor(top_k * n))
+    if n == 0:
+        if record is not None:
+            record.append((0, k, u.new_zeros(()), 0, 0))
+        return u.sum()
+    tau = torch.topk(u.detach(), k, sorted=True).values[-1]
+    gt, eq = u.detach() > tau, u.detach() == tau
+    n_gt, n_eq = int(gt.sum()), int(eq.sum())
+    if record is not None:
+        record.append((n, k, tau, n_gt, n_eq))
+    return (u[gt].sum() + u[eq].sum() * ((k - n_gt) / n_eq)) / k
 
 
 class _SegLossFn(torch.autograd.Function):
@@ -389,6 +420,42 @@ class _SegLossFn(torch.autograd.Function):
         return dz, None, None, None
 
 
+def _seg_topk_record_offset(B: int, vol: int) -> int:
+    """Word offset of the record in a mivp_seg_topk workspace (include/mivp.h)."""
+    return (int(L.lib().mivp_seg_loss_ws(B, vol)) + 3) // 4 * 4
+
+
+class _SegTopkFn(torch.autograd.Function):
+    """``_SegLossFn`` with the top-k voxel term (csrc/segtopk.hip).  The caller owns the workspace: it holds the record that
+    ``SegLoss.top_k_stats`` reads."""
+
+    @staticmethod
+    def forward(ctx, logits_cl, target, weights, spec, ws):
+        B, H, W, D, Cc = logits_cl.shape
+        loss = torch.empty(1, dtype=torch.float32, device=logits_cl.device)
+        ig = spec.ignore_index
+        L.call("mivp_seg_topk", L.ptr(logits_cl), L.ptr(target), B, H * W * D, Cc, 1 if spec.include_background else 0,
+               1 if spec.batch else 0, spec.alpha, spec.beta, spec.focal_gamma, L.ptr(weights), 0 if ig is None else ig,
+               0 if ig is None else 1, spec.lambda_region, spec.lambda_voxel, spec.top_k, L.ptr(ws), L.ptr(loss), L.ptr(None),
+               L.stream())
+        ctx.save_for_backward(logits_cl, target, ws)
+        ctx.weights, ctx.spec = weights, spec
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits_cl, target, ws = ctx.saved_tensors
+        spec, ig = ctx.spec, ctx.spec.ignore_index
+        B, H, W, D, Cc = logits_cl.shape
+        g = g.detach().to(torch.float32).contiguous()
+        dz = torch.empty_like(logits_cl)
+        L.call("mivp_seg_topk_grad", L.ptr(logits_cl), L.ptr(target), B, H * W * D, Cc, 1 if spec.include_background else 0,
+               1 if spec.batch else 0, spec.alpha, spec.beta, spec.focal_gamma, L.ptr(ctx.weights), 0 if ig is None else ig,
+               0 if ig is None else 1, spec.lambda_region, spec.lambda_voxel, spec.top_k, L.ptr(ws), L.ptr(g), L.ptr(dz),
+               L.stream())
+        return dz, None, None, None, None
+
+
 _seg_weight_cache = {}
 
 
@@ -414,7 +481,7 @@ def _seg_weights(spec: SegLossSpec, class_weights, n_classes: int, device) -> Op
 
 
 def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
-             class_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+             class_weights: Optional[torch.Tensor] = None, _record=None) -> torch.Tensor:
     """Tversky region term + weighted (focal) softmax cross-entropy with an ignore label.  logits [B, C, H, W, D], target
     [B, 1, H, W, D] (or [B, H, W, D]) class indices of any dtype; ``class_weights``: a [C] tensor on the logits' device that
     replaces ``spec.class_weights``.
@@ -431,8 +498,19 @@ def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
     alpha = beta = 0.5 is ``dice_loss``'s Dice, in general MONAI's ``TverskyLoss(smooth_nr = smooth_dr = s / 2)``; focal_gamma
     = 0 is ``F.cross_entropy(weight=, ignore_index=, reduction="mean")``.
 
-    Channels-last f32 CUDA logits (the view the HIP model returns) with C <= 8 take the fused kernels: two streaming passes,
-    nothing read back, recordable.  Any other layout, dtype or device takes the same formulas as plain torch ops."""
+    With ``spec.top_k`` the voxel term is the mean over the hardest voxels of the batch only (nnU-Net's
+    ``DC_and_topk_loss``).  Over the N valid voxels of the batch, u_v = w[y_v] (1 - p_y)^focal_gamma (-log p_y),
+    k = max(1, floor(top_k N)), tau = the k-th largest u, n_gt = #{u > tau}, n_eq = #{u == tau}::
+
+        voxel   = (sum_{u > tau} u + (k - n_gt) tau) / k                   (= torch.topk(u, k)[0].mean(); 0 when N == 0)
+        d voxel = (1 / k) sum_v s_v d u_v,  s_v = 1 (u_v > tau), (k - n_gt) / n_eq (u_v == tau), 0 (u_v < tau)
+
+    The normaliser is k, not the weight sum; tied voxels share the remaining weight equally, so the gradient does not
+    depend on the order of the voxels; without ties it is autograd's through ``torch.topk``.  Finite logits only.
+
+    Channels-last f32 CUDA logits (the view the HIP model returns) with C <= 8 take the fused kernels: two streaming passes
+    (with ``top_k``: an exact radix select on one stored 32-bit key per voxel between them), nothing read back, recordable.
+    Any other layout, dtype or device takes the same formulas as plain torch ops."""
     if not isinstance(spec, SegLossSpec):
         raise TypeError(f"spec must be a SegLossSpec, got {type(spec).__name__}")
     if logits.dim() != 5:
@@ -448,8 +526,16 @@ def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
         tgt = target.detach().to(torch.float32).contiguous()
         if w is not None and (w.dtype != torch.float32 or not w.is_contiguous()):
             w = w.detach().float().contiguous()
-        return _SegLossFn.apply(base, tgt, None if w is None else w.detach(), spec)
-    return _seg_loss_torch(base.reshape(B, -1, Cc), target.detach().reshape(B, -1), spec, None if w is None else w.detach())
+        if spec.top_k is None:
+            return _SegLossFn.apply(base, tgt, None if w is None else w.detach(), spec)
+        vol = tgt.numel() // B
+        ws = torch.empty(L.lib().mivp_seg_topk_ws(B, vol), dtype=torch.float32, device=logits.device)
+        if _record is not None:
+            off = _seg_topk_record_offset(B, vol)
+            _record.append(ws[off:off + 5])
+        return _SegTopkFn.apply(base, tgt, None if w is None else w.detach(), spec, ws)
+    return _seg_loss_torch(base.reshape(B, -1, Cc), target.detach().reshape(B, -1), spec, None if w is None else w.detach(),
+                           _record)
 
 
 class SegLoss(torch.nn.Module):
@@ -465,9 +551,28 @@ class SegLoss(torch.nn.Module):
         self.spec = spec
         self.register_buffer("class_weights", None if spec.class_weights is None
                              else torch.tensor(spec.class_weights, dtype=torch.float32))
+        self._topk_record = None
 
     def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        return seg_loss(logits, target, self.spec, self.class_weights)
+        if self.spec.top_k is None:
+            return seg_loss(logits, target, self.spec, self.class_weights)
+        record = []
+        loss = seg_loss(logits, target, self.spec, self.class_weights, record)
+        self._topk_record = record[0]
+        return loss
+
+    def top_k_stats(self):
+        """The select of the last call with ``top_k`` set: N valid voxels, k, the threshold tau, the voxels above it and
+        the voxels tied at it.  The fused path keeps these words in its workspace on the device; this is the one explicit
+        device-to-host copy of them (after a replay of a recorded step: that replay's)."""
+        rec = self._topk_record
+        if rec is None:
+            raise RuntimeError("top_k_stats: no call with top_k set has run yet")
+        if isinstance(rec, torch.Tensor):
+            raw = rec.detach().cpu().contiguous().view(torch.int32).numpy()
+            return dict(N=int(raw[0]), k=int(raw[1]), tau=float(raw[2:3].view(np.float32)[0]), n_gt=int(raw[3]), n_eq=int(raw[4]))
+        n, k, tau, n_gt, n_eq = rec
+        return dict(N=int(n), k=int(k), tau=float(tau), n_gt=int(n_gt), n_eq=int(n_eq))
 
     def extra_repr(self) -> str:
         return repr(self.spec)

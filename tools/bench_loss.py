@@ -6,6 +6,8 @@ Shapes: 96^3 at B = 4 (the `downstream` step's) and 128 x 128 x 8 at B = 14, bot
   (a) Dice-equivalent options (alpha = beta = 0.5), lambda_voxel = 0
   (b) Dice + weighted cross-entropy, an ignore label on 20 % of the voxels
   (c) Tversky (0.3, 0.7) + focal cross-entropy with gamma = 2, same weights and ignore label
+  (d) top-k: Dice + weighted cross-entropy over the hardest 10 % of the valid voxels (mivp_seg_topk, csrc/segtopk.hip), the
+      operands of (b); its yardsticks are (b) and the eager composition ``cross_entropy(reduction="none")`` + ``topk``
 Baselines in the same job: mivp_dice_focal on the same operands with gamma = 4 and with the Dice term alone (gamma < 0), and
 the plain-torch composition of (b) (losses.seg_loss on a contiguous channels-first tensor) with autograd, eager.
 
@@ -73,6 +75,16 @@ def seg_variant(z, y, w, dz, loss, alpha, beta, gamma, weighted, ignore, lam_r, 
     return call
 
 
+def topk_variant(z, y, w, dz, loss, top_k):
+    B, vol, Cc = z.shape
+    ws = torch.empty(int(L.lib().mivp_seg_topk_ws(B, vol)), dtype=torch.float32, device=DEV)
+
+    def call():
+        L.call("mivp_seg_topk", L.ptr(z), L.ptr(y), B, vol, Cc, 1, 0, 0.5, 0.5, 0.0, L.ptr(w), IGNORE, 1, 1.0, 1.0, top_k,
+               L.ptr(ws), L.ptr(loss), L.ptr(dz), L.stream())
+    return call
+
+
 def dice_focal_variant(z, y, dz, loss, gamma):
     B, vol, Cc = z.shape
     ws = torch.empty(int(L.lib().mivp_dice_focal_ws(B, vol)), dtype=torch.float32, device=DEV)
@@ -106,6 +118,7 @@ def main():
             ("seg (a) dice-equivalent", seg_variant(z, y, w, dz, loss, 0.5, 0.5, 0.0, False, False, 1.0, 0.0)),
             ("seg (b) dice + weighted CE, 20% ignored", seg_variant(z, y_ig, w, dz, loss, 0.5, 0.5, 0.0, True, True, 1.0, 1.0)),
             ("seg (c) tversky + focal CE gamma 2", seg_variant(z, y_ig, w, dz, loss, 0.3, 0.7, 2.0, True, True, 1.0, 1.0)),
+            ("seg (d) dice + top-k 10% weighted CE, 20% ignored", topk_variant(z, y_ig, w, dz, loss, 0.1)),
         ]
         for label, call in variants:
             r = timed(recorded(call), args.runs, args.replays, args.warmup)
@@ -123,6 +136,19 @@ def main():
         r = timed(eager, args.runs, max(3, args.replays // 10), 3)
         r.update(shape=name, variant="torch composition of (b), eager", share_of_step=r["ms"] / STEP_MS)
         summary[f"{name} | torch (b) eager"] = round(r["ms"], 4)
+        print(json.dumps(r), flush=True)
+        # eager composition of (d)'s voxel term alone: per-voxel cross-entropy, a sort-based top-k, autograd through the indices
+        flat = z.view(-1, Cc).clone().requires_grad_(True)
+        labels = y_ig.view(-1).long()
+        k = max(1, int(0.1 * int((labels != IGNORE).sum())))
+
+        def eager_topk():
+            flat.grad = None
+            ce = torch.nn.functional.cross_entropy(flat, labels, weight=w, ignore_index=IGNORE, reduction="none")
+            torch.topk(ce, k, sorted=False)[0].mean().backward()
+        r = timed(eager_topk, args.runs, max(3, args.replays // 10), 3)
+        r.update(shape=name, variant="torch cross_entropy(none) + topk, eager (voxel term of (d) alone)", share_of_step=r["ms"] / STEP_MS)
+        summary[f"{name} | torch topk eager"] = round(r["ms"], 4)
         print(json.dumps(r), flush=True)
     print(json.dumps({"bench_loss_ms": summary}))
 
