@@ -511,6 +511,51 @@ int mivp_seg_topk_grad(const float* logits, const float* target, int32_t B, int6
                        float lambda_voxel, double top_k, float* workspace, const float* gscale, float* dlogits,
                        mivp_stream_t stream);
 
+/* Boundary (signed-distance) loss term with batched on-device distance maps (csrc/distmap.hip; mivp_amd/losses.py
+ * signed_distance_maps / boundary_loss / SegLossSpec(lambda_boundary=...)).  These entry points joined ABI 18
+ * without a bump: they are additive and no earlier signature changed.
+ *
+ * mivp_distmap_signed: target f32 [B][H][W][D] class indices (dims = {H, W, D}, host) -> phi f32 [B][K][H][W][D], K = C - c0
+ * classes c0 .. C - 1, c0 = include_background ? 0 : 1, 1 <= K <= 16.  Per (b, c), M = {label == c}; a label that is no class
+ * (non-integer, outside [0, C), NaN, or, with has_ignore != 0, equal to ignore_index) belongs to no M.  With distances
+ * sqrt(sum_a (spacing[a] delta_a)^2) (spacing: host f32 {s0, s1, s2}, finite and > 0) and the space beyond the volume border
+ * neither inside nor outside:
+ *   phi = distance to the nearest voxel of M                 at voxels outside M   (> 0)
+ *   phi = -(distance to the nearest voxel outside M - 1)     at voxels inside M    (<= 0 at unit spacing)
+ *   phi = +0 everywhere in (b, c)                            when M is empty or the whole sample
+ * Four launches whatever B and K are (seed / D pass, W pass, H pass, closing), no atomics, nothing read back, every launch
+ * unconditional: equal calls give equal bits, and a recording holds for any later content.  At unit spacing the squared
+ * distances under the root are the exact integers (those of mivp_edt_sq).  Limits: H, W <= 65535 and B K H W D < 2^31.
+ * workspace: mivp_distmap_ws(B, K, dims) bytes (0 for arguments the call would refuse), 256-byte aligned:
+ *   [0, 8 B K vol)                 the squared fields f32 [2][B][K][vol]: side 0 = distance to M, side 1 = to its complement
+ *   [that rounded up to 256, + 16 B K vol)   the lower envelope's stack, int32 pairs [depth][line]
+ * reused by every call in stream order.
+ *
+ * mivp_boundary_loss: logits f32 [B, vol, C] channels-last (2 <= C <= 8), target f32 [B, vol], phi f32 [B][K][vol] (any
+ * values; a constant of the step).  Validity rule of mivp_seg_loss.  With p = softmax_c(z), V the valid voxels of the batch,
+ * N = |V|, w = lambda_boundary weight[0] (weight: DEVICE pointer to one float, NULL = 1; lambda_boundary >= 0):
+ *   loss[0]   = w sum_{v in V} sum_{c >= c0} p_c phi_c / (K max(N, 1))
+ *   dlogits_j = w p_j (phit_j - sum_c p_c phit_c) / (K max(N, 1)),   phit_c = phi_c for c >= c0, else 0;  exactly 0 at an
+ *               invalid voxel
+ * dlogits may be NULL: the value pass alone.  accumulate == 0: every element of dlogits is stored once; accumulate != 0: the
+ * value is added to what dlogits holds (one rounded add per element: the bits of dlogits + g).  mivp_boundary_loss_grad runs
+ * the gradient pass on the SAME workspace with the SAME options, scaled by gscale[0] (device pointer, NULL = 1).
+ * workspace: mivp_boundary_loss_ws(B, vol) floats = partial rows [B][bpb][2] (sum p phi, valid voxels), then
+ * {sum p phi, N, 1 / (K max(N, 1)), spare}.  No atomics: equal calls give equal bits. */
+size_t mivp_distmap_ws(int32_t B, int32_t K, const int32_t* dims);
+int mivp_distmap_signed(const float* target, int32_t B, int32_t C, int32_t include_background, int32_t ignore_index,
+                        int32_t has_ignore, const int32_t* dims, const float* spacing, float* phi, void* workspace,
+                        mivp_stream_t stream);
+size_t mivp_boundary_loss_ws(int32_t B, int64_t vol);
+int mivp_boundary_loss(const float* logits, const float* target, const float* phi, int32_t B, int64_t vol, int32_t C,
+                       int32_t include_background, int32_t ignore_index, int32_t has_ignore, float lambda_boundary,
+                       const float* weight, float* workspace, float* loss, float* dlogits, int32_t accumulate,
+                       mivp_stream_t stream);
+int mivp_boundary_loss_grad(const float* logits, const float* target, const float* phi, int32_t B, int64_t vol, int32_t C,
+                            int32_t include_background, int32_t ignore_index, int32_t has_ignore, float lambda_boundary,
+                            const float* weight, const float* workspace, const float* gscale, float* dlogits,
+                            int32_t accumulate, mivp_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* downstream head on the LOW-resolution decoder output                      */
 /* (swin_unetr.py:351-355 nn.Upsample x2 trilinear, then :229-237 BatchNorm3d */

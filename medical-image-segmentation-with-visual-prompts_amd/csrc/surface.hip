@@ -18,9 +18,8 @@
 // two ranks P_p needs (from the device-resident surface count), and sums the slab in a fixed order.  A second pass
 // histograms the low 16 bits inside the lower rank's bin (16-bit LDS counters, two per word) and takes the minimum low
 // half inside the upper rank's bin when that is another bin; one workgroup finishes the select.
-#include "common.hpp"
+#include "edt_common.hpp"
 #include <limits.h>
-#include <math.h>
 
 namespace {
 constexpr int MAXC = 16;
@@ -29,8 +28,7 @@ constexpr int SEL_TPB = 1024;
 constexpr int HI_BINS = 32768;      // high 16 bits of a non-negative float key (sign clear)
 constexpr int LO_BINS = 65536;
 constexpr int SAMPLE_VOX = 32768;   // voxels per sampling workgroup: bounds a 16-bit LDS counter below 65536
-constexpr int NO_SEED = 1 << 29;
-constexpr int UNROLL = 8;
+constexpr int NO_SEED = EDT_NO_SEED;
 
 // one thread per voxel of both maps: class id on surface voxels (6-neighbourhood, the outside counts as background),
 // 255 elsewhere; per-class counts summed in LDS, one integer atomic per (class, map) and workgroup
@@ -98,84 +96,20 @@ __global__ __launch_bounds__(TPB) void k_edt_d(const uint8_t* __restrict__ smap,
             const int right = mr ? 64 * k + __builtin_ctzll(mr) : next;
             if (m) prev = 64 * k + 63 - __builtin_clzll(m);
             if (p >= D) continue;
-            const int dd = min(p - left, right - p);
-            float val;
-            if (dd >= NO_SEED / 2) val = INFINITY;
-            else val = intp ? (float)((long long)dd * dd) : a * (float)((long long)dd * dd);
-            out[p] = val;
+            out[p] = edt_d_value(min(p - left, right - p), a, intp);
         }
     }
 }
 
-// W / H pass: Meijster's lower envelope along one axis of n elements at `stride`, in place over f.  Lines are (outer,
-// inner) pairs, inner = d fastest across lanes; stack entries [depth][line] = (site | boundary << 16, bits of f(site)).
+// W / H pass: Meijster's lower envelope along one axis of n elements at `stride`, in place over f (edt_line of
+// csrc/edt_common.hpp, shared with csrc/distmap.hip).  Lines are (outer, inner) pairs, inner = d fastest across lanes; stack
+// entries [depth][line] = (site | boundary << 16, bits of f(site)).
 template <bool INTP>
 __global__ __launch_bounds__(TPB) void k_edt_line(float* __restrict__ f, long nlines, int inner, long outer_stride,
                                                   long stride, int n, float a, int2* __restrict__ stack) {
     const long line = (long)blockIdx.x * TPB + threadIdx.x;
     if (line >= nlines) return;
-    float* base = f + (line / inner) * outer_stride + (line % inner);
-    // F(x, i) = a (x - i)^2 + f(i); integers at unit spacing
-    using val_t = typename std::conditional<INTP, long long, float>::type;
-    auto F = [&](int x, int i, float fi) -> val_t {
-        const long long dx = x - i;
-        if (INTP) return (val_t)(dx * dx + (long long)fi);
-        return (val_t)(a * (float)(dx * dx) + fi);
-    };
-    // first x where u's parabola is below i's (i < u): 1 + floor((a (u^2 - i^2) + f(u) - f(i)) / (2 a (u - i)))
-    auto start = [&](int i, float fi, int u, float fu) -> int {
-        long long sep;
-        if (INTP) {
-            const long long num = (long long)u * u - (long long)i * i + (long long)fu - (long long)fi;
-            const long long den = 2LL * (u - i);
-            sep = num >= 0 ? num / den : -((-num + den - 1) / den);
-        } else {
-            const float q = (fu - fi + a * (float)((long long)u * u - (long long)i * i)) / (2.f * a * (float)(u - i));
-            sep = (long long)floorf(fminf(fmaxf(q, -2.f), (float)n + 1.f));
-        }
-        return (int)min(max(sep + 1, 0LL), (long long)n + 1);
-    };
-    int k = -1;
-    int ts = 0, tt = 0;                                        // top of the stack: site, boundary, f(site)
-    float tf = 0.f;
-    for (int u0 = 0; u0 < n; u0 += UNROLL) {
-        float fv[UNROLL];
-#pragma unroll
-        for (int e = 0; e < UNROLL; ++e) fv[e] = u0 + e < n ? base[(long)(u0 + e) * stride] : INFINITY;
-#pragma unroll
-        for (int e = 0; e < UNROLL; ++e) {
-            const int u = u0 + e;
-            const float fu = fv[e];
-            if (isinf(fu)) continue;
-            while (k >= 0 && F(tt, ts, tf) > F(tt, u, fu)) {
-                --k;
-                if (k >= 0) {
-                    const int2 s = stack[(long)k * nlines + line];
-                    ts = s.x & 0xffff; tt = (unsigned)s.x >> 16; tf = __int_as_float(s.y);
-                }
-            }
-            int w = 0;
-            if (k >= 0) {
-                w = start(ts, tf, u, fu);
-                if (w >= n) continue;
-            }
-            ++k;
-            ts = u; tt = w; tf = fu;
-            stack[(long)k * nlines + line] = make_int2(u | (w << 16), __float_as_int(fu));
-        }
-    }
-    if (k < 0) {
-        for (int u = 0; u < n; ++u) base[(long)u * stride] = INFINITY;
-        return;
-    }
-    for (int u = n - 1; u >= 0; --u) {
-        while (k > 0 && tt > u) {
-            --k;
-            const int2 s = stack[(long)k * nlines + line];
-            ts = s.x & 0xffff; tt = (unsigned)s.x >> 16; tf = __int_as_float(s.y);
-        }
-        base[(long)u * stride] = (float)F(u, ts, tf);
-    }
+    edt_line<INTP>(f + (line / inner) * outer_stride + (line % inner), stride, n, a, stack, nlines, line);
 }
 
 // ---------------------------------------------------------------------------------------------------- statistics

@@ -13,6 +13,9 @@
   ignore label (csrc/segloss.hip): not in the reference; ``train.step_loss`` uses it when ``conf.seg_loss`` is set.
   ``SegLossSpec(top_k=...)`` averages the cross-entropy over the hardest k % of the batch's voxels only (nnU-Net's
   ``DC_and_topk_loss``; csrc/segtopk.hip).
+* ``signed_distance_maps`` / ``boundary_loss`` / ``SegLossSpec(lambda_boundary=...)`` -- the boundary loss of Kervadec et al.
+  (MIDL 2019): softmax probabilities integrated against the signed distance maps of the labels, the maps built on the device
+  per step by a batched exact distance transform (csrc/distmap.hip).
 """
 from __future__ import annotations
 
@@ -26,7 +29,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from ._host import ImmutableValue, check_at_least, check_finite, check_flag, plain_int
+from ._host import (ImmutableValue, check_at_least, check_classes, check_finite, check_flag, check_gpu, check_spacing, i3,
+                    plain_int)
 
 
 def reduced_size(dims: Sequence[int], reduction_factor: float) -> List[int]:
@@ -295,25 +299,35 @@ class SegLossSpec(ImmutableValue):
     ``batch``: region sums over the whole batch instead of per sample; ``include_background``: class 0 in the region term;
     ``focal_gamma``: 0 (plain cross-entropy) or >= 1 (an exponent in (0, 1) has an unbounded gradient at p -> 1);
     ``class_weights``: one weight >= 0 per class, or None (all ones); ``ignore_index``: the label of voxels that take no part,
-    or None; ``lambda_region``, ``lambda_voxel`` >= 0, not both 0; ``top_k``: None, or the fraction in (0, 1] of the batch's
-    valid voxels -- the hardest ones -- that the cross-entropy is averaged over (needs ``lambda_voxel`` > 0)."""
+    or None; ``lambda_region``, ``lambda_voxel``, ``lambda_boundary`` >= 0, not all three 0; ``top_k``: None, or the fraction
+    in (0, 1] of the batch's valid voxels -- the hardest ones -- that the cross-entropy is averaged over (needs
+    ``lambda_voxel`` > 0); ``lambda_boundary``: the weight of the boundary term (``boundary_loss``; not together with
+    ``top_k``), ``boundary_spacing``: the voxel size (mm along H, W, D) its distance maps are measured in."""
 
     __slots__ = ("alpha", "beta", "batch", "include_background", "focal_gamma", "class_weights", "ignore_index",
-                 "lambda_region", "lambda_voxel", "top_k")
+                 "lambda_region", "lambda_voxel", "top_k", "lambda_boundary", "boundary_spacing")
 
     def __init__(self, alpha: float = 0.5, beta: float = 0.5, batch: bool = False, include_background: bool = True,
                  focal_gamma: float = 0.0, class_weights: Optional[Sequence[float]] = None,
                  ignore_index: Optional[int] = None, lambda_region: float = 1.0, lambda_voxel: float = 1.0,
-                 top_k: Optional[float] = None):
+                 top_k: Optional[float] = None, lambda_boundary: float = 0.0,
+                 boundary_spacing: Sequence[float] = (1.0, 1.0, 1.0)):
         f32_max = float(np.finfo(np.float32).max)
-        for name, v in (("alpha", alpha), ("beta", beta), ("lambda_region", lambda_region), ("lambda_voxel", lambda_voxel)):
+        for name, v in (("alpha", alpha), ("beta", beta), ("lambda_region", lambda_region), ("lambda_voxel", lambda_voxel),
+                        ("lambda_boundary", lambda_boundary)):
             if check_at_least(name, v, 0.0) > f32_max:
                 raise ValueError(f"{name} must be finite in fp32, got {v!r}")
         gamma = check_at_least("focal_gamma", focal_gamma, 0.0)
         if 0.0 < gamma < 1.0 or gamma > f32_max:
             raise ValueError(f"focal_gamma must be 0 or >= 1 (its gradient is unbounded at p -> 1 in between), got {focal_gamma!r}")
-        if float(lambda_region) == 0.0 and float(lambda_voxel) == 0.0:
-            raise ValueError("lambda_region and lambda_voxel must not both be 0")
+        if float(lambda_region) == 0.0 and float(lambda_voxel) == 0.0 and float(lambda_boundary) == 0.0:
+            raise ValueError("lambda_region and lambda_voxel and lambda_boundary must not all be 0")
+        try:
+            boundary_spacing = check_spacing(boundary_spacing)
+        except TypeError:
+            raise ValueError(f"boundary_spacing must be three positive sizes in mm, got {boundary_spacing!r}") from None
+        if any(a > f32_max for a in boundary_spacing):
+            raise ValueError(f"boundary_spacing must be finite in fp32, got {boundary_spacing!r}")
         if class_weights is not None:
             if isinstance(class_weights, torch.Tensor):
                 class_weights = class_weights.detach().cpu().tolist()
@@ -332,10 +346,13 @@ class SegLossSpec(ImmutableValue):
                 raise ValueError(f"top_k must be None or a fraction in (0, 1], got {top_k!r}")
             if float(lambda_voxel) == 0.0:
                 raise ValueError("top_k selects the voxels of the cross-entropy term: it needs lambda_voxel > 0")
+            if float(lambda_boundary) > 0.0:
+                raise ValueError("top_k together with lambda_boundary > 0 is not supported")
         self._set(alpha=float(alpha), beta=float(beta), batch=check_flag("batch", batch),
                   include_background=check_flag("include_background", include_background), focal_gamma=gamma,
                   class_weights=class_weights, ignore_index=ignore_index, lambda_region=float(lambda_region),
-                  lambda_voxel=float(lambda_voxel), top_k=top_k)
+                  lambda_voxel=float(lambda_voxel), top_k=top_k, lambda_boundary=float(lambda_boundary),
+                  boundary_spacing=boundary_spacing)
 
 
 def _seg_loss_torch(z: torch.Tensor, y: torch.Tensor, spec: SegLossSpec, w: Optional[torch.Tensor], record=None) -> torch.Tensor:
@@ -456,6 +473,207 @@ class _SegTopkFn(torch.autograd.Function):
         return dz, None, None, None, None
 
 
+# ---------------------------------------------------------------------------------------------
+# Boundary (signed-distance) term: batched distance maps + a fused value / gradient pass (csrc/distmap.hip)
+# ---------------------------------------------------------------------------------------------
+def _check_ignore(ignore_index):
+    if ignore_index is None:
+        return None
+    if not plain_int(ignore_index) or abs(int(ignore_index)) > 2 ** 24:
+        raise ValueError(f"ignore_index must be None or an int with |ignore_index| <= 2^24, got {ignore_index!r}")
+    return int(ignore_index)
+
+
+def _label_batch(target: torch.Tensor):
+    """``[B, 1, H, W, D]`` or ``[B, H, W, D]`` labels of any dtype -> (contiguous f32 ``[B, H, W, D]``, (H, W, D))."""
+    if target.dim() == 5 and target.shape[1] == 1:
+        target = target[:, 0]
+    if target.dim() != 4:
+        raise ValueError(f"target must be [B, 1, H, W, D] or [B, H, W, D], got {tuple(target.shape)}")
+    return target.detach().to(torch.float32).contiguous(), tuple(int(v) for v in target.shape[1:])
+
+
+def _distmap_launch(tgt: torch.Tensor, dims, num_classes: int, spacing, include_background: bool, ignore_index) -> torch.Tensor:
+    """tgt f32 [B, ...] with prod(dims) voxels per sample -> phi f32 [B, K, H, W, D]; the four launches, nothing else."""
+    B = tgt.shape[0]
+    K = num_classes - (0 if include_background else 1)
+    H, W, D = dims
+    if H > 65535 or W > 65535 or B * K * H * W * D >= 2 ** 31:
+        raise ValueError(f"distance maps of {B} x {K} x {dims}: H and W must be <= 65535 and B K H W D < 2^31")
+    phi = torch.empty((B, K, H, W, D), dtype=torch.float32, device=tgt.device)
+    ws = torch.empty(max(int(L.lib().mivp_distmap_ws(B, K, i3(dims))), 1), dtype=torch.uint8, device=tgt.device)
+    L.call("mivp_distmap_signed", L.ptr(tgt), B, num_classes, 1 if include_background else 0,
+           0 if ignore_index is None else ignore_index, 0 if ignore_index is None else 1, i3(dims), (C.c_float * 3)(*spacing),
+           L.ptr(phi), L.ptr(ws), L.stream())
+    return phi
+
+
+def signed_distance_maps(target: torch.Tensor, num_classes: int, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                         include_background: bool = False, ignore_index: Optional[int] = None) -> torch.Tensor:
+    """Signed Euclidean distance maps of a batch of label maps, on the GPU.  ``target [B, 1, H, W, D]`` (or ``[B, H, W, D]``)
+    class indices of any dtype -> float32 ``phi [B, K, H, W, D]`` for the classes c0 .. num_classes - 1 (c0 = 0 with
+    ``include_background``, else 1).  Per sample and class, M = {label == c}; a label that is no class for ``seg_loss``
+    (non-integer, outside [0, num_classes), or equal to ``ignore_index``) belongs to no M::
+
+        phi = distance to the nearest voxel of M                at voxels outside M     (> 0)
+        phi = -(distance to the nearest voxel outside M - 1)    at voxels inside M      (<= 0 at unit spacing)
+        phi = 0 everywhere                                      when M is empty or the whole sample
+
+    with distances ``sqrt(sum_a (spacing[a] delta_a)^2)``: ``one_hot2dist`` of the boundary-loss authors,
+    ``edt(~M, spacing) * ~M - (edt(M, spacing) - 1) * M`` with scipy's ``distance_transform_edt``.  Exact (the squared
+    distances are the exact integers at unit spacing), four launches whatever the batch and class counts are, nothing read
+    back: recordable.  H, W <= 65535 and B K H W D < 2^31."""
+    sp = check_spacing(spacing)
+    ncls = check_classes(num_classes)
+    check_gpu("target", target)
+    bg = check_flag("include_background", include_background)
+    ig = _check_ignore(ignore_index)
+    if ncls - (0 if bg else 1) < 1:
+        raise ValueError("num_classes=1 has no foreground class: pass include_background=True")
+    tgt, dims = _label_batch(target)
+    return _distmap_launch(tgt, dims, ncls, sp, bg, ig)
+
+
+class _BoundaryFn(torch.autograd.Function):
+    """The boundary term alone: value from a streaming pass + a one-workgroup reduction, the gradient from a second
+    streaming pass when backward asks for it (csrc/distmap.hip).  ``phi`` and ``weight`` are constants."""
+
+    @staticmethod
+    def forward(ctx, logits_cl, target, phi, weight, bg, ig, lam):
+        B, H, W, D, Cc = logits_cl.shape
+        vol = H * W * D
+        ws = torch.empty(L.lib().mivp_boundary_loss_ws(B, vol), dtype=torch.float32, device=logits_cl.device)
+        loss = torch.empty(1, dtype=torch.float32, device=logits_cl.device)
+        L.call("mivp_boundary_loss", L.ptr(logits_cl), L.ptr(target), L.ptr(phi), B, vol, Cc, 1 if bg else 0,
+               0 if ig is None else ig, 0 if ig is None else 1, lam, L.ptr(weight), L.ptr(ws), L.ptr(loss), L.ptr(None), 0,
+               L.stream())
+        ctx.save_for_backward(logits_cl, target, phi, ws)
+        ctx.weight, ctx.opts = weight, (bg, ig, lam)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits_cl, target, phi, ws = ctx.saved_tensors
+        B, H, W, D, Cc = logits_cl.shape
+        bg, ig, lam = ctx.opts
+        g = g.detach().to(torch.float32).contiguous()
+        dz = torch.empty_like(logits_cl)
+        L.call("mivp_boundary_loss_grad", L.ptr(logits_cl), L.ptr(target), L.ptr(phi), B, H * W * D, Cc, 1 if bg else 0,
+               0 if ig is None else ig, 0 if ig is None else 1, lam, L.ptr(ctx.weight), L.ptr(ws), L.ptr(g), L.ptr(dz), 0,
+               L.stream())
+        return dz, None, None, None, None, None, None
+
+
+class _SegBoundaryFn(torch.autograd.Function):
+    """``_SegLossFn`` plus the boundary term: mivp_seg_loss, the distance maps of the step's labels, mivp_boundary_loss; the
+    backward runs mivp_seg_loss_grad and adds the boundary term's gradient onto the same ``dz`` (accumulate = 1)."""
+
+    @staticmethod
+    def forward(ctx, logits_cl, target, weights, spec, bweight):
+        B, H, W, D, Cc = logits_cl.shape
+        vol = H * W * D
+        dev = logits_cl.device
+        ws = torch.empty(L.lib().mivp_seg_loss_ws(B, vol), dtype=torch.float32, device=dev)
+        bws = torch.empty(L.lib().mivp_boundary_loss_ws(B, vol), dtype=torch.float32, device=dev)
+        loss = torch.empty(2, dtype=torch.float32, device=dev)
+        ig = spec.ignore_index
+        L.call("mivp_seg_loss", L.ptr(logits_cl), L.ptr(target), B, vol, Cc, 1 if spec.include_background else 0,
+               1 if spec.batch else 0, spec.alpha, spec.beta, spec.focal_gamma, L.ptr(weights), 0 if ig is None else ig,
+               0 if ig is None else 1, spec.lambda_region, spec.lambda_voxel, L.ptr(ws), L.ptr(loss), L.ptr(None), L.stream())
+        phi = _distmap_launch(target, (H, W, D), Cc, spec.boundary_spacing, spec.include_background, ig)
+        L.call("mivp_boundary_loss", L.ptr(logits_cl), L.ptr(target), L.ptr(phi), B, vol, Cc,
+               1 if spec.include_background else 0, 0 if ig is None else ig, 0 if ig is None else 1, spec.lambda_boundary,
+               L.ptr(bweight), L.ptr(bws), C.c_void_p(loss.data_ptr() + 4), L.ptr(None), 0, L.stream())
+        ctx.save_for_backward(logits_cl, target, ws, phi, bws)
+        ctx.weights, ctx.spec, ctx.bweight = weights, spec, bweight
+        return loss[0] + loss[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits_cl, target, ws, phi, bws = ctx.saved_tensors
+        spec, ig = ctx.spec, ctx.spec.ignore_index
+        B, H, W, D, Cc = logits_cl.shape
+        g = g.detach().to(torch.float32).contiguous()
+        dz = torch.empty_like(logits_cl)
+        L.call("mivp_seg_loss_grad", L.ptr(logits_cl), L.ptr(target), B, H * W * D, Cc, 1 if spec.include_background else 0,
+               1 if spec.batch else 0, spec.alpha, spec.beta, spec.focal_gamma, L.ptr(ctx.weights), 0 if ig is None else ig,
+               0 if ig is None else 1, spec.lambda_region, spec.lambda_voxel, L.ptr(ws), L.ptr(g), L.ptr(dz), L.stream())
+        L.call("mivp_boundary_loss_grad", L.ptr(logits_cl), L.ptr(target), L.ptr(phi), B, H * W * D, Cc,
+               1 if spec.include_background else 0, 0 if ig is None else ig, 0 if ig is None else 1, spec.lambda_boundary,
+               L.ptr(ctx.bweight), L.ptr(bws), L.ptr(g), L.ptr(dz), 1, L.stream())
+        return dz, None, None, None, None
+
+
+def _boundary_torch(z: torch.Tensor, y: torch.Tensor, dist: torch.Tensor, bg: bool, ig, weight) -> torch.Tensor:
+    """The formulas of ``boundary_loss`` in plain torch ops, differentiable by autograd: z [B, vol, C], y [B, vol] labels,
+    dist [B, K, vol]."""
+    Cc = z.shape[-1]
+    y = y.to(z.dtype if z.dtype in (torch.float32, torch.float64) else torch.float32)
+    valid = (y >= 0) & (y < Cc) & (y == y.floor())
+    if ig is not None:
+        valid = valid & (y != ig)
+    c0 = 0 if bg else 1
+    p = torch.softmax(z, dim=-1)[..., c0:]
+    num = (p * dist.to(z.dtype).transpose(1, 2) * valid.to(z.dtype).unsqueeze(-1)).sum()
+    loss = num / ((Cc - c0) * valid.sum().clamp(min=1).to(z.dtype))
+    return loss if weight is None else loss * weight.to(z.dtype).reshape(())
+
+
+def _check_boundary_weight(weight, device):
+    if weight is None:
+        return None
+    if not isinstance(weight, torch.Tensor) or weight.numel() != 1:
+        raise ValueError("weight must be None or a tensor holding one number")
+    if weight.device != device:
+        raise ValueError(f"weight must be on the logits' device {device}, got {weight.device}")
+    return weight.detach()
+
+
+def boundary_loss(logits: torch.Tensor, target: torch.Tensor, *, include_background: bool = False,
+                  ignore_index: Optional[int] = None, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                  dist: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The boundary loss of Kervadec et al. (MIDL 2019).  logits [B, C, H, W, D], target [B, 1, H, W, D] (or [B, H, W, D])
+    class indices of any dtype.  With p = softmax_c(z), phi = ``signed_distance_maps(target, C, spacing, ...)`` (or ``dist``,
+    [B, K, H, W, D], when given), V the valid voxels of the batch (the rule of ``seg_loss``), N = |V|, K = C - c0::
+
+        loss = weight sum_{v in V} sum_{c >= c0} p_c(v) phi_c(v) / (K max(N, 1))
+
+    ``weight``: a one-element tensor on the logits' device (None = 1) that is read on the device, so a recorded step follows
+    a schedule of it.  ``phi`` is a constant of the step.  Channels-last f32 CUDA logits with C <= 8 take the kernels: the
+    four launches of the maps (unless ``dist`` is given), then two streaming passes; nothing read back, recordable.  Any
+    other layout, dtype or device takes the same formulas as plain torch ops and needs ``dist``."""
+    if logits.dim() != 5:
+        raise ValueError(f"logits must be [B, C, H, W, D], got {tuple(logits.shape)}")
+    B, Cc = logits.shape[0], logits.shape[1]
+    if Cc < 2:
+        raise ValueError(f"logits must have at least 2 classes, got {Cc}")
+    if target.numel() != logits.numel() // Cc or target.shape[0] != B:
+        raise ValueError(f"target must be [B, 1, H, W, D] for logits {tuple(logits.shape)}, got {tuple(target.shape)}")
+    bg = check_flag("include_background", include_background)
+    ig = _check_ignore(ignore_index)
+    sp = check_spacing(spacing)
+    weight = _check_boundary_weight(weight, logits.device)
+    K = Cc - (0 if bg else 1)
+    dims = tuple(int(v) for v in logits.shape[2:])
+    if dist is not None:
+        if not isinstance(dist, torch.Tensor) or tuple(dist.shape) != (B, K) + dims or dist.device != logits.device:
+            raise ValueError(f"dist must be a [B, K, H, W, D] = {(B, K) + dims} tensor on the logits' device, got "
+                             f"{tuple(dist.shape) if isinstance(dist, torch.Tensor) else dist!r}")
+        dist = dist.detach()
+    base = logits.permute(0, 2, 3, 4, 1)
+    if logits.is_cuda and logits.dtype == torch.float32 and base.is_contiguous() and Cc <= SEG_LOSS_MAX_CLASSES:
+        tgt = target.detach().to(torch.float32).contiguous()
+        phi = _distmap_launch(tgt, dims, Cc, sp, bg, ig) if dist is None else dist.to(torch.float32).contiguous()
+        if weight is not None:
+            weight = weight.to(torch.float32).contiguous()
+        return _BoundaryFn.apply(base, tgt, phi, weight, bg, ig, 1.0)
+    if dist is None:
+        raise RuntimeError("boundary_loss: only channels-last f32 GPU logits with at most 8 classes build their distance maps "
+                           "(on the device); any other layout, dtype or device needs dist=, e.g. signed_distance_maps(target, "
+                           "...) of a GPU copy of the labels (the package does not import scipy)")
+    return _boundary_torch(base.reshape(B, -1, Cc), target.detach().reshape(B, -1), dist.reshape(B, K, -1), bg, ig, weight)
+
+
 _seg_weight_cache = {}
 
 
@@ -481,7 +699,8 @@ def _seg_weights(spec: SegLossSpec, class_weights, n_classes: int, device) -> Op
 
 
 def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
-             class_weights: Optional[torch.Tensor] = None, _record=None) -> torch.Tensor:
+             class_weights: Optional[torch.Tensor] = None, _record=None,
+             boundary_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Tversky region term + weighted (focal) softmax cross-entropy with an ignore label.  logits [B, C, H, W, D], target
     [B, 1, H, W, D] (or [B, H, W, D]) class indices of any dtype; ``class_weights``: a [C] tensor on the logits' device that
     replaces ``spec.class_weights``.
@@ -508,9 +727,16 @@ def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
     The normaliser is k, not the weight sum; tied voxels share the remaining weight equally, so the gradient does not
     depend on the order of the voxels; without ties it is autograd's through ``torch.topk``.  Finite logits only.
 
+    With ``spec.lambda_boundary`` > 0 the loss gains ``lambda_boundary boundary_weight boundary`` with ``boundary`` the value
+    of ``boundary_loss(logits, target, include_background=, ignore_index=, spacing=spec.boundary_spacing)``: the signed
+    distance maps of the step's labels are built on the device inside the call.  ``boundary_weight``: a one-element tensor
+    on the logits' device (None = 1), read on the device (``SegLoss`` owns one).
+
     Channels-last f32 CUDA logits (the view the HIP model returns) with C <= 8 take the fused kernels: two streaming passes
-    (with ``top_k``: an exact radix select on one stored 32-bit key per voxel between them), nothing read back, recordable.
-    Any other layout, dtype or device takes the same formulas as plain torch ops."""
+    (with ``top_k``: an exact radix select on one stored 32-bit key per voxel between them; with the boundary term: the four
+    launches of the maps and two more passes, the gradient added onto the same buffer), nothing read back, recordable.
+    Any other layout, dtype or device takes the same formulas as plain torch ops (the boundary term then still needs GPU
+    labels for its maps)."""
     if not isinstance(spec, SegLossSpec):
         raise TypeError(f"spec must be a SegLossSpec, got {type(spec).__name__}")
     if logits.dim() != 5:
@@ -522,10 +748,20 @@ def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
         raise ValueError(f"target must be [B, 1, H, W, D] for logits {tuple(logits.shape)}, got {tuple(target.shape)}")
     w = _seg_weights(spec, class_weights, Cc, logits.device)
     base = logits.permute(0, 2, 3, 4, 1)
+    boundary = spec.lambda_boundary > 0.0
+    bw = _check_boundary_weight(boundary_weight, logits.device) if boundary else None
     if logits.is_cuda and logits.dtype == torch.float32 and base.is_contiguous() and Cc <= SEG_LOSS_MAX_CLASSES:
         tgt = target.detach().to(torch.float32).contiguous()
         if w is not None and (w.dtype != torch.float32 or not w.is_contiguous()):
             w = w.detach().float().contiguous()
+        if boundary:
+            if bw is not None:
+                bw = bw.to(torch.float32).contiguous()
+            if spec.lambda_region == 0.0 and spec.lambda_voxel == 0.0:     # the boundary term alone
+                dims = tuple(int(v) for v in logits.shape[2:])
+                phi = _distmap_launch(tgt, dims, Cc, spec.boundary_spacing, spec.include_background, spec.ignore_index)
+                return _BoundaryFn.apply(base, tgt, phi, bw, spec.include_background, spec.ignore_index, spec.lambda_boundary)
+            return _SegBoundaryFn.apply(base, tgt, None if w is None else w.detach(), spec, bw)
         if spec.top_k is None:
             return _SegLossFn.apply(base, tgt, None if w is None else w.detach(), spec)
         vol = tgt.numel() // B
@@ -534,8 +770,18 @@ def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
             off = _seg_topk_record_offset(B, vol)
             _record.append(ws[off:off + 5])
         return _SegTopkFn.apply(base, tgt, None if w is None else w.detach(), spec, ws)
-    return _seg_loss_torch(base.reshape(B, -1, Cc), target.detach().reshape(B, -1), spec, None if w is None else w.detach(),
-                           _record)
+    zf, yf = base.reshape(B, -1, Cc), target.detach().reshape(B, -1)
+    if not boundary:
+        return _seg_loss_torch(zf, yf, spec, None if w is None else w.detach(), _record)
+    if not target.is_cuda:
+        raise RuntimeError("seg_loss: the distance maps of the boundary term are built on the GPU (no CPU fallback, the "
+                           "package does not import scipy); use boundary_loss(dist=...) with maps of your own")
+    dist = signed_distance_maps(target, Cc, spec.boundary_spacing, spec.include_background, spec.ignore_index)
+    term = spec.lambda_boundary * _boundary_torch(zf, yf, dist.reshape(B, dist.shape[1], -1), spec.include_background,
+                                                  spec.ignore_index, bw)
+    if spec.lambda_region == 0.0 and spec.lambda_voxel == 0.0:
+        return term
+    return _seg_loss_torch(zf, yf, spec, None if w is None else w.detach(), _record) + term
 
 
 class SegLoss(torch.nn.Module):
@@ -551,9 +797,22 @@ class SegLoss(torch.nn.Module):
         self.spec = spec
         self.register_buffer("class_weights", None if spec.class_weights is None
                              else torch.tensor(spec.class_weights, dtype=torch.float32))
+        # the weight of the boundary term on the device: a recorded step reads it, ``set_boundary_weight`` schedules it
+        self.register_buffer("boundary_weight", torch.ones(1, dtype=torch.float32), persistent=False)
         self._topk_record = None
 
+    def set_boundary_weight(self, value: float) -> None:
+        """Set the factor of the boundary term (``lambda_boundary`` times it is the term's weight): a stream-ordered copy into
+        the module's buffer, legal between the replays of a recorded step."""
+        v = check_finite("boundary weight", value)
+        if self.boundary_weight.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("SegLoss.set_boundary_weight inside a recording: a recording must not freeze today's weight "
+                               "into the graph; call it between replays")
+        self.boundary_weight.copy_(torch.tensor([v], dtype=torch.float32))
+
     def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if self.spec.lambda_boundary > 0.0:
+            return seg_loss(logits, target, self.spec, self.class_weights, boundary_weight=self.boundary_weight)
         if self.spec.top_k is None:
             return seg_loss(logits, target, self.spec, self.class_weights)
         record = []

@@ -1,6 +1,6 @@
 """Time the recorded loss + gradient of mivp_seg_loss (csrc/segloss.hip) against the Dice-focal kernels and eager torch.
 
-    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10]
+    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10] [--boundary]
 
 Shapes: 96^3 at B = 4 (the `downstream` step's) and 128 x 128 x 8 at B = 14, both C = 2.  Settings of the new entry:
   (a) Dice-equivalent options (alpha = beta = 0.5), lambda_voxel = 0
@@ -11,10 +11,22 @@ Shapes: 96^3 at B = 4 (the `downstream` step's) and 128 x 128 x 8 at B = 14, bot
 Baselines in the same job: mivp_dice_focal on the same operands with gamma = 4 and with the Dice term alone (gamma < 0), and
 the plain-torch composition of (b) (losses.seg_loss on a contiguous channels-first tensor) with autograd, eager.
 
+``--boundary`` times the boundary term instead (csrc/distmap.hip), same shapes, C = 2, no background class:
+  (a) Dice + weighted cross-entropy with 20 % ignored, the launches of SegLoss's forward and backward (mivp_seg_loss,
+      then mivp_seg_loss_grad): the path without the term
+  (b) the same with lambda_boundary > 0: plus the four launches of the distance maps, the term's value pass and its
+      gradient pass accumulating onto the same dz (the launches of losses._SegBoundaryFn)
+  (c) mivp_distmap_signed alone
+  (d) mivp_boundary_loss alone (value + gradient) on precomputed maps
+  (e) for scale, eager and on the CPU: scipy's distance_transform_edt per sample and side plus the torch term with autograd
+(a) - (d) are C-ABI call sequences on operands allocated beforehand, recorded in a HIP graph on one stream (no autograd
+inside a recording); (b) - (a) is written as a share of the `downstream` step.
+
 Each kernel variant is one call (value + gradient) recorded in a HIP graph; a run is `replays` replays between two device
 events after `warmup` replays; the figure is the median over `runs` runs with the spread (min .. max).  One JSON line per
 variant, then one summary line.  No time is a pass criterion."""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -94,13 +106,110 @@ def dice_focal_variant(z, y, dz, loss, gamma):
     return call
 
 
+def boundary_main(args):
+    """The boundary term: see the module docstring."""
+    import time
+    summary = {}
+    for name, B, dims in SHAPES:
+        vol, Cc = dims[0] * dims[1] * dims[2], 2
+        g = torch.Generator().manual_seed(1)
+        z = (2.0 * torch.randn((B, vol, Cc), generator=g)).to(DEV)
+        hh, ww, dd = torch.meshgrid(*[torch.arange(n) for n in dims], indexing="ij")
+        y = torch.zeros((B, 1) + dims)
+        for b in range(B):                                        # a few ellipsoid lesions per sample
+            for _ in range(4):
+                c = [float(torch.rand(1, generator=g)) * n for n in dims]
+                r = [max(1.5, (0.05 + 0.15 * float(torch.rand(1, generator=g))) * n) for n in dims]
+                y[b, 0][((hh - c[0]) / r[0]) ** 2 + ((ww - c[1]) / r[1]) ** 2 + ((dd - c[2]) / r[2]) ** 2 <= 1.0] = 1.0
+        y[torch.rand(y.shape, generator=g) < 0.2] = float(IGNORE)
+        yf = y.view(B, vol).to(DEV)
+        w = torch.tensor(WEIGHTS, dtype=torch.float32, device=DEV)
+        # every operand is allocated here, outside the recordings: the recorded calls are the launches of the product path
+        # (losses._SegLossFn / _SegBoundaryFn, forward then backward) and nothing else
+        dz, loss = torch.empty_like(z), torch.empty(2, dtype=torch.float32, device=DEV)
+        one = torch.ones(1, dtype=torch.float32, device=DEV)     # the incoming gradient, the boundary weight
+        sws = torch.empty(int(L.lib().mivp_seg_loss_ws(B, vol)), dtype=torch.float32, device=DEV)
+        bws = torch.empty(int(L.lib().mivp_boundary_loss_ws(B, vol)), dtype=torch.float32, device=DEV)
+        K, d3, sp = Cc - 1, (C.c_int32 * 3)(*dims), (C.c_float * 3)(1.0, 1.0, 1.0)
+        mws = torch.empty(int(L.lib().mivp_distmap_ws(B, K, d3)), dtype=torch.uint8, device=DEV)
+        phi = torch.empty((B, K, vol), dtype=torch.float32, device=DEV)
+        lam = 0.01
+
+        def seg_value():
+            L.call("mivp_seg_loss", L.ptr(z), L.ptr(yf), B, vol, Cc, 0, 0, 0.5, 0.5, 0.0, L.ptr(w), IGNORE, 1, 1.0, 1.0, L.ptr(sws),
+                   L.ptr(loss), None, L.stream())
+
+        def seg_grad():
+            L.call("mivp_seg_loss_grad", L.ptr(z), L.ptr(yf), B, vol, Cc, 0, 0, 0.5, 0.5, 0.0, L.ptr(w), IGNORE, 1, 1.0, 1.0,
+                   L.ptr(sws), L.ptr(one), L.ptr(dz), L.stream())
+
+        def maps_alone():
+            L.call("mivp_distmap_signed", L.ptr(yf), B, Cc, 0, IGNORE, 1, d3, sp, L.ptr(phi), L.ptr(mws), L.stream())
+
+        def plain_step():
+            seg_value()
+            seg_grad()
+
+        def boundary_step():
+            seg_value()
+            maps_alone()
+            L.call("mivp_boundary_loss", L.ptr(z), L.ptr(yf), L.ptr(phi), B, vol, Cc, 0, IGNORE, 1, lam, L.ptr(one), L.ptr(bws),
+                   C.c_void_p(loss.data_ptr() + 4), None, 0, L.stream())
+            seg_grad()
+            L.call("mivp_boundary_loss_grad", L.ptr(z), L.ptr(yf), L.ptr(phi), B, vol, Cc, 0, IGNORE, 1, lam, L.ptr(one),
+                   L.ptr(bws), L.ptr(one), L.ptr(dz), 1, L.stream())
+
+        def term_alone():
+            L.call("mivp_boundary_loss", L.ptr(z), L.ptr(yf), L.ptr(phi), B, vol, Cc, 0, IGNORE, 1, 1.0, None, L.ptr(bws),
+                   L.ptr(loss), L.ptr(dz), 0, L.stream())
+
+        res = {}
+        for key, label, call in (("a", "(a) dice + weighted CE, value then gradient", plain_step),
+                                 ("b", "(b) the same with the boundary term", boundary_step),
+                                 ("c", "(c) the distance maps alone", maps_alone),
+                                 ("d", "(d) mivp_boundary_loss alone, maps given", term_alone)):
+            r = timed(recorded(call), args.runs, args.replays, args.warmup)
+            r.update(shape=name, variant=label, share_of_step=r["ms"] / STEP_MS)
+            res[key] = r
+            summary[f"{name} | {label}"] = [round(r[k], 4) for k in ("ms", "lo", "hi")]
+            print(json.dumps(r), flush=True)
+        extra = res["b"]["ms"] - res["a"]["ms"]
+        summary[f"{name} | (b) - (a)"] = dict(ms=round(extra, 4), share_of_step=round(extra / STEP_MS, 4))
+        try:
+            from scipy import ndimage
+        except ImportError:
+            ndimage = None
+        if ndimage is not None:
+            yc, zc = y[:, 0].numpy(), z.cpu()
+            ms = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                maps = []
+                for b in range(B):
+                    M = yc[b] == 1.0
+                    maps.append(ndimage.distance_transform_edt(~M) * ~M - (ndimage.distance_transform_edt(M) - 1.0) * M
+                                if M.any() and not M.all() else 0.0 * M)
+                dist = torch.from_numpy(__import__("numpy").stack(maps)).float().view(B, 1, *dims)
+                zl = zc.clone().requires_grad_(True)
+                losses.boundary_loss(zl.view(B, *dims, Cc).permute(0, 4, 1, 2, 3).contiguous(), y, ignore_index=IGNORE,
+                                     dist=dist).backward()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            r = dict(ms=statistics.median(ms), lo=min(ms), hi=max(ms), shape=name, variant="(e) scipy EDT + eager torch term, CPU")
+            summary[f"{name} | (e) scipy + torch, CPU"] = [round(r[k], 2) for k in ("ms", "lo", "hi")]
+            print(json.dumps(r), flush=True)
+    print(json.dumps({"bench_boundary_ms": summary}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--replays", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--boundary", action="store_true", help="time the boundary term (DESIGN 4.35) instead")
     args = ap.parse_args()
     assert args.runs >= 3
+    if args.boundary:
+        return boundary_main(args)
     summary = {}
     for name, B, dims in SHAPES:
         vol, Cc = dims[0] * dims[1] * dims[2], 2
