@@ -556,6 +556,55 @@ int mivp_boundary_loss_grad(const float* logits, const float* target, const floa
                             const float* weight, const float* workspace, const float* gscale, float* dlogits,
                             int32_t accumulate, mivp_stream_t stream);
 
+/* clDice (soft-skeleton) loss term (Shit et al., CVPR 2021) and the soft skeleton itself (csrc/cldice.hip; mivp_amd/losses.py
+ * soft_skeleton / cldice_loss / SegLossSpec(lambda_cldice=...)).  These entry points joined ABI 18 without a
+ * bump: they are additive and no earlier signature changed.
+ *
+ * Fields are planar f32 [nf][H][W][D] (dims = {H, W, D}, host), finite values.  For a field x and n = iterations in 1 .. 16:
+ *   erode(x)(v)  = min of x over v and its 6 face neighbours inside the volume
+ *   dilate(x)(v) = max of x over the 3x3x3 cube around v inside the volume
+ *   E_0 = x, E_{j+1} = erode(E_j);  O_j = dilate(E_{j+1});  d_j = relu(E_j - O_j)                j = 0 .. n
+ *   S_0 = d_0, S_j = S_{j-1} + relu(d_j - S_{j-1} d_j)                                           j = 1 .. n
+ * every operation rounded on its own (no fused multiply-add), relu(x) = x > 0 ? x : +0: the bits of the clDice authors'
+ * soft_skel.  mivp_cldice_skeleton writes skel = S_n in n + 1 launches whatever nf is.  keep != 0 stores what the backward
+ * needs; workspace = mivp_cldice_skeleton_ws(nf, dims, iterations, keep) FLOATS (0 for arguments the call would refuse), with
+ * F = nf H W D:  keep: E_1 .. E_{n+1} [n + 1][F] | O_0 .. O_n [n + 1][F] | two gradient fields [2][F];  else [2][F].
+ * mivp_cldice_skeleton_grad: dx = d loss / d x from gskel = d loss / d S_n, on the keep workspace of the forward of the same
+ * x.  Min and max hand the gradient of a pooled voxel to the k voxels of its window that hold the selected value, 1 / k each
+ * (the result does not depend on memory order); relu'(0) = 0.  It overwrites the O fields: ONE backward per forward.
+ * Gather form, no atomics, n + 3 launches.  Limits: nf <= 32767, H W D < 2^31, nf H W D (2 n + 8) <= 2^40.
+ *
+ * mivp_cldice_loss: logits f32 [B, vol, C] channels-last (2 <= C <= 8), target f32 [B, vol]; validity rule of mivp_seg_loss.
+ * p = softmax_c(z) and t = one-hot(label), both taken as 0 at invalid voxels; classes c >= 1 always, K = C - 1; s = smooth > 0;
+ * sums over the voxels of a sample (of the batch with batch != 0):
+ *   SP_c = S_n(p_c), SL_c = S_n(t_c);  Tprec = (sum SP_c t_c + s) / (sum SP_c + s),  Tsens = (sum SL_c p_c + s) / (sum SL_c + s)
+ *   cl_c = 1 - 2 Tprec Tsens / (Tprec + Tsens);  loss[0] = lambda_cldice weight[0] mean over (row, c >= 1) of cl_c
+ * (weight: DEVICE pointer to one float, NULL = 1).  dlogits may be NULL: the value alone.  Otherwise d loss / d logits
+ * (through SP, through Tsens' p, then the softmax; exactly 0 at an invalid voxel) is stored once per element, or with
+ * accumulate != 0 added to what dlogits holds with one rounded add (the bits of dlogits + g).  mivp_cldice_loss_grad runs
+ * the gradient on the SAME workspace with the SAME options, scaled by gscale[0] (device pointer, NULL = 1): once per value call.
+ * workspace: mivp_cldice_ws(B, C, dims, iterations) floats; with F = B K vol, fields [B][K][vol]:
+ *   [0, F)                       the planar p (p_c of class c = k + 1; 0 at invalid voxels)
+ *   [F, (2 n + 5) F)             the keep workspace of the p side (above); its two gradient fields also serve the
+ *                                erosions of the t side and end holding d loss / d p through SP
+ *   [(2 n + 5) F, (2 n + 7) F)   SP, SL
+ *   then partial rows [B K][bpb][4], sums [B K][4], gradient coefficients [B K][3]
+ * 2 n + 7 fields in all.  No atomics, nothing read back, every launch unconditional: equal calls give equal bits. */
+size_t mivp_cldice_skeleton_ws(int32_t nf, const int32_t* dims, int32_t iterations, int32_t keep);
+int mivp_cldice_skeleton(const float* x, int32_t nf, const int32_t* dims, int32_t iterations, float* skel, float* workspace,
+                         int32_t keep, mivp_stream_t stream);
+int mivp_cldice_skeleton_grad(const float* x, const float* gskel, int32_t nf, const int32_t* dims, int32_t iterations,
+                              float* workspace, float* dx, mivp_stream_t stream);
+size_t mivp_cldice_ws(int32_t B, int32_t C, const int32_t* dims, int32_t iterations);
+int mivp_cldice_loss(const float* logits, const float* target, int32_t B, int32_t C, const int32_t* dims, int32_t iterations,
+                     float smooth, int32_t batch, int32_t ignore_index, int32_t has_ignore, float lambda_cldice,
+                     const float* weight, float* workspace, float* loss, float* dlogits, int32_t accumulate,
+                     mivp_stream_t stream);
+int mivp_cldice_loss_grad(const float* logits, const float* target, int32_t B, int32_t C, const int32_t* dims,
+                          int32_t iterations, float smooth, int32_t batch, int32_t ignore_index, int32_t has_ignore,
+                          float lambda_cldice, const float* weight, float* workspace, const float* gscale, float* dlogits,
+                          int32_t accumulate, mivp_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* downstream head on the LOW-resolution decoder output                      */
 /* (swin_unetr.py:351-355 nn.Upsample x2 trilinear, then :229-237 BatchNorm3d */

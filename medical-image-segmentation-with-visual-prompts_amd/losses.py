@@ -16,6 +16,9 @@
 * ``signed_distance_maps`` / ``boundary_loss`` / ``SegLossSpec(lambda_boundary=...)`` -- the boundary loss of Kervadec et al.
   (MIDL 2019): softmax probabilities integrated against the signed distance maps of the labels, the maps built on the device
   per step by a batched exact distance transform (csrc/distmap.hip).
+* ``soft_skeleton`` / ``cldice_loss`` / ``SegLossSpec(lambda_cldice=...)`` -- the clDice topology term of Shit et al. (CVPR
+  2021): each mask against the other one's soft skeleton, skeletons and their backward as 3-D min / max brick kernels
+  (csrc/cldice.hip).
 """
 from __future__ import annotations
 
@@ -292,6 +295,22 @@ SEG_LOSS_MAX_CLASSES = 8
 SEG_LOSS_SMOOTH = 1e-5
 
 
+CLDICE_MAX_ITERATIONS = 16
+
+
+def _check_iterations(n, name="iterations") -> int:
+    if not plain_int(n) or not 1 <= int(n) <= CLDICE_MAX_ITERATIONS:
+        raise ValueError(f"{name} must be an int in 1..{CLDICE_MAX_ITERATIONS}, got {n!r}")
+    return int(n)
+
+
+def _check_smooth(v, name="smooth") -> float:
+    s = check_finite(name, v)
+    if not s > 0.0 or s > float(np.finfo(np.float32).max) or float(np.float32(s)) == 0.0:
+        raise ValueError(f"{name} must be > 0 and finite in fp32, got {v!r}")
+    return s
+
+
 class SegLossSpec(ImmutableValue):
     """Options of ``seg_loss`` (an immutable value; the formulas are in the docstring of ``seg_loss``).
 
@@ -302,26 +321,33 @@ class SegLossSpec(ImmutableValue):
     or None; ``lambda_region``, ``lambda_voxel``, ``lambda_boundary`` >= 0, not all three 0; ``top_k``: None, or the fraction
     in (0, 1] of the batch's valid voxels -- the hardest ones -- that the cross-entropy is averaged over (needs
     ``lambda_voxel`` > 0); ``lambda_boundary``: the weight of the boundary term (``boundary_loss``; not together with
-    ``top_k``), ``boundary_spacing``: the voxel size (mm along H, W, D) its distance maps are measured in."""
+    ``top_k``), ``boundary_spacing``: the voxel size (mm along H, W, D) its distance maps are measured in;
+    ``lambda_cldice`` >= 0: the weight of the clDice term (``cldice_loss``; not together with ``top_k``; the four lambdas
+    must not all be 0), ``cldice_iterations``: its skeleton iterations, an int in 1..16, ``cldice_smooth`` > 0."""
 
     __slots__ = ("alpha", "beta", "batch", "include_background", "focal_gamma", "class_weights", "ignore_index",
-                 "lambda_region", "lambda_voxel", "top_k", "lambda_boundary", "boundary_spacing")
+                 "lambda_region", "lambda_voxel", "top_k", "lambda_boundary", "boundary_spacing", "lambda_cldice",
+                 "cldice_iterations", "cldice_smooth")
 
     def __init__(self, alpha: float = 0.5, beta: float = 0.5, batch: bool = False, include_background: bool = True,
                  focal_gamma: float = 0.0, class_weights: Optional[Sequence[float]] = None,
                  ignore_index: Optional[int] = None, lambda_region: float = 1.0, lambda_voxel: float = 1.0,
                  top_k: Optional[float] = None, lambda_boundary: float = 0.0,
-                 boundary_spacing: Sequence[float] = (1.0, 1.0, 1.0)):
+                 boundary_spacing: Sequence[float] = (1.0, 1.0, 1.0), lambda_cldice: float = 0.0,
+                 cldice_iterations: int = 3, cldice_smooth: float = 1.0):
         f32_max = float(np.finfo(np.float32).max)
         for name, v in (("alpha", alpha), ("beta", beta), ("lambda_region", lambda_region), ("lambda_voxel", lambda_voxel),
-                        ("lambda_boundary", lambda_boundary)):
+                        ("lambda_boundary", lambda_boundary), ("lambda_cldice", lambda_cldice)):
             if check_at_least(name, v, 0.0) > f32_max:
                 raise ValueError(f"{name} must be finite in fp32, got {v!r}")
         gamma = check_at_least("focal_gamma", focal_gamma, 0.0)
         if 0.0 < gamma < 1.0 or gamma > f32_max:
             raise ValueError(f"focal_gamma must be 0 or >= 1 (its gradient is unbounded at p -> 1 in between), got {focal_gamma!r}")
-        if float(lambda_region) == 0.0 and float(lambda_voxel) == 0.0 and float(lambda_boundary) == 0.0:
+        if float(lambda_region) == 0.0 and float(lambda_voxel) == 0.0 and float(lambda_boundary) == 0.0 \
+                and float(lambda_cldice) == 0.0:                   # (the message of the three-lambda rule, kept)
             raise ValueError("lambda_region and lambda_voxel and lambda_boundary must not all be 0")
+        cldice_iterations = _check_iterations(cldice_iterations, "cldice_iterations")
+        cldice_smooth = _check_smooth(cldice_smooth, "cldice_smooth")
         try:
             boundary_spacing = check_spacing(boundary_spacing)
         except TypeError:
@@ -348,11 +374,14 @@ class SegLossSpec(ImmutableValue):
                 raise ValueError("top_k selects the voxels of the cross-entropy term: it needs lambda_voxel > 0")
             if float(lambda_boundary) > 0.0:
                 raise ValueError("top_k together with lambda_boundary > 0 is not supported")
+            if float(lambda_cldice) > 0.0:
+                raise ValueError("top_k together with lambda_cldice > 0 is not supported")
         self._set(alpha=float(alpha), beta=float(beta), batch=check_flag("batch", batch),
                   include_background=check_flag("include_background", include_background), focal_gamma=gamma,
                   class_weights=class_weights, ignore_index=ignore_index, lambda_region=float(lambda_region),
                   lambda_voxel=float(lambda_voxel), top_k=top_k, lambda_boundary=float(lambda_boundary),
-                  boundary_spacing=boundary_spacing)
+                  boundary_spacing=boundary_spacing, lambda_cldice=float(lambda_cldice),
+                  cldice_iterations=cldice_iterations, cldice_smooth=cldice_smooth)
 
 
 def _seg_loss_torch(z: torch.Tensor, y: torch.Tensor, spec: SegLossSpec, w: Optional[torch.Tensor], record=None) -> torch.Tensor:
@@ -674,6 +703,274 @@ def boundary_loss(logits: torch.Tensor, target: torch.Tensor, *, include_backgro
     return _boundary_torch(base.reshape(B, -1, Cc), target.detach().reshape(B, -1), dist.reshape(B, K, -1), bg, ig, weight)
 
 
+# ---------------------------------------------------------------------------------------------
+# clDice (soft-skeleton) term: brick kernels for the skeleton and its backward (csrc/cldice.hip)
+# ---------------------------------------------------------------------------------------------
+_CROSS = ((0, 0, 0), (0, 0, -1), (0, 0, 1), (0, -1, 0), (0, 1, 0), (-1, 0, 0), (1, 0, 0))
+_CUBE = tuple((a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1))
+
+
+def _shifted(xp: torch.Tensor, off) -> torch.Tensor:
+    """The one-voxel-padded tensor seen from every voxel v at v + off."""
+    h, w, d = (n - 2 for n in xp.shape[-3:])
+    return xp[..., 1 + off[0]:1 + off[0] + h, 1 + off[1]:1 + off[1] + w, 1 + off[2]:1 + off[2] + d]
+
+
+class _WindowPoolFn(torch.autograd.Function):
+    """min (7-point cross) or max (3x3x3 cube) over the window inside the volume, as plain torch ops.  Backward: the voxels
+    of a window that hold the selected value share its gradient equally (``max_pool3d`` gives all to the first)."""
+
+    @staticmethod
+    def forward(ctx, x, is_max):
+        window = _CUBE if is_max else _CROSS
+        xp = F.pad(x, (1,) * 6, value=float("-inf") if is_max else float("inf"))
+        out = _shifted(xp, window[0]).clone()
+        for off in window[1:]:
+            out = torch.maximum(out, _shifted(xp, off)) if is_max else torch.minimum(out, _shifted(xp, off))
+        ctx.save_for_backward(x, out)
+        ctx.window = window
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, out = ctx.saved_tensors
+        xp = F.pad(x, (1,) * 6, value=float("nan"))
+        k = torch.zeros_like(x)
+        for off in ctx.window:
+            k = k + (_shifted(xp, off) == out).to(x.dtype)
+        hp = F.pad(g / k.clamp(min=1.0), (1,) * 6, value=0.0)
+        mp = F.pad(out, (1,) * 6, value=float("nan"))
+        gx = torch.zeros_like(x)
+        for off in ctx.window:
+            back = tuple(-o for o in off)
+            gx = gx + torch.where(_shifted(mp, back) == x, _shifted(hp, back), torch.zeros_like(x))
+        return gx, None
+
+
+def _relu0(x: torch.Tensor) -> torch.Tensor:
+    return torch.where(x > 0, x, torch.zeros_like(x))               # +0 at 0 and below, gradient 0 there
+
+
+def _soft_skeleton_torch(x: torch.Tensor, n: int) -> torch.Tensor:
+    """The definition of ``soft_skeleton`` in plain torch ops on [..., H, W, D]."""
+    e = x
+    s = None
+    for j in range(n + 1):
+        e1 = _WindowPoolFn.apply(e, False)
+        d = _relu0(e - _WindowPoolFn.apply(e1, True))
+        s = d if j == 0 else s + _relu0(d - s * d)
+        e = e1
+    return s
+
+
+class _SkeletonFn(torch.autograd.Function):
+    """``soft_skeleton`` on the kernels: n + 1 launches forward, n + 3 backward."""
+
+    @staticmethod
+    def forward(ctx, x, n):
+        B, K, H, W, D = x.shape
+        keep = 1 if ctx.needs_input_grad[0] else 0
+        ws = torch.empty(max(int(L.lib().mivp_cldice_skeleton_ws(B * K, i3((H, W, D)), n, keep)), 1), dtype=torch.float32,
+                         device=x.device)
+        out = torch.empty_like(x)
+        L.call("mivp_cldice_skeleton", L.ptr(x), B * K, i3((H, W, D)), n, L.ptr(out), L.ptr(ws), keep, L.stream())
+        ctx.save_for_backward(x, ws)
+        ctx.n, ctx.spent = n, False
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, ws = ctx.saved_tensors
+        if ctx.spent:
+            raise RuntimeError("soft_skeleton: the backward overwrites its workspace; a second backward needs a new forward")
+        ctx.spent = True
+        B, K, H, W, D = x.shape
+        g = g.detach().to(torch.float32).contiguous()
+        dx = torch.empty_like(x)
+        L.call("mivp_cldice_skeleton_grad", L.ptr(x), L.ptr(g), B * K, i3((H, W, D)), ctx.n, L.ptr(ws), L.ptr(dx), L.stream())
+        return dx, None
+
+
+def soft_skeleton(x: torch.Tensor, iterations: int = 3) -> torch.Tensor:
+    """The soft skeleton of the clDice authors (``soft_skel``), differentiable.  x [B, K, H, W, D], finite; with::
+
+        erode(x)(v)  = min of x over v and its 6 face neighbours inside the volume
+        dilate(x)(v) = max of x over the 3x3x3 cube around v inside the volume
+        E_0 = x, E_{j+1} = erode(E_j);  O_j = dilate(E_{j+1});  d_j = relu(E_j - O_j)            j = 0 .. iterations
+        S_0 = d_0, S_j = S_{j-1} + relu(d_j - S_{j-1} d_j)
+
+    it returns S_iterations, every operation rounded on its own.  Backward: the voxels of a window that hold the selected
+    minimum / maximum share its gradient equally (so it does not depend on memory order), relu'(0) = 0.  Contiguous f32
+    CUDA tensors take the kernels (csrc/cldice.hip; one backward per forward); anything else the same definition as plain
+    torch ops."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        raise ValueError(f"x must be a [B, K, H, W, D] tensor, got {tuple(x.shape) if isinstance(x, torch.Tensor) else x!r}")
+    n = _check_iterations(iterations)
+    if x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0:
+        return _SkeletonFn.apply(x, n)
+    return _soft_skeleton_torch(x, n)
+
+
+def _cldice_torch(z: torch.Tensor, y: torch.Tensor, dims, n: int, smooth: float, batch: bool, ig, weight) -> torch.Tensor:
+    """The formulas of ``cldice_loss`` in plain torch ops: z [B, vol, C], y [B, vol] labels."""
+    B, _, Cc = z.shape
+    y = y.to(z.dtype if z.dtype in (torch.float32, torch.float64) else torch.float32)
+    valid = (y >= 0) & (y < Cc) & (y == y.floor())
+    if ig is not None:
+        valid = valid & (y != ig)
+    idx = torch.where(valid, y, torch.zeros_like(y)).long()
+    m = valid.to(z.dtype).unsqueeze(-1)
+    p = (torch.softmax(z, dim=-1) * m)[..., 1:].transpose(1, 2).reshape(B, Cc - 1, *dims)
+    t = (F.one_hot(idx, Cc).to(z.dtype) * m)[..., 1:].transpose(1, 2).reshape(B, Cc - 1, *dims)
+    sp, sl = _soft_skeleton_torch(p, n), _soft_skeleton_torch(t, n)
+    ax = (0, 2, 3, 4) if batch else (2, 3, 4)
+    tprec = ((sp * t).sum(ax) + smooth) / (sp.sum(ax) + smooth)
+    tsens = ((sl * p).sum(ax) + smooth) / (sl.sum(ax) + smooth)
+    loss = (1.0 - 2.0 * tprec * tsens / (tprec + tsens)).mean()
+    return loss if weight is None else loss * weight.to(z.dtype).reshape(())
+
+
+def _cldice_args(spec_or_opts):
+    n, smooth, batch, ig, lam = spec_or_opts
+    return n, smooth, 1 if batch else 0, 0 if ig is None else ig, 0 if ig is None else 1, lam
+
+
+class _ClDiceFn(torch.autograd.Function):
+    """The clDice term alone (csrc/cldice.hip).  ``weight`` is a constant; opts = (iterations, smooth, batch, ignore, lambda)."""
+
+    @staticmethod
+    def forward(ctx, logits_cl, target, weight, opts):
+        B, H, W, D, Cc = logits_cl.shape
+        d3 = i3((H, W, D))
+        n, smooth, batch, ign, has, lam = _cldice_args(opts)
+        ws = torch.empty(int(L.lib().mivp_cldice_ws(B, Cc, d3, n)), dtype=torch.float32, device=logits_cl.device)
+        loss = torch.empty(1, dtype=torch.float32, device=logits_cl.device)
+        L.call("mivp_cldice_loss", L.ptr(logits_cl), L.ptr(target), B, Cc, d3, n, smooth, batch, ign, has, lam, L.ptr(weight),
+               L.ptr(ws), L.ptr(loss), L.ptr(None), 0, L.stream())
+        ctx.save_for_backward(logits_cl, target, ws)
+        ctx.weight, ctx.opts, ctx.spent = weight, opts, False
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits_cl, target, ws = ctx.saved_tensors
+        if ctx.spent:
+            raise RuntimeError("cldice_loss: the backward overwrites its workspace; a second backward needs a new forward")
+        ctx.spent = True
+        B, H, W, D, Cc = logits_cl.shape
+        n, smooth, batch, ign, has, lam = _cldice_args(ctx.opts)
+        g = g.detach().to(torch.float32).contiguous()
+        dz = torch.empty_like(logits_cl)
+        L.call("mivp_cldice_loss_grad", L.ptr(logits_cl), L.ptr(target), B, Cc, i3((H, W, D)), n, smooth, batch, ign, has, lam,
+               L.ptr(ctx.weight), L.ptr(ws), L.ptr(g), L.ptr(dz), 0, L.stream())
+        return dz, None, None, None
+
+
+class _SegTermsFn(torch.autograd.Function):
+    """The region + voxel terms (when either lambda is > 0), the boundary term (when lambda_boundary > 0) and the clDice
+    term, in that order; the backward runs their gradient passes in the same order, the first storing ``dz`` and the
+    others adding onto it (accumulate = 1)."""
+
+    @staticmethod
+    def forward(ctx, logits_cl, target, weights, spec, bweight, cweight):
+        B, H, W, D, Cc = logits_cl.shape
+        vol, dev, ig = H * W * D, logits_cl.device, spec.ignore_index
+        ign, has, bg = 0 if ig is None else ig, 0 if ig is None else 1, 1 if spec.include_background else 0
+        d3 = i3((H, W, D))
+        loss = torch.zeros(3, dtype=torch.float32, device=dev)
+        saved = [logits_cl, target]
+        ctx.base = spec.lambda_region > 0.0 or spec.lambda_voxel > 0.0
+        ctx.boundary = spec.lambda_boundary > 0.0
+        if ctx.base:
+            ws = torch.empty(L.lib().mivp_seg_loss_ws(B, vol), dtype=torch.float32, device=dev)
+            L.call("mivp_seg_loss", L.ptr(logits_cl), L.ptr(target), B, vol, Cc, bg, 1 if spec.batch else 0, spec.alpha, spec.beta,
+                   spec.focal_gamma, L.ptr(weights), ign, has, spec.lambda_region, spec.lambda_voxel, L.ptr(ws), L.ptr(loss),
+                   L.ptr(None), L.stream())
+            saved.append(ws)
+        if ctx.boundary:
+            bws = torch.empty(L.lib().mivp_boundary_loss_ws(B, vol), dtype=torch.float32, device=dev)
+            phi = _distmap_launch(target, (H, W, D), Cc, spec.boundary_spacing, spec.include_background, ig)
+            L.call("mivp_boundary_loss", L.ptr(logits_cl), L.ptr(target), L.ptr(phi), B, vol, Cc, bg, ign, has,
+                   spec.lambda_boundary, L.ptr(bweight), L.ptr(bws), C.c_void_p(loss.data_ptr() + 4), L.ptr(None), 0, L.stream())
+            saved += [phi, bws]
+        cws = torch.empty(int(L.lib().mivp_cldice_ws(B, Cc, d3, spec.cldice_iterations)), dtype=torch.float32, device=dev)
+        L.call("mivp_cldice_loss", L.ptr(logits_cl), L.ptr(target), B, Cc, d3, spec.cldice_iterations, spec.cldice_smooth,
+               1 if spec.batch else 0, ign, has, spec.lambda_cldice, L.ptr(cweight), L.ptr(cws), C.c_void_p(loss.data_ptr() + 8),
+               L.ptr(None), 0, L.stream())
+        saved.append(cws)
+        ctx.save_for_backward(*saved)
+        ctx.weights, ctx.spec, ctx.bweight, ctx.cweight, ctx.spent = weights, spec, bweight, cweight, False
+        return (loss[0] + loss[1]) + loss[2]
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = list(ctx.saved_tensors)
+        logits_cl, target = saved[0], saved[1]
+        rest = saved[2:]
+        if ctx.spent:
+            raise RuntimeError("seg_loss: the clDice backward overwrites its workspace; a second backward needs a new forward")
+        ctx.spent = True
+        spec, ig = ctx.spec, ctx.spec.ignore_index
+        ign, has, bg = 0 if ig is None else ig, 0 if ig is None else 1, 1 if spec.include_background else 0
+        B, H, W, D, Cc = logits_cl.shape
+        vol = H * W * D
+        g = g.detach().to(torch.float32).contiguous()
+        dz = torch.empty_like(logits_cl)
+        acc = 0
+        if ctx.base:
+            ws = rest.pop(0)
+            L.call("mivp_seg_loss_grad", L.ptr(logits_cl), L.ptr(target), B, vol, Cc, bg, 1 if spec.batch else 0, spec.alpha,
+                   spec.beta, spec.focal_gamma, L.ptr(ctx.weights), ign, has, spec.lambda_region, spec.lambda_voxel, L.ptr(ws),
+                   L.ptr(g), L.ptr(dz), L.stream())
+            acc = 1
+        if ctx.boundary:
+            phi, bws = rest.pop(0), rest.pop(0)
+            L.call("mivp_boundary_loss_grad", L.ptr(logits_cl), L.ptr(target), L.ptr(phi), B, vol, Cc, bg, ign, has,
+                   spec.lambda_boundary, L.ptr(ctx.bweight), L.ptr(bws), L.ptr(g), L.ptr(dz), acc, L.stream())
+            acc = 1
+        cws = rest.pop(0)
+        L.call("mivp_cldice_loss_grad", L.ptr(logits_cl), L.ptr(target), B, Cc, i3((H, W, D)), spec.cldice_iterations,
+               spec.cldice_smooth, 1 if spec.batch else 0, ign, has, spec.lambda_cldice, L.ptr(ctx.cweight), L.ptr(cws), L.ptr(g),
+               L.ptr(dz), acc, L.stream())
+        return dz, None, None, None, None, None
+
+
+def cldice_loss(logits: torch.Tensor, target: torch.Tensor, *, iterations: int = 3, smooth: float = 1.0, batch: bool = False,
+                ignore_index: Optional[int] = None, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The clDice loss of Shit et al. (CVPR 2021).  logits [B, C, H, W, D], target [B, 1, H, W, D] (or [B, H, W, D]) class
+    indices of any dtype.  p = softmax_c(z) and t = one-hot(label), both taken as 0 at invalid voxels (the rule of
+    ``seg_loss``; ``dz`` is exactly 0 there); classes c >= 1 always (the skeleton of the background is not meaningful);
+    with SP_c = ``soft_skeleton(p_c, iterations)``, SL_c = ``soft_skeleton(t_c, iterations)`` (a constant), s = ``smooth``
+    and sums over the voxels of a sample (of the batch with ``batch``)::
+
+        Tprec = (sum SP_c t_c + s) / (sum SP_c + s)        Tsens = (sum SL_c p_c + s) / (sum SL_c + s)
+        loss  = weight mean over (b, c >= 1) [over c >= 1 with batch] of 1 - 2 Tprec Tsens / (Tprec + Tsens)
+
+    ``weight``: a one-element tensor on the logits' device (None = 1), read on the device.  Channels-last f32 CUDA logits
+    with C <= 8 take the kernels (2 n + 8 launches for value and gradient, nothing read back, recordable; one backward per
+    forward); any other layout, dtype or device takes the same formulas as plain torch ops."""
+    if logits.dim() != 5:
+        raise ValueError(f"logits must be [B, C, H, W, D], got {tuple(logits.shape)}")
+    B, Cc = logits.shape[0], logits.shape[1]
+    if Cc < 2:
+        raise ValueError(f"logits must have at least 2 classes, got {Cc}")
+    if target.numel() != logits.numel() // Cc or target.shape[0] != B:
+        raise ValueError(f"target must be [B, 1, H, W, D] for logits {tuple(logits.shape)}, got {tuple(target.shape)}")
+    n = _check_iterations(iterations)
+    s = _check_smooth(smooth)
+    bt = check_flag("batch", batch)
+    ig = _check_ignore(ignore_index)
+    weight = _check_boundary_weight(weight, logits.device)
+    dims = tuple(int(v) for v in logits.shape[2:])
+    base = logits.permute(0, 2, 3, 4, 1)
+    if logits.is_cuda and logits.dtype == torch.float32 and base.is_contiguous() and Cc <= SEG_LOSS_MAX_CLASSES:
+        tgt = target.detach().to(torch.float32).contiguous()
+        if weight is not None:
+            weight = weight.to(torch.float32).contiguous()
+        return _ClDiceFn.apply(base, tgt, weight, (n, s, bt, ig, 1.0))
+    return _cldice_torch(base.reshape(B, -1, Cc), target.detach().reshape(B, -1), dims, n, s, bt, ig, weight)
+
+
 _seg_weight_cache = {}
 
 
@@ -700,7 +997,7 @@ def _seg_weights(spec: SegLossSpec, class_weights, n_classes: int, device) -> Op
 
 def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
              class_weights: Optional[torch.Tensor] = None, _record=None,
-             boundary_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+             boundary_weight: Optional[torch.Tensor] = None, cldice_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Tversky region term + weighted (focal) softmax cross-entropy with an ignore label.  logits [B, C, H, W, D], target
     [B, 1, H, W, D] (or [B, H, W, D]) class indices of any dtype; ``class_weights``: a [C] tensor on the logits' device that
     replaces ``spec.class_weights``.
@@ -732,6 +1029,11 @@ def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
     distance maps of the step's labels are built on the device inside the call.  ``boundary_weight``: a one-element tensor
     on the logits' device (None = 1), read on the device (``SegLoss`` owns one).
 
+    With ``spec.lambda_cldice`` > 0 the loss gains ``lambda_cldice cldice_weight cldice`` with ``cldice`` the value of
+    ``cldice_loss(logits, target, iterations=spec.cldice_iterations, smooth=spec.cldice_smooth, batch=spec.batch,
+    ignore_index=)`` (classes c >= 1 whatever ``include_background`` says); ``cldice_weight`` like ``boundary_weight``.  Its
+    gradient pass adds onto the same buffer as the other terms'.
+
     Channels-last f32 CUDA logits (the view the HIP model returns) with C <= 8 take the fused kernels: two streaming passes
     (with ``top_k``: an exact radix select on one stored 32-bit key per voxel between them; with the boundary term: the four
     launches of the maps and two more passes, the gradient added onto the same buffer), nothing read back, recordable.
@@ -750,10 +1052,16 @@ def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
     base = logits.permute(0, 2, 3, 4, 1)
     boundary = spec.lambda_boundary > 0.0
     bw = _check_boundary_weight(boundary_weight, logits.device) if boundary else None
+    cldice = spec.lambda_cldice > 0.0
+    cw = _check_boundary_weight(cldice_weight, logits.device) if cldice else None
     if logits.is_cuda and logits.dtype == torch.float32 and base.is_contiguous() and Cc <= SEG_LOSS_MAX_CLASSES:
         tgt = target.detach().to(torch.float32).contiguous()
         if w is not None and (w.dtype != torch.float32 or not w.is_contiguous()):
             w = w.detach().float().contiguous()
+        if cldice:
+            bw = None if bw is None else bw.to(torch.float32).contiguous()
+            cw = None if cw is None else cw.to(torch.float32).contiguous()
+            return _SegTermsFn.apply(base, tgt, None if w is None else w.detach(), spec, bw, cw)
         if boundary:
             if bw is not None:
                 bw = bw.to(torch.float32).contiguous()
@@ -771,6 +1079,14 @@ def seg_loss(logits: torch.Tensor, target: torch.Tensor, spec: SegLossSpec,
             _record.append(ws[off:off + 5])
         return _SegTopkFn.apply(base, tgt, None if w is None else w.detach(), spec, ws)
     zf, yf = base.reshape(B, -1, Cc), target.detach().reshape(B, -1)
+    if cldice:
+        dims = tuple(int(v) for v in logits.shape[2:])
+        term = spec.lambda_cldice * _cldice_torch(zf, yf, dims, spec.cldice_iterations, spec.cldice_smooth, spec.batch,
+                                                  spec.ignore_index, cw)
+        if not (boundary or spec.lambda_region > 0.0 or spec.lambda_voxel > 0.0):
+            return term
+        rest = SegLossSpec(**{**{k: getattr(spec, k) for k in SegLossSpec.__slots__}, "lambda_cldice": 0.0})
+        return seg_loss(logits, target, rest, class_weights, _record, boundary_weight) + term
     if not boundary:
         return _seg_loss_torch(zf, yf, spec, None if w is None else w.detach(), _record)
     if not target.is_cuda:
@@ -799,7 +1115,17 @@ class SegLoss(torch.nn.Module):
                              else torch.tensor(spec.class_weights, dtype=torch.float32))
         # the weight of the boundary term on the device: a recorded step reads it, ``set_boundary_weight`` schedules it
         self.register_buffer("boundary_weight", torch.ones(1, dtype=torch.float32), persistent=False)
+        # the same for the clDice term
+        self.register_buffer("cldice_weight", torch.ones(1, dtype=torch.float32), persistent=False)
         self._topk_record = None
+
+    def set_cldice_weight(self, value: float) -> None:
+        """Set the factor of the clDice term (``lambda_cldice`` times it is the term's weight), like ``set_boundary_weight``."""
+        v = check_finite("cldice weight", value)
+        if self.cldice_weight.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("SegLoss.set_cldice_weight inside a recording: a recording must not freeze today's weight "
+                               "into the graph; call it between replays")
+        self.cldice_weight.copy_(torch.tensor([v], dtype=torch.float32))
 
     def set_boundary_weight(self, value: float) -> None:
         """Set the factor of the boundary term (``lambda_boundary`` times it is the term's weight): a stream-ordered copy into
@@ -811,6 +1137,9 @@ class SegLoss(torch.nn.Module):
         self.boundary_weight.copy_(torch.tensor([v], dtype=torch.float32))
 
     def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if self.spec.lambda_cldice > 0.0:
+            return seg_loss(logits, target, self.spec, self.class_weights, boundary_weight=self.boundary_weight,
+                            cldice_weight=self.cldice_weight)
         if self.spec.lambda_boundary > 0.0:
             return seg_loss(logits, target, self.spec, self.class_weights, boundary_weight=self.boundary_weight)
         if self.spec.top_k is None:

@@ -1,6 +1,6 @@
 """Time the recorded loss + gradient of mivp_seg_loss (csrc/segloss.hip) against the Dice-focal kernels and eager torch.
 
-    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10] [--boundary]
+    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10] [--boundary | --cldice]
 
 Shapes: 96^3 at B = 4 (the `downstream` step's) and 128 x 128 x 8 at B = 14, both C = 2.  Settings of the new entry:
   (a) Dice-equivalent options (alpha = beta = 0.5), lambda_voxel = 0
@@ -21,6 +21,13 @@ the plain-torch composition of (b) (losses.seg_loss on a contiguous channels-fir
   (e) for scale, eager and on the CPU: scipy's distance_transform_edt per sample and side plus the torch term with autograd
 (a) - (d) are C-ABI call sequences on operands allocated beforehand, recorded in a HIP graph on one stream (no autograd
 inside a recording); (b) - (a) is written as a share of the `downstream` step.
+
+``--cldice`` times the clDice term instead (csrc/cldice.hip), same shapes and operands, C = 2, 3 iterations:
+  (a) as above: the path without the term
+  (b) the same with lambda_cldice > 0: mivp_cldice_loss after the value pass and mivp_cldice_loss_grad accumulating onto
+      the same dz after the gradient pass (the launches of losses._SegTermsFn)
+  (c) the skeleton passes of one side alone: mivp_cldice_skeleton (kept) + mivp_cldice_skeleton_grad on p_1 [B, 1, H, W, D]
+  (d) the clDice authors' max-pool composition of the term with autograd, eager, on the same GPU
 
 Each kernel variant is one call (value + gradient) recorded in a HIP graph; a run is `replays` replays between two device
 events after `warmup` replays; the figure is the median over `runs` runs with the spread (min .. max).  One JSON line per
@@ -106,22 +113,120 @@ def dice_focal_variant(z, y, dz, loss, gamma):
     return call
 
 
+def lesion_case(B, dims, Cc):
+    """(logits [B, vol, C] on the device, labels [B, 1, H, W, D] on the CPU): 2 randn logits, a few ellipsoid lesions of class 1
+    per sample, 20 % of the voxels the ignore label."""
+    vol = dims[0] * dims[1] * dims[2]
+    g = torch.Generator().manual_seed(1)
+    z = (2.0 * torch.randn((B, vol, Cc), generator=g)).to(DEV)
+    hh, ww, dd = torch.meshgrid(*[torch.arange(n) for n in dims], indexing="ij")
+    y = torch.zeros((B, 1) + dims)
+    for b in range(B):
+        for _ in range(4):
+            c = [float(torch.rand(1, generator=g)) * n for n in dims]
+            r = [max(1.5, (0.05 + 0.15 * float(torch.rand(1, generator=g))) * n) for n in dims]
+            y[b, 0][((hh - c[0]) / r[0]) ** 2 + ((ww - c[1]) / r[1]) ** 2 + ((dd - c[2]) / r[2]) ** 2 <= 1.0] = 1.0
+    y[torch.rand(y.shape, generator=g) < 0.2] = float(IGNORE)
+    return z, y
+
+
+def cldice_main(args):
+    """The clDice term: see the module docstring."""
+    import torch.nn.functional as F
+    summary = {}
+    n, lam = 3, 0.5
+    for name, B, dims in SHAPES:
+        vol, Cc = dims[0] * dims[1] * dims[2], 2
+        z, y = lesion_case(B, dims, Cc)
+        yf = y.view(B, vol).to(DEV)
+        w = torch.tensor(WEIGHTS, dtype=torch.float32, device=DEV)
+        # every operand is allocated here, outside the recordings: the recorded calls are the launches of the product path
+        # (losses._SegLossFn / _SegTermsFn, forward then backward) and nothing else
+        dz, loss = torch.empty_like(z), torch.empty(2, dtype=torch.float32, device=DEV)
+        one = torch.ones(1, dtype=torch.float32, device=DEV)     # the incoming gradient, the term's weight
+        d3 = (C.c_int32 * 3)(*dims)
+        sws = torch.empty(int(L.lib().mivp_seg_loss_ws(B, vol)), dtype=torch.float32, device=DEV)
+        cws = torch.empty(int(L.lib().mivp_cldice_ws(B, Cc, d3, n)), dtype=torch.float32, device=DEV)
+        kws = torch.empty(int(L.lib().mivp_cldice_skeleton_ws(B, d3, n, 1)), dtype=torch.float32, device=DEV)
+        field = torch.softmax(z, -1)[..., 1].contiguous()        # [B, vol]: what the skeleton of the term works on
+        skel, gfield, dfield = torch.empty_like(field), torch.randn_like(field), torch.empty_like(field)
+
+        def seg_value():
+            L.call("mivp_seg_loss", L.ptr(z), L.ptr(yf), B, vol, Cc, 0, 0, 0.5, 0.5, 0.0, L.ptr(w), IGNORE, 1, 1.0, 1.0, L.ptr(sws),
+                   L.ptr(loss), None, L.stream())
+
+        def seg_grad():
+            L.call("mivp_seg_loss_grad", L.ptr(z), L.ptr(yf), B, vol, Cc, 0, 0, 0.5, 0.5, 0.0, L.ptr(w), IGNORE, 1, 1.0, 1.0,
+                   L.ptr(sws), L.ptr(one), L.ptr(dz), L.stream())
+
+        def plain_step():
+            seg_value()
+            seg_grad()
+
+        def cldice_step():
+            seg_value()
+            L.call("mivp_cldice_loss", L.ptr(z), L.ptr(yf), B, Cc, d3, n, 1.0, 0, IGNORE, 1, lam, L.ptr(one), L.ptr(cws),
+                   C.c_void_p(loss.data_ptr() + 4), None, 0, L.stream())
+            seg_grad()
+            L.call("mivp_cldice_loss_grad", L.ptr(z), L.ptr(yf), B, Cc, d3, n, 1.0, 0, IGNORE, 1, lam, L.ptr(one), L.ptr(cws),
+                   L.ptr(one), L.ptr(dz), 1, L.stream())
+
+        def skeleton_alone():
+            L.call("mivp_cldice_skeleton", L.ptr(field), B, d3, n, L.ptr(skel), L.ptr(kws), 1, L.stream())
+            L.call("mivp_cldice_skeleton_grad", L.ptr(field), L.ptr(gfield), B, d3, n, L.ptr(kws), L.ptr(dfield), L.stream())
+
+        res = {}
+        for key, label, call in (("a", "(a) dice + weighted CE, value then gradient", plain_step),
+                                 ("b", "(b) the same with the clDice term", cldice_step),
+                                 ("c", "(c) one side's skeleton passes alone, forward + backward", skeleton_alone)):
+            r = timed(recorded(call), args.runs, args.replays, args.warmup)
+            r.update(shape=name, variant=label, share_of_step=r["ms"] / STEP_MS)
+            res[key] = r
+            summary[f"{name} | {label}"] = [round(r[k], 4) for k in ("ms", "lo", "hi")]
+            print(json.dumps(r), flush=True)
+        extra = res["b"]["ms"] - res["a"]["ms"]
+        summary[f"{name} | (b) - (a)"] = dict(ms=round(extra, 4), share_of_step=round(extra / STEP_MS, 4))
+
+        # the clDice authors' composition on the same GPU: max-pool erosions / dilations, autograd (first-index ties)
+        def erode(img):
+            return torch.min(torch.min(-F.max_pool3d(-img, (3, 1, 1), 1, (1, 0, 0)), -F.max_pool3d(-img, (1, 3, 1), 1, (0, 1, 0))),
+                             -F.max_pool3d(-img, (1, 1, 3), 1, (0, 0, 1)))
+
+        def skel_of(img):
+            s = F.relu(img - F.max_pool3d(erode(img), 3, 1, 1))
+            for _ in range(n):
+                img = erode(img)
+                d = F.relu(img - F.max_pool3d(erode(img), 3, 1, 1))
+                s = s + F.relu(d - s * d)
+            return s
+
+        plain = z.view(B, *dims, Cc).permute(0, 4, 1, 2, 3).contiguous().requires_grad_(True)
+        yd = y.to(DEV)
+        valid = (yd != float(IGNORE)).float()
+        t = (yd == 1.0).float()
+
+        def eager():
+            plain.grad = None
+            p = torch.softmax(plain, 1)[:, 1:] * valid
+            sp, sl = skel_of(p), skel_of(t)
+            ax = (2, 3, 4)
+            tprec = ((sp * t).sum(ax) + 1.0) / (sp.sum(ax) + 1.0)
+            tsens = ((sl * p).sum(ax) + 1.0) / (sl.sum(ax) + 1.0)
+            (lam * (1.0 - 2.0 * tprec * tsens / (tprec + tsens)).mean()).backward()
+        r = timed(eager, args.runs, max(3, args.replays // 10), 3)
+        r.update(shape=name, variant="(d) torch max-pool composition of the term, eager", share_of_step=r["ms"] / STEP_MS)
+        summary[f"{name} | (d) torch eager"] = [round(r[k], 4) for k in ("ms", "lo", "hi")]
+        print(json.dumps(r), flush=True)
+    print(json.dumps({"bench_cldice_ms": summary}))
+
+
 def boundary_main(args):
     """The boundary term: see the module docstring."""
     import time
     summary = {}
     for name, B, dims in SHAPES:
         vol, Cc = dims[0] * dims[1] * dims[2], 2
-        g = torch.Generator().manual_seed(1)
-        z = (2.0 * torch.randn((B, vol, Cc), generator=g)).to(DEV)
-        hh, ww, dd = torch.meshgrid(*[torch.arange(n) for n in dims], indexing="ij")
-        y = torch.zeros((B, 1) + dims)
-        for b in range(B):                                        # a few ellipsoid lesions per sample
-            for _ in range(4):
-                c = [float(torch.rand(1, generator=g)) * n for n in dims]
-                r = [max(1.5, (0.05 + 0.15 * float(torch.rand(1, generator=g))) * n) for n in dims]
-                y[b, 0][((hh - c[0]) / r[0]) ** 2 + ((ww - c[1]) / r[1]) ** 2 + ((dd - c[2]) / r[2]) ** 2 <= 1.0] = 1.0
-        y[torch.rand(y.shape, generator=g) < 0.2] = float(IGNORE)
+        z, y = lesion_case(B, dims, Cc)
         yf = y.view(B, vol).to(DEV)
         w = torch.tensor(WEIGHTS, dtype=torch.float32, device=DEV)
         # every operand is allocated here, outside the recordings: the recorded calls are the launches of the product path
@@ -206,10 +311,13 @@ def main():
     ap.add_argument("--replays", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--boundary", action="store_true", help="time the boundary term (DESIGN 4.35) instead")
+    ap.add_argument("--cldice", action="store_true", help="time the clDice term (DESIGN 4.36) instead")
     args = ap.parse_args()
     assert args.runs >= 3
     if args.boundary:
         return boundary_main(args)
+    if args.cldice:
+        return cldice_main(args)
     summary = {}
     for name, B, dims in SHAPES:
         vol, Cc = dims[0] * dims[1] * dims[2], 2
