@@ -1056,6 +1056,38 @@ int mivp_lesion_match(const MivpRegionTable* pred, const MivpRegionTable* target
 int mivp_lesion_best_score(const MivpRegionTable* pred, const MivpRegionTable* target, const void* pairs,
                            int64_t max_pairs, int64_t min_size, double iou_threshold, float* best_score, float* score,
                            mivp_stream_t stream);
+/* Per-lesion shape descriptors (csrc/region_shape.hip; mivp_amd/regions.py region_shape).  These entry points
+ * joined ABI 18 without a bump: they are additive and no earlier signature changed.  Two launches after mivp_region_stats,
+ * nothing read back; every output is a DEVICE array of `capacity` entries, entry r describes the component labelled r + 1,
+ * every entry is written by every call and an absent region's entry is zero.
+ *   mivp_region_shape: one pass over labels, the dense int32 [H][W][D] map that mivp_region_stats wrote (values 0..n; labels
+ *     above capacity are skipped).  dims = {H, W, D} (host), fewer than 2^31 voxels and NO DIMENSION ABOVE 65535: a
+ *     coordinate product is then below 2^32 and, with fewer than 2^31 voxels, no sum can reach 2^63.  The outputs are zeroed
+ *     inside the call, on the stream.  Integer atomics only: exact and bitwise reproducible.
+ *       moment2 int64 [capacity][6]: the sums over the region's voxels of h*h, w*w, d*d, h*w, h*d, w*d on voxel indices.
+ *       faces   int64 [capacity][3]: the exposed voxel faces normal to h, w and d.  A face of a voxel of region r is exposed
+ *               when the voxel across it does not carry label r or lies outside the volume; both sides of the region
+ *               count, so an isolated voxel gives (2, 2, 2).
+ *       cells   int64 [capacity][2]: the distinct vertices and the distinct edges of the region's closed cubical complex
+ *               (the union of its closed unit cubes).  A vertex is shared by up to 8 voxels and an edge by up to 4; the first
+ *               incident voxel of the region in raster order counts it.  The distinct faces follow from
+ *               F = (6 * size + faces[0] + faces[1] + faces[2]) / 2, and the Euler number is V - E + F - size.
+ *   mivp_region_axes: one thread per region, float64.  size, coord_sum: the arrays of the MivpRegionTable; moment2 as above;
+ *     sh, sw, sd: the voxel spacing in mm (> 0).  covariance, eigenvalues and axes are float64 arrays, 8-byte aligned.
+ *       covariance  [capacity][3][3]: (n * M_ab - S_a * S_b), formed exactly in 128-bit integers, converted to float64 once
+ *                   (correctly rounded), divided by (double)n * (double)n (exact below 2^26 voxels) and multiplied by
+ *                   spacing_a * spacing_b: the covariance of the voxel centres in mm^2, without a 1/12 voxel-extent term.
+ *                   A one-voxel region and a region flat along an axis have exact zeros in that row and column.
+ *       eigenvalues [capacity][3]: of that matrix, descending, by a cyclic Jacobi iteration with the fixed sweep order
+ *                   (h,w), (h,d), (w,d) and at most 16 sweeps (it ends early only when all off-diagonals are exactly 0);
+ *                   values that round below zero are clamped to 0.
+ *       axes        [capacity][3][3]: row i is the unit eigenvector of eigenvalue i in (h, w, d) order, its sign chosen so
+ *                   that its largest-magnitude component is positive (ties: the first such component).
+ *     Entries with size == 0 are all zero. */
+int mivp_region_shape(const int32_t* labels, const int32_t* dims, int32_t capacity, int64_t* moment2, int64_t* faces,
+                      int64_t* cells, mivp_stream_t stream);
+int mivp_region_axes(const int64_t* size, const int64_t* coord_sum, const int64_t* moment2, int32_t capacity, double sh,
+                     double sw, double sd, void* covariance, void* eigenvalues, void* axes, mivp_stream_t stream);
 
 /* Calibration and threshold-sweep tables (csrc/calibration.hip; mivp_amd/calibration.py).  These entry points
  * joined ABI 18 without a bump: they are additive and no earlier signature changed.  probs: contiguous fp32 [C][H][W][D],

@@ -15,7 +15,7 @@ __all__ = ["_lib", "geometry"]
 def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
-                "components", "scan", "regions", "augment", "calibration", "scanstats", "window_fit"):
+                "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -32,7 +32,8 @@ def __getattr__(name):
     if name in ("label_components", "postprocess_labels"):
         from . import components
         return getattr(components, name)
-    if name in ("region_stats", "lesion_metrics", "lesion_score_metrics", "RegionTable", "LesionReport"):
+    if name in ("region_stats", "lesion_metrics", "lesion_score_metrics", "RegionTable", "LesionReport", "region_shape",
+                "RegionShape"):
         from . import regions
         return getattr(regions, name)
     if name in ("calibration_tables", "CalibrationReport"):

@@ -38,14 +38,38 @@ Definitions (written out, as in ``mivp_amd.components``; ``tests/regions_ref.py`
   = tp_pred / (tp_pred + fp), ``average_precision`` = sum_i (S_i - S_{i-1}) P_i along the thresholds; ``froc_score`` =
   the mean over the fp levels of the largest sensitivity among the thresholds with fp <= level, 0 where none.  ``vmax`` is
   exact, so all of this is bitwise reproducible (``vmean`` comes from float64 atomics and is not the score).
+- **Shape descriptors** (``region_shape(table)``, csrc/region_shape.hip; ``tests/shape_ref.py`` restates them
+  with Python sets and integers).  ``RegionShape`` holds device tensors of ``max_regions`` entries: ``moment2`` int64
+  ``[6]`` = the sums of h*h, w*w, d*d, h*w, h*d, w*d over the region's voxel indices; ``faces`` int64 ``[3]`` = the
+  exposed voxel faces normal to h, w, d (the voxel across does not carry the region's label or lies outside the volume;
+  an isolated voxel has (2, 2, 2)); ``cells`` int64 ``[2]`` = the distinct vertices V and edges E of the union of the
+  region's closed unit cubes; ``covariance_mm2`` float64 ``[3, 3]`` = (n M_ab - S_a S_b) / n^2 * spacing_a * spacing_b with
+  the numerator formed exactly (the covariance of the voxel centres, **without the 1/12 voxel-extent term**: the
+  pyradiomics convention); ``eigenvalues`` float64 ``[3]`` of it, descending, clamped at 0; ``axes`` float64 ``[3, 3]``,
+  row i the unit eigenvector of eigenvalue i in (h, w, d) order with its largest-magnitude component positive.  Derived,
+  in float64: ``euler`` (int64) = V - E + F - size with F = (6 size + sum(faces)) / 2; ``major_axis_length``,
+  ``minor_axis_length``, ``least_axis_length`` = 4 sqrt(lambda_i); ``elongation`` = sqrt(lambda_1 / lambda_0) and
+  ``flatness`` = sqrt(lambda_2 / lambda_0), NaN where lambda_0 is 0; ``surface_area_mm2`` = faces_h sw sd + faces_w sh sd +
+  faces_d sh sw; ``surface_to_volume`` = surface_area_mm2 / volume_mm3; ``sphericity`` = (36 pi V^2)^(1/3) / A with V the
+  volume and A the surface area.  Three conventions:
+
+  - The Euler number is that of the **union of closed voxels**: the 26-connectivity convention (voxels that share only a
+    vertex or an edge are joined), whatever connectivity labelled the map.  It equals components - tunnels + cavities.
+  - The surface area is the **voxel-face area**.  It overestimates a smooth surface: a digital ball tends to 1.5 times its
+    true area, so its sphericity tends to 2/3.  A weighted (Lindblad) or mesh estimator is out of scope.
+  - The maximum Feret diameter, convex hulls and shape on the scan's native grid are out of scope.
+
+  The integer fields and ``euler`` are exact and bitwise reproducible; the float64 fields are a fixed sequence of
+  operations on them and reproducible too.  No dimension may exceed 65535 (the int64 moments then cannot overflow).
 
 Numerics: every integer field is exact and bitwise reproducible, and so is everything derived from integers.  For float32
 images ``vmin`` / ``vmax`` are exact, and ``vsum`` / ``vsqsum`` are float64 sums added with hardware atomics: **these two
 (and ``vmean`` / ``vstd`` from them) are the one pair of fields that is not bitwise reproducible**; their error is within
 ``size * 2^-53 * sum|x|`` (``sum x^2``) of any other float64 summation order.
 
-Nothing here reads back to the host, so ``region_stats`` and ``lesion_metrics`` can be recorded in a ``torch.cuda.graph``.
-``RegionTable.cpu()`` and ``LesionReport.cpu()`` are the synchronising calls; they raise ``RuntimeError`` on overflow.
+Nothing here reads back to the host, so ``region_stats``, ``region_shape`` and ``lesion_metrics`` can be recorded in a
+``torch.cuda.graph``.  ``RegionTable.cpu()``, ``RegionShape.cpu()`` and ``LesionReport.cpu()`` are the synchronising calls;
+they raise ``RuntimeError`` on overflow.
 """
 from __future__ import annotations
 
@@ -61,6 +85,7 @@ from . import _lib as L
 from ._lib import RegionTable as _CTable
 from ._host import (LABEL_DTYPES, check_classes, check_connectivity, check_gpu, check_min_size, check_spacing, class_mask,
                     i3, label_volume, workspace)
+from .shape import MAX_SHAPE_DIM, RegionShape, _check_shape_table, region_shape  # noqa: F401  (regions.region_shape)
 
 _IMAGE_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.float32: 3, torch.int16: 4}
 

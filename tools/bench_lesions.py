@@ -15,6 +15,12 @@ fused reduction, with the image), ``lesion_metrics_ms`` (two labellings + reduct
 ``scatter_reduce`` over ``label_components`` output, labelling included) and, unless ``--no-scipy``, ``scipy_stats_cpu_s``
 (``scipy.ndimage.label`` + ``find_objects`` / ``sum`` / ``center_of_mass`` on the CPU).
 
+``--shape`` runs something else and nothing of the above: ``region_shape`` (mivp_amd.regions) recorded in a
+graph and replayed, on the ``lesions`` reference map and on ``all_fg``, three timings each, next to ``region_stats`` (no
+image) and an eager torch composition of the second moments and exposed-face counts, all in the one job.  One JSON line per
+case with the three timings of each, ``shape_over_stats``, and ``shape_over_bytes`` = the replay over what the label map's
+bytes take at 6.3 TB/s.
+
 Kernel shares: ``rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o les -- python tools/bench_lesions.py --volumes 2
 --no-scipy --no-torch``."""
 import argparse
@@ -150,15 +156,78 @@ def run_case(name, pred, tgt, image, conn, volumes, warmup, scipy_too, torch_too
     return rec
 
 
+STREAM_TBS = 6.3          # the streaming rate DESIGN 4.8 measured; what the bytes of a pass predict is bytes / this
+
+
+def torch_shape(labels, cap=MAX_REGIONS):
+    """The second moments and the exposed-face counts of ``region_shape`` from eager torch ops over the dense labels (the
+    vertex and edge counts have no short composition and are left out, so this does less than the fused pass)."""
+    import torch
+    H, W, D = labels.shape
+    ok = (labels > 0) & (labels <= cap)
+    idx = torch.nonzero(ok.reshape(-1)).squeeze(1)
+    r = labels.reshape(-1)[idx].long() - 1
+    c = (idx // (W * D), (idx // D) % W, idx % D)
+    out = {}
+    for name, (a, b) in zip(("hh", "ww", "dd", "hw", "hd", "wd"), ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+        out[name] = torch.zeros(cap, dtype=torch.int64, device=labels.device).scatter_add(0, r, c[a] * c[b])
+    for axis, name in enumerate("hwd"):
+        differs = labels.narrow(axis, 1, labels.shape[axis] - 1) != labels.narrow(axis, 0, labels.shape[axis] - 1)
+        edge = torch.ones_like(labels.narrow(axis, 0, 1), dtype=torch.bool)
+        exposed = torch.cat([edge, differs], axis).to(torch.int64) + torch.cat([differs, edge], axis).to(torch.int64)
+        out["faces_" + name] = torch.zeros(cap, dtype=torch.int64, device=labels.device).scatter_add(
+            0, r, exposed.reshape(-1)[idx])
+    return out
+
+
+def run_shape_case(name, x, conn, volumes, warmup, runs=3):
+    """``region_shape`` recorded in a graph against ``region_stats`` and the eager torch composition, `runs` timings each."""
+    import torch
+    from mivp_amd.regions import region_shape, region_stats
+    tab = region_stats(x, 2, connectivity=conn, max_regions=MAX_REGIONS)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        region_shape(tab)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        shp = region_shape(tab)
+    replays = max(volumes, 20)                           # a replay is short: time more of them
+    shape_ms = [timed(g.replay, replays, warmup) for _ in range(runs)]
+    stats_ms = [timed(lambda: region_stats(x, 2, connectivity=conn, max_regions=MAX_REGIONS), volumes, warmup)
+                for _ in range(runs)]
+    torch_ms = [timed(lambda: torch_shape(tab.labels), volumes, warmup) for _ in range(runs)]
+    nbytes = tab.labels.numel() * 4                      # the pass reads the label map once
+    bytes_ms = nbytes / (STREAM_TBS * 1e12) * 1e3
+    mid = sorted(shape_ms)[runs // 2]
+    return {"case": name, "shape": list(x.shape), "connectivity": conn, "regions": int(tab.n),
+            "euler_sum": int(shp.euler.sum()), "region_shape_graph_ms": shape_ms, "region_stats_ms": stats_ms,
+            "torch_shape_ms": torch_ms, "shape_over_stats": round(mid / sorted(stats_ms)[runs // 2], 3),
+            "torch_over_shape": round(sorted(torch_ms)[runs // 2] / mid, 1), "label_bytes": nbytes,
+            "bytes_at_stream_rate_ms": round(bytes_ms, 4), "shape_over_bytes": round(mid / bytes_ms, 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--volumes", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-scipy", action="store_true", help="skip the CPU scipy timing")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch composition (kernel traces of this change alone)")
+    ap.add_argument("--shape", action="store_true",
+                    help="time region_shape (recorded in a graph) on the lesion map and on all_fg, next to region_stats and "
+                         "an eager torch composition of the moments and face counts, three runs each; nothing else runs")
     a = ap.parse_args()
     import torch
     import mivp_amd  # noqa: F401
+    if a.shape:
+        dev = torch.device("cuda:0")
+        _, tgt = lesions(SHAPE, dev)
+        print(json.dumps(run_shape_case("lesions", tgt, 26, a.volumes, a.warmup)), flush=True)
+        ones = torch.ones(SHAPE, dtype=torch.uint8, device=dev)
+        print(json.dumps(run_shape_case("all_fg", ones, 26, a.volumes, a.warmup)), flush=True)
+        return
     try:
         import scipy.ndimage  # noqa: F401
         have_scipy = not a.no_scipy
