@@ -1089,6 +1089,47 @@ int mivp_region_shape(const int32_t* labels, const int32_t* dims, int32_t capaci
 int mivp_region_axes(const int64_t* size, const int64_t* coord_sum, const int64_t* moment2, int32_t capacity, double sh,
                      double sw, double sd, void* covariance, void* eigenvalues, void* axes, mivp_stream_t stream);
 
+/* Centreline extraction by 3-D thinning and the centreline counts (csrc/skeleton.hip; mivp_amd/skeleton.py).
+ * These entry points joined ABI 18 without a bump: they are additive and no earlier signature changed.  dims = {H, W, D}
+ * (host), volumes [H][W][D] row-major, fewer than 2^31 voxels; label dtypes as mivp_label_components (0 uint8, 1 int32,
+ * 2 int64, 3 float32); class_mask: bits 1..C-1 only, not empty; C <= 16.  No host synchronisation, integer arithmetic and
+ * integer atomics only: every result is exact and bitwise reproducible.
+ *   The object of a voxel is the set of voxels that hold its (selected) class; everything else, the outside of the volume
+ *   included, is background.  With obj the object voxels among the 26 neighbours, a voxel is SIMPLE iff obj is not empty and
+ *   is one component under 26-adjacency within the neighbourhood, and the background voxels among the 18-neighbours contain a
+ *   6-neighbour and all background 6-neighbours lie in one component of them under 6-adjacency; an END POINT has at most one
+ *   object neighbour.  One iteration marks the object voxels with a face neighbour outside their object, on the state it
+ *   starts from, then runs eight sub-passes, subfield s = (h&1)<<2 | (w&1)<<1 | (d&1) for s = 0..7: a sub-pass deletes every
+ *   marked voxel of its subfield that is simple on the current state and, with keep_endpoints, is no end point on it.
+ *   mivp_skeleton_begin: skeleton (uint8 [H][W][D]) = the class of labels where it is a set bit of class_mask, else 0.  With
+ *     workspace (mivp_skeleton_ws(dims) bytes, 4-byte aligned; may be NULL when only the selection is wanted) it also resets
+ *     the iteration state kept there.
+ *   mivp_skeleton_iter: iteration number `iteration` (1, 2, 3, .. in this order after mivp_skeleton_begin) on skeleton, in
+ *     place: one mark launch and up to eight sub-pass launches (a subfield without voxels has none).  The deletions of an
+ *     iteration are counted in the int32 word iteration & 1 at the start of the workspace (the mark launch zeroes it); every
+ *     launch of an iteration > 1 returns at once when the word of the iteration before is zero, so any number of iterations
+ *     may be issued without reading anything back.
+ *   mivp_skeleton_end: after `iteration` iterations were issued, iterations[0] (DEVICE int32) = the number that ran, the one
+ *     that deleted nothing included, and converged[0] = 1 when the last one issued deleted nothing (or did not run).
+ *   mivp_centerline_counts: one pass over the two label maps and their two skeletons.  counts: DEVICE int64 [C][4], per class
+ *     c: the voxels with skeleton_pred == c, those of them where target is c, the voxels with skeleton_target == c, those of
+ *     them where pred is c.  The launch ADDS to counts: zero it first, or pool scans in it.
+ *   mivp_skeleton_stats: one pass over one skeleton.  counts: DEVICE int64 [C][18], per class c of class_mask: the voxels that
+ *     hold c; those with 0, 1, 2 and >= 3 26-neighbours that hold c; then, for the 13 offsets (dh, dw, dd) whose first
+ *     non-zero component is positive, in lexicographic order, the voxel pairs that far apart that both hold c.  ADDS. */
+size_t mivp_skeleton_ws(const int32_t* dims);
+int mivp_skeleton_begin(const void* labels, int32_t dtype, const int32_t* dims, int32_t C, uint32_t class_mask,
+                        uint8_t* skeleton, void* workspace, mivp_stream_t stream);
+int mivp_skeleton_iter(uint8_t* skeleton, const int32_t* dims, int32_t keep_endpoints, int32_t iteration, void* workspace,
+                       mivp_stream_t stream);
+int mivp_skeleton_end(const void* workspace, int32_t iteration, int32_t* iterations, int32_t* converged,
+                      mivp_stream_t stream);
+int mivp_centerline_counts(const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype,
+                           const uint8_t* skeleton_pred, const uint8_t* skeleton_target, const int32_t* dims, int32_t C,
+                           int64_t* counts, mivp_stream_t stream);
+int mivp_skeleton_stats(const uint8_t* skeleton, const int32_t* dims, int32_t C, uint32_t class_mask, int64_t* counts,
+                        mivp_stream_t stream);
+
 /* Calibration and threshold-sweep tables (csrc/calibration.hip; mivp_amd/calibration.py).  These entry points
  * joined ABI 18 without a bump: they are additive and no earlier signature changed.  probs: contiguous fp32 [C][H][W][D],
  * target: a class map [H][W][D] of target_dtype (0 uint8, 1 int32, 2 int64, 3 float32), dims = {H, W, D} (host), fewer

@@ -15,7 +15,8 @@ __all__ = ["_lib", "geometry"]
 def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
-                "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit"):
+                "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit",
+                "skeleton"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -36,6 +37,10 @@ def __getattr__(name):
                 "RegionShape"):
         from . import regions
         return getattr(regions, name)
+    if name in ("skeletonize", "skeleton_stats", "centerline_metrics", "evaluate_volume_centerline", "SkeletonResult",
+                "SkeletonStats", "CenterlineReport"):
+        from . import skeleton
+        return getattr(skeleton, name)
     if name in ("calibration_tables", "CalibrationReport"):
         from . import calibration
         return getattr(calibration, name)

@@ -1,5 +1,5 @@
 """Host-side argument checks and small helpers shared by the evaluation modules (``inference``, ``surface``,
-``components``, ``regions``, ``calibration``, ``scan``, ``scanstats``).  One definition each: a module that needs one
+``components``, ``regions``, ``calibration``, ``scan``, ``scanstats``, ``skeleton``).  One definition each: a module that needs one
 imports it from here, not from a sibling.  Also the two things the predictor's pieces share that are not checks: the
 ``ImmutableValue`` base of ``WindowSkip`` / ``WindowFit`` and ``channels_last_or_copy``, the layout in which the kernels
 read a model's logits.  Nothing here launches a kernel except ``workspace``'s size query."""
