@@ -556,6 +556,58 @@ int mivp_boundary_loss_grad(const float* logits, const float* target, const floa
                             const float* weight, const float* workspace, const float* gscale, float* dlogits,
                             int32_t accumulate, mivp_stream_t stream);
 
+/* Hausdorff distance-transform loss term (Karimi & Salcudean, IEEE TMI 2019, "HD_DT") with on-device distance fields of the
+ * hard prediction and of the labels (csrc/hausdorff.hip; mivp_amd/losses.py hausdorff_weight_maps / hausdorff_dt_loss /
+ * HausdorffDTLoss).  These entry points joined ABI 18 without a bump: they are additive and no earlier signature
+ * changed.
+ *
+ * mivp_hausdorff_maps: logits f32 [B][vol][C] channels-last (2 <= C <= 8, vol = H W D), target f32 [B][H][W][D] class indices
+ * (dims = {H, W, D}, host) -> wmap f32 [B][K][H][W][D], K = C - c0 classes c0 .. C - 1, c0 = include_background ? 0 : 1.  Per
+ * (b, c) two masks:
+ *   P = {argmax_j z_j == c}   the hard prediction: comparisons on the logits alone, the LOWEST index among exact maxima, at
+ *                             every voxel, valid or not (NaN logits are out of contract)
+ *   G = {label == c}          the rule of mivp_distmap_signed: a label that is no class (non-integer, outside [0, C), NaN, or,
+ *                             with has_ignore != 0, equal to ignore_index) belongs to no G
+ * field(M)(v) = the distance sqrt(sum_a (spacing[a] delta_a)^2) from v to the nearest voxel on the other side of M (to the
+ * complement of M inside M, to M outside; the space beyond the volume border is neither side), +0 everywhere in (b, c) when M
+ * is empty or the whole sample.
+ *   wmap = field(P)^alpha + field(G)^alpha,   0 < alpha <= 4
+ * alpha == 2: the sum of the two squared fields, no root and no pow taken (exact integers at unit spacing); any other alpha:
+ * powf(squared field, alpha / 2) of each.  Four launches whatever B and K are (seed / D pass over both sources with the
+ * argmax fused in, W pass, H pass, closing), no atomics, nothing read back, every launch unconditional: equal calls give equal
+ * bits, and a recording holds for any later content.  Limits: H, W <= 65535 and 4 B K H W D < 2^31.
+ * workspace: mivp_hausdorff_maps_ws(B, K, dims) bytes (0 for arguments the call would refuse), 256-byte aligned:
+ *   [0, 16 B K vol)                the squared fields f32 [2][2][B][K][vol]: source (0 = P, 1 = G), then side (0 = distance to
+ *                                  M, 1 = to its complement; +inf where that side has no voxel), those of mivp_edt_sq
+ *   [that rounded up to 256, + 32 B K vol)   the lower envelope's stack, int32 pairs [depth][line]
+ * reused by every call in stream order.
+ *
+ * mivp_hausdorff_loss: logits f32 [B, vol, C] channels-last (2 <= C <= 8), target f32 [B, vol], wmap f32 [B][K][vol] (any
+ * values; a constant of the step: no gradient flows through it).  Validity rule of mivp_seg_loss.  With p = softmax_c(z),
+ * g_c = [y == c], V the valid voxels of the batch, N = |V|, w = lambda_hausdorff weight[0] (weight: DEVICE pointer to one
+ * float, NULL = 1; lambda_hausdorff >= 0):
+ *   loss[0]   = w sum_{v in V} sum_{c >= c0} (p_c - g_c)^2 wmap_c / (K max(N, 1))
+ *   dlogits_j = w p_j sum_c p_c (q_j - q_c) / (K max(N, 1)),   q_c = 2 (p_c - g_c) wmap_c for c >= c0, else 0;  exactly +0 at
+ *               an invalid voxel
+ * dlogits may be NULL: the value pass alone.  accumulate == 0: every element of dlogits is stored once; accumulate != 0: the
+ * value is added to what dlogits holds (one rounded add per element: the bits of dlogits + g).  mivp_hausdorff_loss_grad runs
+ * the gradient pass on the SAME workspace with the SAME options, scaled by gscale[0] (device pointer, NULL = 1).
+ * workspace: mivp_hausdorff_loss_ws(B, vol) floats = partial rows [B][bpb][2] (the sum, valid voxels), then
+ * {the sum, N, 1 / (K max(N, 1)), spare}.  No atomics: equal calls give equal bits. */
+size_t mivp_hausdorff_maps_ws(int32_t B, int32_t K, const int32_t* dims);
+int mivp_hausdorff_maps(const float* logits, const float* target, int32_t B, int32_t C, int32_t include_background,
+                        int32_t ignore_index, int32_t has_ignore, const int32_t* dims, const float* spacing, float alpha,
+                        float* wmap, void* workspace, mivp_stream_t stream);
+size_t mivp_hausdorff_loss_ws(int32_t B, int64_t vol);
+int mivp_hausdorff_loss(const float* logits, const float* target, const float* wmap, int32_t B, int64_t vol, int32_t C,
+                        int32_t include_background, int32_t ignore_index, int32_t has_ignore, float lambda_hausdorff,
+                        const float* weight, float* workspace, float* loss, float* dlogits, int32_t accumulate,
+                        mivp_stream_t stream);
+int mivp_hausdorff_loss_grad(const float* logits, const float* target, const float* wmap, int32_t B, int64_t vol, int32_t C,
+                             int32_t include_background, int32_t ignore_index, int32_t has_ignore, float lambda_hausdorff,
+                             const float* weight, const float* workspace, const float* gscale, float* dlogits,
+                             int32_t accumulate, mivp_stream_t stream);
+
 /* clDice (soft-skeleton) loss term (Shit et al., CVPR 2021) and the soft skeleton itself (csrc/cldice.hip; mivp_amd/losses.py
  * soft_skeleton / cldice_loss / SegLossSpec(lambda_cldice=...)).  These entry points joined ABI 18 without a
  * bump: they are additive and no earlier signature changed.

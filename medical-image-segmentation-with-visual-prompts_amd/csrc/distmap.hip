@@ -32,12 +32,6 @@ namespace {
 constexpr int DM_MAXK = 16;
 constexpr int DM_TPB = 256;
 
-// class of a label, -1 when it is no class: the rule of seg_class (csrc/segloss_common.hpp) at a run-time C
-MIVP_DEV int dm_class(float yv, int C, int has_ignore, float ignore) {
-    const bool ok = yv >= 0.f && yv < (float)C && yv == floorf(yv) && !(has_ignore && yv == ignore);
-    return ok ? (int)yv : -1;
-}
-
 // seed / D pass.  Lane i < 2 K owns the sweep state of pair i = 2 (c - c0) + side: the last seed before the current step
 // and the first seed after some step (stale once passed); a pair's state is read with a uniform-index shuffle.
 __global__ __launch_bounds__(DM_TPB) void k_distmap_d(const float* __restrict__ y, int B, int C, int c0, int has_ignore,
@@ -55,7 +49,7 @@ __global__ __launch_bounds__(DM_TPB) void k_distmap_d(const float* __restrict__ 
         int prev = -EDT_NO_SEED, next = -1;
         for (int k = 0; k < nch; ++k) {
             const int p = 64 * k + lane;
-            const int cls = p < D ? dm_class(row[p], C, has_ignore, ignore) : -2;
+            const int cls = p < D ? seg_class_rt(row[p], C, has_ignore, ignore) : -2;
             for (int pr = 0; pr < 2 * K; ++pr) {
                 const int c = c0 + (pr >> 1), side = pr & 1;
                 const unsigned long long m = __ballot(p < D && (side ? cls != c : cls == c));
@@ -68,7 +62,7 @@ __global__ __launch_bounds__(DM_TPB) void k_distmap_d(const float* __restrict__ 
                     nx = EDT_NO_SEED;
                     for (int j = k + 1; j < nch; ++j) {
                         const int q = 64 * j + lane;
-                        const int cq = q < D ? dm_class(row[q], C, has_ignore, ignore) : -2;
+                        const int cq = q < D ? seg_class_rt(row[q], C, has_ignore, ignore) : -2;
                         const unsigned long long mm = __ballot(q < D && (side ? cq != c : cq == c));
                         if (mm) { nx = 64 * j + __builtin_ctzll(mm); break; }
                     }
@@ -105,7 +99,7 @@ __global__ __launch_bounds__(DM_TPB) void k_distmap_close(const float* __restric
     for (long i = (long)blockIdx.x * DM_TPB + threadIdx.x; i < total; i += (long)gridDim.x * DM_TPB) {
         const long bk = i / vol, v = i - bk * vol;
         const int b = (int)(bk / K), k = (int)(bk - (long)b * K);
-        const bool inside = dm_class(y[(long)b * vol + v], C, has_ignore, ignore) == c0 + k;
+        const bool inside = seg_class_rt(y[(long)b * vol + v], C, has_ignore, ignore) == c0 + k;
         const float d2 = fields[(inside ? total : 0L) + i];        // side 1 starts B K vol floats in
         const float r = sqrtf(d2);
         phi[i] = isinf(d2) ? 0.f : (inside ? 1.f - r : r);
@@ -134,7 +128,7 @@ struct BdVoxel {
     float p[C];
     bool valid;
     MIVP_DEV BdVoxel(const float* zz, float yv, const BdOpt& o) {
-        valid = dm_class(yv, C, o.has_ignore, o.ignore) >= 0;
+        valid = seg_class_rt(yv, C, o.has_ignore, o.ignore) >= 0;
         float mx = -INFINITY;
 #pragma unroll
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, zz[c]);

@@ -26,6 +26,12 @@ MIVP_DEV int seg_class(float yv, const SegOpt& o) {
     return ok ? (int)yv : -1;
 }
 
+// the same rule at a run-time C (csrc/distmap.hip, csrc/hausdorff.hip: one kernel for every class count)
+MIVP_DEV int seg_class_rt(float yv, int C, int has_ignore, float ignore) {
+    const bool ok = yv >= 0.f && yv < (float)C && yv == floorf(yv) && !(has_ignore && yv == ignore);
+    return ok ? (int)yv : -1;
+}
+
 // om^g for g == 0 or g >= 1 (om = 1 - p_y in [0, 1]); the exponents in common use take no transcendental
 MIVP_DEV float seg_pow(float om, float g) {
     if (g == 0.f) return 1.f;

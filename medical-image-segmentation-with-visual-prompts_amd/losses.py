@@ -19,6 +19,10 @@
 * ``soft_skeleton`` / ``cldice_loss`` / ``SegLossSpec(lambda_cldice=...)`` -- the clDice topology term of Shit et al. (CVPR
   2021): each mask against the other one's soft skeleton, skeletons and their backward as 3-D min / max brick kernels
   (csrc/cldice.hip).
+* ``hausdorff_weight_maps`` / ``hausdorff_dt_loss`` / ``HausdorffDTLoss`` -- the Hausdorff distance-transform loss of Karimi &
+  Salcudean (IEEE TMI 2019): the squared error weighted by the distance fields of the hard prediction and of the labels, both
+  built on the device per step by the batched transform (csrc/hausdorff.hip); a module around an optional base
+  loss, not a field of ``SegLossSpec``.
 """
 from __future__ import annotations
 
@@ -1164,3 +1168,255 @@ class SegLoss(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return repr(self.spec)
+
+
+# ---------------------------------------------------------------------------------------------
+# Hausdorff distance-transform term: the fields of the hard prediction and of the labels, a weighted squared error
+# (csrc/hausdorff.hip)
+# ---------------------------------------------------------------------------------------------
+def _check_alpha(alpha) -> float:
+    a = check_finite("alpha", alpha)
+    if not 0.0 < a <= 4.0:
+        raise ValueError(f"alpha must be in (0, 4], got {alpha!r}")
+    return a
+
+
+def _hausdorff_args(logits, target, alpha, include_background, ignore_index, spacing):
+    """The checks the three public entries share -> (alpha, bg, ig, spacing, B, C, K, dims)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 5:
+        raise ValueError(f"logits must be [B, C, H, W, D], got {tuple(logits.shape) if isinstance(logits, torch.Tensor) else logits!r}")
+    B, Cc = int(logits.shape[0]), int(logits.shape[1])
+    if not 2 <= Cc <= SEG_LOSS_MAX_CLASSES:
+        raise ValueError(f"logits must have 2 .. {SEG_LOSS_MAX_CLASSES} classes, got {Cc}")
+    if not isinstance(target, torch.Tensor) or target.numel() != logits.numel() // Cc or target.shape[0] != B:
+        raise ValueError(f"target must be [B, 1, H, W, D] for logits {tuple(logits.shape)}, got "
+                         f"{tuple(target.shape) if isinstance(target, torch.Tensor) else target!r}")
+    if target.device != logits.device:
+        raise ValueError(f"target must be on the logits' device {logits.device}, got {target.device}")
+    a = _check_alpha(alpha)
+    bg = check_flag("include_background", include_background)
+    ig = _check_ignore(ignore_index)
+    sp = check_spacing(spacing)
+    dims = tuple(int(v) for v in logits.shape[2:])
+    return a, bg, ig, sp, B, Cc, Cc - (0 if bg else 1), dims
+
+
+def _edt_sq_np(seeds: np.ndarray, spacing) -> np.ndarray:
+    """Exact squared Euclidean distance to the nearest True voxel of ``seeds [H, W, D]`` (inf without one), float64: the
+    separable min-plus form, one pass per axis (the CPU restatement of the transform; small volumes)."""
+    f = np.where(seeds, 0.0, np.inf)
+    for axis, s in enumerate(spacing):
+        f = np.moveaxis(f, axis, -1)
+        n = f.shape[-1]
+        x = np.arange(n, dtype=np.float64)
+        out = np.full(f.shape, np.inf)
+        for i in range(n):
+            np.minimum(out, (float(s) * (x - i)) ** 2 + f[..., i:i + 1], out=out)
+        f = np.moveaxis(out, -1, axis)
+    return f
+
+
+def _hausdorff_maps_np(z: np.ndarray, y: np.ndarray, alpha: float, spacing, bg: bool, ig) -> np.ndarray:
+    """The weight maps on the CPU: z [B, H, W, D, C], y [B, H, W, D] -> float64 [B, K, H, W, D]."""
+    B, Cc = z.shape[0], z.shape[-1]
+    c0 = 0 if bg else 1
+    yy = y.astype(np.float64)
+    ok = (yy >= 0) & (yy < Cc) & (yy == np.floor(yy))
+    if ig is not None:
+        ok &= yy != float(ig)
+    pred = np.argmax(z, axis=-1)                                   # the first maximum
+    out = np.zeros((B, Cc - c0) + z.shape[1:4])
+    for b in range(B):
+        for c in range(c0, Cc):
+            for M in (pred[b] == c, ok[b] & (yy[b] == float(c))):
+                if M.any() and not M.all():
+                    d2 = np.where(M, _edt_sq_np(~M, spacing), _edt_sq_np(M, spacing))
+                    out[b, c - c0] += d2 if alpha == 2.0 else d2 ** (0.5 * alpha)
+    return out
+
+
+def _hausdorff_maps_launch(logits_cl: torch.Tensor, tgt: torch.Tensor, dims, alpha, spacing, bg, ig, ws=None) -> torch.Tensor:
+    """logits_cl f32 [B, H, W, D, C] contiguous, tgt f32 with B prod(dims) labels -> wmap f32 [B, K, H, W, D]: the four launches."""
+    B, Cc = logits_cl.shape[0], logits_cl.shape[-1]
+    K = Cc - (0 if bg else 1)
+    H, W, D = dims
+    if H > 65535 or W > 65535 or 4 * B * K * H * W * D >= 2 ** 31:
+        raise ValueError(f"Hausdorff weight maps of {B} x {K} x {dims}: H and W must be <= 65535 and 4 B K H W D < 2^31")
+    wmap = torch.empty((B, K, H, W, D), dtype=torch.float32, device=logits_cl.device)
+    if ws is None:
+        ws = torch.empty(max(int(L.lib().mivp_hausdorff_maps_ws(B, K, i3(dims))), 1), dtype=torch.uint8, device=logits_cl.device)
+    L.call("mivp_hausdorff_maps", L.ptr(logits_cl), L.ptr(tgt), B, Cc, 1 if bg else 0, 0 if ig is None else ig,
+           0 if ig is None else 1, i3(dims), (C.c_float * 3)(*spacing), alpha, L.ptr(wmap), L.ptr(ws), L.stream())
+    return wmap
+
+
+def _channels_last_f32(logits: torch.Tensor) -> torch.Tensor:
+    """[B, C, H, W, D] -> contiguous f32 [B, H, W, D, C]: the view when the storage is that already, else a copy."""
+    return logits.detach().permute(0, 2, 3, 4, 1).to(torch.float32).contiguous()
+
+
+def hausdorff_weight_maps(logits: torch.Tensor, target: torch.Tensor, *, alpha: float = 2.0,
+                          spacing: Sequence[float] = (1.0, 1.0, 1.0), include_background: bool = False,
+                          ignore_index: Optional[int] = None) -> torch.Tensor:
+    """The weight maps of the Hausdorff distance-transform loss.  logits [B, C, H, W, D] (2 <= C <= 8), target
+    [B, 1, H, W, D] (or [B, H, W, D]) class indices of any dtype -> float32 ``[B, K, H, W, D]`` for the classes c0 .. C - 1.  Per
+    sample and class, P = {argmax_j logits_j == c} (the hard prediction; the lowest index among exact maxima) and
+    G = {label == c} (a label that is no class for ``seg_loss`` belongs to no G)::
+
+        field(M)(v) = distance from v to the nearest voxel on the other side of M; 0 everywhere when M is empty or the sample
+        maps        = field(P)^alpha + field(G)^alpha
+
+    with distances ``sqrt(sum_a (spacing[a] delta_a)^2)``.  A constant: nothing flows back into the logits.  On the GPU four
+    launches whatever the batch and class counts are, nothing read back (csrc/hausdorff.hip); exact integers at ``alpha == 2``
+    and unit spacing.  CPU tensors take a numpy restatement of the same definition (small volumes)."""
+    a, bg, ig, sp, B, Cc, K, dims = _hausdorff_args(logits, target, alpha, include_background, ignore_index, spacing)
+    if logits.is_cuda:
+        tgt = target.detach().to(torch.float32).contiguous()
+        return _hausdorff_maps_launch(_channels_last_f32(logits), tgt, dims, a, sp, bg, ig)
+    z = logits.detach().permute(0, 2, 3, 4, 1).numpy()
+    y = target.detach().reshape((B,) + dims).numpy()
+    return torch.from_numpy(_hausdorff_maps_np(z, y, a, sp, bg, ig)).to(torch.float32)
+
+
+class _HausdorffFn(torch.autograd.Function):
+    """The term on given weight maps: value from a streaming pass + a one-workgroup reduction, the gradient from a second
+    streaming pass when backward asks for it (csrc/hausdorff.hip).  ``wmap`` and ``weight`` are constants."""
+
+    @staticmethod
+    def forward(ctx, logits_cl, target, wmap, weight, bg, ig, lam):
+        B, H, W, D, Cc = logits_cl.shape
+        vol = H * W * D
+        ws = torch.empty(L.lib().mivp_hausdorff_loss_ws(B, vol), dtype=torch.float32, device=logits_cl.device)
+        loss = torch.empty(1, dtype=torch.float32, device=logits_cl.device)
+        L.call("mivp_hausdorff_loss", L.ptr(logits_cl), L.ptr(target), L.ptr(wmap), B, vol, Cc, 1 if bg else 0,
+               0 if ig is None else ig, 0 if ig is None else 1, lam, L.ptr(weight), L.ptr(ws), L.ptr(loss), L.ptr(None), 0,
+               L.stream())
+        ctx.save_for_backward(logits_cl, target, wmap, ws)
+        ctx.weight, ctx.opts = weight, (bg, ig, lam)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits_cl, target, wmap, ws = ctx.saved_tensors
+        B, H, W, D, Cc = logits_cl.shape
+        bg, ig, lam = ctx.opts
+        g = g.detach().to(torch.float32).contiguous()
+        dz = torch.empty_like(logits_cl)
+        L.call("mivp_hausdorff_loss_grad", L.ptr(logits_cl), L.ptr(target), L.ptr(wmap), B, H * W * D, Cc, 1 if bg else 0,
+               0 if ig is None else ig, 0 if ig is None else 1, lam, L.ptr(ctx.weight), L.ptr(ws), L.ptr(g), L.ptr(dz), 0,
+               L.stream())
+        return dz, None, None, None, None, None, None
+
+
+def _hausdorff_torch(z: torch.Tensor, y: torch.Tensor, wmap: torch.Tensor, bg: bool, ig, weight) -> torch.Tensor:
+    """The formulas of ``hausdorff_dt_loss`` in plain torch ops, differentiable by autograd: z [B, vol, C], y [B, vol] labels,
+    wmap [B, K, vol]."""
+    Cc = z.shape[-1]
+    y = y.to(z.dtype if z.dtype in (torch.float32, torch.float64) else torch.float32)
+    valid = (y >= 0) & (y < Cc) & (y == y.floor())
+    if ig is not None:
+        valid = valid & (y != ig)
+    c0 = 0 if bg else 1
+    onehot = (y.unsqueeze(-1) == torch.arange(Cc, dtype=y.dtype, device=y.device)) & valid.unsqueeze(-1)
+    err = (torch.softmax(z, dim=-1) - onehot.to(z.dtype))[..., c0:]
+    num = (err * err * wmap.to(z.dtype).transpose(1, 2) * valid.to(z.dtype).unsqueeze(-1)).sum()
+    loss = num / ((Cc - c0) * valid.sum().clamp(min=1).to(z.dtype))
+    return loss if weight is None else loss * weight.to(z.dtype).reshape(())
+
+
+def _hausdorff_term(logits, target, a, bg, ig, sp, B, Cc, K, dims, weight, maps, lam, maps_ws=None) -> torch.Tensor:
+    """``lam weight`` times the term; the kernels for channels-last f32 GPU logits, else the torch composition."""
+    if maps is not None:
+        if not isinstance(maps, torch.Tensor) or tuple(maps.shape) != (B, K) + dims or maps.device != logits.device:
+            raise ValueError(f"maps must be a [B, K, H, W, D] = {(B, K) + dims} tensor on the logits' device, got "
+                             f"{tuple(maps.shape) if isinstance(maps, torch.Tensor) else maps!r}")
+        maps = maps.detach()
+    base = logits.permute(0, 2, 3, 4, 1)
+    if logits.is_cuda and logits.dtype == torch.float32 and base.is_contiguous():
+        tgt = target.detach().to(torch.float32).contiguous()
+        wmap = _hausdorff_maps_launch(base.detach(), tgt, dims, a, sp, bg, ig, maps_ws) if maps is None \
+            else maps.to(torch.float32).contiguous()
+        if weight is not None:
+            weight = weight.to(torch.float32).contiguous()
+        return _HausdorffFn.apply(base, tgt, wmap, weight, bg, ig, lam)
+    if maps is None:
+        maps = hausdorff_weight_maps(logits, target, alpha=a, spacing=sp, include_background=bg, ignore_index=ig)
+    term = _hausdorff_torch(base.reshape(B, -1, Cc), target.detach().reshape(B, -1), maps.reshape(B, K, -1), bg, ig, weight)
+    return term if lam == 1.0 else lam * term
+
+
+def hausdorff_dt_loss(logits: torch.Tensor, target: torch.Tensor, *, alpha: float = 2.0, include_background: bool = False,
+                      ignore_index: Optional[int] = None, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                      weight: Optional[torch.Tensor] = None, maps: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The Hausdorff distance-transform loss of Karimi & Salcudean (IEEE TMI 2019, "HD_DT").  logits [B, C, H, W, D]
+    (2 <= C <= 8), target [B, 1, H, W, D] (or [B, H, W, D]) class indices of any dtype.  With p = softmax_c(z), g_c = [y == c],
+    Wm = ``hausdorff_weight_maps(logits, target, alpha=, spacing=, ...)`` (or ``maps``, [B, K, H, W, D], when given), V the
+    valid voxels of the batch (the rule of ``seg_loss``), N = |V|, K = C - c0::
+
+        loss = weight sum_{v in V} sum_{c >= c0} (p_c(v) - g_c(v))^2 Wm_c(v) / (K max(N, 1))
+
+    The prediction's mask is the hard prediction (the arg-max of the logits), where MONAI's ``HausdorffDTLoss`` thresholds
+    the softmax at 0.5: the same set for C = 2 up to exact ties, and independent of how a softmax is rounded.  ``Wm`` is a
+    constant of the step; ``weight``: a one-element tensor on the logits' device (None = 1) that is read on the device, so a
+    recorded step follows a schedule of it.  Channels-last f32 CUDA logits take the kernels: the four launches of the maps
+    (unless ``maps`` is given), then two streaming passes; nothing read back, recordable.  Any other layout, dtype or device
+    takes the same formulas as plain torch ops, with the maps from ``hausdorff_weight_maps``."""
+    a, bg, ig, sp, B, Cc, K, dims = _hausdorff_args(logits, target, alpha, include_background, ignore_index, spacing)
+    weight = _check_boundary_weight(weight, logits.device)
+    return _hausdorff_term(logits, target, a, bg, ig, sp, B, Cc, K, dims, weight, maps, 1.0)
+
+
+class HausdorffDTLoss(torch.nn.Module):
+    """``base(logits, target) + lambda_hausdorff weight hausdorff_dt_loss(logits, target, **options)`` (the term alone
+    without a ``base``); ``options``: ``alpha``, ``include_background``, ``ignore_index``, ``spacing``.  ``base`` is any
+    module of (logits, target), e.g. a ``SegLoss``; ``train.step_loss`` takes the whole as ``conf.seg_loss``.  ``weight`` is a
+    device float outside ``state_dict`` that ``set_weight`` schedules between the replays of a recorded step.  The scratch of
+    the distance transform (the large part) is allocated once per shape; the maps a backward pass reads are the call's own."""
+
+    def __init__(self, base: Optional[torch.nn.Module] = None, lambda_hausdorff: float = 1.0, *, alpha: float = 2.0,
+                 include_background: bool = False, ignore_index: Optional[int] = None,
+                 spacing: Sequence[float] = (1.0, 1.0, 1.0)):
+        super().__init__()
+        if base is not None and not isinstance(base, torch.nn.Module):
+            raise TypeError(f"base must be None or a torch.nn.Module of (logits, target), got {base!r}")
+        lam = check_at_least("lambda_hausdorff", lambda_hausdorff, 0.0)
+        if lam > float(np.finfo(np.float32).max):
+            raise ValueError(f"lambda_hausdorff must be finite in fp32, got {lambda_hausdorff!r}")
+        self.base = base
+        self.lambda_hausdorff = lam
+        self.alpha = _check_alpha(alpha)
+        self.include_background = check_flag("include_background", include_background)
+        self.ignore_index = _check_ignore(ignore_index)
+        self.spacing = check_spacing(spacing)
+        self.register_buffer("weight", torch.ones(1, dtype=torch.float32), persistent=False)
+        self._maps_ws = {}
+
+    def set_weight(self, value: float) -> None:
+        """Set the factor of the term (``lambda_hausdorff`` times it is the term's weight): a stream-ordered copy into the
+        module's buffer, legal between the replays of a recorded step."""
+        v = check_finite("weight", value)
+        if self.weight.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("HausdorffDTLoss.set_weight inside a recording: a recording must not freeze today's weight "
+                               "into the graph; call it between replays")
+        self.weight.copy_(torch.tensor([v], dtype=torch.float32))
+
+    def _scratch(self, device, B: int, K: int, dims):
+        key = (str(device), B, K, dims)
+        ws = self._maps_ws.get(key)
+        if ws is None:
+            ws = torch.empty(max(int(L.lib().mivp_hausdorff_maps_ws(B, K, i3(dims))), 1), dtype=torch.uint8, device=device)
+            self._maps_ws[key] = ws
+        return ws
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        a, bg, ig, sp, B, Cc, K, dims = _hausdorff_args(logits, target, self.alpha, self.include_background,
+                                                        self.ignore_index, self.spacing)
+        if self.weight.device != logits.device:
+            raise ValueError(f"the module is on {self.weight.device}, the logits on {logits.device}: move it with .to()")
+        ws = self._scratch(logits.device, B, K, dims) if logits.is_cuda else None
+        term = _hausdorff_term(logits, target, a, bg, ig, sp, B, Cc, K, dims, self.weight, None, self.lambda_hausdorff, ws)
+        return term if self.base is None else self.base(logits, target) + term
+
+    def extra_repr(self) -> str:
+        return (f"lambda_hausdorff={self.lambda_hausdorff}, alpha={self.alpha}, include_background={self.include_background}, "
+                f"ignore_index={self.ignore_index}, spacing={self.spacing}")

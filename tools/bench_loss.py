@@ -1,6 +1,6 @@
 """Time the recorded loss + gradient of mivp_seg_loss (csrc/segloss.hip) against the Dice-focal kernels and eager torch.
 
-    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10] [--boundary | --cldice]
+    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10] [--boundary | --cldice | --hausdorff]
 
 Shapes: 96^3 at B = 4 (the `downstream` step's) and 128 x 128 x 8 at B = 14, both C = 2.  Settings of the new entry:
   (a) Dice-equivalent options (alpha = beta = 0.5), lambda_voxel = 0
@@ -28,6 +28,16 @@ inside a recording); (b) - (a) is written as a share of the `downstream` step.
       the same dz after the gradient pass (the launches of losses._SegTermsFn)
   (c) the skeleton passes of one side alone: mivp_cldice_skeleton (kept) + mivp_cldice_skeleton_grad on p_1 [B, 1, H, W, D]
   (d) the clDice authors' max-pool composition of the term with autograd, eager, on the same GPU
+
+``--hausdorff`` times the Hausdorff distance-transform term instead (csrc/hausdorff.hip), same shapes and
+operands as ``--boundary``, alpha = 2:
+  (a) as above: the path without the term
+  (b) the same plus the term through HausdorffDTLoss: mivp_hausdorff_maps, the term's value pass and, after the base's
+      gradient pass, its gradient pass (here accumulating onto the same dz; the module leaves that add to autograd)
+  (c) mivp_hausdorff_maps alone
+  (d) mivp_hausdorff_loss alone (value + gradient) on given maps
+  (e) mivp_distmap_signed alone, the maps of ``--boundary``, in the same job: half the fields of (c)
+  (f) for scale, eager and on the CPU: scipy's distance_transform_edt of both masks and sides plus the torch term with autograd
 
 Each kernel variant is one call (value + gradient) recorded in a HIP graph; a run is `replays` replays between two device
 events after `warmup` replays; the figure is the median over `runs` runs with the spread (min .. max).  One JSON line per
@@ -305,6 +315,99 @@ def boundary_main(args):
     print(json.dumps({"bench_boundary_ms": summary}))
 
 
+def hausdorff_main(args):
+    """The Hausdorff distance-transform term: see the module docstring."""
+    import time
+    summary = {}
+    for name, B, dims in SHAPES:
+        vol, Cc = dims[0] * dims[1] * dims[2], 2
+        z, y = lesion_case(B, dims, Cc)
+        yf = y.view(B, vol).to(DEV)
+        w = torch.tensor(WEIGHTS, dtype=torch.float32, device=DEV)
+        # every operand is allocated here, outside the recordings
+        dz, loss = torch.empty_like(z), torch.empty(2, dtype=torch.float32, device=DEV)
+        one = torch.ones(1, dtype=torch.float32, device=DEV)     # the incoming gradient, the term's weight
+        sws = torch.empty(int(L.lib().mivp_seg_loss_ws(B, vol)), dtype=torch.float32, device=DEV)
+        hws = torch.empty(int(L.lib().mivp_hausdorff_loss_ws(B, vol)), dtype=torch.float32, device=DEV)
+        K, d3, sp = Cc - 1, (C.c_int32 * 3)(*dims), (C.c_float * 3)(1.0, 1.0, 1.0)
+        mws = torch.empty(int(L.lib().mivp_hausdorff_maps_ws(B, K, d3)), dtype=torch.uint8, device=DEV)
+        bws = torch.empty(int(L.lib().mivp_distmap_ws(B, K, d3)), dtype=torch.uint8, device=DEV)
+        wmap = torch.empty((B, K, vol), dtype=torch.float32, device=DEV)
+        phi = torch.empty((B, K, vol), dtype=torch.float32, device=DEV)
+        lam = 0.01
+
+        def seg_value():
+            L.call("mivp_seg_loss", L.ptr(z), L.ptr(yf), B, vol, Cc, 0, 0, 0.5, 0.5, 0.0, L.ptr(w), IGNORE, 1, 1.0, 1.0, L.ptr(sws),
+                   L.ptr(loss), None, L.stream())
+
+        def seg_grad():
+            L.call("mivp_seg_loss_grad", L.ptr(z), L.ptr(yf), B, vol, Cc, 0, 0, 0.5, 0.5, 0.0, L.ptr(w), IGNORE, 1, 1.0, 1.0,
+                   L.ptr(sws), L.ptr(one), L.ptr(dz), L.stream())
+
+        def maps_alone():
+            L.call("mivp_hausdorff_maps", L.ptr(z), L.ptr(yf), B, Cc, 0, IGNORE, 1, d3, sp, 2.0, L.ptr(wmap), L.ptr(mws), L.stream())
+
+        def boundary_maps():
+            L.call("mivp_distmap_signed", L.ptr(yf), B, Cc, 0, IGNORE, 1, d3, sp, L.ptr(phi), L.ptr(bws), L.stream())
+
+        def plain_step():
+            seg_value()
+            seg_grad()
+
+        def hausdorff_step():
+            seg_value()
+            maps_alone()
+            L.call("mivp_hausdorff_loss", L.ptr(z), L.ptr(yf), L.ptr(wmap), B, vol, Cc, 0, IGNORE, 1, lam, L.ptr(one), L.ptr(hws),
+                   C.c_void_p(loss.data_ptr() + 4), None, 0, L.stream())
+            seg_grad()
+            L.call("mivp_hausdorff_loss_grad", L.ptr(z), L.ptr(yf), L.ptr(wmap), B, vol, Cc, 0, IGNORE, 1, lam, L.ptr(one),
+                   L.ptr(hws), L.ptr(one), L.ptr(dz), 1, L.stream())
+
+        def term_alone():
+            L.call("mivp_hausdorff_loss", L.ptr(z), L.ptr(yf), L.ptr(wmap), B, vol, Cc, 0, IGNORE, 1, 1.0, None, L.ptr(hws),
+                   L.ptr(loss), L.ptr(dz), 0, L.stream())
+
+        res = {}
+        for key, label, call in (("a", "(a) dice + weighted CE, value then gradient", plain_step),
+                                 ("b", "(b) the same with the Hausdorff term", hausdorff_step),
+                                 ("c", "(c) mivp_hausdorff_maps alone", maps_alone),
+                                 ("d", "(d) mivp_hausdorff_loss alone, maps given", term_alone),
+                                 ("e", "(e) mivp_distmap_signed alone (the --boundary maps)", boundary_maps)):
+            r = timed(recorded(call), args.runs, args.replays, args.warmup)
+            r.update(shape=name, variant=label, share_of_step=r["ms"] / STEP_MS)
+            res[key] = r
+            summary[f"{name} | {label}"] = [round(r[k], 4) for k in ("ms", "lo", "hi")]
+            print(json.dumps(r), flush=True)
+        extra = res["b"]["ms"] - res["a"]["ms"]
+        summary[f"{name} | (b) - (a)"] = dict(ms=round(extra, 4), share_of_step=round(extra / STEP_MS, 4))
+        summary[f"{name} | (c) / (e)"] = round(res["c"]["ms"] / res["e"]["ms"], 3)
+        try:
+            from scipy import ndimage
+        except ImportError:
+            ndimage = None
+        if ndimage is not None:
+            import numpy as np
+            yc, zc = y[:, 0].numpy(), z.cpu()
+
+            def field_sq(M):
+                if not M.any() or M.all():
+                    return np.zeros(M.shape)
+                return np.where(M, ndimage.distance_transform_edt(M), ndimage.distance_transform_edt(~M)) ** 2
+            ms = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                pred = zc.view(B, *dims, Cc).argmax(-1).numpy()
+                maps = np.stack([field_sq(pred[b] == 1) + field_sq(yc[b] == 1.0) for b in range(B)])
+                zl = zc.clone().requires_grad_(True)
+                losses.hausdorff_dt_loss(zl.view(B, *dims, Cc).permute(0, 4, 1, 2, 3).contiguous(), y, ignore_index=IGNORE,
+                                         maps=torch.from_numpy(maps).float().view(B, 1, *dims)).backward()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            r = dict(ms=statistics.median(ms), lo=min(ms), hi=max(ms), shape=name, variant="(f) scipy EDT + eager torch term, CPU")
+            summary[f"{name} | (f) scipy + torch, CPU"] = [round(r[k], 2) for k in ("ms", "lo", "hi")]
+            print(json.dumps(r), flush=True)
+    print(json.dumps({"bench_hausdorff_ms": summary}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
@@ -312,8 +415,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--boundary", action="store_true", help="time the boundary term (DESIGN 4.35) instead")
     ap.add_argument("--cldice", action="store_true", help="time the clDice term (DESIGN 4.36) instead")
+    ap.add_argument("--hausdorff", action="store_true", help="time the Hausdorff distance-transform term (DESIGN 4.39) instead")
     args = ap.parse_args()
     assert args.runs >= 3
+    if args.hausdorff:
+        return hausdorff_main(args)
     if args.boundary:
         return boundary_main(args)
     if args.cldice:
