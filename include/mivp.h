@@ -608,6 +608,54 @@ int mivp_hausdorff_loss_grad(const float* logits, const float* target, const flo
                              const float* weight, const float* workspace, const float* gscale, float* dlogits,
                              int32_t accumulate, mivp_stream_t stream);
 
+/* Lovasz-Softmax loss term (Berman, Triki & Blaschko, CVPR 2018) on an exact device-wide key sort (csrc/lovasz.hip,
+ * csrc/sort_common.hpp; mivp_amd/losses.py lovasz_softmax_loss / LovaszSoftmaxLoss).  These entry points joined
+ * ABI 18 without a bump: they are additive and no earlier signature changed.
+ *
+ * mivp_sort_u32: keys u32 [segments][n] (device) -> every segment sorted ascending in place, the bits of a stable sort (keys
+ * only, so of any exact sort).  LSD radix sort, four passes of 8 bits, three launches each (tile histograms, scan, stable
+ * scatter; the segment is a grid dimension): twelve launches whatever segments, n and the data are; no float arithmetic, no
+ * global atomics.  mivp_sort_tile(): the keys one workgroup handles.  Limits: segments <= 65535, segments n < 2^31.
+ * workspace: mivp_sort_u32_ws(segments, n) bytes (0 for arguments the call would refuse): the second key buffer, the tile
+ * histograms [segments][tiles][256] and the digit bases [segments][256].
+ *
+ * mivp_lovasz_loss: logits f32 [B, vol, C] channels-last (2 <= C <= 8), target f32 [B, vol].  Validity rule of mivp_seg_loss.
+ * A segment is class c >= c0 (c0 = include_background ? 0 : 1) of sample b (per_image != 0) or of the batch; S segments of N
+ * voxels.  Per segment over its valid voxels, with p = softmax_c(z), g = [y == c], e = g ? 1 - p_c : p_c, G = sum g,
+ * J(F, K) = 1 - (G - F) / (G + K) and J(0, 0) = 0:
+ *   loss_seg  = sum_j e_(j) (J_j - J_(j-1))            the errors in descending order, F_j / K_j the foreground / background
+ *                                                      voxels among the first j
+ *   d loss_seg / d e_i, tie rule: inside a group of equal e the foreground voxels come first and get 1 / (G + K) each, K the
+ *               background voxels with a larger error; the b tied background voxels share J(F, K + b) - J(F, K) equally, F the
+ *               foreground voxels with an error >= theirs.  Independent of memory order, and a subgradient.
+ * A group (a sample with per_image, else the batch) averages its segments with G > 0 (classes_all != 0: all of them; no
+ * segment: 0); loss[0] = w x the mean of the groups, w = lambda_lovasz weight[0] (weight: DEVICE pointer to one float, NULL =
+ * 1; lambda_lovasz >= 0).  dlogits_k = w sum_c factor_c s_c sgn_c p_c (delta_ck - p_k), exactly +0 at an invalid voxel.
+ * dlogits may be NULL; accumulate and mivp_lovasz_loss_grad (gscale) as for mivp_hausdorff_loss.  Every launch is
+ * unconditional and their number (20 with the gradient) depends on nothing; integer atomics only for the two counts per
+ * segment: equal calls give equal bits, nothing is read back, a recording holds for any later content.
+ * Limits: B <= 65535, S N < 2^31.  workspace: mivp_lovasz_ws(B, C, include_background, per_image, vol) bytes (0 for arguments
+ * the call would refuse): sorted keys [S][N], the sort's workspace, prefix u32 [S][N] (foreground keys up to a position), tile
+ * counts, counts u32 [S][2] = (G, valid voxels), partial sums f32 [S][tiles], factors f32 [S].
+ *
+ * mivp_lovasz_keys: the key pass alone.  keys u32 [S][N] in memory order: 0x7F000001 - ((bits(e) << 1) | g) at a valid voxel
+ * (ascending keys = descending errors, foreground first), 0xFFFFFFFF at an invalid one; counts u32 [S][2]. */
+int mivp_sort_tile(void);
+size_t mivp_sort_u32_ws(int32_t segments, int64_t n);
+int mivp_sort_u32(uint32_t* keys, int32_t segments, int64_t n, void* workspace, mivp_stream_t stream);
+size_t mivp_lovasz_ws(int32_t B, int32_t C, int32_t include_background, int32_t per_image, int64_t vol);
+int mivp_lovasz_keys(const float* logits, const float* target, int32_t B, int64_t vol, int32_t C, int32_t include_background,
+                     int32_t ignore_index, int32_t has_ignore, int32_t per_image, uint32_t* keys, uint32_t* counts,
+                     mivp_stream_t stream);
+int mivp_lovasz_loss(const float* logits, const float* target, int32_t B, int64_t vol, int32_t C, int32_t include_background,
+                     int32_t ignore_index, int32_t has_ignore, int32_t per_image, int32_t classes_all, float lambda_lovasz,
+                     const float* weight, void* workspace, float* loss, float* dlogits, int32_t accumulate,
+                     mivp_stream_t stream);
+int mivp_lovasz_loss_grad(const float* logits, const float* target, int32_t B, int64_t vol, int32_t C,
+                          int32_t include_background, int32_t ignore_index, int32_t has_ignore, int32_t per_image,
+                          int32_t classes_all, float lambda_lovasz, const float* weight, const void* workspace,
+                          const float* gscale, float* dlogits, int32_t accumulate, mivp_stream_t stream);
+
 /* clDice (soft-skeleton) loss term (Shit et al., CVPR 2021) and the soft skeleton itself (csrc/cldice.hip; mivp_amd/losses.py
  * soft_skeleton / cldice_loss / SegLossSpec(lambda_cldice=...)).  These entry points joined ABI 18 without a
  * bump: they are additive and no earlier signature changed.

@@ -23,6 +23,10 @@
   Salcudean (IEEE TMI 2019): the squared error weighted by the distance fields of the hard prediction and of the labels, both
   built on the device per step by the batched transform (csrc/hausdorff.hip); a module around an optional base
   loss, not a field of ``SegLossSpec``.
+* ``lovasz_softmax_loss`` / ``LovaszSoftmaxLoss`` -- the Lovasz-Softmax loss of Berman, Triki & Blaschko (CVPR 2018), the
+  convex surrogate of the per-class Jaccard index: one 32-bit key per (segment, voxel), an exact device-wide radix sort, a
+  prefix pass and a gradient pass with an order-independent tie rule (csrc/lovasz.hip, csrc/sort_common.hpp); a
+  module around an optional base loss like ``HausdorffDTLoss``.
 """
 from __future__ import annotations
 
@@ -1420,3 +1424,204 @@ class HausdorffDTLoss(torch.nn.Module):
     def extra_repr(self) -> str:
         return (f"lambda_hausdorff={self.lambda_hausdorff}, alpha={self.alpha}, include_background={self.include_background}, "
                 f"ignore_index={self.ignore_index}, spacing={self.spacing}")
+
+
+# ---------------------------------------------------------------------------------------------
+# Lovasz-Softmax term: the Lovasz extension of the per-class Jaccard loss on an exact device-wide key sort
+# (csrc/lovasz.hip, csrc/sort_common.hpp)
+# ---------------------------------------------------------------------------------------------
+LOVASZ_CLASSES = ("present", "all")
+
+
+def _lovasz_args(logits, target, classes, per_image, include_background, ignore_index):
+    """The checks the function and the module share -> (all, per_image, bg, ig, B, C, dims)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 5:
+        raise ValueError(f"logits must be [B, C, H, W, D], got {tuple(logits.shape) if isinstance(logits, torch.Tensor) else logits!r}")
+    B, Cc = int(logits.shape[0]), int(logits.shape[1])
+    if not 2 <= Cc <= SEG_LOSS_MAX_CLASSES:
+        raise ValueError(f"logits must have 2 .. {SEG_LOSS_MAX_CLASSES} classes, got {Cc}")
+    if not isinstance(target, torch.Tensor) or target.numel() != logits.numel() // Cc or target.shape[0] != B:
+        raise ValueError(f"target must be [B, 1, H, W, D] for logits {tuple(logits.shape)}, got "
+                         f"{tuple(target.shape) if isinstance(target, torch.Tensor) else target!r}")
+    if target.device != logits.device:
+        raise ValueError(f"target must be on the logits' device {logits.device}, got {target.device}")
+    if classes not in LOVASZ_CLASSES:
+        raise ValueError(f"classes must be one of {LOVASZ_CLASSES}, got {classes!r}")
+    return (classes == "all", check_flag("per_image", per_image), check_flag("include_background", include_background),
+            _check_ignore(ignore_index), B, Cc, tuple(int(v) for v in logits.shape[2:]))
+
+
+def _lovasz_tie_weights(e: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """d loss_seg / d e of one segment by the tie rule: e [n] errors of the valid voxels, g [n] bool foreground.  Inside a group
+    of equal e the foreground comes first and gets 1 / (G + K) each (K: background voxels with a larger error); the b tied
+    background voxels share J(F, K + b) - J(F, K) = (G - F) / ((G + K)(G + K + b)) equally (1 / b when G + K == 0)."""
+    n = e.numel()
+    if n == 0:
+        return e.new_zeros(0)
+    order = torch.argsort(e, descending=True, stable=True)
+    es, gs = e[order], g[order].to(e.dtype)
+    _, inverse, size = torch.unique_consecutive(es, return_inverse=True, return_counts=True)
+    last = torch.cumsum(size, 0) - 1                                  # last sorted position of each group of equal e
+    f_end, k_end = torch.cumsum(gs, 0)[last], torch.cumsum(1.0 - gs, 0)[last]
+    f_grp = torch.zeros_like(f_end).index_add_(0, inverse, gs)
+    b_grp = size.to(e.dtype) - f_grp
+    G = gs.sum()
+    gk = G + (k_end - b_grp)                                          # G + K, K the background in front of the group
+    fg_w = 1.0 / gk.clamp(min=1.0)
+    bg_w = torch.where(gk > 0, (G - f_end) / (gk * (gk + b_grp)).clamp(min=1.0), 1.0 / b_grp.clamp(min=1.0))
+    ws = torch.where(gs > 0, fg_w[inverse], bg_w[inverse])
+    return torch.zeros_like(e).index_put_((order,), ws)
+
+
+def _lovasz_torch(z: torch.Tensor, y: torch.Tensor, all_classes: bool, per_image: bool, bg: bool, ig, weight) -> torch.Tensor:
+    """The formulas of ``lovasz_softmax_loss`` in plain torch ops: z [B, vol, C], y [B, vol] labels.  A segment's value is
+    sum_i s_i e_i with s the (constant) tie-rule weights: the Lovasz extension's value, and the tie rule's gradient by autograd."""
+    B, _, Cc = z.shape
+    y = y.to(z.dtype if z.dtype in (torch.float32, torch.float64) else torch.float32)
+    valid = (y >= 0) & (y < Cc) & (y == y.floor())
+    if ig is not None:
+        valid = valid & (y != ig)
+    ex = (z - z.max(-1, keepdim=True).values).exp()
+    den = ex.sum(-1, keepdim=True)
+    hot = (y.unsqueeze(-1) == torch.arange(Cc, dtype=y.dtype, device=y.device)) & valid.unsqueeze(-1)
+    others = (ex * (~hot).to(z.dtype)).sum(-1, keepdim=True)          # 1 - p_y as the sum of the others over the denominator
+    err = torch.where(hot, others / den, ex / den)
+    total = z.new_zeros(())
+    groups = [(err[b], hot[b], valid[b]) for b in range(B)] if per_image else [(err.reshape(-1, Cc), hot.reshape(-1, Cc), valid.reshape(-1))]
+    for e_g, h_g, v_g in groups:
+        terms = []
+        for c in range(0 if bg else 1, Cc):
+            e, g = e_g[v_g, c], h_g[v_g, c]
+            if all_classes or bool(g.any()):
+                terms.append((_lovasz_tie_weights(e.detach(), g) * e).sum())
+        if terms:
+            total = total + torch.stack(terms).mean()
+    loss = total / len(groups)
+    return loss if weight is None else loss * weight.to(z.dtype).reshape(())
+
+
+class _LovaszFn(torch.autograd.Function):
+    """The term on the kernels: keys, sort, prefix, statistics and the f64 finalize in forward; the gradient pass on the same
+    workspace when backward asks for it (csrc/lovasz.hip).  ``weight`` is a constant."""
+
+    @staticmethod
+    def forward(ctx, logits_cl, target, weight, opts, ws):
+        B, H, W, D, Cc = logits_cl.shape
+        all_classes, per_image, bg, ig, lam = opts
+        loss = torch.empty(1, dtype=torch.float32, device=logits_cl.device)
+        L.call("mivp_lovasz_loss", L.ptr(logits_cl), L.ptr(target), B, H * W * D, Cc, 1 if bg else 0, 0 if ig is None else ig,
+               0 if ig is None else 1, 1 if per_image else 0, 1 if all_classes else 0, lam, L.ptr(weight), L.ptr(ws),
+               L.ptr(loss), L.ptr(None), 0, L.stream())
+        ctx.save_for_backward(logits_cl, target, ws)
+        ctx.weight, ctx.opts = weight, opts
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits_cl, target, ws = ctx.saved_tensors
+        B, H, W, D, Cc = logits_cl.shape
+        all_classes, per_image, bg, ig, lam = ctx.opts
+        g = g.detach().to(torch.float32).contiguous()
+        dz = torch.empty_like(logits_cl)
+        L.call("mivp_lovasz_loss_grad", L.ptr(logits_cl), L.ptr(target), B, H * W * D, Cc, 1 if bg else 0,
+               0 if ig is None else ig, 0 if ig is None else 1, 1 if per_image else 0, 1 if all_classes else 0, lam,
+               L.ptr(ctx.weight), L.ptr(ws), L.ptr(g), L.ptr(dz), 0, L.stream())
+        return dz, None, None, None, None
+
+
+def _lovasz_workspace(device, B: int, Cc: int, bg: bool, per_image: bool, vol: int) -> torch.Tensor:
+    nbytes = int(L.lib().mivp_lovasz_ws(B, Cc, 1 if bg else 0, 1 if per_image else 0, vol))
+    if nbytes == 0:
+        raise ValueError(f"Lovasz-Softmax of {B} x {Cc} x {vol} voxels: B must be <= 65535 and the keys fewer than 2^31")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _lovasz_term(logits, target, all_classes, per_image, bg, ig, B, Cc, dims, weight, lam, ws=None) -> torch.Tensor:
+    """``lam weight`` times the term; the kernels for channels-last f32 GPU logits, else the torch composition."""
+    base = logits.permute(0, 2, 3, 4, 1)
+    if logits.is_cuda and logits.dtype == torch.float32 and base.is_contiguous():
+        tgt = target.detach().to(torch.float32).contiguous()
+        if weight is not None:
+            weight = weight.to(torch.float32).contiguous()
+        if ws is None:
+            ws = _lovasz_workspace(logits.device, B, Cc, bg, per_image, math.prod(dims))
+        return _LovaszFn.apply(base, tgt, weight, (all_classes, per_image, bg, ig, lam), ws)
+    term = _lovasz_torch(base.reshape(B, -1, Cc), target.detach().reshape(B, -1), all_classes, per_image, bg, ig, weight)
+    return term if lam == 1.0 else lam * term
+
+
+def lovasz_softmax_loss(logits: torch.Tensor, target: torch.Tensor, classes: str = "present", per_image: bool = False,
+                        include_background: bool = True, ignore_index: Optional[int] = None,
+                        weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The Lovasz-Softmax loss of Berman, Triki & Blaschko (CVPR 2018): the convex surrogate of the per-class Jaccard index.
+    logits [B, C, H, W, D] (2 <= C <= 8), target [B, 1, H, W, D] (or [B, H, W, D]) class indices of any dtype.  A segment is one
+    class c >= c0 of one sample (``per_image``) or of the batch; over its valid voxels (the rule of ``seg_loss``), with
+    p = softmax_c(z), g = [y == c], e = g ? 1 - p_c : p_c, G = sum g, J(F, K) = 1 - (G - F) / (G + K), J(0, 0) = 0::
+
+        loss_seg = sum_j e_(j) (J_j - J_(j-1))        errors in descending order; F_j, K_j: foreground, background among the first j
+
+    ``classes="present"`` averages the segments with G > 0 (none: 0, decided on the device), ``"all"`` every segment;
+    ``per_image`` averages the samples' means.  Gradient on ties: inside a group of equal e the foreground voxels come first
+    and get 1 / (G + K) each, the tied background voxels share their group's difference of J equally -- independent of memory
+    order, equal bits from call to call.  ``weight``: a one-element tensor on the logits' device (None = 1), read on the device.
+    Channels-last f32 CUDA logits take the kernels (a fixed number of launches, nothing read back, recordable); any other
+    layout, dtype or device takes the same formulas and tie rule as plain torch ops."""
+    all_classes, per_image, bg, ig, B, Cc, dims = _lovasz_args(logits, target, classes, per_image, include_background, ignore_index)
+    weight = _check_boundary_weight(weight, logits.device)
+    return _lovasz_term(logits, target, all_classes, per_image, bg, ig, B, Cc, dims, weight, 1.0)
+
+
+class LovaszSoftmaxLoss(torch.nn.Module):
+    """``base(logits, target) + lambda_lovasz weight lovasz_softmax_loss(logits, target, **options)`` (the term alone without
+    a ``base``); ``options``: ``classes``, ``per_image``, ``include_background``, ``ignore_index``.  ``base`` is any module of
+    (logits, target), e.g. a ``SegLoss``; ``train.step_loss`` takes the whole as ``conf.seg_loss``.  ``weight`` is a device
+    float outside ``state_dict`` that ``set_weight`` schedules between the replays of a recorded step.  The workspace (keys,
+    the sort's second buffer, the prefix) is allocated once per shape; a backward pass reads it before the next forward."""
+
+    def __init__(self, base: Optional[torch.nn.Module] = None, lambda_lovasz: float = 1.0, *, classes: str = "present",
+                 per_image: bool = False, include_background: bool = True, ignore_index: Optional[int] = None):
+        super().__init__()
+        if base is not None and not isinstance(base, torch.nn.Module):
+            raise TypeError(f"base must be None or a torch.nn.Module of (logits, target), got {base!r}")
+        lam = check_at_least("lambda_lovasz", lambda_lovasz, 0.0)
+        if lam > float(np.finfo(np.float32).max):
+            raise ValueError(f"lambda_lovasz must be finite in fp32, got {lambda_lovasz!r}")
+        if classes not in LOVASZ_CLASSES:
+            raise ValueError(f"classes must be one of {LOVASZ_CLASSES}, got {classes!r}")
+        self.base = base
+        self.lambda_lovasz = lam
+        self.classes = classes
+        self.per_image = check_flag("per_image", per_image)
+        self.include_background = check_flag("include_background", include_background)
+        self.ignore_index = _check_ignore(ignore_index)
+        self.register_buffer("weight", torch.ones(1, dtype=torch.float32), persistent=False)
+        self._ws = {}
+
+    def set_weight(self, value: float) -> None:
+        """Set the factor of the term (``lambda_lovasz`` times it is the term's weight): a stream-ordered copy into the
+        module's buffer, legal between the replays of a recorded step."""
+        v = check_finite("weight", value)
+        if self.weight.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("LovaszSoftmaxLoss.set_weight inside a recording: a recording must not freeze today's weight "
+                               "into the graph; call it between replays")
+        self.weight.copy_(torch.tensor([v], dtype=torch.float32))
+
+    def _scratch(self, device, B: int, Cc: int, vol: int):
+        key = (str(device), B, Cc, vol)
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = _lovasz_workspace(device, B, Cc, self.include_background, self.per_image, vol)
+        return ws
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        all_classes, per_image, bg, ig, B, Cc, dims = _lovasz_args(logits, target, self.classes, self.per_image,
+                                                                   self.include_background, self.ignore_index)
+        if self.weight.device != logits.device:
+            raise ValueError(f"the module is on {self.weight.device}, the logits on {logits.device}: move it with .to()")
+        ws = self._scratch(logits.device, B, Cc, math.prod(dims)) if logits.is_cuda else None
+        term = _lovasz_term(logits, target, all_classes, per_image, bg, ig, B, Cc, dims, self.weight, self.lambda_lovasz, ws)
+        return term if self.base is None else self.base(logits, target) + term
+
+    def extra_repr(self) -> str:
+        return (f"lambda_lovasz={self.lambda_lovasz}, classes={self.classes!r}, per_image={self.per_image}, "
+                f"include_background={self.include_background}, ignore_index={self.ignore_index}")

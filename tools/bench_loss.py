@@ -1,6 +1,6 @@
 """Time the recorded loss + gradient of mivp_seg_loss (csrc/segloss.hip) against the Dice-focal kernels and eager torch.
 
-    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10] [--boundary | --cldice | --hausdorff]
+    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10] [--boundary | --cldice | --hausdorff | --lovasz]
 
 Shapes: 96^3 at B = 4 (the `downstream` step's) and 128 x 128 x 8 at B = 14, both C = 2.  Settings of the new entry:
   (a) Dice-equivalent options (alpha = beta = 0.5), lambda_voxel = 0
@@ -38,6 +38,17 @@ operands as ``--boundary``, alpha = 2:
   (d) mivp_hausdorff_loss alone (value + gradient) on given maps
   (e) mivp_distmap_signed alone, the maps of ``--boundary``, in the same job: half the fields of (c)
   (f) for scale, eager and on the CPU: scipy's distance_transform_edt of both masks and sides plus the torch term with autograd
+
+``--lovasz`` times the Lovasz-Softmax term instead (csrc/lovasz.hip), same shapes and operands, C = 2, both
+classes, the batch as one segment per class (7.1 M and 3.7 M keys):
+  (a) as above: the path without the term
+  (b) the same plus the term through LovaszSoftmaxLoss: mivp_lovasz_loss after the base's value pass and, after the base's
+      gradient pass, mivp_lovasz_loss_grad (here accumulating onto the same dz; the module leaves that add to autograd)
+  (c) mivp_lovasz_loss alone, value only: keys, sort, prefix, statistics, finalize
+  (d) mivp_lovasz_loss_grad alone: the searches
+  (e) a device copy of the term's unsorted keys + mivp_sort_u32 on them, and (f) that copy alone: (e) - (f) is the sort, set
+      against the 4 passes x 2 x 4 N bytes its keys have to move (an estimate, at 6.3 TB/s)
+  (g) the authors' composition with autograd, eager, on the same GPU: torch.sort per class, cumsum, a gather back
 
 Each kernel variant is one call (value + gradient) recorded in a HIP graph; a run is `replays` replays between two device
 events after `warmup` replays; the figure is the median over `runs` runs with the spread (min .. max).  One JSON line per
@@ -408,6 +419,110 @@ def hausdorff_main(args):
     print(json.dumps({"bench_hausdorff_ms": summary}))
 
 
+def lovasz_main(args):
+    """The Lovasz-Softmax term: see the module docstring."""
+    summary = {}
+    lam = 0.5
+    for name, B, dims in SHAPES:
+        vol, Cc = dims[0] * dims[1] * dims[2], 2
+        z, y = lesion_case(B, dims, Cc)
+        yf = y.view(B, vol).to(DEV)
+        w = torch.tensor(WEIGHTS, dtype=torch.float32, device=DEV)
+        # every operand is allocated here, outside the recordings
+        dz, loss = torch.empty_like(z), torch.empty(2, dtype=torch.float32, device=DEV)
+        one = torch.ones(1, dtype=torch.float32, device=DEV)     # the incoming gradient, the term's weight
+        sws = torch.empty(int(L.lib().mivp_seg_loss_ws(B, vol)), dtype=torch.float32, device=DEV)
+        lws = torch.empty(int(L.lib().mivp_lovasz_ws(B, Cc, 1, 0, vol)), dtype=torch.uint8, device=DEV)
+        S, N = Cc, B * vol
+        fresh = torch.empty((S, N), dtype=torch.int32, device=DEV)
+        keys, counts = torch.empty_like(fresh), torch.empty((S, 2), dtype=torch.int32, device=DEV)
+        L.call("mivp_lovasz_keys", L.ptr(z), L.ptr(yf), B, vol, Cc, 1, IGNORE, 1, 0, L.ptr(fresh), L.ptr(counts), L.stream())
+        kws = torch.empty(int(L.lib().mivp_sort_u32_ws(S, N)), dtype=torch.uint8, device=DEV)
+
+        def seg_value():
+            L.call("mivp_seg_loss", L.ptr(z), L.ptr(yf), B, vol, Cc, 0, 0, 0.5, 0.5, 0.0, L.ptr(w), IGNORE, 1, 1.0, 1.0, L.ptr(sws),
+                   L.ptr(loss), None, L.stream())
+
+        def seg_grad():
+            L.call("mivp_seg_loss_grad", L.ptr(z), L.ptr(yf), B, vol, Cc, 0, 0, 0.5, 0.5, 0.0, L.ptr(w), IGNORE, 1, 1.0, 1.0,
+                   L.ptr(sws), L.ptr(one), L.ptr(dz), L.stream())
+
+        def term_value():
+            L.call("mivp_lovasz_loss", L.ptr(z), L.ptr(yf), B, vol, Cc, 1, IGNORE, 1, 0, 0, lam, L.ptr(one), L.ptr(lws),
+                   C.c_void_p(loss.data_ptr() + 4), None, 0, L.stream())
+
+        def term_grad():
+            L.call("mivp_lovasz_loss_grad", L.ptr(z), L.ptr(yf), B, vol, Cc, 1, IGNORE, 1, 0, 0, lam, L.ptr(one), L.ptr(lws),
+                   L.ptr(one), L.ptr(dz), 1, L.stream())
+
+        def plain_step():
+            seg_value()
+            seg_grad()
+
+        def lovasz_step():
+            seg_value()
+            term_value()
+            seg_grad()
+            term_grad()
+
+        def copy_alone():
+            keys.copy_(fresh)
+
+        def copy_and_sort():
+            keys.copy_(fresh)
+            L.call("mivp_sort_u32", L.ptr(keys), S, N, L.ptr(kws), L.stream())
+
+        res = {}
+        term_value()                                              # (d) reads the workspace of a value pass
+        for key, label, call in (("a", "(a) dice + weighted CE, value then gradient", plain_step),
+                                 ("b", "(b) the same with the Lovasz-Softmax term", lovasz_step),
+                                 ("c", "(c) mivp_lovasz_loss alone, value only", term_value),
+                                 ("d", "(d) mivp_lovasz_loss_grad alone", term_grad),
+                                 ("e", "(e) copy of the unsorted keys + mivp_sort_u32", copy_and_sort),
+                                 ("f", "(f) that copy alone", copy_alone)):
+            r = timed(recorded(call), args.runs, args.replays, args.warmup)
+            r.update(shape=name, variant=label, share_of_step=r["ms"] / STEP_MS)
+            res[key] = r
+            summary[f"{name} | {label}"] = [round(r[k], 4) for k in ("ms", "lo", "hi")]
+            print(json.dumps(r), flush=True)
+        extra = res["b"]["ms"] - res["a"]["ms"]
+        summary[f"{name} | (b) - (a)"] = dict(ms=round(extra, 4), share_of_step=round(extra / STEP_MS, 4))
+        sort_ms = res["e"]["ms"] - res["f"]["ms"]
+        est_gb = 4 * 2 * 4 * S * N / 1e9
+        summary[f"{name} | (e) - (f), the sort of {S * N} keys"] = dict(
+            ms=round(sort_ms, 4), estimate_gb=round(est_gb, 4), estimate_ms_at_6p3_tb_s=round(est_gb / 6.3, 4),
+            multiple_of_estimate=round(sort_ms / (est_gb / 6.3), 2))
+
+        # the authors' composition on the same GPU: softmax, then per class a sort of the errors, the Jaccard recurrence on the
+        # sorted labels and a dot product; autograd gathers back through the sort's indices
+        plain = z.view(B, *dims, Cc).permute(0, 4, 1, 2, 3).contiguous().requires_grad_(True)
+        lab = yf.view(-1)
+        keep = lab != float(IGNORE)
+
+        def eager():
+            plain.grad = None
+            p = torch.softmax(plain, 1).permute(0, 2, 3, 4, 1).reshape(-1, Cc)[keep]
+            yk = lab[keep]
+            terms = []
+            for c in range(Cc):
+                fg = (yk == c).float()
+                if fg.sum() == 0:
+                    continue
+                es, perm = torch.sort((fg - p[:, c]).abs(), 0, descending=True)
+                fs = fg[perm]
+                gts = fs.sum()
+                jac = 1.0 - (gts - fs.cumsum(0)) / (gts + (1.0 - fs).cumsum(0))
+                jac = torch.cat([jac[:1], jac[1:] - jac[:-1]])
+                terms.append(torch.dot(es, jac))
+            (lam * torch.stack(terms).mean()).backward()
+        r = timed(eager, args.runs, max(3, args.replays // 10), 3)
+        r.update(shape=name, variant="(g) torch.sort composition of the term, eager", share_of_step=r["ms"] / STEP_MS)
+        summary[f"{name} | (g) torch eager"] = [round(r[k], 4) for k in ("ms", "lo", "hi")]
+        summary[f"{name} | (g) / ((c) + (d))"] = round(r["ms"] / (res["c"]["ms"] + res["d"]["ms"]), 2)
+        print(json.dumps(r), flush=True)
+    print(json.dumps({"bench_lovasz_ms": summary}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
@@ -416,8 +531,11 @@ def main():
     ap.add_argument("--boundary", action="store_true", help="time the boundary term (DESIGN 4.35) instead")
     ap.add_argument("--cldice", action="store_true", help="time the clDice term (DESIGN 4.36) instead")
     ap.add_argument("--hausdorff", action="store_true", help="time the Hausdorff distance-transform term (DESIGN 4.39) instead")
+    ap.add_argument("--lovasz", action="store_true", help="time the Lovasz-Softmax term (DESIGN 4.40) instead")
     args = ap.parse_args()
     assert args.runs >= 3
+    if args.lovasz:
+        return lovasz_main(args)
     if args.hausdorff:
         return hausdorff_main(args)
     if args.boundary:
