@@ -18,6 +18,193 @@
 //   head-major layout (a tile never straddles a window: Nqp % 16 == 0), so the pieces are first moved into address
 //   order across the lanes (ds_bpermute: lane l takes piece l = token l/3, part l%3; the crossbar, no LDS memory) and
 //   leave as one 48-lane contiguous store per chunk.
+//   A wave of this form owns QKV_C48_PAIRS consecutive tile pairs: the rows of all of them are requested
+//   at once (unconditional loads at clamped addresses, the selects after them), and each third (q | k | v) of the weight
+//   image is fetched once and passes over all the pairs -- 18 fragment loads per 32 * QKV_C48_PAIRS tokens instead of per
+//   32.  The workgroup's waves stay independent: no LDS, no barrier.  The per-token arithmetic is the generic path's, with
+//   the two places where the compiler is free to fuse or not written out as the generic path's code has them (c48_ln).
+constexpr int QKV_C48_PAIRS = 2;
+
+struct C48Tile { int src; long xrow, chunk; };          // per lane: source voxel of token r; uniform: first x row of the batch,
+                                                        // element offset of head 0's chunk of the tile
+// tile `tile` (16 tokens of one window, Nqp % 16 == 0): its index load and its uniform bases
+MIVP_DEV C48Tile c48_tile(const MivpSwinDesc& d, const int* __restrict__ tok_src, long tile, int r) {
+    const unsigned Nqp = (unsigned)d.Nqp, tt = (unsigned)(tile * 16);       // T = B*P*Nqp fits 32 bits (checked on the host)
+    // (the divisions are expanded on the vector ALU: pin their uniform results to scalar registers, or every address
+    // below is formed per lane in 64-bit vector arithmetic)
+    const unsigned bpu = (unsigned)__builtin_amdgcn_readfirstlane((int)(tt / Nqp));
+    const unsigned slot0 = tt - bpu * Nqp;
+    const unsigned b = (unsigned)__builtin_amdgcn_readfirstlane((int)(bpu / (unsigned)d.P));
+    const unsigned pw = bpu - b * (unsigned)d.P;
+    C48Tile t;
+    t.src = tok_src[pw * Nqp + slot0 + (unsigned)r];
+    t.xrow = (long)b * d.vol_in;
+    t.chunk = ((long)bpu * 4 * Nqp + slot0) * 12;
+    return t;
+}
+
+// the two row pieces of token r (channels 8g.. and 32 + 8g..; lanes g >= 2 have no second piece at C = 48 and a padded token
+// has no row: both read a valid address and are deselected in c48_ln)
+MIVP_DEV void c48_gather(const bf16_t* __restrict__ x, const C48Tile& t, int g, bf16x8 (&raw)[2]) {
+    const long row = (t.xrow + max(t.src, 0)) * 48L;
+    raw[0] = ld8(x + (row + 8 * g));
+    raw[1] = ld8(x + (row + min(32 + 8 * g, 40)));
+}
+
+// LayerNorm of token r from its pieces -> its two B fragments.  The expressions are the generic path's below, its branches as
+// selects.  Where the generic path's code leaves the choice to the compiler, this one states what that code does, so that
+// both give the same bits: the squares of the variance are rounded before they are added (packed multiplies there), and the
+// affine step is one fused multiply-add.
+MIVP_DEV void c48_ln(const MivpSwinDesc& d, const bf16x8 (&raw)[2], int src, int g, const float* __restrict__ ln_w,
+                     const float* __restrict__ ln_b, bf16x8 (&xb)[2]) {
+    const int C = d.C;
+    float xs[2][8];
+    float sum = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const bool ok = src >= 0 && 32 * s + 8 * g < C;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { xs[s][i] = sel(ok, (float)raw[s][i], 0.f); sum += xs[s][i]; }
+    }
+    const float mean = col_sum(sum) / (float)C;
+    float var = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const bool in = 32 * s + 8 * g < C;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+#pragma clang fp contract(off)
+            const float dv = xs[s][i] - mean;
+            const float sq = dv * dv;
+            var = sel(in, var + sq, var);
+        }
+    }
+    const float rstd = rsqrtf(col_sum(var) / (float)C + d.ln_eps);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int c = min(32 * s + 8 * g, 40);
+        const bool ok = src >= -1 && 32 * s + 8 * g < C;           // -1: zero-pad token still goes through LN (-> beta)
+        bf16x8 y;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) y[i] = (bf16_t)__builtin_fmaf((xs[s][i] - mean) * rstd, ln_w[c + i], ln_b[c + i]);
+        xb[s] = keep_if(y, ok);
+    }
+}
+
+// where lane l's 8-byte piece of a chunk comes from: lane l takes piece l = token l/3, part l%3
+struct C48Route { int dl, src_addr[4]; bool from_b[4]; };
+MIVP_DEV C48Route c48_route(int lane) {
+    C48Route rt;
+    // lanes 48-63 repeat the pieces of lanes 32-47 (same bytes to the same addresses): no exec-mask region around each of
+    // the 24 stores (three scalar instructions and a branch apiece in a kernel bound by instruction issue)
+    rt.dl = lane < 48 ? lane : lane - 16;
+    const int rq = rt.dl / 3, gq = rt.dl - 3 * rq;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int ch = 12 * h + 4 * gq;                         // channel of this lane's piece inside the q|k|v third
+        rt.src_addr[h] = 4 * (rq + 16 * ((ch & 15) >> 2));
+        rt.from_b[h] = (ch >> 4) != ((12 * h) >> 4);
+    }
+    return rt;
+}
+
+// the six fragments of third sl (q | k | v) of the weight image
+MIVP_DEV void c48_wthird(const bf16_t* __restrict__ wqkv, int sl, int lane, bf16x8 (&w)[3][2]) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            // scalar fragment base + one 32-bit lane offset (the 64-bit per-lane form was two VALU instructions per load)
+            const char* fb = reinterpret_cast<const char*>(wqkv) + (size_t)(((3 * sl + t) * 2 + s) * 1024);
+            w[t][s] = *reinterpret_cast<const bf16x8*>(fb + (unsigned)(16 * lane));
+        }
+    }
+}
+
+// one third of a tile pair: products, scale, pack, the pieces moved into address order, eight 48-lane contiguous stores
+MIVP_DEV void c48_third(const MivpSwinDesc& d, const bf16x8 (&w)[3][2], const bf16x8 (&xb)[2][2], float sc, bf16_t* base,
+                        const long (&chunk)[2], const C48Route& rt) {
+    const unsigned Nqp = (unsigned)d.Nqp;
+    u32x2 pk[3][2];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        f32x4 acc0 = fzero4(), acc1 = fzero4();
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            acc0 = mfma16(w[t][s], xb[0][s], acc0);
+            acc1 = mfma16(w[t][s], xb[1][s], acc1);
+        }
+        pk[t][0] = __builtin_bit_cast(u32x2, pack4(acc0 * sc));
+        pk[t][1] = __builtin_bit_cast(u32x2, pack4(acc1 * sc));
+    }
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int ta = (12 * h) >> 4, tb = (12 * h + 8) >> 4;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            u32x2 piece;
+            piece[0] = (unsigned)__builtin_amdgcn_ds_bpermute(rt.src_addr[h], (int)pk[ta][u][0]);
+            piece[1] = (unsigned)__builtin_amdgcn_ds_bpermute(rt.src_addr[h], (int)pk[ta][u][1]);
+            if (tb != ta) {
+                const unsigned b0 = (unsigned)__builtin_amdgcn_ds_bpermute(rt.src_addr[h], (int)pk[tb][u][0]);
+                const unsigned b1 = (unsigned)__builtin_amdgcn_ds_bpermute(rt.src_addr[h], (int)pk[tb][u][1]);
+                piece[0] = rt.from_b[h] ? b0 : piece[0];
+                piece[1] = rt.from_b[h] ? b1 : piece[1];
+            }
+            char* cb = reinterpret_cast<char*>(base + (chunk[u] + (long)h * Nqp * 12));     // uniform
+            *reinterpret_cast<u32x2*>(cb + (unsigned)(8 * rt.dl)) = piece;
+        }
+    }
+}
+
+// T % 32 == 0 here (the launcher asks for Nqp % 32 == 0): a tile pair is live or dead as a whole; a wave's trip count is
+// clamped to the live pairs (the clamped repeats of the last pair are loaded and normalised but not stored), and a wave
+// with no live pair leaves
+template <int R>
+MIVP_DEV void qkv_c48_tiles(const MivpSwinDesc& d, const bf16_t* __restrict__ x, const int* __restrict__ tok_src,
+                            const float* __restrict__ ln_w, const float* __restrict__ ln_b, const bf16_t* __restrict__ wqkv,
+                            bf16_t* __restrict__ q, bf16_t* __restrict__ k, bf16_t* __restrict__ v) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = lane & 15, g = lane >> 4;
+    const long pairs = ((long)d.B * d.P * d.Nqp) >> 5;
+    const long pair0 = ((long)blockIdx.x * 4 + wave) * R;
+    if (pair0 >= pairs) return;
+    const int n = (int)min((long)R, pairs - pair0);
+    C48Tile tl[R][2];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) tl[j][u] = c48_tile(d, tok_src, (pair0 + min(j, n - 1)) * 2 + u, r);
+    }
+    bf16x8 raw[R][2][2];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) c48_gather(x, tl[j][u], g, raw[j][u]);
+    }
+    bf16x8 xb[R][2][2];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) c48_ln(d, raw[j][u], tl[j][u].src, g, ln_w, ln_b, xb[j][u]);
+    }
+    const C48Route rt = c48_route(lane);
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) {
+        bf16x8 w[3][2];
+        c48_wthird(wqkv, sl, lane, w);
+        const float sc = sl == 0 ? d.q_scale : (sl == 1 ? MIVP_LOG2E : 1.0f);       // K carries log2(e): common.hpp
+        bf16_t* base = sl == 0 ? q : (sl == 1 ? k : v);
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            if (j < n) {                                        // uniform
+                const long chunk[2] = {tl[j][0].chunk, tl[j][1].chunk};
+                c48_third(d, w, xb[j], sc, base, chunk, rt);
+            }
+        }
+    }
+}
+
 template <int KS, bool CH12>
 __global__ __launch_bounds__(256, 4) void k_swin_qkv_fwd(MivpSwinDesc d, const bf16_t* __restrict__ x,
                                                       const int* __restrict__ tok_src,
@@ -25,6 +212,10 @@ __global__ __launch_bounds__(256, 4) void k_swin_qkv_fwd(MivpSwinDesc d, const b
                                                       const bf16_t* __restrict__ wqkv,
                                                       bf16_t* __restrict__ q, bf16_t* __restrict__ k,
                                                       bf16_t* __restrict__ v) {
+    if constexpr (CH12) {
+        qkv_c48_tiles<QKV_C48_PAIRS>(d, x, tok_src, ln_w, ln_b, wqkv, q, k, v);
+        return;
+    }
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar wave index
     const int r = lane & 15, g = lane >> 4;
     const int C = d.C, hd = C / d.heads;
@@ -82,71 +273,6 @@ __global__ __launch_bounds__(256, 4) void k_swin_qkv_fwd(MivpSwinDesc d, const b
         }
     }
 
-    if constexpr (CH12) {
-        const unsigned Nqp = (unsigned)d.Nqp;
-        // T % 32 == 0 here (the launcher asks for Nqp % 32 == 0): a wave's two tiles are live or dead together, and a dead
-        // wave leaves (no barrier in this instantiation)
-        if (tile0 * 16 >= T) return;
-        long chunk[2];                                          // element offset of head 0's chunk of each token tile
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const unsigned tt = (unsigned)((tile0 + u) * 16);
-            // (the division is expanded on the vector ALU: pin its uniform result to a scalar register, or every chunk address
-            // below is formed per lane in 64-bit vector arithmetic)
-            const unsigned bpu = (unsigned)__builtin_amdgcn_readfirstlane((int)(tt / Nqp));
-            chunk[u] = ((long)bpu * 4 * Nqp + (tt - bpu * Nqp)) * 12;
-        }
-        // lanes 48-63 repeat the pieces of lanes 32-47 (same bytes to the same addresses): no exec-mask region around each of
-        // the 24 stores (three scalar instructions and a branch apiece in a kernel bound by instruction issue)
-        const int dl = lane < 48 ? lane : lane - 16, rq = dl / 3, gq = dl - 3 * rq;
-        int src_addr[4];
-        bool from_b[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const int ch = 12 * h + 4 * gq;                     // channel of this lane's piece inside the q|k|v third
-            src_addr[h] = 4 * (rq + 16 * ((ch & 15) >> 2));
-            from_b[h] = (ch >> 4) != ((12 * h) >> 4);
-        }
-#pragma unroll
-        for (int sl = 0; sl < 3; ++sl) {
-            const float sc = sl == 0 ? d.q_scale : (sl == 1 ? MIVP_LOG2E : 1.0f);
-            u32x2 pk[3][2];
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                f32x4 acc0 = fzero4(), acc1 = fzero4();
-#pragma unroll
-                for (int s = 0; s < KS; ++s) {
-                    // scalar fragment base + one 32-bit lane offset (the 64-bit per-lane form was two VALU instructions per load)
-                    const char* fb = reinterpret_cast<const char*>(wqkv) + (size_t)(((3 * sl + t) * KS + s) * 1024);
-                    const bf16x8 a = *reinterpret_cast<const bf16x8*>(fb + (unsigned)(16 * lane));
-                    acc0 = mfma16(a, xb[0][s], acc0);
-                    acc1 = mfma16(a, xb[1][s], acc1);
-                }
-                pk[t][0] = __builtin_bit_cast(u32x2, pack4(acc0 * sc));
-                pk[t][1] = __builtin_bit_cast(u32x2, pack4(acc1 * sc));
-            }
-            bf16_t* base = sl == 0 ? q : (sl == 1 ? k : v);
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const int ta = (12 * h) >> 4, tb = (12 * h + 8) >> 4;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    u32x2 piece;
-                    piece[0] = (unsigned)__builtin_amdgcn_ds_bpermute(src_addr[h], (int)pk[ta][u][0]);
-                    piece[1] = (unsigned)__builtin_amdgcn_ds_bpermute(src_addr[h], (int)pk[ta][u][1]);
-                    if (tb != ta) {
-                        const unsigned b0 = (unsigned)__builtin_amdgcn_ds_bpermute(src_addr[h], (int)pk[tb][u][0]);
-                        const unsigned b1 = (unsigned)__builtin_amdgcn_ds_bpermute(src_addr[h], (int)pk[tb][u][1]);
-                        piece[0] = from_b[h] ? b0 : piece[0];
-                        piece[1] = from_b[h] ? b1 : piece[1];
-                    }
-                    char* cb = reinterpret_cast<char*>(base + (chunk[u] + (long)h * Nqp * 12));     // uniform
-                    *reinterpret_cast<u32x2*>(cb + (unsigned)(8 * dl)) = piece;
-                }
-            }
-        }
-        return;
-    }
     const int n_out = 3 * C;
     const int n_tiles = (n_out + 15) / 16;
     const int per_split = (n_tiles + gridDim.y - 1) / gridDim.y;
@@ -1116,8 +1242,12 @@ extern "C" int mivp_swin_qkv_fwd(const MivpSwinDesc* d, const void* x, const int
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, *d, (const bf16_t*)x, tok_src, ln_w, ln_b, (const bf16_t*)wqkv,
                            (bf16_t*)q, (bf16_t*)k, (bf16_t*)v);
     };
-    if (ch12) launch(k_swin_qkv_fwd<2, true>);
-    else if (!for_tile_count<1, 2, 3, 4, 6>(KS, [&](auto ks) { launch(k_swin_qkv_fwd<decltype(ks)::value, false>); })) {
+    if (ch12) {                                                 // a wave owns QKV_C48_PAIRS pairs of 16-token tiles
+        const long pairs = T / 32;
+        const unsigned gp = (unsigned)((pairs + 4 * QKV_C48_PAIRS - 1) / (4 * QKV_C48_PAIRS));
+        hipLaunchKernelGGL((k_swin_qkv_fwd<2, true>), dim3(gp), dim3(256), 0, st, *d, (const bf16_t*)x, tok_src, ln_w, ln_b,
+                           (const bf16_t*)wqkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v);
+    } else if (!for_tile_count<1, 2, 3, 4, 6>(KS, [&](auto ks) { launch(k_swin_qkv_fwd<decltype(ks)::value, false>); })) {
         mivp_set_error("swin_qkv_fwd: C/32 not in {1,2,3,4,6}");
         return MIVP_EUNSUPPORTED;
     }
