@@ -4,7 +4,9 @@ torch on the CPU: bit-equal at every element, no tolerance (method and condition
 3/4 weights); every case asserts conditions (a) and (b) on 100 % of its float64 reference before it looks at the kernel.
 The one assertion that is not an equality is the 4-ulp bar on the BatchNorm affine (three fp32 roundings after exact
 sums).  Not covered here, with their own tests elsewhere: LeakyReLU prologues (0.01 is not dyadic), align_corners=True
-(weights are not dyadic), LayerNorm / softmax / attention (transcendental), uphead (folds measured statistics)."""
+(weights are not dyadic), LayerNorm / softmax / attention (transcendental).  The low-resolution head (uphead) folds
+measured statistics only at the level of functional.uphead; its kernels are exact below that level, where the test
+chooses scale, shift, mean and rstd: tests/test_hip_uphead.py."""
 import contextlib
 import ctypes
 import os

@@ -381,7 +381,8 @@ def test_head_conv_fused(cin, cout, dims):
 
 
 @pytest.mark.parametrize("C,cout,dims,training", [(48, 2, (6, 5, 7), True), (48, 2, (4, 4, 4), False), (8, 1, (3, 9, 2), True),
-                                                   (16, 2, (1, 2, 3), True)])
+                                                   (16, 2, (1, 2, 3), True), (48, 2, (5, 4, 17), True),
+                                                   (56, 1, (2, 3, 33), False)])
 def test_uphead_low_resolution_head(C, cout, dims, training):
     """upsample x2 (trilinear, align_corners=False) -> BatchNorm3d -> Conv3d 3^3 evaluated from the low-resolution
     tensor (csrc/uphead.hip): logits and the four parameter gradients against torch on the same bf16 input.
@@ -400,6 +401,7 @@ def test_uphead_low_resolution_head(C, cout, dims, training):
     bn.train(training)
     import copy
     bn2, conv2 = copy.deepcopy(bn).to(DEV), copy.deepcopy(conv).to(DEV)
+    bn3, conv3 = copy.deepcopy(bn).to(DEV), copy.deepcopy(conv).to(DEV)
     up = F.interpolate(x, scale_factor=2, mode="trilinear", align_corners=False)
     y = conv(bn(up))
     dy = torch.randn(y.shape, generator=g)
@@ -416,6 +418,15 @@ def test_uphead_low_resolution_head(C, cout, dims, training):
     assert rel_l2(conv2.bias.grad.cpu(), conv.bias.grad) < 6e-3
     assert rel_l2(bn2.weight.grad.cpu(), bn.weight.grad) < 6e-3
     assert rel_l2(bn2.bias.grad.cpu(), bn.bias.grad) < 6e-3
+    # a second backward in which x needs no gradient: the adjoint tensor is written at ldD = 56 (Cout = 2) / 32 (Cout = 1)
+    # instead of 64 and no dx is formed
+    out3 = Fn.uphead(bn3, conv3, cl(x.detach()))
+    out3.backward(dy.permute(0, 2, 3, 4, 1).contiguous().to(DEV))
+    torch.cuda.synchronize()
+    assert rel_l2(conv3.weight.grad.cpu(), conv.weight.grad) < 6e-3
+    assert rel_l2(conv3.bias.grad.cpu(), conv.bias.grad) < 6e-3
+    assert rel_l2(bn3.weight.grad.cpu(), bn.weight.grad) < 6e-3
+    assert rel_l2(bn3.bias.grad.cpu(), bn.bias.grad) < 6e-3
     if training:
         assert rel_l2(bn2.running_mean.cpu(), bn.running_mean) < 2e-3
         assert rel_l2(bn2.running_var.cpu(), bn.running_var) < 2e-3
