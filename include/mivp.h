@@ -1092,6 +1092,27 @@ int mivp_scan_prepare_dev(const void* raw, int32_t dtype, int32_t C, const int32
                           const int32_t* axes, const int32_t* tables, int32_t interp, const float* slot, int32_t clip,
                           int32_t flags, float* out, mivp_stream_t stream);
 
+/* Otsu foreground thresholds from the device histogram (csrc/scanstats.hip; mivp_amd/otsu.py otsu_slot / foreground_mask /
+ * window_slot_above, mivp_amd/scanstats.py IntensityWindow(foreground="otsu")).  These entry points joined
+ * ABI 18 without a bump: they are additive and no earlier signature changed.  No workspace, no host synchronisation.
+ *   mivp_scan_otsu_plan: hist [C][65536] (what mivp_scan_hist wrote) -> otsu: DEVICE int64 [C][4], 8-byte aligned, one
+ *     workgroup per channel.  With N = sum n_v and S = sum v n_v, a candidate t is a counted value that is not the largest
+ *     counted value; n0 = sum_{v<=t} n_v, A = sum_{v<=t} v n_v, P = A N - S n0, q = n0 (N - n0).  The threshold is the
+ *     candidate with the largest P^2 / q (Otsu's between-class variance is P^2 / (N^2 q)): two candidates compare by the
+ *     integers P_a^2 q_b and P_b^2 q_a in 256 bits, equal values pick the lower t.  No floating-point arithmetic: bitwise
+ *     reproducible.  otsu[c] = {t, n_le, n_gt, valid}: the counts at or below t and above it.  Fewer than two distinct
+ *     counted values, N == 0 or N >= 2^33: valid = 0, t = the largest counted value (0 if none), n_le = N, n_gt = 0.
+ *   mivp_scan_window_plan_above: mivp_scan_window_plan with the bins at or below otsu[c][0] read as zero (for N, S1, S2
+ *     and both ranks) where otsu[c][3] is set: the plan of mivp_scan_hist with above = t added.  valid = 0: the
+ *     unrestricted plan.  otsu must not be NULL.
+ *   mivp_scan_threshold_mask: out uint8 [H][W][D] = (raw[channel] > otsu[channel][0]), all ones where otsu[channel][3] is
+ *     0.  raw, dtype, C, dims as mivp_scan_hist; 0 <= channel < C; out needs no alignment.  One streaming launch. */
+int mivp_scan_otsu_plan(const int64_t* hist, int32_t C, int64_t* otsu, mivp_stream_t stream);
+int mivp_scan_window_plan_above(const int64_t* hist, int32_t C, int32_t mode, double q_lo, double q_hi, double b_min,
+                                double b_max, int32_t clip, const int64_t* otsu, float* slot, mivp_stream_t stream);
+int mivp_scan_threshold_mask(const void* raw, int32_t dtype, int32_t C, const int32_t* dims, int32_t channel,
+                             const int64_t* otsu, uint8_t* out, mivp_stream_t stream);
+
 /* Per-lesion region statistics and lesion-wise detection metrics (csrc/regions.hip; mivp_amd/regions.py).
  * These entry points joined ABI 18 without a bump: they are additive and no earlier signature changed.  dims = {H, W, D}
  * (host), volumes [H][W][D] row-major, fewer than 2^31 voxels; connectivity as mivp_label_components.  No host

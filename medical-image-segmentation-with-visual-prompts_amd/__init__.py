@@ -16,7 +16,7 @@ def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
                 "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit",
-                "skeleton"):
+                "skeleton", "otsu"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -24,7 +24,7 @@ def __getattr__(name):
         return SwinUnetR
     if name in ("SlidingWindowPredictor", "predict_volume", "evaluate_volume", "evaluate_volume_surface",
                 "predict_scan_volume", "evaluate_volume_lesions", "evaluate_volume_calibration", "WindowSkip", "WindowFit",
-                "foreground_box"):
+                "foreground_box", "AutoForeground"):
         from . import inference
         return getattr(inference, name)
     if name in ("surface_map", "distance_transform_sq", "surface_metrics"):
@@ -47,7 +47,8 @@ def __getattr__(name):
     if name in ("ScanGeometry", "prepare_scan", "prepare_labels", "restore_labels", "restore_labels_from_logits"):
         from . import scan
         return getattr(scan, name)
-    if name in ("scan_histogram", "window_slot", "IntensityWindow", "ScanHistogram", "WindowSlot", "ScanReport"):
+    if name in ("scan_histogram", "window_slot", "IntensityWindow", "ScanHistogram", "WindowSlot", "ScanReport", "OtsuSlot",
+                "otsu_slot", "foreground_mask", "window_slot_above"):
         from . import scanstats
         return getattr(scanstats, name)
     if name in ("IntensityDraws", "IntensitySlot", "draw_intensity", "augment_intensity", "FilterDraws", "FilterSlot",

@@ -244,6 +244,39 @@ class WindowSkip(ImmutableValue):
                   fill_logit=float(fill_logit))
 
 
+class AutoForeground:
+    """Foreground of a raw scan from its own histogram, for ``predict_scan(..., foreground=AutoForeground())`` on a
+    predictor built with ``skip=`` or ``fit=``: the voxels of ``raw[channel]`` above the Otsu threshold of
+    the scan's histogram (``mivp_amd.scanstats``; ``above``: count only voxels with a value greater than it, so that
+    ``above=0`` on MR separates tissue from the dark rim) take the place of the rule's fixed threshold on the prepared
+    volume, which means nothing for a z-scored scan.  A plain spec.  Like ``IntensityWindow`` it keeps the buffers its
+    calls work in -- histogram, Otsu record, the mask on the native grid and the mask on the model grid -- one set per
+    (device, channels, native shape, model grid), made at the first call, so **a spec serves one stream at a time**."""
+
+    def __init__(self, channel: int = 0, above: Optional[int] = None):
+        from . import scanstats
+        check_int_from("channel", channel, 0)
+        self.channel, self.above = int(channel), scanstats._check_above(above)
+        self._buffers: Dict[tuple, tuple] = {}
+
+    def buffers(self, channels: int, shape: Sequence[int], size: Sequence[int], device) -> tuple:
+        """(ScanHistogram, OtsuSlot, uint8 ``shape`` native-grid mask, uint8 ``[1, 1] + size`` model-grid mask) for scans
+        of ``channels`` channels and native ``shape`` on ``device``, predicted on the model grid ``size``."""
+        from . import scanstats
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        key = (str(dev), int(channels), tuple(int(n) for n in shape), tuple(int(n) for n in size))
+        if key not in self._buffers:
+            self._buffers[key] = (scanstats.ScanHistogram(channels, dev), scanstats.OtsuSlot(channels, dev),
+                                  torch.zeros(key[2], dtype=torch.uint8, device=dev),
+                                  torch.zeros((1, 1) + key[3], dtype=torch.uint8, device=dev))
+        return self._buffers[key]
+
+    def __repr__(self):
+        return f"AutoForeground(channel={self.channel}, above={self.above})"
+
+
 def _model_factor(conf) -> Tuple[int, int, int]:
     """Per-axis size multiple the SwinUnetR accepts: the patch embedding times the encoder's patch mergings (every stage
     halves H and W, only the first one D: swin_unetr.py merge_last_dim)."""
@@ -286,7 +319,9 @@ class SlidingWindowPredictor(CenterlineEvaluation):
     A compacted sub-batch can span any union box, so the blend is then ``mivp_window_blend_any``: the unfiltered launch
     grid, walked with a stride over a larger box (the same sums per voxel).  After a run
     ``n_kept`` is the number of windows kept and ``n_sub_run`` the number of sub-batches run.  ``set_region(mask)``
-    replaces the threshold rule by a resident uint8 ``[H, W, D]`` mask (foreground: ``mask != 0``).
+    replaces the threshold rule by a resident uint8 ``[H, W, D]`` mask (foreground: ``mask != 0``);
+    ``predict_scan(..., foreground=AutoForeground())`` computes such a mask per scan from the raw scan's own Otsu
+    threshold (for ``skip`` and ``fit`` alike).
 
     ``fit`` (a ``WindowFit``; ``None``, the default, launches what the predictor always launched and reads nothing back;
     not together with ``skip``) tiles the foreground's bounding box instead of the whole volume, so windows are removed
@@ -385,6 +420,7 @@ class SlidingWindowPredictor(CenterlineEvaluation):
         self.cc_ws = None        # post-processing workspace (8 bytes per voxel), allocated on first use
         # window skipping: the full work list stays as built; self.table is the active (compacted) list of the volume
         self.occupancy, self.region = None, None
+        self._auto_mask = None   # graph mode: the model-grid mask predict_scan(foreground=...) writes
         self.n_kept, self.n_sub_run = self.n_windows, self.n_sub
         self.box = None
         if self._rule is not None:
@@ -678,6 +714,47 @@ class SlidingWindowPredictor(CenterlineEvaluation):
             out = self.vol
         return scan.prepare_scan(r, geom, out=out, **intensity)
 
+    def _check_foreground(self, foreground, raw, geom):
+        """The host-side checks of ``foreground=`` (no device work)."""
+        from . import scan, scanstats
+        if foreground is None:
+            return
+        if self._rule is None:
+            raise ValueError("foreground= needs a predictor built with skip=WindowSkip(...) or fit=WindowFit(...)")
+        if not isinstance(foreground, AutoForeground):
+            raise ValueError(f"foreground must be an AutoForeground or None, got {type(foreground).__name__}")
+        if foreground.channel >= self.cin:
+            raise ValueError(f"foreground.channel {foreground.channel} is not a channel of a {self.cin}-channel scan")
+        r = scan._raw_view(raw, scan._check_geom(geom))
+        if r.dtype not in scanstats._DTYPES:
+            raise ValueError(f"foreground= takes int16 or uint8 scans, got {r.dtype}")
+
+    def _auto_region(self, foreground: AutoForeground, raw, geom) -> torch.Tensor:
+        """histogram -> Otsu plan -> mask on the native grid -> nearest to the model grid: four launches on the current
+        stream, no host read.  In graph mode the model-grid mask is the predictor's own buffer."""
+        from . import scan, scanstats
+        r = scan._raw_view(raw, geom)
+        hist, otsu, native, region = foreground.buffers(r.shape[0], geom.shape, self.image_size, r.device)
+        if self.graph_mode:
+            if self._auto_mask is None:
+                self._auto_mask = torch.zeros((1, 1) + self.image_size, dtype=torch.uint8, device=self.dev)
+            region = self._auto_mask
+        scanstats.scan_histogram(r, above=foreground.above, out=hist.zero_())
+        scanstats.otsu_slot(hist, out=otsu)
+        scanstats.foreground_mask(r, otsu, foreground.channel, out=native)
+        return scan.prepare_labels(native, geom, out=region, check=False)[0, 0]
+
+    def _with_foreground(self, foreground, raw, geom, run):
+        """``run()`` with the region of ``foreground`` (if given) in place of the one ``set_region`` holds."""
+        if foreground is None:
+            return run()
+        held = self.region
+        self.region = self._auto_region(foreground, raw, geom)
+        try:
+            return run()
+        finally:
+            self.region = held
+
     def predict_scan(self, raw: torch.Tensor, geom, restore: str = "labels", postprocess: Optional[Dict] = None,
                      **intensity) -> Dict[str, torch.Tensor]:
         """A raw scan on its native grid (``[C, H, W, D]`` int16 / uint8 / int32 / float32, ``geom`` a
@@ -688,11 +765,21 @@ class SlidingWindowPredictor(CenterlineEvaluation):
         blended logits on the native grid and takes the arg-max there (``restore_labels_from_logits``).  ``intensity``:
         ``a_min``, ``a_max``, ``b_min``, ``b_max``, ``clip`` of ``prepare_scan``, or its ``window`` (and ``mask``): a
         data-driven window (``mivp_amd.scanstats``) adds two launches in front of the prepare launch and no host read,
-        in graph mode too, where the prepare launch writes the predictor's resident volume as before."""
+        in graph mode too, where the prepare launch writes the predictor's resident volume as before.
+
+        ``foreground`` (one more keyword of ``intensity``: an ``AutoForeground``, on a predictor built with ``skip=`` or
+        ``fit=``; int16 / uint8 scans): for this call foreground is where the raw scan lies above its own Otsu threshold, in place of the
+        rule's threshold on the prepared volume.  Histogram -> Otsu plan -> ``foreground_mask`` -> ``prepare_labels``
+        (nearest, to the model grid) run in front of the occupancy / box launch with no host read, and the result equals
+        ``set_region(prepare_labels(foreground_mask(...))[0, 0])`` followed by ``predict_scan`` bit for bit.  A region
+        set with ``set_region`` is kept and holds again afterwards."""
         from . import scan
         post = self._post(postprocess)
+        foreground = intensity.pop("foreground", None)
+        self._check_foreground(foreground, raw, geom)
         x = self._prepare_scan(raw, geom, restore, postprocess, intensity)
-        labels, logits, _ = self._run(x, restore == "logits", None, post)
+        labels, logits, _ = self._with_foreground(foreground, raw, geom,
+                                                  lambda: self._run(x, restore == "logits", None, post))
         native = scan.restore_labels(labels, geom) if restore == "labels" else scan.restore_labels_from_logits(logits, geom)
         return {"labels": native, "labels_oriented": labels}
 
@@ -700,12 +787,14 @@ class SlidingWindowPredictor(CenterlineEvaluation):
                       **intensity) -> Tuple[float, float]:
         """``evaluate`` for a raw scan and a ground truth stored on the scan's native grid: ``prepare_labels`` takes the
         ground truth to the model grid and the scoring happens there, on the grid the model saw (as the reference's
-        ``test()`` does).  Returns (mean IoU, mean Dice)."""
+        ``test()`` does).  Returns (mean IoU, mean Dice).  ``intensity`` as in ``predict_scan``, its ``foreground`` included."""
         from . import scan
         self._post(postprocess)
+        foreground = intensity.pop("foreground", None)
+        self._check_foreground(foreground, raw, geom)
         x = self._prepare_scan(raw, geom, "labels", postprocess, intensity)
         seg = scan.prepare_labels(seg_native, geom)
-        return self.evaluate(x, seg, postprocess)
+        return self._with_foreground(foreground, raw, geom, lambda: self.evaluate(x, seg, postprocess))
 
 
 def _one_shot(model, x_or_shape, cin, num_classes, roi, overlap, mode, sigma_scale, sub_batch, graph, mirror_axes, skip,
@@ -728,7 +817,7 @@ def predict_scan_volume(model, raw: torch.Tensor, affine, roi: Sequence[int], nu
                         **intensity) -> Dict[str, torch.Tensor]:
     """One-shot ``SlidingWindowPredictor(...).predict_scan(raw, geom, restore, postprocess, **intensity)`` with
     ``geom = ScanGeometry.from_affine(raw's spatial shape, affine, axcodes, out_size)``; also returns ``"geometry"``.
-    Keyword-only ``fit``: the predictor's ``fit=``."""
+    Keyword-only ``fit``: the predictor's ``fit=``.  ``intensity`` may carry ``predict_scan``'s ``foreground=``."""
     from . import scan
     if not isinstance(raw, torch.Tensor) or raw.dim() not in (3, 4, 5):
         raise ValueError("raw must be a [C, H, W, D] (or [H, W, D] / [1, C, H, W, D]) tensor")

@@ -34,12 +34,27 @@ table is the same for every ``base`` (the lowest value counted in LDS) and only 
 -4096 for int16 (CT in Hounsfield units with its usual padding values, and MR up to 12287) and 0 for uint8, cover real
 scans; pass ``base=`` for data that sits elsewhere.
 
-Nothing here reads back to the host; ``ScanHistogram.cpu()`` and ``WindowSlot.cpu()`` are the synchronising calls.
+Otsu foreground thresholds (``tests/otsu_ref.py`` restates them in Python integers).  Per channel, with
+``N = sum n_v`` and ``S = sum v n_v`` over the table: a candidate ``t`` is a counted value that is not the largest counted
+value; ``n0 = sum_{v<=t} n_v``, ``A = sum_{v<=t} v n_v``, ``P = A N - S n0``, ``q = n0 (N - n0)``.  Otsu's between-class
+variance is ``P^2 / (N^2 q)``; the threshold is the candidate that maximises ``P^2 / q``, compared in exact integers
+(``P_a^2 q_b`` against ``P_b^2 q_a``, 256-bit on the device), equal values picking the lower ``t``.  It is always a value of
+the scan, and foreground is ``v > t``.  The record is int64 ``(t, n_le, n_gt, valid)``; fewer than two distinct counted
+values, ``N == 0`` or ``N >= 2^33`` give ``valid = 0`` (``t`` = the largest counted value, 0 if none; ``n_le = N``), and
+every consumer then applies no restriction: the mask is all ones, the restricted plan is the unrestricted one.
+``otsu_slot`` computes the record from a histogram, ``foreground_mask`` the uint8 mask on the native grid,
+``window_slot_above`` the plan of a (pooled) histogram over the bins above the threshold (the three live in
+``mivp_amd/otsu.py`` and are reachable through this module too), and ``foreground="otsu"`` on a window spec
+restricts its statistics the same way -- a restriction on bins, not a second pass over voxels.  ``above=`` still selects what is counted; Otsu acts on what was counted.
+
+Nothing here reads back to the host; ``ScanHistogram.cpu()``, ``WindowSlot.cpu()`` and ``OtsuSlot.cpu()`` are the
+synchronising calls.
 """
 from __future__ import annotations
 
 import math
 import numbers
+from fractions import Fraction
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -61,6 +76,18 @@ def _check_q(name: str, q) -> float:
     if isinstance(q, bool) or not isinstance(q, numbers.Real) or not 0.0 <= float(q) <= 1.0:
         raise ValueError(f"{name} must be a number in [0, 1], got {q!r}")
     return float(q)
+
+
+def _check_foreground(foreground) -> Optional[str]:
+    if foreground is not None and foreground != "otsu":
+        raise ValueError(f"foreground must be None or 'otsu', got {foreground!r}")
+    return foreground
+
+
+def _check_channels(channels) -> int:
+    if isinstance(channels, bool) or not isinstance(channels, numbers.Integral) or not 1 <= channels <= 4:
+        raise ValueError(f"channels must be 1..4, got {channels!r}")
+    return int(channels)
 
 
 def _check_above(above) -> Optional[int]:
@@ -113,14 +140,37 @@ class ScanReport:
                 out[c] = int(np.searchsorted(np.cumsum(self.table[c]), k, side="left")) - OFFSET
         return out
 
+    def otsu(self) -> Dict[str, np.ndarray]:
+        """Otsu's threshold per channel from the exact table, in Python integers (the module docstring has the
+        definition): ``{"t", "n_le", "n_gt", "valid"}`` int64 ``[C]``, what ``otsu_slot`` writes on the device, and
+        ``"eta"`` float64 ``[C]``: the separability ``sigma_b^2 / sigma_total^2`` of the chosen threshold (0 where
+        ``valid`` is 0), for reporting."""
+        out = {k: np.zeros(self.channels, dtype=np.int64) for k in ("t", "n_le", "n_gt", "valid")}
+        out["eta"] = np.zeros(self.channels, dtype=np.float64)
+        for c in range(self.channels):
+            occ = [(int(b) - OFFSET, int(self.table[c, b])) for b in np.flatnonzero(self.table[c])]
+            N = sum(k for _, k in occ)
+            S = sum(v * k for v, k in occ)
+            out["t"][c], out["n_le"][c] = (occ[-1][0] if occ else 0), N
+            if len(occ) < 2 or N >= 2 ** 33:
+                continue
+            n0, A, best = 0, 0, None                                             # best = (P^2, q, t, n0)
+            for v, k in occ[:-1]:
+                n0, A = n0 + k, A + v * k
+                P, q = A * N - S * n0, n0 * (N - n0)
+                if best is None or P * P * best[1] > best[0] * q:               # equal: the lower t stays
+                    best = (P * P, q, v, n0)
+            S2 = sum(v * v * k for v, k in occ)
+            out["t"][c], out["n_le"][c], out["n_gt"][c], out["valid"][c] = best[2], best[3], N - best[3], 1
+            out["eta"][c] = float(Fraction(best[0], best[1] * (S2 * N - S * S)))
+        return out
+
 
 class ScanHistogram:
     """The device table int64 ``[C, 65536]`` of one or more scans (``table[c, v + 32768]``)."""
 
     def __init__(self, channels: int, device):
-        if isinstance(channels, bool) or not isinstance(channels, numbers.Integral) or not 1 <= channels <= 4:
-            raise ValueError(f"channels must be 1..4, got {channels!r}")
-        self.channels = int(channels)
+        self.channels = _check_channels(channels)
         self.table = torch.zeros((self.channels, NBINS), dtype=torch.int64, device=device)
 
     def zero_(self) -> "ScanHistogram":
@@ -136,13 +186,23 @@ class WindowSlot:
     """The device plan fp32 ``[C, 8]`` of ``window_slot``: ``(s, t, lo, hi, a_lo, a_hi, mean, std)`` per channel."""
 
     def __init__(self, channels: int, device, mode: int = MODE_PERCENTILE):
-        if isinstance(channels, bool) or not isinstance(channels, numbers.Integral) or not 1 <= channels <= 4:
-            raise ValueError(f"channels must be 1..4, got {channels!r}")
-        self.channels, self.mode = int(channels), int(mode)
+        self.channels, self.mode = _check_channels(channels), int(mode)
         self.words = torch.zeros((self.channels, 8), dtype=torch.float32, device=device)
 
     def cpu(self) -> np.ndarray:
         """The synchronising call: the words as a numpy fp32 ``[C, 8]`` array."""
+        return self.words.cpu().numpy()
+
+
+class OtsuSlot:
+    """The device record int64 ``[C, 4]`` of ``otsu_slot``: ``(t, n_le, n_gt, valid)`` per channel."""
+
+    def __init__(self, channels: int, device):
+        self.channels = _check_channels(channels)
+        self.words = torch.zeros((self.channels, 4), dtype=torch.int64, device=device)
+
+    def cpu(self) -> np.ndarray:
+        """The synchronising call: the record as a numpy int64 ``[C, 4]`` array."""
         return self.words.cpu().numpy()
 
 
@@ -152,9 +212,12 @@ class IntensityWindow:
     buffers ``prepare_scan(window=spec)`` works in, one pair per (device, channels), made at the first call: a later
     call, and a graph recording after an eager warm-up, allocates nothing.  Every call with the spec writes those
     buffers, so **a spec serves one stream at a time**: calls that may overlap on different streams need a spec each (or
-    their own ``ScanHistogram`` / ``WindowSlot`` through ``scan_histogram`` and ``window_slot``)."""
+    their own ``ScanHistogram`` / ``WindowSlot`` through ``scan_histogram`` and ``window_slot``).  ``foreground="otsu"``
+    takes the statistics over the counted values above the histogram's own Otsu threshold (one more plan launch; the
+    buffers then hold an ``OtsuSlot`` as well)."""
 
-    def __init__(self, mode: int, q_lo: float, q_hi: float, b_min: float, b_max: float, above: Optional[int], clip: bool):
+    def __init__(self, mode: int, q_lo: float, q_hi: float, b_min: float, b_max: float, above: Optional[int], clip: bool,
+                 foreground: Optional[str] = None):
         self.mode = int(mode)
         self.q_lo, self.q_hi = _check_q("q_lo", q_lo), _check_q("q_hi", q_hi)
         if self.q_lo > self.q_hi:
@@ -166,43 +229,49 @@ class IntensityWindow:
             raise ValueError(f"b_max must not be below b_min, got b_min={b_min}, b_max={b_max}")
         self.above = _check_above(above)
         self.clip = bool(clip)
-        self._buffers: Dict[Tuple[str, int], Tuple[ScanHistogram, WindowSlot]] = {}
+        self.foreground = _check_foreground(foreground)
+        self._buffers: Dict[Tuple[str, int], tuple] = {}
 
     @classmethod
     def percentile(cls, q_lo: float = 0.005, q_hi: float = 0.995, b_min: float = 0.0, b_max: float = 1.0,
-                   above: Optional[int] = None) -> "IntensityWindow":
+                   above: Optional[int] = None, foreground: Optional[str] = None) -> "IntensityWindow":
         """``[a_lo, a_hi]``, the nearest-rank order statistics of ``q_lo`` and ``q_hi`` over the selected voxels, maps
-        linearly to ``[b_min, b_max]``.  ``above``: count only voxels with a value greater than it."""
-        return cls(MODE_PERCENTILE, q_lo, q_hi, b_min, b_max, above, True)
+        linearly to ``[b_min, b_max]``.  ``above``: count only voxels with a value greater than it.  ``foreground``:
+        ``None``, or ``"otsu"`` for the counted voxels above their Otsu threshold."""
+        return cls(MODE_PERCENTILE, q_lo, q_hi, b_min, b_max, above, True, foreground)
 
     @classmethod
-    def zscore(cls, above: Optional[int] = None, clip: Optional[Tuple[float, float]] = None) -> "IntensityWindow":
+    def zscore(cls, above: Optional[int] = None, clip: Optional[Tuple[float, float]] = None,
+               foreground: Optional[str] = None) -> "IntensityWindow":
         """``(x - mean) / std`` of the selected voxels, with ``clip=(q_lo, q_hi)`` clamped to the images of those two
-        order statistics."""
+        order statistics.  ``foreground`` as in ``percentile``."""
         if clip is None:
-            return cls(MODE_ZSCORE, 0.0, 1.0, 0.0, 1.0, above, False)
+            return cls(MODE_ZSCORE, 0.0, 1.0, 0.0, 1.0, above, False, foreground)
         try:
             q_lo, q_hi = clip
         except (TypeError, ValueError):
             raise ValueError(f"clip must be (q_lo, q_hi) or None, got {clip!r}") from None
-        return cls(MODE_ZSCORE, q_lo, q_hi, 0.0, 1.0, above, True)
+        return cls(MODE_ZSCORE, q_lo, q_hi, 0.0, 1.0, above, True, foreground)
 
-    def buffers(self, channels: int, device) -> Tuple[ScanHistogram, WindowSlot]:
+    def buffers(self, channels: int, device) -> tuple:
         """The (histogram, slot) pair ``prepare_scan(window=self)`` uses for scans of ``channels`` channels on
-        ``device``; call it ahead of a graph recording to keep the allocation out of it."""
+        ``device`` -- (histogram, slot, Otsu record) with ``foreground="otsu"``; call it ahead of a graph recording to
+        keep the allocation out of it."""
         dev = torch.device(device)
         if dev.type == "cuda" and dev.index is None:                              # "cuda" and "cuda:0" are one device
             dev = torch.device("cuda", torch.cuda.current_device())
         key = (str(dev), int(channels))
         if key not in self._buffers:
-            self._buffers[key] = (ScanHistogram(channels, device), WindowSlot(channels, device, self.mode))
+            bufs = (ScanHistogram(channels, device), WindowSlot(channels, device, self.mode))
+            self._buffers[key] = bufs + (OtsuSlot(channels, device),) if self.foreground else bufs
         return self._buffers[key]
 
     def __repr__(self):
+        fg = "" if self.foreground is None else f", foreground={self.foreground!r}"
         if self.mode == MODE_PERCENTILE:
             return (f"IntensityWindow.percentile(q_lo={self.q_lo}, q_hi={self.q_hi}, b_min={self.b_min}, "
-                    f"b_max={self.b_max}, above={self.above})")
-        return f"IntensityWindow.zscore(above={self.above}, clip={(self.q_lo, self.q_hi) if self.clip else None})"
+                    f"b_max={self.b_max}, above={self.above}{fg})")
+        return f"IntensityWindow.zscore(above={self.above}, clip={(self.q_lo, self.q_hi) if self.clip else None}{fg})"
 
 
 def _check_raw(raw) -> Tuple[int, Tuple[int, int, int]]:
@@ -261,11 +330,31 @@ def scan_histogram(raw: torch.Tensor, mask: Optional[torch.Tensor] = None, above
     return hist
 
 
-def window_slot(hist: ScanHistogram, spec: IntensityWindow, out: Optional[WindowSlot] = None) -> WindowSlot:
-    """A histogram (of one scan, or pooled over a data set) -> the device plan of ``spec``, in one launch with no host
-    read.  ``prepare_scan(window=slot)`` applies it to any scan of that many channels."""
+def _check_hist(hist) -> ScanHistogram:
     if not isinstance(hist, ScanHistogram):
         raise ValueError(f"hist must be a ScanHistogram, got {type(hist).__name__}")
+    return hist
+
+
+def _check_otsu(otsu, channels: int, device, like: str) -> None:
+    if not isinstance(otsu, OtsuSlot):
+        raise ValueError(f"otsu must be an OtsuSlot, got {type(otsu).__name__}")
+    if otsu.channels != channels:
+        raise ValueError(f"otsu was made for {otsu.channels} channels, {like} has {channels}")
+    if otsu.words.device != device:
+        raise ValueError(f"otsu is on {otsu.words.device}, {like} on {device}")
+
+
+def window_slot(hist: ScanHistogram, spec: IntensityWindow, out: Optional[WindowSlot] = None) -> WindowSlot:
+    """A histogram (of one scan, or pooled over a data set) -> the device plan of ``spec``, in one launch with no host
+    read.  ``prepare_scan(window=slot)`` applies it to any scan of that many channels.  (``window_slot_above`` takes
+    the plan over the counted values above an Otsu threshold.)"""
+    return _plan(hist, spec, out, None)
+
+
+def _plan(hist, spec, out, otsu) -> WindowSlot:
+    """``window_slot`` (``otsu`` None) and ``otsu.window_slot_above``: the checks and the one plan launch."""
+    _check_hist(hist)
     if not isinstance(spec, IntensityWindow):
         raise ValueError(f"spec must be an IntensityWindow, got {type(spec).__name__}")
     if out is not None:
@@ -273,10 +362,16 @@ def window_slot(hist: ScanHistogram, spec: IntensityWindow, out: Optional[Window
             raise ValueError(f"out must be a WindowSlot of {hist.channels} channels")
         if out.words.device != hist.table.device:
             raise ValueError(f"out is on {out.words.device}, hist on {hist.table.device}")
+    if otsu is not None:
+        _check_otsu(otsu, hist.channels, hist.table.device, "hist")
     if not hist.table.is_cuda:
         raise RuntimeError("hist must live on the GPU (no CPU fallback)")
     slot = WindowSlot(hist.channels, hist.table.device) if out is None else out
     slot.mode = spec.mode
+    if otsu is not None:
+        L.call("mivp_scan_window_plan_above", L.ptr(hist.table), hist.channels, spec.mode, spec.q_lo, spec.q_hi, spec.b_min,
+               spec.b_max, int(spec.clip), L.ptr(otsu.words), L.ptr(slot.words), L.stream())
+        return slot
     L.call("mivp_scan_window_plan", L.ptr(hist.table), hist.channels, spec.mode, spec.q_lo, spec.q_hi, spec.b_min, spec.b_max,
            int(spec.clip), L.ptr(slot.words), L.stream())
     return slot
@@ -298,11 +393,23 @@ def check_window_args(window, raw: torch.Tensor, mask, shape) -> None:
 
 def resolve_window(window, raw: torch.Tensor, mask) -> WindowSlot:
     """``prepare_scan``'s device side of ``window=``: a ``WindowSlot`` as it is; an ``IntensityWindow`` runs histogram ->
-    plan on ``raw`` itself in the spec's own buffers (a clear and two launches, no host read)."""
+    plan on ``raw`` itself in the spec's own buffers (a clear and two launches, no host read); with
+    ``foreground="otsu"`` histogram -> Otsu plan -> restricted plan (a clear and three launches)."""
     if isinstance(window, WindowSlot):
         if window.words.device != raw.device:
             raise ValueError(f"window is on {window.words.device}, raw on {raw.device}")
         return window
-    hist, slot = window.buffers(raw.shape[0], raw.device)
+    hist, slot, *rest = window.buffers(raw.shape[0], raw.device)
     scan_histogram(raw, mask=mask, above=window.above, out=hist.zero_())
-    return window_slot(hist, window, out=slot)
+    if window.foreground is None:
+        return window_slot(hist, window, out=slot)
+    from . import otsu
+    return otsu.window_slot_above(hist, window, otsu.otsu_slot(hist, out=rest[0]), out=slot)
+
+
+def __getattr__(name):
+    # the Otsu calls live in mivp_amd/otsu.py (which imports this module) and are reachable from here as well
+    if name in ("otsu_slot", "foreground_mask", "window_slot_above"):
+        from . import otsu
+        return getattr(otsu, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

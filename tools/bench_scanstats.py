@@ -15,7 +15,13 @@ window composed from eager torch ops on the same GPU (``bincount`` of the shifte
 then the host-map ``prepare_scan``, which needs the two values on the host).  The eager histogram and order statistics are
 compared with the kernels' before anything is timed.  One JSON line per case: ms per call, the eager ms and their ratio,
 the bytes of the scan over the histogram's time as a fraction of the 6.3 TB/s HBM rate DESIGN 4.8 uses, and each as a
-share of the 187 ms ``predict``.  The lines are appended to profiles/scanstats_bench.jsonl."""
+share of the 187 ms ``predict``.  The lines are appended to profiles/scanstats_bench.jsonl.
+
+``--otsu`` times the Otsu foreground threshold on the ``half_air`` field instead, every figure as the median
+of three timed runs with min .. max: the Otsu plan next to the window plan (both one workgroup per channel over the same
+512 KB table), the mask kernel against its bytes (2 read, 1 written per voxel) at the 6.3 TB/s rate,
+``prepare_scan(window=zscore(above=0, foreground="otsu"))`` next to ``prepare_scan(window=zscore(above=0))``, and an eager
+torch composition of the threshold (float64 ``cumsum`` over the table, then ``argmax``) on the same GPU.  One JSON line."""
 import argparse
 import json
 import math
@@ -76,12 +82,71 @@ def eager_window(raw):
     return [int(b) - 32768 for b in torch.searchsorted(cum, ks).tolist()]
 
 
+def eager_otsu(table):
+    """Otsu's threshold of one channel's table with eager torch ops in float64 (a device scalar)."""
+    import torch
+    h = table.double()
+    v = torch.arange(-32768, 32768, device=table.device, dtype=torch.float64)
+    n0, a = torch.cumsum(h, 0), torch.cumsum(h * v, 0)
+    n, s = n0[-1], a[-1]
+    p, q = a * n - s * n0, n0 * (n - n0)
+    score = torch.where((h > 0) & (q > 0), p * p / q.clamp(min=1.0), torch.full_like(p, -1.0))
+    return torch.argmax(score) - 32768
+
+
+def three(fn, calls, warmup):
+    """(median, min, max) of three timed runs."""
+    ms = sorted(timed(fn, calls, warmup) for _ in range(3))
+    return [round(ms[1], 4), round(ms[0], 4), round(ms[2], 4)]
+
+
+def otsu_main(a):
+    import torch
+    import mivp_amd  # noqa: F401
+    from mivp_amd import scan
+    from mivp_amd import scanstats as S
+    dev = torch.device("cuda:0")
+    raw = field("half_air", dev, torch.Generator(device=dev).manual_seed(1))
+    geom = scan.ScanGeometry.identity(SHAPE)
+    out = torch.empty((1, 1) + SHAPE, dtype=torch.float32, device=dev)
+    hist = S.scan_histogram(raw)
+    rec_slot, mask = S.otsu_slot(hist), torch.empty(SHAPE, dtype=torch.uint8, device=dev)
+    t, _, n_gt, valid = (int(x) for x in rec_slot.cpu()[0])
+    assert valid and int(S.foreground_mask(raw, rec_slot, out=mask).sum()) == n_gt == int((raw > t).sum())
+    t_eager = int(eager_otsu(hist.table[0]))
+    spec = S.IntensityWindow.zscore()
+    slot = S.WindowSlot(1, dev)
+    plain, auto = S.IntensityWindow.zscore(above=0), S.IntensityWindow.zscore(above=0, foreground="otsu")
+    otsu_ms = three(lambda: S.otsu_slot(hist, out=rec_slot), a.calls, a.warmup)
+    plan_ms = three(lambda: S.window_slot(hist, spec, out=slot), a.calls, a.warmup)
+    above_ms = three(lambda: S.window_slot_above(hist, spec, rec_slot, out=slot), a.calls, a.warmup)
+    mask_ms = three(lambda: S.foreground_mask(raw, rec_slot, out=mask), a.calls, a.warmup)
+    prep_plain_ms = three(lambda: scan.prepare_scan(raw, geom, window=plain, out=out), a.calls, a.warmup)
+    prep_auto_ms = three(lambda: scan.prepare_scan(raw, geom, window=auto, out=out), a.calls, a.warmup)
+    eager_ms = three(lambda: eager_otsu(hist.table[0]), a.calls, a.warmup)
+    nbytes = 3 * raw.numel()
+    rec = {"shape": list(SHAPE), "dtype": "int16", "field": "half_air", "case": "otsu", "threshold": t,
+           "eager_threshold": t_eager, "median_min_max": True, "otsu_plan_ms": otsu_ms, "window_plan_ms": plan_ms,
+           "window_plan_above_ms": above_ms, "otsu_over_window_plan": round(otsu_ms[0] / plan_ms[0], 2),
+           "mask_ms": mask_ms, "mask_bytes": int(nbytes), "mask_hbm_fraction": round(nbytes / (mask_ms[0] * 1e-3) / HBM, 4),
+           "prepare_zscore_above0_ms": prep_plain_ms, "prepare_zscore_above0_otsu_ms": prep_auto_ms,
+           "prepare_otsu_minus_plain_ms": round(prep_auto_ms[0] - prep_plain_ms[0], 4), "eager_otsu_ms": eager_ms,
+           "eager_over_otsu_plan": round(eager_ms[0] / otsu_ms[0], 2)}
+    print(json.dumps(rec), flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write(json.dumps(rec) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scanstats_bench.jsonl"))
+    ap.add_argument("--otsu", action="store_true", help="time the Otsu threshold, mask and restricted window instead")
     a = ap.parse_args()
+    if a.otsu:
+        return otsu_main(a)
     import torch
     import mivp_amd  # noqa: F401
     from mivp_amd import scan
