@@ -370,6 +370,11 @@ int mivp_patch_embed(const MivpEmbedDesc* d, int mode, const float* x, const flo
 /* bf16 im2col of the 2x2x2 patches, p [B*(H/2)*(W/2)*(D/2)][Cin*8] with columns in nn.Conv3d.weight order:
  * the input-side operand of mivp_gemm_tn for the patch-embedding weight gradient */
 int mivp_patch_im2col(const MivpEmbedDesc* d, const float* x, void* p, mivp_stream_t stream);
+/* data gradient of the k = s = 2 convolution: dx[b,ci,2h+a,2w+b,2d+c] = sum_co w[co,ci,a,b,c] * dz[b,h,w,d,co]
+ *   dz bf16 [B,H/2,W/2,D/2,C] (the BatchNorm backward's output for the recomputed conv output), w f32 nn.Conv3d weight,
+ *   dx f32 [B,Cin,H,W,D]: every element written exactly once (no atomics, no zero fill), co ascending in fp32.
+ *   Even dims, C % 8 == 0, C*Cin*32 bytes of LDS <= 64 KiB; nblk caps the grid (no channel-group rule here) */
+int mivp_patch_embed_dgrad(const MivpEmbedDesc* d, const void* dz, const float* w, float* dx, mivp_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* BatchNorm3d, training mode (batch statistics), channels-last bf16         */
@@ -1557,6 +1562,22 @@ int mivp_crop_corrupt_range(const float* x, int32_t C, const int32_t* dims, cons
                             float* range, mivp_stream_t stream);
 int mivp_crop_corrupt(float* x, int32_t C, const int32_t* dims, const int32_t* records, int32_t B, const float* range,
                       mivp_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* Pixel-space visual prompt (csrc/input_prompt.hip)                        */
+/* ------------------------------------------------------------------------ */
+/* y = x + scale[0] * T(p): x, y f32 [B,Cin,H,W,D]; p f32 [Cin,gh,gw,gd]; scale a DEVICE float; T = trilinear
+ * interpolation of the lattice to the roi under torch's align_corners=True rule, evaluated on the fly (no roi-sized
+ * prompt volume).  Voxel o of an axis sits at o (g-1) / (n-1) as an exact rational (0 when g == 1 or n == 1):
+ * i0 = floor, lambda = remainder / (n-1), i1 = min(i0+1, g-1); g == n gives lambda == 0 everywhere (y = x + scale p).
+ * The lattice is staged in LDS up to 32 KiB, read from global memory above.  1 <= g <= n per axis, H+W+D <= 4096,
+ * B Cin H W D < 2^31.
+ * mivp_input_prompt_bwd: dp[ci][node] = scale[0] * sum_b sum_voxels weight * dy, a gather per node over its support
+ * in a fixed order (stated in the source file): no atomics, nothing zero-filled, equal calls give equal bits. */
+int mivp_input_prompt_fwd(const float* x, const float* p, const float* scale, int32_t B, int32_t Cin, int32_t H, int32_t W,
+                          int32_t D, int32_t gh, int32_t gw, int32_t gd, float* y, mivp_stream_t stream);
+int mivp_input_prompt_bwd(const float* dy, const float* scale, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t D,
+                          int32_t gh, int32_t gw, int32_t gd, float* dp, mivp_stream_t stream);
 
 #ifdef __cplusplus
 }

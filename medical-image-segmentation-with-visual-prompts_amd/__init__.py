@@ -16,7 +16,7 @@ def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
                 "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit",
-                "skeleton", "otsu"):
+                "skeleton", "otsu", "prompting"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -55,4 +55,7 @@ def __getattr__(name):
                 "draw_filters", "augment_filters"):
         from . import augment
         return getattr(augment, name)
+    if name in ("InputPrompt", "PromptedModel", "build_prompt_optimizer", "input_gradient", "saliency_map", "fgsm"):
+        from . import prompting
+        return getattr(prompting, name)
     raise AttributeError(name)

@@ -134,6 +134,88 @@ extern "C" int mivp_patch_im2col(const MivpEmbedDesc* d, const float* x, void* p
 }
 
 // ---------------------------------------------------------------------------------------------
+// patch embedding, data gradient: dx[b,ci,2h+a,2w+b,2d+c] = sum_co w[co,ci,a,b,c] * dz[b,h,w,d,co]
+//   kernel == stride: the 2x2x2 patches tile the input, so one thread owns one output voxel of dz and writes its eight
+//   input voxels per input channel -- every dx element exactly once, no atomics, no zero fill, one summation order
+//   (co ascending, fp32).  A lane reads its voxel's C bf16 as 16-byte pieces; the weights are the same for every lane,
+//   so they sit in LDS as [ci][co][8 taps] and every ds_read_b128 is one address for the whole wave (a broadcast, no
+//   bank conflict, no padding).  In registers they would be 8 C values per thread; in LDS the kernel stays at 8 waves
+//   per SIMD, which is what hides the latency of the 96-byte-strided dz loads.  Stores are float2 along D, four rows
+//   per (voxel, ci); lanes are consecutive along d, so a wave writes contiguous runs.
+//   Cin > 1 walks the channels inside the item and re-reads the voxel's dz from L1 (CIN1: read once).
+// ---------------------------------------------------------------------------------------------
+template <bool CIN1>
+__global__ __launch_bounds__(256) void k_patch_embed_dgrad(MivpEmbedDesc d, const bf16_t* __restrict__ dz,
+                                                           const float* __restrict__ w, float* __restrict__ dx) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int C = d.C, Cin = CIN1 ? 1 : d.Cin, G = C / 8;
+    float* wl = reinterpret_cast<float*>(smem);               // [Cin][C][8]
+    const int tid = threadIdx.x;
+    for (int i = tid; i < C * Cin * 8; i += 256) {
+        const int r = i >> 3, co = r / Cin, ci = r - co * Cin;
+        wl[(ci * C + co) * 8 + (i & 7)] = w[i];
+    }
+    __syncthreads();
+    const int H = d.dims[0], W = d.dims[1], D = d.dims[2];
+    const int oh = H / 2, ow = W / 2, od = D / 2;
+    const long ovol = (long)oh * ow * od, ivol = (long)H * W * D;
+    const long items = (long)d.B * ovol;
+    const long stride = (long)gridDim.x * 256;
+    const unsigned uovol = (unsigned)ovol, uwd = (unsigned)(ow * od);      // host checks items < 2^31: 32-bit decode
+    for (long it = (long)blockIdx.x * 256 + tid; it < items; it += stride) {
+        const unsigned vox = (unsigned)it;
+        const unsigned b = vox / uovol;
+        unsigned rem = vox - b * uovol;
+        const int h = (int)(rem / uwd);
+        rem -= (unsigned)h * uwd;
+        const int ww = (int)(rem / (unsigned)od);
+        const int z = (int)(rem - (unsigned)ww * (unsigned)od);
+        const bf16_t* zp = dz + (long)vox * C;
+        float* xb = dx + (long)b * Cin * ivol + ((long)(2 * h) * W + 2 * ww) * D + 2 * z;
+        for (int ci = 0; ci < Cin; ++ci) {
+            const float* wc = wl + ci * C * 8;
+            float acc[8];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) acc[t] = 0.f;
+            for (int g = 0; g < G; ++g) {
+                const bf16x8 v = ld8(zp + g * 8);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const float f = (float)v[i];
+                    const float4 wa = *reinterpret_cast<const float4*>(wc + (g * 8 + i) * 8);
+                    const float4 wb = *reinterpret_cast<const float4*>(wc + (g * 8 + i) * 8 + 4);
+                    acc[0] += f * wa.x; acc[1] += f * wa.y; acc[2] += f * wa.z; acc[3] += f * wa.w;
+                    acc[4] += f * wb.x; acc[5] += f * wb.y; acc[6] += f * wb.z; acc[7] += f * wb.w;
+                }
+            }
+            float* xc = xb + (long)ci * ivol;
+            *reinterpret_cast<float2*>(xc) = make_float2(acc[0], acc[1]);
+            *reinterpret_cast<float2*>(xc + D) = make_float2(acc[2], acc[3]);
+            *reinterpret_cast<float2*>(xc + (long)W * D) = make_float2(acc[4], acc[5]);
+            *reinterpret_cast<float2*>(xc + (long)W * D + D) = make_float2(acc[6], acc[7]);
+        }
+    }
+}
+
+extern "C" int mivp_patch_embed_dgrad(const MivpEmbedDesc* d, const void* dz, const float* w, float* dx, mivp_stream_t stream) {
+    MIVP_REQUIRE(d && dz && w && dx);
+    MIVP_REQUIRE(d->C > 0 && d->C % 8 == 0 && d->Cin > 0 && d->B > 0 && d->nblk > 0);
+    MIVP_REQUIRE(d->dims[0] > 0 && d->dims[1] > 0 && d->dims[2] > 0);
+    MIVP_REQUIRE(d->dims[0] % 2 == 0 && d->dims[1] % 2 == 0 && d->dims[2] % 2 == 0);
+    MIVP_REQUIRE((long)d->B * (d->dims[0] / 2) * (d->dims[1] / 2) * (d->dims[2] / 2) * (d->C / 8) < (1L << 31));   // 32-bit decode
+    const size_t lds = (size_t)d->C * d->Cin * 8 * sizeof(float);
+    MIVP_REQUIRE(lds <= 64 * 1024);
+    const long items = (long)d->B * (d->dims[0] / 2) * (d->dims[1] / 2) * (d->dims[2] / 2);
+    const long want = (items + 255) / 256;
+    const unsigned grid = (unsigned)(want < d->nblk ? want : d->nblk);   // nblk caps the grid; the walk strides beyond it
+    if (d->Cin == 1)
+        hipLaunchKernelGGL((k_patch_embed_dgrad<true>), dim3(grid), dim3(256), lds, (hipStream_t)stream, *d, (const bf16_t*)dz, w, dx);
+    else
+        hipLaunchKernelGGL((k_patch_embed_dgrad<false>), dim3(grid), dim3(256), lds, (hipStream_t)stream, *d, (const bf16_t*)dz, w, dx);
+    return mivp_check_launch("patch_embed_dgrad");
+}
+
+// ---------------------------------------------------------------------------------------------
 // BatchNorm statistics of a bf16 [n_vox][C] tensor
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_bn_stats(const bf16_t* __restrict__ x, long n_vox, int C,

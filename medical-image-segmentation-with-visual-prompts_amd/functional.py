@@ -143,7 +143,8 @@ def bn_momentum(bn) -> float:
 # patch embedding + BatchNorm
 # ----------------------------------------------------------------------------------------------
 class _PatchEmbedFn(torch.autograd.Function):
-    """BN(conv_k2s2(x)); backward = parameter gradients only (the input volume is data)."""
+    """BN(conv_k2s2(x)); backward = parameter gradients, and the input volume's gradient when it is asked for (pixel-space
+    prompts, saliency, adversarial steps): one more launch, csrc/norm_embed.hip k_patch_embed_dgrad."""
 
     @staticmethod
     def forward(ctx, x, conv_w, conv_b, bn_w, bn_b, bn):
@@ -161,15 +162,22 @@ class _PatchEmbedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, conv_w, conv_b, scale, shift, mean_rstd = ctx.saved_tensors
-        dw, db, dgamma, dbeta = ops.patch_embed_backward(x, conv_w, conv_b, dy, (scale, shift, mean_rstd), ctx.training)
         g = ctx.needs_input_grad
-        return (None, dw if g[1] else None, db if g[2] else None, dgamma if g[3] else None, dbeta if g[4] else None, None)
+        if not g[0]:
+            dw, db, dgamma, dbeta = ops.patch_embed_backward(x, conv_w, conv_b, dy, (scale, shift, mean_rstd), ctx.training)
+            dx = None
+        else:
+            dw, db, dgamma, dbeta, dx = ops.patch_embed_backward(x, conv_w, conv_b, dy, (scale, shift, mean_rstd), ctx.training,
+                                                                 need_dx=True, need_params=g[1] or g[2])
+        return (dx, dw if g[1] else None, db if g[2] else None, dgamma if g[3] else None, dbeta if g[4] else None, None)
 
 
 def patch_embed(owner, conv, bn, x):
-    if x.requires_grad:
-        raise NotImplementedError("mivp_amd: gradient w.r.t. the input volume is not built")
     params = [conv.weight, conv.bias, bn.weight, bn.bias]
+    if torch.is_grad_enabled() and x.requires_grad:
+        if not x.is_floating_point():
+            raise TypeError("mivp_amd: an input volume that requires a gradient must be floating point")
+        return _PatchEmbedFn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn)
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
         return _PatchEmbedFn.apply(x.detach(), conv.weight, conv.bias, bn.weight, bn.bias, bn)
     training = bn.training

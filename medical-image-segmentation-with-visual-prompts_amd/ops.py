@@ -421,10 +421,13 @@ def patch_embed(x, w, bias, bn_w, bn_b, eps, running_mean, running_var, training
     return y
 
 
-def patch_embed_backward(x, w, bias, dy, stats, training=True):
-    """Parameter gradients of BN(conv_k2s2(x)): (dW [C, Cin, 2,2,2], dbias, dgamma, dbeta), all f32.
-    The conv output is recomputed (bf16) instead of having been kept, the BatchNorm backward is the generic one,
-    and dW = dz^T patches runs on the TN GEMM."""
+def patch_embed_backward(x, w, bias, dy, stats, training=True, need_dx=False, need_params=True):
+    """Gradients of BN(conv_k2s2(x)): (dW [C, Cin, 2,2,2], dbias, dgamma, dbeta), all f32, and with ``need_dx`` a fifth
+    result dx f32 [B, Cin, H, W, D].  The conv output is recomputed (bf16) instead of having been kept, the BatchNorm
+    backward is the generic one, and dW = dz^T patches runs on the TN GEMM.  ``need_dx`` adds ONE launch after the BatchNorm
+    backward (mivp_patch_embed_dgrad: kernel == stride, every input voxel written once).  ``need_params=False`` (a frozen
+    encoder) skips the im2col, the TN GEMM and the column sum: dW and dbias come back as None (dgamma / dbeta are by-products
+    of the BatchNorm backward).  The defaults issue the launches they always did."""
     scale, shift, mean_rstd = stats
     B, cin, H, W, D = x.shape
     Cc = w.shape[0]
@@ -443,11 +446,19 @@ def patch_embed_backward(x, w, bias, dy, stats, training=True):
     L.call("mivp_patch_embed", C.byref(d), 1, L.ptr(x), L.ptr(wf), L.ptr(bf), L.ptr(one), L.ptr(torch.zeros_like(one)),
            L.ptr(None), L.ptr(z), st)
     dz, dgamma, dbeta = (bn_backward if training else bn_backward_eval)(z, dy.contiguous(), scale, shift, mean_rstd, False)
-    patches = torch.empty((n_out, cin * 8), dtype=BF16, device=x.device)
-    L.call("mivp_patch_im2col", C.byref(d), L.ptr(x), L.ptr(patches), st)
-    dw = gemm_tn(dz, operand_rows(Cc), patches, operand_rows(cin * 8), n_out, Cc, cin * 8)
-    db = _colsum_bf16(dz.view(n_out, Cc))
-    return dw.view(Cc, cin, 2, 2, 2), db, dgamma, dbeta
+    dx = None
+    if need_dx:
+        dx = torch.empty((B, cin, H, W, D), dtype=torch.float32, device=x.device)
+        L.call("mivp_patch_embed_dgrad", C.byref(d), L.ptr(dz), L.ptr(wf), L.ptr(dx), st)
+    dw = db = None
+    if need_params:
+        patches = torch.empty((n_out, cin * 8), dtype=BF16, device=x.device)
+        L.call("mivp_patch_im2col", C.byref(d), L.ptr(x), L.ptr(patches), st)
+        dw = gemm_tn(dz, operand_rows(Cc), patches, operand_rows(cin * 8), n_out, Cc, cin * 8).view(Cc, cin, 2, 2, 2)
+        db = _colsum_bf16(dz.view(n_out, Cc))
+    if need_dx:
+        return dw, db, dgamma, dbeta, dx
+    return dw, db, dgamma, dbeta
 
 
 # ------------------------------------------------------------------------------------------
