@@ -1146,6 +1146,55 @@ int mivp_scan_window_plan_above(const int64_t* hist, int32_t C, int32_t mode, do
 int mivp_scan_threshold_mask(const void* raw, int32_t dtype, int32_t C, const int32_t* dims, int32_t channel,
                              const int64_t* otsu, uint8_t* out, mivp_stream_t stream);
 
+/* Intensity transfer tables: equalisation, matching and Nyul-Udupa landmark standardisation (csrc/scan_transfer.hip;
+ * mivp_amd/transfer.py).  These entry points joined ABI 18 without a bump: they are additive and no earlier
+ * signature changed.  No workspace, no host synchronisation, no atomics: equal calls give equal bits, and the launches record
+ * into a graph as a linear chain.  hist: DEVICE int64 [C][65536] as mivp_scan_hist wrote it, n_v the count of value v,
+ * C(v) = sum_{w <= v} n_w, N = C(32767).  otsu: DEVICE int64 [C][4] of mivp_scan_otsu_plan or NULL; where otsu[c][3] is set
+ * the bins at or below otsu[c][0] read as zero everywhere below, as in mivp_scan_window_plan_above.  table: DEVICE f32
+ * [C][65536], table[c][v + 32768] the model-input intensity of raw value v, written for every v.  meta: DEVICE int32 [C][4] =
+ * {lowest counted value, highest counted value, valid, 0}, both values 0 when nothing is counted.  One workgroup per
+ * channel; every float64 operation below rounds on its own and the result rounds to float32 once.
+ *   mivp_scan_transfer_equalize: v0 the lowest counted value, c0 = n_v0, d = N - c0; r = (double)max(C(v) - c0, 0) / (double)d
+ *     (0 when d == 0); table = r * (b_max - b_min) + b_min, multiply then add.  b_min <= b_max, finite.  valid = N > 0.
+ *   mivp_scan_transfer_match: u(v) = the smallest value u with C_ref(u) * N_src >= max(C_src(v), 1) * N_ref in 128-bit
+ *     integers (ref_hist: the reference histogram, DEVICE int64 [C][65536]; otsu restricts hist, not ref_hist); N_src == 0
+ *     or N_ref == 0: u(v) = v; a histogram with N >= 2^33: u(v) = v and valid = 0.  table = fmaf((float)u, s, t), clamped
+ *     to [lo, hi] when clip, with {s, t, lo, hi} = words 0..3 of ref_slot[c] (DEVICE f32 [C][8], what mivp_scan_window_plan
+ *     wrote for ref_hist): the map mivp_scan_prepare_dev applies, so matching a scan to its own histogram reproduces it.
+ *   mivp_scan_landmarks: landmarks: DEVICE int64 [C][17] = {valid, m_0 .. m_{n-1}, 0 ..}, m_i the k-th smallest counted
+ *     value for k = max(1, ceil(quantiles[i] * (double)N)) (nearest rank, as mivp_scan_window_plan; all 0 when N == 0);
+ *     valid = N > 0 and m_{n-1} > m_0.  quantiles: HOST float64 [n] (void*: the header's pointer vocabulary has no
+ *     pointer to double), 2 <= n <= 16, strictly increasing in [0, 1].
+ *   mivp_scan_landmark_bank_add: bank: DEVICE float64 [C][17] (void*) = {count, sum_0 .. sum_{n-1}, 0 ..}, zeroed by the caller.  A
+ *     valid record adds 1 to count and s_lo + (double)(m_i - m_0) / (double)(m_{n-1} - m_0) * (s_hi - s_lo) to sum_i (divide,
+ *     multiply, add s_lo); an invalid one adds nothing.  s_lo <= s_hi, finite.  One tiny launch.
+ *   mivp_scan_transfer_landmarks: S_i = sum_i / count; the knots M_j are the distinct m_i in increasing order and T_j the
+ *     mean of the S_i that share M_j (summed in index order, divided by their number), j < K.  Segment j serves
+ *     M_j <= v < M_{j+1}, segment 0 every v below M_0, segment K - 2 every v from M_{K-1} on:
+ *     table = T_j + (double)(v - M_j) / (double)(M_{j+1} - M_j) * (T_{j+1} - T_j) (divide, multiply, add), with clip clamped
+ *     to [T_0, T_{K-1}].  K < 2: T_0 everywhere, 0 when N == 0.  count == 0: 0 everywhere.  valid = count > 0, N > 0 and
+ *     K >= 2.  hist (and otsu) are those the record was taken from: they give N and the two values of meta.
+ *   mivp_scan_transfer_apply: out f32 [C][H][W][D] = table[c][raw[c] + 32768] on the native grid, one streaming launch.
+ *     raw, dtype, C, dims as mivp_scan_hist; out needs 4-byte alignment only (16-byte stores are used where out is aligned
+ *     like raw).  By default a workgroup first copies the table entries of the values meta[c][0] .. meta[c][1], 16384 at
+ *     most (all 256 for uint8), into LDS and gathers from there, a value outside them from the table itself; flags bit 0
+ *     gathers every value from the table in global memory.  The same bits either way (tools/bench_transfer.py times both).
+ * MIVP_EINVAL before any launch for a NULL (other than otsu) or misaligned pointer, C outside 1..4, n outside 2..16,
+ * quantiles not strictly increasing in [0, 1], and an unknown dtype or flag bit. */
+int mivp_scan_transfer_equalize(const int64_t* hist, int32_t C, double b_min, double b_max, const int64_t* otsu,
+                                float* table, int32_t* meta, mivp_stream_t stream);
+int mivp_scan_transfer_match(const int64_t* hist, const int64_t* ref_hist, const float* ref_slot, int32_t C, int32_t clip,
+                             const int64_t* otsu, float* table, int32_t* meta, mivp_stream_t stream);
+int mivp_scan_landmarks(const int64_t* hist, int32_t C, const void* quantiles, int32_t n, const int64_t* otsu,
+                        int64_t* landmarks, mivp_stream_t stream);
+int mivp_scan_landmark_bank_add(const int64_t* landmarks, int32_t C, int32_t n, double s_lo, double s_hi, void* bank,
+                                mivp_stream_t stream);
+int mivp_scan_transfer_landmarks(const int64_t* hist, const int64_t* landmarks, const void* bank, int32_t C, int32_t n,
+                                 int32_t clip, const int64_t* otsu, float* table, int32_t* meta, mivp_stream_t stream);
+int mivp_scan_transfer_apply(const void* raw, int32_t dtype, int32_t C, const int32_t* dims, const float* table,
+                             const int32_t* meta, int32_t flags, float* out, mivp_stream_t stream);
+
 /* Per-lesion region statistics and lesion-wise detection metrics (csrc/regions.hip; mivp_amd/regions.py).
  * These entry points joined ABI 18 without a bump: they are additive and no earlier signature changed.  dims = {H, W, D}
  * (host), volumes [H][W][D] row-major, fewer than 2^31 voxels; connectivity as mivp_label_components.  No host

@@ -16,7 +16,7 @@ def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
                 "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit",
-                "skeleton", "otsu", "prompting"):
+                "skeleton", "otsu", "prompting", "transfer"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -51,6 +51,10 @@ def __getattr__(name):
                 "otsu_slot", "foreground_mask", "window_slot_above"):
         from . import scanstats
         return getattr(scanstats, name)
+    if name in ("IntensityTransfer", "TransferTable", "LandmarkSlot", "LandmarkBank", "equalize_table", "match_table",
+                "scan_landmarks", "landmark_table", "apply_table"):
+        from . import transfer
+        return getattr(transfer, name)
     if name in ("IntensityDraws", "IntensitySlot", "draw_intensity", "augment_intensity", "FilterDraws", "FilterSlot",
                 "draw_filters", "augment_filters"):
         from . import augment

@@ -244,6 +244,14 @@ class ScanGeometry:
             self._dev[key] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
         return self._dev[key]
 
+    def transfer_workspace(self, device, channels: int) -> torch.Tensor:
+        """fp32 ``[C, H, W, D]`` on the native grid for ``channels`` channels on ``device``, allocated once: what a
+        transfer table's apply launch writes and the prepare launch reads (``prepare_scan(window=IntensityTransfer)``)."""
+        key = ("transfer_ws", str(device), int(channels))
+        if key not in self._dev:
+            self._dev[key] = torch.empty((int(channels),) + self.shape, dtype=torch.float32, device=device)
+        return self._dev[key]
+
     def device_tables(self, kind: str, device) -> torch.Tensor:
         key = (kind, str(device))
         if key not in self._dev:
@@ -326,7 +334,10 @@ def prepare_scan(raw: torch.Tensor, geom: ScanGeometry, a_min: Optional[float] =
     voxels it counts.  A ``WindowSlot`` -- ``window_slot`` of a histogram pooled over a data set -- is applied as it is.
     ``a_min`` / ``a_max`` must then be left out, and so must ``b_min`` / ``b_max``, which belong to the spec
     (``ValueError`` otherwise); ``clip`` holds for a percentile window (a z-score window clamps by its own ``clip=``
-    percentiles).
+    percentiles).  An ``IntensityTransfer`` or a ``TransferTable`` (``mivp_amd.transfer``, DESIGN 4.44: equalisation,
+    histogram matching, landmark standardisation) maps every value through a table instead: histogram -> table plan ->
+    one streaming launch that writes the table's values on the native grid into a workspace the geometry keeps -> the
+    float32 launch of this function with the identity map.  ``clip`` then belongs to the spec; ``mask`` goes with a spec only.
 
     ``flags=FLAG_ANTIALIAS`` (``antialias=True`` of ``predict_scan`` / ``evaluate_scan`` / ``predict_scan_volume``; a flag
     bit because this function's signature is frozen) filters every minified axis with the normalised triangle filter of support ``n_in / n_out``
@@ -362,6 +373,11 @@ def prepare_scan(raw: torch.Tensor, geom: ScanGeometry, a_min: Optional[float] =
     src, dst, axes, interp, _ = geom.tables("image")
     if aa:
         aa_tab, ws = L.ptr(geom.device_tables("image_aa", r.device)), L.ptr(geom.aa_workspace(r.device, r.shape[0]))
+    if window is not None and scanstats._is_transfer(window):
+        # the table's values on the native grid, then the float32 launches below with the identity map and no clip
+        from . import transfer
+        r = transfer.apply_table(r, transfer.resolve_table(window, r, mask), out=geom.transfer_workspace(r.device, r.shape[0]))
+        window, mp, clip = None, (1.0, 0.0, 0.0, 1.0), False
     if window is not None:
         slot = scanstats.resolve_window(window, r, mask)
         dev_clip = bool(clip) if slot.mode == scanstats.MODE_PERCENTILE else True

@@ -377,10 +377,20 @@ def _plan(hist, spec, out, otsu) -> WindowSlot:
     return slot
 
 
+def _is_transfer(window) -> bool:
+    """``window=`` is a transfer table or its spec (``mivp_amd.transfer``), not a linear window."""
+    from . import transfer
+    return isinstance(window, (transfer.IntensityTransfer, transfer.TransferTable))
+
+
 def check_window_args(window, raw: torch.Tensor, mask, shape) -> None:
     """The host-side checks of ``prepare_scan(window=...)`` (``raw`` already ``[C, H, W, D]``)."""
+    if _is_transfer(window):
+        from . import transfer
+        return transfer.check_transfer_args(window, raw, mask, shape)
     if not isinstance(window, (IntensityWindow, WindowSlot)):
-        raise ValueError(f"window must be an IntensityWindow or a WindowSlot, got {type(window).__name__}")
+        raise ValueError("window must be an IntensityWindow, a WindowSlot, an IntensityTransfer or a TransferTable, got "
+                         f"{type(window).__name__}")
     if raw.dtype not in _DTYPES:
         raise ValueError(f"a data-driven window takes int16 or uint8 scans, got {raw.dtype}")
     if isinstance(window, WindowSlot):
@@ -394,7 +404,8 @@ def check_window_args(window, raw: torch.Tensor, mask, shape) -> None:
 def resolve_window(window, raw: torch.Tensor, mask) -> WindowSlot:
     """``prepare_scan``'s device side of ``window=``: a ``WindowSlot`` as it is; an ``IntensityWindow`` runs histogram ->
     plan on ``raw`` itself in the spec's own buffers (a clear and two launches, no host read); with
-    ``foreground="otsu"`` histogram -> Otsu plan -> restricted plan (a clear and three launches)."""
+    ``foreground="otsu"`` histogram -> Otsu plan -> restricted plan (a clear and three launches).  (The transfer types
+    of ``_is_transfer`` resolve to a table, not a slot: ``transfer.resolve_table``.)"""
     if isinstance(window, WindowSlot):
         if window.words.device != raw.device:
             raise ValueError(f"window is on {window.words.device}, raw on {raw.device}")
