@@ -1656,6 +1656,65 @@ int mivp_input_prompt_fwd(const float* x, const float* p, const float* scale, in
 int mivp_input_prompt_bwd(const float* dy, const float* scale, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t D,
                           int32_t gh, int32_t gw, int32_t gd, float* dp, mivp_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* Multi-label targets: overlapping label groups (csrc/multilabel.hip)      */
+/* ------------------------------------------------------------------------ */
+/* Loss, decode and counts for R overlapping label GROUPS with one sigmoid channel each (mivp_amd/multilabel.py LabelGroups /
+ * MultiLabelSpec / multilabel_loss / decode_groups / group_counts).  These entry points joined ABI 18 without a
+ * bump: they are additive and no earlier signature changed.
+ *
+ * member: DEVICE int32 [256]; bits 0..R-1 of entry l = the groups that contain label l, bit 8 = l is a known label.
+ * lut:    DEVICE uint8 [2^R]; the label of each pattern of predicted groups.
+ *
+ * Loss.  logits f32 [B, vol, R] channels-last (1 <= R <= 8), target f32 [B, vol] labels.  A voxel is VALID when its label is
+ * an integer in 0..255, known (member bit 8) and, with has_ignore != 0, differs from ignore_index (compared as a float);
+ * V = the valid voxels, N = |V| over the whole batch.  With t_r = [label in group r], p_r = sigmoid(z_r), s = 1e-5 and sums
+ * over V of a sample (of the whole batch when batch != 0):
+ *   I_r = sum p_r t_r,  P_r = sum p_r,  T_r = sum t_r
+ *   TI_r   = (2 I + s) / (2 I + 2 alpha (P - I) + 2 beta (T - I) + s)
+ *   region = mean over (b, r) [over r when batch] of 1 - TI_r
+ *   f_r    = w_r [ t_r pi_r (1 - p_r)^gamma (-log p_r) + (1 - t_r) p_r^gamma (-log(1 - p_r)) ]
+ *   voxel  = sum_{v in V} sum_r f_r / (R max(N, 1))
+ *   loss[0] = lambda_region region + lambda_voxel voxel
+ * An invalid voxel adds to no sum and gets an exactly zero gradient in all R channels.  log p and log(1 - p) come from
+ * e = exp(-|z|), log1p(e) and one reciprocal: finite, and with their digits, at |z| = 30.  alpha, beta >= 0; gamma =
+ * focal_gamma == 0 or >= 1; lambda_region, lambda_voxel >= 0, not both 0; group_weights (w) and pos_weight (pi): DEVICE
+ * pointers to R floats >= 0, NULL = all ones (the values are not read back to be checked).
+ * workspace: mivp_multilabel_loss_ws(B, vol) floats, the layout of mivp_seg_loss_ws (row: (I, P, T) x 8 groups, voxel
+ * numerator, N).  Three launches: a statistics pass with one partial row per workgroup, a one-workgroup f64 finalize in a
+ * fixed order, and the gradient pass.  dlogits may be NULL: the value alone; mivp_multilabel_loss_grad then runs the gradient
+ * pass on the SAME workspace with the SAME options, scaled by gscale[0] (device pointer, NULL = 1); it writes every element
+ * of dlogits once.  No atomics, no host read, every launch unconditional: equal calls give equal bits. */
+size_t mivp_multilabel_loss_ws(int32_t B, int64_t vol);
+int mivp_multilabel_loss(const float* logits, const float* target, int32_t B, int64_t vol, int32_t R,
+                         const int32_t* member, int32_t batch, float alpha, float beta, float focal_gamma,
+                         const float* group_weights, const float* pos_weight, int32_t ignore_index, int32_t has_ignore,
+                         float lambda_region, float lambda_voxel, float* workspace, float* loss, float* dlogits,
+                         mivp_stream_t stream);
+int mivp_multilabel_loss_grad(const float* logits, const float* target, int32_t B, int64_t vol, int32_t R,
+                              const int32_t* member, int32_t batch, float alpha, float beta, float focal_gamma,
+                              const float* group_weights, const float* pos_weight, int32_t ignore_index,
+                              int32_t has_ignore, float lambda_region, float lambda_voxel, float* workspace,
+                              const float* gscale, float* dlogits, mivp_stream_t stream);
+
+/* Decode, one streaming launch.  logits f32 [B][R][vol] (channels_last == 0) or [B][vol][R]; thresholds: DEVICE f32 [R] in
+ * logit space (the host turns a probability q into log(q / (1 - q)); q = 0.5 is exactly 0).  bits = sum_r [z_r > tau_r] << r
+ * (a logit equal to its threshold gives bit 0).  Each output is written when its pointer is non-NULL (at least one is):
+ * labels uint8 [B][vol] = lut[bits], bits uint8 [B][vol], probs f32 [B][R][vol] = sigmoid(z).  With vol % 4 == 0 and aligned
+ * pointers a thread owns four voxels: 16-byte loads, one 32-bit store per byte map, 16-byte stores of the probabilities. */
+int mivp_multilabel_decode(const float* logits, int32_t B, int64_t vol, int32_t R, int32_t channels_last,
+                           const float* thresholds, const uint8_t* lut, uint8_t* labels, uint8_t* bits, float* probs,
+                           mivp_stream_t stream);
+
+/* Group counts, one launch: counts int64 [R][3] += (|pred_r & t_r|, |pred_r|, |t_r|) over the valid voxels of target (the
+ * validity rule of the loss; nvox < 2^31).  dtype codes: 0 = uint8, 3 = float32.  pred is a bits map (pred_is_labels == 0;
+ * uint8) or a label map mapped through member (pred_is_labels != 0; a predicted value that is no label in 0..255 is in no
+ * group).  Per-wave ballots and popcounts, an LDS table, one set of 64-bit integer atomics per workgroup: the result does
+ * not depend on the order.  counts accumulates across calls, like mivp_seg_counts. */
+int mivp_group_counts(const void* pred, int32_t pred_dtype, int32_t pred_is_labels, const void* target,
+                      int32_t target_dtype, int64_t nvox, int32_t R, const int32_t* member, int32_t ignore_index,
+                      int32_t has_ignore, int64_t* counts, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

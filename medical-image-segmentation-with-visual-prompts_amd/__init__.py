@@ -16,7 +16,7 @@ def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
                 "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit",
-                "skeleton", "otsu", "prompting", "transfer"):
+                "skeleton", "otsu", "prompting", "transfer", "multilabel"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -62,4 +62,8 @@ def __getattr__(name):
     if name in ("InputPrompt", "PromptedModel", "build_prompt_optimizer", "input_gradient", "saliency_map", "fgsm"):
         from . import prompting
         return getattr(prompting, name)
+    if name in ("LabelGroups", "MultiLabelSpec", "MultiLabelLoss", "multilabel_loss", "decode_groups", "group_counts",
+                "group_scores", "evaluate_volume_groups"):
+        from . import multilabel
+        return getattr(multilabel, name)
     raise AttributeError(name)

@@ -14,6 +14,7 @@ import torch
 from . import _lib as L
 from ._host import (ImmutableValue, channels_last_or_copy, check_classes, check_fill_logit, check_finite, check_flag,
                     check_gpu, check_int_from, check_region_mask, i3, iou_dice)
+from .multilabel import GroupEvaluation, evaluate_volume_groups  # noqa: F401  (inference.evaluate_volume_groups)
 from .skeleton import CenterlineEvaluation, evaluate_volume_centerline  # noqa: F401  (inference.evaluate_volume_centerline)
 from .window_fit import WindowFit, foreground_box
 
@@ -285,7 +286,7 @@ def _model_factor(conf) -> Tuple[int, int, int]:
     return ps[0] * 2 ** depth, ps[1] * 2 ** depth, ps[2] * 2 ** min(depth, 1)
 
 
-class SlidingWindowPredictor(CenterlineEvaluation):
+class SlidingWindowPredictor(CenterlineEvaluation, GroupEvaluation):
     """Whole-volume sliding-window prediction of a ``downstream`` model on the GPU.
 
     For one image size it owns the window table, the device sub-batch index, the model's input batch, the blend

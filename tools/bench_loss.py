@@ -1,6 +1,7 @@
 """Time the recorded loss + gradient of mivp_seg_loss (csrc/segloss.hip) against the Dice-focal kernels and eager torch.
 
-    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10] [--boundary | --cldice | --hausdorff | --lovasz]
+    python tools/bench_loss.py [--runs 5] [--replays 50] [--warmup 10] [--boundary | --cldice | --hausdorff | --lovasz |
+                                --multilabel]
 
 Shapes: 96^3 at B = 4 (the `downstream` step's) and 128 x 128 x 8 at B = 14, both C = 2.  Settings of the new entry:
   (a) Dice-equivalent options (alpha = beta = 0.5), lambda_voxel = 0
@@ -49,6 +50,16 @@ classes, the batch as one segment per class (7.1 M and 3.7 M keys):
   (e) a device copy of the term's unsorted keys + mivp_sort_u32 on them, and (f) that copy alone: (e) - (f) is the sort, set
       against the 4 passes x 2 x 4 N bytes its keys have to move (an estimate, at 6.3 TB/s)
   (g) the authors' composition with autograd, eager, on the same GPU: torch.sort per class, cumsum, a gather back
+
+``--multilabel`` times the multi-label loss, decode and counts instead (csrc/multilabel.hip), same two shapes,
+R = 3 (the BraTS groups), 20 % of the voxels ignored:
+  (a) mivp_multilabel_loss, value + gradient: Dice + binary cross-entropy
+  (b) the same with Tversky (0.3, 0.7), gamma = 2, group weights and pos_weight
+  (c) mivp_seg_loss at C = 3 on the same logits: Dice + weighted cross-entropy, the softmax sibling moving the same bytes
+  (d) the torch composition of (a) with autograd, eager, on the same GPU (multilabel._multilabel_loss_torch)
+  (e) on a 512 x 512 x 96 volume: mivp_multilabel_decode (labels + bits) then mivp_group_counts on the bits, (f) the decode
+      alone with the probabilities as well, and (g) the eager torch composition of (e): sigmoid, three compares, a table
+      lookup, an ``isin`` per group and nine sums
 
 Each kernel variant is one call (value + gradient) recorded in a HIP graph; a run is `replays` replays between two device
 events after `warmup` replays; the figure is the median over `runs` runs with the spread (min .. max).  One JSON line per
@@ -523,6 +534,98 @@ def lovasz_main(args):
     print(json.dumps({"bench_lovasz_ms": summary}))
 
 
+def multilabel_main(args):
+    """The multi-label loss, decode and counts: see the module docstring."""
+    from mivp_amd import multilabel as M
+    brats = M.LabelGroups([(1, 2, 3), (2, 3), (3,)])
+    Rg = brats.R
+    member, lut = brats.tables(torch.device(DEV))
+    summary = {}
+
+    def put(name, label, r, digits=4):
+        r.update(shape=name, variant=label)
+        summary[f"{name} | {label}"] = [round(r[k], digits) for k in ("ms", "lo", "hi")]
+        print(json.dumps(r), flush=True)
+        return r
+
+    for name, B, dims in SHAPES:
+        vol = dims[0] * dims[1] * dims[2]
+        g = torch.Generator().manual_seed(1)
+        z = (2.0 * torch.randn((B, vol, Rg), generator=g)).to(DEV)
+        y = torch.randint(0, 4, (B, vol), generator=g).float()
+        y[torch.rand((B, vol), generator=g) < 0.2] = float(IGNORE)
+        y = y.to(DEV)
+        dz, loss = torch.empty_like(z), torch.empty(1, dtype=torch.float32, device=DEV)
+        gw = torch.tensor((0.5, 2.0, 1.0), dtype=torch.float32, device=DEV)
+        pw = torch.tensor((2.0, 0.5, 3.0), dtype=torch.float32, device=DEV)
+        ws = torch.empty(int(L.lib().mivp_multilabel_loss_ws(B, vol)), dtype=torch.float32, device=DEV)
+
+        def ml_plain():
+            L.call("mivp_multilabel_loss", L.ptr(z), L.ptr(y), B, vol, Rg, L.ptr(member), 0, 0.5, 0.5, 0.0, None, None, IGNORE, 1,
+                   1.0, 1.0, L.ptr(ws), L.ptr(loss), L.ptr(dz), L.stream())
+
+        def ml_full():
+            L.call("mivp_multilabel_loss", L.ptr(z), L.ptr(y), B, vol, Rg, L.ptr(member), 0, 0.3, 0.7, 2.0, L.ptr(gw), L.ptr(pw),
+                   IGNORE, 1, 1.0, 1.0, L.ptr(ws), L.ptr(loss), L.ptr(dz), L.stream())
+
+        res = {}
+        for key, label, call in (("a", "(a) multilabel dice + BCE, R = 3", ml_plain),
+                                 ("b", "(b) multilabel tversky + focal BCE gamma 2, weights", ml_full),
+                                 ("c", "(c) seg_loss dice + weighted CE, C = 3",
+                                  seg_variant(z, y, gw, dz, loss, 0.5, 0.5, 0.0, True, True, 1.0, 1.0))):
+            r = put(name, label, timed(recorded(call), args.runs, args.replays, args.warmup))
+            r.update(gb_s=3 * z.numel() * 4 / r["ms"] / 1e6)
+            res[key] = r
+        plain = z.view(B, *dims, Rg).permute(0, 4, 1, 2, 3).contiguous().requires_grad_(True)
+        spec = M.MultiLabelSpec(ignore_index=IGNORE)
+
+        def eager():
+            plain.grad = None
+            M._multilabel_loss_torch(plain.permute(0, 2, 3, 4, 1).reshape(B, -1, Rg), y, member, spec, None, None).backward()
+        r = put(name, "(d) torch composition of (a), eager", timed(eager, args.runs, max(3, args.replays // 10), 3))
+        summary[f"{name} | (d) / (a)"] = round(r["ms"] / res["a"]["ms"], 2)
+        summary[f"{name} | (a) / (c)"] = round(res["a"]["ms"] / res["c"]["ms"], 3)
+    # decode + counts on one whole volume, the planes predict(return_logits=True) returns
+    name, dims = "512x512x96", (512, 512, 96)
+    vol = dims[0] * dims[1] * dims[2]
+    g = torch.Generator().manual_seed(2)
+    planes = (2.0 * torch.randn((Rg, vol), generator=g)).to(DEV)
+    seg = torch.randint(0, 4, (vol,), generator=g).to(torch.uint8).to(DEV)
+    tau = torch.zeros(Rg, dtype=torch.float32, device=DEV)
+    labels, bitsmap = torch.empty(vol, dtype=torch.uint8, device=DEV), torch.empty(vol, dtype=torch.uint8, device=DEV)
+    probs = torch.empty((Rg, vol), dtype=torch.float32, device=DEV)
+    counts = torch.zeros((Rg, 3), dtype=torch.int64, device=DEV)
+
+    def decode_counts():
+        L.call("mivp_multilabel_decode", L.ptr(planes), 1, vol, Rg, 0, L.ptr(tau), L.ptr(lut), L.ptr(labels), L.ptr(bitsmap), None,
+               L.stream())
+        L.call("mivp_group_counts", L.ptr(bitsmap), 0, 0, L.ptr(seg), 0, vol, Rg, L.ptr(member), 0, 0, L.ptr(counts), L.stream())
+
+    def decode_probs():
+        L.call("mivp_multilabel_decode", L.ptr(planes), 1, vol, Rg, 0, L.ptr(tau), L.ptr(lut), L.ptr(labels), L.ptr(bitsmap),
+               L.ptr(probs), L.stream())
+
+    e = put(name, "(e) decode (labels + bits) + group counts", timed(recorded(decode_counts), args.runs, args.replays, args.warmup))
+    e.update(gb_s=(planes.numel() * 4 + 4 * vol) / e["ms"] / 1e6)
+    f = put(name, "(f) decode with probabilities", timed(recorded(decode_probs), args.runs, args.replays, args.warmup))
+    f.update(gb_s=(2 * planes.numel() * 4 + 2 * vol) / f["ms"] / 1e6)
+    lut_l = lut.long()
+    sets = [torch.tensor(s, dtype=torch.uint8, device=DEV) for s in brats.groups]
+
+    def eager_decode():
+        on = torch.sigmoid(planes) > 0.5
+        b = on[0].long() + 2 * on[1].long() + 4 * on[2].long()
+        lab = lut_l[b]
+        out = []
+        for r in range(Rg):
+            t = torch.isin(seg, sets[r])
+            out += [(on[r] & t).sum(), on[r].sum(), t.sum()]
+        return lab, torch.stack(out)
+    r = put(name, "(g) torch composition of (e), eager", timed(eager_decode, args.runs, max(3, args.replays // 10), 3))
+    summary[f"{name} | (g) / (e)"] = round(r["ms"] / e["ms"], 2)
+    print(json.dumps({"bench_multilabel_ms": summary}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
@@ -532,8 +635,11 @@ def main():
     ap.add_argument("--cldice", action="store_true", help="time the clDice term (DESIGN 4.36) instead")
     ap.add_argument("--hausdorff", action="store_true", help="time the Hausdorff distance-transform term (DESIGN 4.39) instead")
     ap.add_argument("--lovasz", action="store_true", help="time the Lovasz-Softmax term (DESIGN 4.40) instead")
+    ap.add_argument("--multilabel", action="store_true", help="time the multi-label loss, decode and counts (DESIGN 4.45) instead")
     args = ap.parse_args()
     assert args.runs >= 3
+    if args.multilabel:
+        return multilabel_main(args)
     if args.lovasz:
         return lovasz_main(args)
     if args.hausdorff:
