@@ -1715,6 +1715,49 @@ int mivp_group_counts(const void* pred, int32_t pred_dtype, int32_t pred_is_labe
                       int32_t target_dtype, int64_t nvox, int32_t R, const int32_t* member, int32_t ignore_index,
                       int32_t has_ignore, int64_t* counts, mivp_stream_t stream);
 
+/* Interactive click prompts (csrc/clicks.hip; mivp_amd/clicks.py).  These entry points joined ABI 18 without a
+ * bump: they are additive and no earlier signature changed.
+ *
+ * The record of a batch, all DEVICE memory: clicks i32 [B][K][4] = (h, w, d, channel), 16-byte aligned, channel 0 = positive,
+ * 1 = negative, any other value = an empty entry; count i32 [B], the first count[b] entries of sample b are read (clamped to
+ * 0 .. K); last i32 [B][4], 16-byte aligned, written by the simulation.  1 <= K <= 64, 1 <= B <= 65535.
+ *
+ * mivp_clicks_encode, one launch: out f32 [B][Ctot][H][W][D] (dims = {H, W, D}, host; H, W, D <= 65535, H W D < 2^31).  Writes
+ * channels channel_offset and channel_offset + 1 (0 <= channel_offset <= Ctot - 2) of every sample, every element of them stored
+ * exactly once, and no other byte.  Per voxel v and channel c, over the valid clicks p of sample b with that channel:
+ *   m = min_p sum_a (spacing[a] (v_a - p_a))^2        +inf without a click; the exact integer at spacing {1, 1, 1}
+ *   kind 0 (gaussian): expf(-m / param), param = 2 sigma^2 > 0      kind 1 (disk): m <= param ? 1 : 0, param = radius^2 >= 0
+ * A channel without a click is +0 everywhere.  spacing: host f32 {s0, s1, s2} mm, > 0.  count is read on the device and the
+ * launch is unconditional: a recording follows later slot contents.  out needs 4-byte alignment only; stores are 16 bytes
+ * wide wherever the two channels' run allows (unaligned head and tail of at most 3 floats each per sample).
+ *
+ * mivp_clicks_simulate: the next corrective click per sample.  pred / target: class maps [B][H][W][D] of dtype 0 uint8,
+ * 1 int32, 2 int64, 3 float32; a value that is no integer in 0 .. 31 is no class.  pred_dtype 4: pred is f32 logits
+ * [B][vol][C] channels-last (1 <= C <= 32) and the class is the LOWEST index among the exact maxima (C is ignored otherwise).
+ * The object = the classes whose bit is set in object_mask.
+ *   E_pos = {target in the object, pred not}  -> a positive click (channel 0)
+ *   E_neg = {pred in the object, target a class outside it}  -> a negative click (channel 1)
+ * A voxel whose target is no class, or equals ignore_index with has_ignore != 0, is in neither.
+ *   depth^2(v), v in a region = the squared distance sqrt(sum_a (spacing[a] delta_a)^2)^2 to the nearest voxel of the sample
+ *   outside that region, the space beyond the volume counting as outside (the transform of the mask padded by one voxel):
+ *   min(the exact transform inside the volume, min_a (spacing[a] (distance to the nearest face along a, >= 1))^2).
+ * The click is the voxel with the largest depth^2 over both regions, ties to E_pos, then to the lowest raster index
+ * (h W + w) D + d.  last[b] = {bits of depth^2, channel, raster index, placed} or {0, -1, -1, 0} when both regions are empty.
+ * The click is appended at clicks[b][count[b]] and count[b] incremented iff a region exists, depth^2 >= min_depth_sq and
+ * 0 <= count[b] < K (placed = 1); otherwise clicks and count are untouched.  Five launches whatever B and the data are (seed
+ * / D pass, W pass, H pass, pick, commit), each unconditional, nothing read back, no float atomics: one 64-bit integer
+ * atomicMax per workgroup on a packed key, so equal calls give equal bits.  Exact integers at unit spacing.
+ * Limits: H, W <= 65535, H W D < 2^31.  workspace: mivp_clicks_simulate_ws(B, dims) bytes (0 for arguments the call would
+ * refuse), 256-byte aligned: the squared fields f32 [2][B][vol], the lower envelope's stack (int32 pairs), the keys u64 [B]. */
+int mivp_clicks_encode(const int32_t* clicks, const int32_t* count, int32_t B, int32_t K, int32_t Ctot,
+                       int32_t channel_offset, const int32_t* dims, const float* spacing, int32_t kind, float param,
+                       float* out, mivp_stream_t stream);
+size_t mivp_clicks_simulate_ws(int32_t B, const int32_t* dims);
+int mivp_clicks_simulate(const void* pred, int32_t pred_dtype, int32_t C, const void* target, int32_t target_dtype,
+                         int32_t B, const int32_t* dims, const float* spacing, uint32_t object_mask,
+                         int32_t ignore_index, int32_t has_ignore, float min_depth_sq, int32_t K, int32_t* clicks,
+                         int32_t* count, int32_t* last, void* workspace, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
                 "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit",
-                "skeleton", "otsu", "prompting", "transfer", "multilabel"):
+                "skeleton", "otsu", "prompting", "transfer", "multilabel", "clicks"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -66,4 +66,8 @@ def __getattr__(name):
                 "group_scores", "evaluate_volume_groups"):
         from . import multilabel
         return getattr(multilabel, name)
+    if name in ("ClickSlot", "GuidedModel", "encode_clicks", "simulate_clicks", "simulate_clicks_from_logits",
+                "simulate_clicks_ws", "click_rounds", "refine_volume"):
+        from . import clicks
+        return getattr(clicks, name)
     raise AttributeError(name)

@@ -1,5 +1,5 @@
 """Host-side argument checks and small helpers shared by the evaluation modules (``inference``, ``surface``,
-``components``, ``regions``, ``calibration``, ``scan``, ``scanstats``, ``skeleton``).  One definition each: a module that needs one
+``components``, ``regions``, ``calibration``, ``scan``, ``scanstats``, ``skeleton``, ``clicks``).  One definition each: a module that needs one
 imports it from here, not from a sibling.  Also the two things the predictor's pieces share that are not checks: the
 ``ImmutableValue`` base of ``WindowSkip`` / ``WindowFit`` and ``channels_last_or_copy``, the layout in which the kernels
 read a model's logits.  Nothing here launches a kernel except ``workspace``'s size query."""
@@ -172,6 +172,42 @@ def label_volume(name: str, t: torch.Tensor) -> torch.Tensor:
     if t.dtype not in LABEL_DTYPES:
         t = t.float()
     return t.contiguous()
+
+
+def label_batch(name: str, t: torch.Tensor) -> torch.Tensor:
+    """``[B, 1, H, W, D]`` (or ``[B, H, W, D]``) GPU class maps -> contiguous ``[B, H, W, D]`` of a dtype in ``LABEL_DTYPES``
+    (the conversions of ``label_volume``; fewer than 2^31 voxels per sample)."""
+    if not isinstance(t, torch.Tensor) or t.dim() not in (4, 5) or (t.dim() == 5 and t.shape[1] != 1):
+        raise ValueError(f"{name} must be [B, 1, H, W, D] or [B, H, W, D] class indices, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    check_gpu(name, t)
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dim() == 5:
+        t = t[:, 0]
+    if t.shape[0] < 1 or min(t.shape[1:]) < 1 or t[0].numel() >= 2 ** 31:
+        raise ValueError(f"{name}: {tuple(t.shape)} must hold at least one voxel and fewer than 2^31 per sample")
+    if t.dtype not in LABEL_DTYPES:
+        t = t.float()
+    return t.contiguous()
+
+
+def check_click(name: str, click, dims=None) -> Tuple[int, int, int, int]:
+    """One click ``(h, w, d, channel)``: plain ints, coordinates in ``0 .. 65534`` (and inside ``dims`` when given), channel 0
+    (positive) or 1 (negative)."""
+    try:
+        vals = None if isinstance(click, (str, bytes)) else tuple(click)
+    except TypeError:
+        vals = None
+    if vals is None or len(vals) != 4 or not all(plain_int(v) for v in vals):
+        raise ValueError(f"{name} must be four integers (h, w, d, channel), got {click!r}")
+    if vals[3] not in (0, 1):
+        raise ValueError(f"{name}: channel must be 0 (positive) or 1 (negative), got {vals[3]!r}")
+    for a in range(3):
+        hi = 65535 if dims is None else int(dims[a])
+        if not 0 <= vals[a] < hi:
+            raise ValueError(f"{name}: coordinate {a} = {vals[a]} is outside 0 .. {hi - 1}")
+    return tuple(int(v) for v in vals)
 
 
 def workspace(kind: str, dims, device) -> torch.Tensor:
