@@ -1758,6 +1758,65 @@ int mivp_clicks_simulate(const void* pred, int32_t pred_dtype, int32_t C, const 
                          int32_t ignore_index, int32_t has_ignore, float min_depth_sq, int32_t K, int32_t* clicks,
                          int32_t* count, int32_t* last, void* workspace, mivp_stream_t stream);
 
+/* Box and scribble prompts (csrc/strokes.hip; mivp_amd/strokes.py).  These entry points joined ABI 18 without a
+ * bump: they are additive and no earlier signature changed.
+ *
+ * The record of a batch, all DEVICE memory, 4-byte aligned: boxes i32 [B][KB][7] = (h0, w0, d0, h1, w1, d1, channel), corners
+ * inclusive with lo <= hi, channel 0 = positive, 1 = negative, any other value = an empty row; box_count i32 [B], the first
+ * box_count[b] rows of sample b are read (clamped to 0 .. KB); mask u8 [B][H][W][D], bit 0 = a positive scribble voxel, bit 1 =
+ * a negative one, its storage a multiple of 4 bytes long; last i32 [B][8], written by the simulations; scratch i32 [B][8], all
+ * zero between calls.  1 <= KB <= 16, 1 <= B <= 65535, dims = {H, W, D} (host), 1 <= H, W, D <= 65535, B (H + 2) W D < 2^31.
+ * spacing: host f32 {s0, s1, s2} mm, > 0.  Label maps [B][H][W][D] of dtype 0 uint8, 1 int32, 2 int64, 3 float32; a value that
+ * is no integer in 0 .. 31 is no class; the object = the classes whose bit is set in object_mask; a voxel whose target is no
+ * class, or equals ignore_index with has_ignore != 0, is not valid.  Nothing is read back and no float atomic is used: equal
+ * calls give equal bits.
+ *
+ * mivp_strokes_draw, one launch: points DEVICE i32 [npts][3], 1 <= npts <= 256, every point inside the volume.  Each pair
+ * a -> b of consecutive points sets bit `channel` of the voxels a + floor((2 i delta + n) / (2 n)), i = 0 .. n, delta = b - a,
+ * n = max |delta_a| (floor towards minus infinity, per axis; n = 0 or a single point: that voxel) of sample b.  max_steps >= the
+ * largest n of the polyline.  One thread per (segment, step), an integer atomicOr on the containing 32-bit word.
+ *
+ * mivp_strokes_encode, four launches whatever the record holds (seed / D pass, W pass, H pass, closing pass): out f32
+ * [B][Ctot][H][W][D]; channels channel_offset and channel_offset + 1 of every sample are written, every element of them exactly
+ * once, and no other byte.  Per voxel v and channel c the value is max(box, stroke):
+ *   box     1 where v is inside a box of the channel (frame == 0), or inside one with a coordinate equal to that box's lo or
+ *           hi (frame != 0: the surface), else 0
+ *   stroke  m = min over the scribble voxels p of the channel of sum_a (spacing[a] (v_a - p_a))^2, the exact transform (the
+ *           exact integer at spacing {1, 1, 1}); kind 0 (gaussian): expf(-m / param), param = 2 sigma^2 > 0; kind 1 (disk):
+ *           m <= param ? 1 : 0, param = radius^2 >= 0; +0 without a scribble voxel
+ * out needs 4-byte alignment only; stores are 16 bytes wide wherever the two channels' run allows.
+ *
+ * mivp_strokes_box, two launches (reduction, finalize): (lo, hi) = the tight bounding box of the valid object voxels of the
+ * target per sample; lo' = clamp(lo - margin + jitter[b][0..2], 0, hi), hi' = clamp(hi + margin + jitter[b][3..5], lo,
+ * dim - 1) per axis (margin: host i32 {3} >= 0; jitter: DEVICE i32 [B][6] or NULL).  The row (lo', hi', channel) is appended at
+ * boxes[b][box_count[b]] and box_count[b] incremented iff the object is not empty and 0 <= box_count[b] < KB.  last[b] =
+ * {lo', hi', placed, 0}, or {-1 x 6, 0, 0} for an empty object.  One set of integer atomicMax per workgroup and sample.
+ *
+ * mivp_strokes_scribbles: E_pos / E_neg and depth^2 as in mivp_clicks_simulate; the core of a region = {depth^2 >=
+ * min_depth_sq}; the scribble = the curve skeleton of each core by the thinning of mivp_skeleton_iter (classes 1 = E_pos,
+ * 2 = E_neg, each thinned on its own, max_iter iterations issued, 1 <= max_iter <= 4096), per sample what that thinning gives
+ * on the sample's own [H][W][D] core map.  Positive skeleton voxels set bit 0 of mask, negative ones bit 1; bits already there
+ * stay.  last[b] = {voxels that gained bit 0, voxels that gained bit 1, converged, 0, 0, 0, 0, 0}; converged = 1 when the
+ * thinning of the batch stopped by itself within max_iter.  6 + 9 max_iter launches at most (fewer where an axis has extent
+ * 1), the count a function of dims and max_iter alone, each unconditional.
+ *
+ * workspace: mivp_strokes_ws(B, dims) bytes (0 for arguments the calls would refuse), 256-byte aligned, serves both
+ * mivp_strokes_encode and mivp_strokes_scribbles: the squared fields f32 [B][2][vol], the lower envelope's stack (int32
+ * pairs), two class maps of the batch stacked along H, the thinning's workspace and two state words. */
+int mivp_strokes_draw(const int32_t* points, int32_t npts, int32_t max_steps, int32_t b, int32_t channel, int32_t B,
+                      const int32_t* dims, uint8_t* mask, mivp_stream_t stream);
+size_t mivp_strokes_ws(int32_t B, const int32_t* dims);
+int mivp_strokes_encode(const int32_t* boxes, const int32_t* box_count, const uint8_t* mask, int32_t B, int32_t KB,
+                        int32_t Ctot, int32_t channel_offset, const int32_t* dims, const float* spacing, int32_t frame,
+                        int32_t kind, float param, float* out, void* workspace, mivp_stream_t stream);
+int mivp_strokes_box(const void* target, int32_t target_dtype, int32_t B, const int32_t* dims, uint32_t object_mask,
+                     int32_t ignore_index, int32_t has_ignore, const int32_t* margin, const int32_t* jitter, int32_t channel,
+                     int32_t KB, int32_t* boxes, int32_t* box_count, int32_t* last, int32_t* scratch, mivp_stream_t stream);
+int mivp_strokes_scribbles(const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype, int32_t B,
+                           const int32_t* dims, const float* spacing, uint32_t object_mask, int32_t ignore_index,
+                           int32_t has_ignore, float min_depth_sq, int32_t max_iter, int32_t keep_endpoints, uint8_t* mask,
+                           int32_t* last, void* workspace, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

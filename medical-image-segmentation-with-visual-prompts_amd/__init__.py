@@ -16,7 +16,7 @@ def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
                 "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit",
-                "skeleton", "otsu", "prompting", "transfer", "multilabel", "clicks"):
+                "skeleton", "otsu", "prompting", "transfer", "multilabel", "clicks", "strokes"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -70,4 +70,8 @@ def __getattr__(name):
                 "simulate_clicks_ws", "click_rounds", "refine_volume"):
         from . import clicks
         return getattr(clicks, name)
+    if name in ("StrokeSlot", "StrokeModel", "encode_strokes", "simulate_box", "simulate_scribbles", "strokes_ws",
+                "draw_box_jitter", "scribble_rounds", "box_then_scribbles"):
+        from . import strokes
+        return getattr(strokes, name)
     raise AttributeError(name)
