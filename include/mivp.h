@@ -1817,6 +1817,52 @@ int mivp_strokes_scribbles(const void* pred, int32_t pred_dtype, const void* tar
                            int32_t has_ignore, float min_depth_sq, int32_t max_iter, int32_t keep_endpoints, uint8_t* mask,
                            int32_t* last, void* workspace, mivp_stream_t stream);
 
+/* Geodesic (image-aware) distance guidance for click and scribble prompts (csrc/geodesic.hip; mivp_amd/geodesic.py, DESIGN
+ * 4.48).  These entry points joined ABI 18 without a bump: they are additive and no earlier signature changed.
+ *
+ * Per sample b and plane r (0 positive, 1 negative), over the 26-neighbour voxel graph of the [H][W][D] volume:
+ *   g(v) = min over paths seed -> v of the left-to-right float32 sum of w(u, u')
+ *   w(u, u') = sqrt(l2 + (gamma (I(u) - I(u')))^2), l2 = (a_h |dh| + a_w |dw|) + a_d |dd|, a = the f32 squares of spacing
+ * every operation a separately rounded float32 one, the square root correctly rounded.  g = 0 at a seed, +inf in a plane without
+ * seeds; an edge whose weight is not finite is never taken.  The converged field equals a float32 Dijkstra's in every bit.
+ * I = channel `channel` of image f32 [B][C][H][W][D].  dims = {H, W, D} (host), 1 <= H, W, D <= 65535, B H W D < 2^31,
+ * 1 <= B <= 65535; spacing: host f32 {s0, s1, s2} mm, finite and > 0 (their squares too); gamma finite and >= 0.  Every entry
+ * refuses other arguments before it touches a pointer.  No float atomics; equal calls give equal bits, converged or not.
+ *
+ * workspace: mivp_geodesic_ws bytes (0 for arguments the calls would refuse), 256-byte aligned: [room for the seed mask, B H W
+ * D bytes][F0 f32 [B][2][vol]][F1, the same][counters i32 [min(vol, 65535) + 1]][room for info, 8 bytes], each part rounded
+ * up to 256 bytes; the first and the last part are the caller's, no entry reads or writes them through `workspace`.
+ *
+ * mivp_geodesic_seed, one launch, two with clicks: seeds u8 [B][H][W][D] (4-byte aligned, its storage a multiple of 4 bytes
+ * long; the front of the workspace serves) = bits 0 and 1 of stroke_mask (the mask of a stroke record; NULL: none) | bit
+ * `channel` at every click of the first count[b] (clamped to 0 .. K) entries of clicks i32 [B][K][4] (the click record, 1 <= K
+ * <= 64; NULL with count NULL: none); an entry whose channel is neither 0 nor 1, or that lies outside the volume, is skipped.
+ * One integer atomicOr per click on the containing 32-bit word.
+ * mivp_geodesic_begin: F0 = F1 = (bit r of seeds ? 0 : +inf) and the counters.
+ * mivp_geodesic_iter: iteration number `iteration` (1, 2, 3, .. in this order after mivp_geodesic_begin, at most min(vol,
+ * 65535)): reads F[(iteration + 1) & 1], writes F[iteration & 1] = that field relaxed inside every 16 x 16 x 32 brick (with the
+ * brick's one-voxel halo held fixed) until the brick stops changing, and adds the number of voxels it lowered to its counter.
+ * It returns at once when the previous iteration lowered nothing.  One launch, unconditional on the host.
+ * mivp_geodesic_end: after `iterations` iterations were issued, info[0] (DEVICE i32 [2]) = the number of them that lowered a
+ * voxel, info[1] = 1 when the last one lowered nothing (the field is the fixed point), else 0.  The field is F[iterations & 1];
+ * once converged, both buffers hold it.
+ * mivp_geodesic_encode, one launch: out f32 [B][Ctot][H][W][D]; channels channel_offset and channel_offset + 1 of every sample
+ * are written, every element of them exactly once, and no other byte (the walk of mivp_strokes_encode).  Per voxel and channel
+ * the value is max(box, f(g)), g from F[iterations & 1], m = g g in float32; kind 0 (gaussian): f = expf(-m / param), param = 2
+ * sigma^2 > 0; kind 1 (disk): f = m <= param ? 1 : 0, param = radius^2 >= 0; g = +inf gives +0.  box: the rule of
+ * mivp_strokes_encode on boxes / box_count (1 <= KB <= 16), or none with both NULL. */
+size_t mivp_geodesic_ws(int32_t B, const int32_t* dims);
+int mivp_geodesic_seed(const uint8_t* stroke_mask, const int32_t* clicks, const int32_t* count, int32_t K, int32_t B,
+                       const int32_t* dims, uint8_t* seeds, mivp_stream_t stream);
+int mivp_geodesic_begin(const uint8_t* seeds, int32_t B, const int32_t* dims, void* workspace, mivp_stream_t stream);
+int mivp_geodesic_iter(int32_t iteration, const float* image, int32_t C, int32_t channel, int32_t B, const int32_t* dims,
+                       const float* spacing, float gamma, void* workspace, mivp_stream_t stream);
+int mivp_geodesic_end(int32_t iterations, int32_t B, const int32_t* dims, const void* workspace, int32_t* info,
+                      mivp_stream_t stream);
+int mivp_geodesic_encode(const int32_t* boxes, const int32_t* box_count, int32_t KB, int32_t iterations, int32_t B,
+                         int32_t Ctot, int32_t channel_offset, const int32_t* dims, int32_t frame, int32_t kind, float param,
+                         float* out, const void* workspace, mivp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ def __getattr__(name):
     # heavy modules are imported lazily so that `import mivp_amd` stays cheap
     if name in ("swin_ops", "ops", "swin_unetr", "train", "multiview", "inference", "surface",
                 "components", "scan", "regions", "shape", "augment", "calibration", "scanstats", "window_fit",
-                "skeleton", "otsu", "prompting", "transfer", "multilabel", "clicks", "strokes"):
+                "skeleton", "otsu", "prompting", "transfer", "multilabel", "clicks", "strokes", "geodesic"):
         import importlib
         return importlib.import_module(f"mivp_amd.{name}")
     if name == "SwinUnetR":
@@ -74,4 +74,8 @@ def __getattr__(name):
                 "draw_box_jitter", "scribble_rounds", "box_then_scribbles"):
         from . import strokes
         return getattr(strokes, name)
+    if name in ("GeodesicField", "GeodesicModel", "geodesic_ws", "seed_mask", "geodesic_distance", "encode_geodesic",
+                "geodesic_rounds"):
+        from . import geodesic
+        return getattr(geodesic, name)
     raise AttributeError(name)

@@ -1,5 +1,5 @@
 """Host-side argument checks and small helpers shared by the evaluation modules (``inference``, ``surface``,
-``components``, ``regions``, ``calibration``, ``scan``, ``scanstats``, ``skeleton``, ``clicks``).  One definition each: a module that needs one
+``components``, ``regions``, ``calibration``, ``scan``, ``scanstats``, ``skeleton``, ``clicks``, ``geodesic``).  One definition each: a module that needs one
 imports it from here, not from a sibling.  Also the two things the predictor's pieces share that are not checks: the
 ``ImmutableValue`` base of ``WindowSkip`` / ``WindowFit`` and ``channels_last_or_copy``, the layout in which the kernels
 read a model's logits.  Nothing here launches a kernel except ``workspace``'s size query."""
@@ -190,6 +190,16 @@ def label_batch(name: str, t: torch.Tensor) -> torch.Tensor:
     if t.dtype not in LABEL_DTYPES:
         t = t.float()
     return t.contiguous()
+
+
+def check_image_batch(name: str, t, contiguous: bool = True) -> torch.Tensor:
+    """A float32 ``[B, C, H, W, D]`` image batch of the prompt encodings (``contiguous``: as the kernels read it)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 5 or t.dtype != torch.float32:
+        raise ValueError(f"{name} must be a float32 [B, C, H, W, D] tensor, got "
+                         f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if contiguous and not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return t
 
 
 def check_click(name: str, click, dims=None) -> Tuple[int, int, int, int]:

@@ -29,10 +29,12 @@
 //    commit (the skeleton's voxels into the mask's bits; a ballot and a popcount per wave, LDS, one integer atomicAdd per
 //    workgroup and counter).  Every launch is unconditional.
 #include "edt_common.hpp"
+#include "guidance_common.hpp"
 
 namespace {
 constexpr int ST_TPB = 256;
 constexpr int ST_MAXKB = 16;
+static_assert(ST_TPB == GUIDE_TPB && ST_MAXKB == GUIDE_MAXKB, "the closing pass runs the shared walk");
 constexpr int ST_MAXPTS = 256;
 constexpr int ST_MAXCLS = 32;                                  // labels are classes 0 .. 31; the object is a 32-bit mask
 
@@ -124,94 +126,25 @@ __global__ __launch_bounds__(ST_TPB) void k_strokes_line(float* __restrict__ fie
 }
 
 // ------------------------------------------------------------------------------------------------------------ encoding
+// the box rule and the walk over the run: csrc/guidance_common.hpp (shared with csrc/geodesic.hip)
 struct StEnc {
-    int H, W, D, KB, Ctot, off, kind, frame;
+    GuideRun run;
+    int kind;
     float param;                                               // 2 sigma^2 (gaussian) or radius^2 (disk)
 };
-
-struct StBox { int l0, l1, l2, h0, h1, h2; };
 
 MIVP_DEV float st_stroke(float m, const StEnc& e) { return e.kind == 0 ? expf(-m / e.param) : (m <= e.param ? 1.f : 0.f); }
 
 // closing pass: grid (blocks per sample, B).  lst[ch][i] = box i of channel ch, n[ch] of them.
 __global__ __launch_bounds__(ST_TPB) void k_strokes_close(const int32_t* __restrict__ boxes, const int32_t* __restrict__ box_count,
                                                           const float* __restrict__ fields, StEnc e, float* __restrict__ out) {
-    __shared__ StBox lst[2][ST_MAXKB];
+    __shared__ GuideBox lst[2][GUIDE_MAXKB];
     __shared__ int n[2];
     const int b = blockIdx.y;
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        const int cnt = min(max(box_count[b], 0), e.KB);
-        StBox c = {0, 0, 0, -1, -1, -1};
-        int chn = -1;
-        if (lane < cnt) {
-            const int32_t* row = boxes + ((long)b * e.KB + lane) * 7;
-            c.l0 = row[0]; c.l1 = row[1]; c.l2 = row[2]; c.h0 = row[3]; c.h1 = row[4]; c.h2 = row[5];
-            chn = row[6];
-        }
-        for (int ch = 0; ch < 2; ++ch) {
-            const unsigned long long m = __ballot(chn == ch);
-            if (chn == ch) lst[ch][__popcll(m & ((1ull << lane) - 1))] = c;
-            if (lane == 0) n[ch] = __popcll(m);
-        }
-    }
+    guide_boxes(boxes, box_count, b, e.run.KB, lst, n);
     __syncthreads();
-    const long vol = (long)e.H * e.W * e.D;
-    const long run = 2 * vol;                                      // the two guidance channels of sample b
-    float* base = out + ((long)b * e.Ctot + e.off) * vol;
-    const float* fb = fields + (long)b * run;                      // the two fields of sample b, in the order of the run
-    const long head = min((long)((16 - ((uintptr_t)base & 15)) & 15) >> 2, run);
-    const long nq = (run - head) >> 2;
-    const long tail0 = head + 4 * nq;                              // first element of the tail
-    const int WD = e.W * e.D;
-    // whether (h, w) is inside box c, and on its surface already
-    auto hw_in = [&](const StBox& c, int h, int w, bool& edge) -> bool {
-        edge = h == c.l0 || h == c.h0 || w == c.l1 || w == c.h1;
-        return h >= c.l0 && h <= c.h0 && w >= c.l1 && w <= c.h1;
-    };
-    auto d_in = [&](const StBox& c, int d, bool edge) -> bool {
-        return d >= c.l2 && d <= c.h2 && (!e.frame || edge || d == c.l2 || d == c.h2);
-    };
-    // value of element el of the run
-    auto one = [&](long el) -> float {
-        const int ch = el >= vol ? 1 : 0;
-        const int r = (int)(el - (ch ? vol : 0L));
-        const int h = r / WD, w = (r - h * WD) / e.D, d = r - h * WD - w * e.D;
-        bool hit = false;
-        for (int i = 0; i < n[ch]; ++i) {
-            const StBox c = lst[ch][i];
-            bool edge;
-            hit |= hw_in(c, h, w, edge) && d_in(c, d, edge);
-        }
-        return fmaxf(hit ? 1.f : 0.f, st_stroke(fb[el], e));
-    };
-    for (long q = (long)blockIdx.x * ST_TPB + threadIdx.x; q <= nq; q += (long)gridDim.x * ST_TPB) {
-        if (q == nq) {                                             // the one item of the unaligned ends
-            for (long el = 0; el < head; ++el) base[el] = one(el);
-            for (long el = tail0; el < run; ++el) base[el] = one(el);
-            continue;
-        }
-        const long el = head + 4 * q;
-        const int ch = el >= vol ? 1 : 0;
-        const int r = (int)(el - (ch ? vol : 0L));
-        const int h = r / WD, w = (r - h * WD) / e.D, d = r - h * WD - w * e.D;
-        float4 v;
-        if (d + 3 < e.D) {                                         // four voxels of one line: the (h, w) part once per box
-            bool h0 = false, h1 = false, h2 = false, h3 = false;
-            for (int i = 0; i < n[ch]; ++i) {
-                const StBox c = lst[ch][i];
-                bool edge;
-                if (!hw_in(c, h, w, edge)) continue;
-                h0 |= d_in(c, d, edge); h1 |= d_in(c, d + 1, edge); h2 |= d_in(c, d + 2, edge); h3 |= d_in(c, d + 3, edge);
-            }
-            const float m0 = fb[el], m1 = fb[el + 1], m2 = fb[el + 2], m3 = fb[el + 3];
-            v = make_float4(fmaxf(h0 ? 1.f : 0.f, st_stroke(m0, e)), fmaxf(h1 ? 1.f : 0.f, st_stroke(m1, e)),
-                            fmaxf(h2 ? 1.f : 0.f, st_stroke(m2, e)), fmaxf(h3 ? 1.f : 0.f, st_stroke(m3, e)));
-        } else {
-            v = make_float4(one(el), one(el + 1), one(el + 2), one(el + 3));
-        }
-        *reinterpret_cast<float4*>(base + el) = v;
-    }
+    const long run = 2L * e.run.H * e.run.W * e.run.D;             // the two fields of sample b, in the order of the run
+    guide_close_run(lst, n, fields + (long)b * run, e.run, out, [&](float m) -> float { return st_stroke(m, e); });
 }
 
 // ------------------------------------------------------------------------------------------------------- label reading
@@ -479,11 +412,10 @@ extern "C" int mivp_strokes_encode(const int32_t* boxes, const int32_t* box_coun
     rc = st_line_passes(fields, stack, B, H, W, D, spacing, st);
     if (rc != MIVP_OK) return rc;
     StEnc e;
-    e.H = H; e.W = W; e.D = D; e.KB = KB; e.Ctot = Ctot; e.off = channel_offset; e.kind = kind; e.frame = frame;
-    e.param = param;
-    const long items = (2L * H * W * D) / 4 + 1;
-    const unsigned gx = (unsigned)((items + ST_TPB - 1) / ST_TPB > 8192 ? 8192 : (items + ST_TPB - 1) / ST_TPB);
-    hipLaunchKernelGGL(k_strokes_close, dim3(gx, (unsigned)B), dim3(ST_TPB), 0, st, boxes, box_count, (const float*)fields, e, out);
+    e.run.H = H; e.run.W = W; e.run.D = D; e.run.KB = KB; e.run.Ctot = Ctot; e.run.off = channel_offset; e.run.frame = frame;
+    e.kind = kind; e.param = param;
+    hipLaunchKernelGGL(k_strokes_close, dim3(guide_grid((long)H * W * D), (unsigned)B), dim3(ST_TPB), 0, st, boxes, box_count,
+                       (const float*)fields, e, out);
     return mivp_check_launch("strokes_close");
 }
 
